@@ -313,6 +313,52 @@ def timed_flow_hist(torch, ctx, _native, batches, B, bins, steps, warmup, barrie
     return dt, launches, ms
 
 
+DUMP_BUDGET_BYTES = 63 * 1000 * 1000   # payload of all --dump-outputs files together (under 64 MB with the .npy headers)
+DUMP_POINTS = 1 << 20                  # flow vectors sampled over every pair when the whole flow does not fit
+DUMP_SEED = 20240607
+
+
+def dump_outputs(torch, out_dir, flow_out, hist_out):
+    """--dump-outputs: what the timed path returned in its last step, as .npy files in out_dir.
+      histogram.npy    (B, 3, bins) float32: the Histogram op's counts (exact in float32)
+      flow.npy         (B, h, w, 2) float32: every flow field, when it fits the budget; otherwise
+      flow_pairs.npy   (k, h, w, 2) float32: whole fields of k pairs -- the first, the last and a seeded choice of the others
+      flow_points.npy  (n, 2) float32: flow vectors at n seeded random (pair, y, x) positions over all B pairs
+    The sample depends only on the output's shape and DUMP_SEED, so two runs with the same arguments dump the same
+    positions.  Returns a description for the result line."""
+    os.makedirs(out_dir, exist_ok=True)
+    B, h, w, _ = flow_out.shape
+    hist = hist_out.cpu().numpy().astype(np.float32)
+    files = {"histogram": hist}
+    desc = {"dir": out_dir}
+    room = DUMP_BUDGET_BYTES - hist.nbytes
+    pair_bytes = h * w * 2 * 4
+    if B * pair_bytes <= room:
+        files["flow"] = flow_out.cpu().numpy()
+    else:
+        rng = np.random.default_rng(DUMP_SEED)
+        n_pts = min(DUMP_POINTS, B * h * w)
+        pts = np.sort(rng.choice(B * h * w, size=n_pts, replace=False))
+        idx = torch.from_numpy(pts).to(flow_out.device)
+        files["flow_points"] = flow_out.reshape(-1, 2).index_select(0, idx).cpu().numpy()
+        k = min(B, (room - files["flow_points"].nbytes) // pair_bytes)
+        if k > 0:
+            rest = rng.permutation(np.arange(1, B - 1))[:max(k - 2, 0)]
+            pairs = sorted(set([0, B - 1][:k]) | set(int(i) for i in rest))
+            files["flow_pairs"] = flow_out[pairs].cpu().numpy()
+            desc["flow_pairs"] = pairs
+        desc["flow_points"] = {"n": n_pts, "seed": DUMP_SEED, "of": "flat (pair, y, x) index, sorted"}
+    total = 0
+    for name, arr in files.items():
+        assert arr.dtype in (np.float32, np.float64), (name, arr.dtype)
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
+        total += arr.nbytes
+    assert total <= DUMP_BUDGET_BYTES, total
+    desc["files"] = {name: list(arr.shape) for name, arr in files.items()}
+    desc["bytes"] = total
+    return desc
+
+
 def concurrent_instances(torch, device, frames, h, w, bins, ks=(1, 2, 4, 8), pairs=(1, 8), reps=3):
     """Aggregate frames/s of K concurrent kernel instances (K contexts, K streams, K host threads) each making
     Histogram + OpticalFlow calls of b pairs, one stream sync per call.  Every cell is measured `reps` times (fresh
@@ -992,6 +1038,8 @@ def run_rank(args):
     dt, blur_launches, blur_ms = timed_flow_hist(torch, ctx, _native, batches, B, args.bins, args.steps, args.warmup,
                                                  barrier, flow_out, hist_out)
     dt_rank = dt
+    # what the last timed step handed its caller, before anything below reuses flow_out / hist_out (rank 0's shard)
+    dumped = dump_outputs(torch, args.dump_outputs, flow_out, hist_out) if (args.dump_outputs and rank == 0) else None
     if world > 1:
         t = torch.tensor([dt], dtype=torch.float64, device="cpu" if share else device)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -1088,6 +1136,7 @@ def run_rank(args):
             "warmup": args.warmup,
             "ms_per_step": dt / args.steps * 1e3,
             **({"ranks_share_gpus": True} if share else {}),
+            **({"dump_outputs": dumped} if dumped else {}),
             "higher_is_better": True,
             "scaling": "weak",
             "vs_baseline": None,
@@ -1235,17 +1284,28 @@ def main():
     ap.add_argument("--master-port", type=int, default=0)
     ap.add_argument("--dry-run", action="store_true",
                     help="launcher self-test on CPU (gloo): rendezvous + barriers + reduction around a dummy step")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (rank 0) to DIR/<name>.npy: the histograms "
+                         "and the flow fields, or a fixed seeded sample of the flow when it exceeds 64 MB")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.dry_run:
+        ap.error("--dump-outputs: a dry run computes nothing")
 
-    # The native libraries are not shipped to the GPU box (.gpurunignore): whoever runs first there compiles them.  In a child
-    # process, so that this one (which may still have to spawn its ranks) loads nothing; ranks under an external launcher
-    # leave it to local rank 0 and wait for the file lock.
+    # The native libraries are never committed: whoever runs first on a machine compiles them.  In a child process, so that
+    # this one (which may still have to spawn its ranks) loads nothing; ranks under an external launcher leave it to the first
+    # of them and wait on the lock.  The lock is taken on the repository directory itself, so that a checkout the benchmark
+    # may not write to (libraries already built) runs as it is.
     if not args.dry_run:
         import fcntl
         import subprocess
-        with open(os.path.join(ROOT, ".build.lock"), "w") as lk:
+        lk = os.open(ROOT, os.O_RDONLY)
+        try:
             fcntl.flock(lk, fcntl.LOCK_EX)
             subprocess.check_call([sys.executable, "-c", "import __graft_entry__ as g; g.ensure_built()"], cwd=ROOT)
+        finally:
+            os.close(lk)
 
     env_world = os.environ.get("WORLD_SIZE")
     if env_world is None and args.gpus > 1:
