@@ -437,8 +437,8 @@ int conv_tile_choose(st_ctx* ctx, int n, int h, int w, int kh, int kw, int cout_
   auto wgs = [&](int th, int tw) { return (long long)n * ((w + tw - 1) / tw) * ((h + th - 1) / th) * (cout_pad / 128); };
   // below this many 4-wave workgroups per 100 CUs a wave takes one 32-pixel instruction tile instead of two (measured over the
   // network, frames per call 1 / 2 / 5 / 8: bf16x3 129 / 230 / 304 / 400 frames/s without, 162 / 279 / 332 / 399 with; float32
-  // 68 / 126 / 161 / 236 and 102 / 183 / 184 / 235); ST_CONV_MT1_PCT moves the line (experiments)
-  static const int mt1_pct = getenv("ST_CONV_MT1_PCT") ? atoi(getenv("ST_CONV_MT1_PCT")) : 150;
+  // 68 / 126 / 161 / 236 and 102 / 183 / 184 / 235)
+  constexpr int mt1_pct = 150;
   int nw = 0;
   if (ctx->conv_tile == 1) nw = ok8 ? 8 : (ok4 ? 4 : 0);
   else if (ctx->conv_tile == 4) nw = ok4 ? 4 : (ok8 ? 8 : 0);

@@ -1099,11 +1099,6 @@ __device__ __forceinline__ float4 ldf4(const float* __restrict__ base, unsigned 
   return *reinterpret_cast<const float4*>(reinterpret_cast<const char*>(base) + byte_off);
 }
 
-// build-time experiment switches (0 in the product; ST_ABLATE is described above k_flow_iter3)
-#ifndef ST_ABLATE
-#define ST_ABLATE 0
-#endif
-
 
 
 // ---------------------------------------------------------------------------------------------
@@ -1300,10 +1295,7 @@ __global__ __launch_bounds__(256) void k_polyexp(PolyArgs a) {
 
 // level 0 straight from the gray frames (default pyramid: 3 x 3 blur, no resize)
 template <int N>
-#ifndef ST_PE_U8_WAVES
-#define ST_PE_U8_WAVES 1   // experiments: 6 = force the float-source instance's six waves per SIMD (80 registers, 9 spilled: 5.0 ms against 4.5)
-#endif
-__global__ __launch_bounds__(256, ST_PE_U8_WAVES) void k_polyexp_u8(PolyArgs a) {
+__global__ __launch_bounds__(256, 1) void k_polyexp_u8(PolyArgs a) {
   polyexp_body<N, PolyArgs, true>(a, nullptr, a.R, a.h, a.w, a.rows_per_seg, (int)blockIdx.x, (int)blockIdx.y, (int)blockIdx.z, a.gray);
 }
 
@@ -1425,17 +1417,12 @@ __device__ __forceinline__ void um_issue(const float* __restrict__ R0, const flo
 // the six R1 loads of the bilinear footprint; the second column's texel is addressed from a base pointer 16 bytes on
 // (uniform arithmetic) rather than by adding 16 to the per-lane offset (a vector instruction per load)
 __device__ __forceinline__ void um_gather(const float* __restrict__ R1, unsigned single, unsigned gi, unsigned gb, UmLoads& L) {
-  // ST_ABLATE 16 / 64 (experiments, wrong results): what perfect lane sharing (no second-column loads) and a perfect
-  // row carry (no top-row loads) would save -- the upper bound of any texel-reuse scheme (profiles/NOTES.md, round 5)
-  if (!(ST_ABLATE & 64)) {
-    L.t0 = ldf4(R1, 16u * gi);
-    if (ST_ABLATE & 16) L.t1 = L.t0; else L.t1 = ldf4(R1 + 4, 16u * gi);
-  }
+  L.t0 = ldf4(R1, 16u * gi);
+  L.t1 = ldf4(R1 + 4, 16u * gi);
   L.b0 = ldf4(R1, 16u * gb);
-  if (ST_ABLATE & 16) L.b1 = L.b0; else L.b1 = ldf4(R1 + 4, 16u * gb);
-  if (!(ST_ABLATE & 64)) L.ts = ldf2(R1, single + 4u * gi);
+  L.b1 = ldf4(R1 + 4, 16u * gb);
+  L.ts = ldf2(R1, single + 4u * gi);
   L.bs = ldf2(R1, single + 4u * gb);
-  if (ST_ABLATE & 64) { L.t0 = L.b0; L.t1 = L.b1; L.ts = L.bs; }
 }
 
 __device__ __forceinline__ void um_finish(const UmLoads& L, int h, int w, int x, int y, float2 f, float m[5]) {
@@ -1480,45 +1467,6 @@ __device__ __forceinline__ void um_finish(const UmLoads& L, int h, int w, int x,
   m[4] = r6 * r2 + r5 * r3;
 }
 
-#if ST_ABLATE & 128
-// ST_ABLATE 128 (experiment, wrong results): the ceiling of "R1 rows kept on chip" (round-5 verdict, item 1) -- the six
-// per-lane R1 gathers of a pixel replaced by ONE coalesced fill (16 + 4 bytes of the row below, written to a 3-row x
-// 272-column window in LDS) and six LDS reads at the gather's column / row offsets.  No barrier orders the fill against
-// the reads and the window never tracks the flow: the values are garbage, the instruction mix is the scheme's best case.
-// ST_ABLATE 256 adds a workgroup barrier per row batch (what a 3-row window needs to be correct).
-constexpr int RW_COLS = 256 + 16;  // B2_T + 16
-struct RWin { float4* q; float* s; int xb; };
-__device__ __forceinline__ void um_issue_win(const float* __restrict__ R0, const float* __restrict__ R1, int np, int h,
-                                             int w, int x, int y, UmLoads& L) {
-  const unsigned o = (unsigned)(y * w + x);
-  const unsigned single = 16u * (unsigned)np;
-  L.q = ldf4(R0, 16u * o);
-  L.qs = ldf(R0, single + 4u * o);
-  const unsigned of = (unsigned)(min(y + 1, h - 1) * w + x);
-  L.t0 = ldf4(R1, 16u * of);
-  L.ts.x = ldf(R1, single + 4u * of);
-}
-__device__ __forceinline__ void um_fill_win(const UmLoads& L, const RWin& win, int slot, int tid) {
-  win.q[slot * RW_COLS + tid + 8] = L.t0;
-  win.s[slot * RW_COLS + tid + 8] = L.ts.x;
-}
-__device__ __forceinline__ void um_gather_win(const UmLoads& L, const RWin& win, int slot, int h, int w, int x, int y,
-                                              float2 f, UmLoads& G) {
-  const float fx = x + f.x, fy = y + f.y;
-  const int x1 = (int)floorf(fx), y1 = (int)floorf(fy);
-  const int c = d_clamp(x1 - win.xb, 0, RW_COLS - 2);
-  const int d = d_clamp(y1 - y + 1, 0, 1);
-  int s0 = slot + 1 + d; s0 = s0 >= 3 ? s0 - 3 : s0;
-  int s1 = s0 + 1; s1 = s1 >= 3 ? s1 - 3 : s1;
-  G.q = L.q; G.qs = L.qs;
-  const float4* q0 = win.q + s0 * RW_COLS + c;
-  const float4* q1 = win.q + s1 * RW_COLS + c;
-  G.t0 = q0[0]; G.t1 = q0[1]; G.b0 = q1[0]; G.b1 = q1[1];
-  const float* p0 = win.s + s0 * RW_COLS + c;
-  const float* p1 = win.s + s1 * RW_COLS + c;
-  G.ts.x = p0[0]; G.ts.y = p0[1]; G.bs.x = p1[0]; G.bs.y = p1[1];
-}
-#endif
 
 // Initial matrices of a level; the flow is zero (coarsest level), a given field, or the
 // previous level's flow resized with INTER_LINEAR and multiplied by 1/pyr_scale.
@@ -1724,8 +1672,8 @@ __global__ __launch_bounds__(BLUR_T) void k_blur_update(BlurArgs a) {
 constexpr int B2_T = 256, B2_HALO = 8, B2_OUT = B2_T - 2 * B2_HALO, B2_RB = 5, B2_SEG = 5;
 constexpr int B2_NSEG = B2_OUT / B2_SEG;  // 48 segments per row
 
-template <int M, bool RING, int U3, int WAVES>
-__global__ __launch_bounds__(B2_T, WAVES) void k_blur_update_v2(BlurArgs a) {
+template <int M>
+__global__ __launch_bounds__(B2_T, 2) void k_blur_update_v2(BlurArgs a) {
   constexpr int W = 2 * M + 1;
   static_assert(W % B2_RB == 0 && M <= B2_HALO, "ring period must be a multiple of the batch");
   __shared__ float V[B2_RB][5][B2_T];
@@ -1758,34 +1706,8 @@ __global__ __launch_bounds__(B2_T, WAVES) void k_blur_update_v2(BlurArgs a) {
   if (a.write_flow) flow = a.flow_ptrs ? st_gl(a.flow_ptrs[pr]) : a.flow + (size_t)pr * 2 * (size_t)np;
 
   // ring slot s holds source row y0 - M + s (clamped) at entry; vs = window sum of row y0
-  float ring[RING ? W : 1][5];
+  float ring[W][5];
   double vs[5];
-  if (!RING) {
-    // no register ring: the row leaving the window is re-read (served by L2 / Infinity Cache / HBM)
-    if (y0 == 0) {
-#pragma unroll
-      for (int c = 0; c < 5; ++c) vs[c] = (double)(Min[c * np + xc] * (float)(M + 2));
-      for (int yy = 1; yy < M; ++yy) {
-        const int o = min(yy, h - 1) * w + xc;
-#pragma unroll
-        for (int c = 0; c < 5; ++c) vs[c] += (double)Min[c * np + o];
-      }
-      const int oa = min(M, h - 1) * w + xc;
-#pragma unroll
-      for (int c = 0; c < 5; ++c) {
-        const float d = Min[c * np + oa] - Min[c * np + xc];
-        vs[c] += d;
-      }
-    } else {
-#pragma unroll
-      for (int c = 0; c < 5; ++c) vs[c] = 0;
-      for (int dy = -M; dy <= M; ++dy) {
-        const int o = d_clamp(y0 + dy, 0, h - 1) * w + xc;
-#pragma unroll
-        for (int c = 0; c < 5; ++c) vs[c] += (double)Min[c * np + o];
-      }
-    }
-  } else {
 #pragma unroll
   for (int s = 0; s < W; ++s) {
     const int o = d_clamp(y0 - M + s, 0, h - 1) * w + xc;
@@ -1814,7 +1736,6 @@ __global__ __launch_bounds__(B2_T, WAVES) void k_blur_update_v2(BlurArgs a) {
 #pragma unroll
       for (int c = 0; c < 5; ++c) vs[c] += (double)ring[s][c];
   }
-  }
 
   for (int yb = y0; yb < y1; yb += W) {
 #pragma unroll
@@ -1822,27 +1743,21 @@ __global__ __launch_bounds__(B2_T, WAVES) void k_blur_update_v2(BlurArgs a) {
       const int ybb = yb + b * B2_RB;
       if (ybb < y1) {  // workgroup-uniform
         // ---- phase 1: vertical window ----
-        float nw[B2_RB][5], od[RING ? 1 : B2_RB][5];
+        float nw[B2_RB][5];
 #pragma unroll
         for (int r = 0; r < B2_RB; ++r) {
           const int o = d_clamp(ybb + r + M + 1, 0, h - 1) * w + xc;
 #pragma unroll
           for (int c = 0; c < 5; ++c) nw[r][c] = Min[c * np + o];
-          if (!RING) {
-            const int oo = d_clamp(ybb + r - M, 0, h - 1) * w + xc;
-#pragma unroll
-            for (int c = 0; c < 5; ++c) od[r][c] = Min[c * np + oo];
-          }
         }
 #pragma unroll
         for (int r = 0; r < B2_RB; ++r) {
 #pragma unroll
           for (int c = 0; c < 5; ++c) {
             V[r][c][tid] = (float)vs[c];
-            const float old = RING ? ring[RING ? b * B2_RB + r : 0][c] : od[RING ? 0 : r][c];
-            const float d = nw[r][c] - old;
+            const float d = nw[r][c] - ring[b * B2_RB + r][c];
             vs[c] += d;
-            if (RING) ring[RING ? b * B2_RB + r : 0][c] = nw[r][c];
+            ring[b * B2_RB + r][c] = nw[r][c];
           }
         }
         __syncthreads();
@@ -1877,7 +1792,7 @@ __global__ __launch_bounds__(B2_T, WAVES) void k_blur_update_v2(BlurArgs a) {
         __syncthreads();
         // ---- phase 3: flow store / UpdateMatrices ----
         if (writer) {
-#pragma unroll U3
+#pragma unroll
           for (int r = 0; r < B2_RB; ++r) {
             const int y = ybb + r;
             if (y < y1) {
@@ -1897,14 +1812,6 @@ __global__ __launch_bounds__(B2_T, WAVES) void k_blur_update_v2(BlurArgs a) {
     }
   }
 }
-
-// ST_ABLATE (build-time bit mask, experiments only -- results are then meaningless): 4 = k_flow_iter3
-// without its expansion loads.  Timing a build with a part removed shows what that part costs in place
-// (profiles/README.md lists the round-2 ablations of the previous kernel generation).
-
-#ifndef ST_EXP_D
-#define ST_EXP_D 1  // gather queue depth of k_flow_iter3 (experiments)
-#endif
 
 // ---------------------------------------------------------------------------------------------
 // One full Farneback iteration without materialising M:
@@ -2150,19 +2057,13 @@ __device__ __forceinline__ void xcd_remap(unsigned& bx, unsigned& by, unsigned& 
   bx = col % gx; by = col / gx; bz = pair;
 }
 
-template <int M, int RB, int MODE, int D>
+template <int MODE>
 __global__ __launch_bounds__(B2_T, 2) void k_flow_iter3(IterArgs a) {
   typedef float f2v __attribute__((ext_vector_type(2)));
-  constexpr int W = 2 * M + 1;
-  static_assert((F3_RING / RB) % D == 0, "the gather queue must rotate a whole number of times per ring period");
+  constexpr int M = 7, W = 2 * M + 1, RB = 2;
   static_assert(W == F3_RING - 1 && F3_GROUP % RB == 0 && M <= B2_HALO, "ring of 16 = window of 15 + the entering row");
   __shared__ float Vs[F3_GROUP][5][F3_PADW];
   __shared__ float2 Fs[F3_GROUP][F3_PADW];
-#if ST_ABLATE & 128
-  __shared__ float4 Rw4[3 * RW_COLS];
-  __shared__ float Rw1[3 * RW_COLS];
-  int wslot = 0;
-#endif
   const int tid = threadIdx.x;
   const int h = a.h, w = a.w;
   const int np = h * w;
@@ -2175,9 +2076,6 @@ __global__ __launch_bounds__(B2_T, 2) void k_flow_iter3(IterArgs a) {
   const int y1 = min(h, y0 + a.rows_per_seg);
   const bool writer = tid >= B2_HALO && tid < B2_T - B2_HALO && x < w;
   const int vpos = f3_pos(tid);
-#if ST_ABLATE & 128
-  const RWin win{Rw4, Rw1, (int)bx * B2_OUT - B2_HALO - 8};
-#endif
   // paired flow stores (even widths): writer k = tid - HALO stores pixels (2 j, 2 j + 1) of rows 4 hh .. 4 hh + 3 of a group,
   // j = k mod (OUT / 2), hh = k / (OUT / 2)
   typedef float f4v __attribute__((ext_vector_type(4), aligned(8)));
@@ -2242,35 +2140,33 @@ __global__ __launch_bounds__(B2_T, 2) void k_flow_iter3(IterArgs a) {
       for (int c = 0; c < 5; ++c) vs[c] += (double)ring[s][c];
   }
 
-  // software pipeline over batches of RB rows: L is a queue of D batches of gathers in flight (fcur their
-  // flows), fnext the flows of the batch that enters the queue next, raw the flow loads of the batch after it.
-  // (D = 2 -- four rows of gathers in flight -- would hide more of the load latency, which is a third of
-  // this kernel's time, but does not fit: 133 spilled registers for the field source.  D = 1 everywhere.)
-  float2 fcur[D][RB], fnext[RB];
-  UmLoads L[D][RB];
+  // software pipeline over batches of RB rows: L holds the gathers of one batch in flight (fcur their flows),
+  // fnext the flows of the next batch, raw the flow loads of the batch after it.  (Two batches of gathers in flight
+  // would hide more of the load latency, which is a third of this kernel's time, but does not fit: 133 spilled
+  // registers for the field source.)
+  float2 fcur[RB], fnext[RB];
+  UmLoads L[RB];
 #pragma unroll
-  for (int d = 0; d < D; ++d)
+  for (int r = 0; r < RB; ++r) {
+    fcur[r] = iter_flow_at<MODE>(a, fin, C, cx, xc, d_clamp(y0 + r + M + 1, 0, h - 1));
+    um_issue(R0, R1, np, h, w, xc, d_clamp(y0 + r + M + 1, 0, h - 1), fcur[r], L[r]);
+  }
 #pragma unroll
-    for (int r = 0; r < RB; ++r) {
-      fcur[d][r] = iter_flow_at<MODE>(a, fin, C, cx, xc, d_clamp(y0 + d * RB + r + M + 1, 0, h - 1));
-      um_issue(R0, R1, np, h, w, xc, d_clamp(y0 + d * RB + r + M + 1, 0, h - 1), fcur[d][r], L[d][r]);
-    }
-#pragma unroll
-  for (int r = 0; r < RB; ++r) fnext[r] = iter_flow_at<MODE>(a, fin, C, cx, xc, d_clamp(y0 + D * RB + r + M + 1, 0, h - 1));
+  for (int r = 0; r < RB; ++r) fnext[r] = iter_flow_at<MODE>(a, fin, C, cx, xc, d_clamp(y0 + RB + r + M + 1, 0, h - 1));
   FlowRaw raw[MODE == FLOW_COARSE2 ? 1 : RB];
   FlowRawN<RB> rawn;
   if (MODE == FLOW_COARSE2) {
-    coarseN_issue<RB>(a, C, cx, d_clamp(y0 + (D + 1) * RB + M + 1, 0, h - 1), rawn);
+    coarseN_issue<RB>(a, C, cx, d_clamp(y0 + 2 * RB + M + 1, 0, h - 1), rawn);
   } else {
 #pragma unroll
-    for (int r = 0; r < RB; ++r) flow_issue<MODE>(a, fin, C, cx, xc, d_clamp(y0 + (D + 1) * RB + r + M + 1, 0, h - 1), raw[r]);
+    for (int r = 0; r < RB; ++r) flow_issue<MODE>(a, fin, C, cx, xc, d_clamp(y0 + 2 * RB + r + M + 1, 0, h - 1), raw[r]);
   }
 
 #pragma unroll 1
   for (int ybase = y0; ybase < y1; ybase += F3_RING) {
     // anchor rows 32 j > 0: the column sums restart from the fresh sum of the 15 window rows in row order
     // (at the top of a 16-row period slot s holds row ybase - 7 + s)
-    if (!(ST_ABLATE & 8) && ybase > y0 && (ybase - y0) % F3_ANCHOR == 0) {
+    if (ybase > y0 && (ybase - y0) % F3_ANCHOR == 0) {
 #pragma unroll
       for (int c = 0; c < 5; ++c) vs[c] = 0;
 #pragma unroll
@@ -2318,56 +2214,34 @@ __global__ __launch_bounds__(B2_T, 2) void k_flow_iter3(IterArgs a) {
 #pragma unroll
       for (int bb = 0; bb < F3_GROUP / RB; ++bb) {
         const int ybb = yg + bb * RB;
-        const int q = (g * (F3_GROUP / RB) + bb) % D;  // queue slot of this batch: compile-time constant
 #pragma unroll
         for (int r = 0; r < RB; ++r) {
           const int t = g * F3_GROUP + bb * RB + r;  // row of the 16-row period: compile-time constant
           float m[5];
-#if ST_ABLATE & 128
-          {
-            UmLoads G;
-            um_fill_win(L[q][r], win, wslot, tid);
-            if ((ST_ABLATE & 256) && r == 0) __syncthreads();
-            um_gather_win(L[q][r], win, wslot, h, w, xc, d_clamp(ybb + r + M + 1, 0, h - 1), fcur[q][r], G);
-            wslot = wslot == 2 ? 0 : wslot + 1;
-            um_finish(G, h, w, xc, d_clamp(ybb + r + M + 1, 0, h - 1), fcur[q][r], m);
-          }
-#else
-          um_finish(L[q][r], h, w, xc, d_clamp(ybb + r + M + 1, 0, h - 1), fcur[q][r], m);
-#endif
+          um_finish(L[r], h, w, xc, d_clamp(ybb + r + M + 1, 0, h - 1), fcur[r], m);
 #pragma unroll
           for (int c = 0; c < 5; ++c) {
             Vs[bb * RB + r][c][vpos] = (float)vs[c];
-            const float d = (ST_ABLATE & 8) ? m[c] * 0.5f : m[c] - ring[t % F3_RING][c];  // ablation 8: no ring
+            const float d = m[c] - ring[t % F3_RING][c];
             vs[c] += d;
-            if (!(ST_ABLATE & 8)) ring[(t + W) % F3_RING][c] = m[c];
+            ring[(t + W) % F3_RING][c] = m[c];
           }
-          fcur[q][r] = fnext[r];
-          if (ST_ABLATE & 4) {  // ablation: no expansion loads
-            L[q][r].q = make_float4(fnext[r].x, fnext[r].y, m[0], m[1]); L[q][r].qs = m[2];
-            L[q][r].t0 = L[q][r].t1 = L[q][r].b0 = L[q][r].b1 = L[q][r].q;
-            L[q][r].ts.x = L[q][r].ts.y = L[q][r].bs.x = L[q][r].bs.y = m[3];
-          } else {
-#if ST_ABLATE & 128
-            um_issue_win(R0, R1, np, h, w, xc, d_clamp(ybb + D * RB + r + M + 1, 0, h - 1), L[q][r]);
-#else
-            um_issue(R0, R1, np, h, w, xc, d_clamp(ybb + D * RB + r + M + 1, 0, h - 1), fcur[q][r], L[q][r]);
-#endif
-          }
+          fcur[r] = fnext[r];
+          um_issue(R0, R1, np, h, w, xc, d_clamp(ybb + RB + r + M + 1, 0, h - 1), fcur[r], L[r]);
         }
         // flows: the loads requested one batch ago become vectors now and the next rows are requested --
         // never a wait on loads issued in the same batch
         if (MODE == FLOW_COARSE2) {
           int ysb[RB];
 #pragma unroll
-          for (int r = 0; r < RB; ++r) ysb[r] = d_clamp(ybb + (D + 1) * RB + r + M + 1, 0, h - 1);
+          for (int r = 0; r < RB; ++r) ysb[r] = d_clamp(ybb + 2 * RB + r + M + 1, 0, h - 1);
           coarse2_finish_batch<RB>(a, cx, ysb[0], ysb, rawn, fnext);
-          coarseN_issue<RB>(a, C, cx, d_clamp(ybb + (D + 2) * RB + M + 1, 0, h - 1), rawn);
+          coarseN_issue<RB>(a, C, cx, d_clamp(ybb + 3 * RB + M + 1, 0, h - 1), rawn);
         } else {
 #pragma unroll
-          for (int r = 0; r < RB; ++r) fnext[r] = flow_finish<MODE>(a, fin, C, cx, d_clamp(ybb + (D + 1) * RB + r + M + 1, 0, h - 1), raw[MODE == FLOW_COARSE2 ? 0 : r]);
+          for (int r = 0; r < RB; ++r) fnext[r] = flow_finish<MODE>(a, fin, C, cx, d_clamp(ybb + 2 * RB + r + M + 1, 0, h - 1), raw[MODE == FLOW_COARSE2 ? 0 : r]);
 #pragma unroll
-          for (int r = 0; r < RB; ++r) flow_issue<MODE>(a, fin, C, cx, xc, d_clamp(ybb + (D + 2) * RB + r + M + 1, 0, h - 1), raw[MODE == FLOW_COARSE2 ? 0 : r]);
+          for (int r = 0; r < RB; ++r) flow_issue<MODE>(a, fin, C, cx, xc, d_clamp(ybb + 3 * RB + r + M + 1, 0, h - 1), raw[MODE == FLOW_COARSE2 ? 0 : r]);
         }
       }
       __builtin_amdgcn_s_setprio(0);
@@ -2452,25 +2326,25 @@ __global__ __launch_bounds__(B2_T, 2) void k_flow_iter3(IterArgs a) {
 // horizontal sums double-buffered: 129 KB (NCW = 4), 158 KB (NCW = 5).
 // ---------------------------------------------------------------------------------------------
 constexpr int FR_G = 4;
-template <int NCW, int NMS>
+template <int NCW>
 struct FrGeom {
   static constexpr int COLS = 64 * NCW, OUTMAX = COLS - 2 * B2_HALO, PADW = COLS + COLS / 8;
   static constexpr int NSEGMAX = OUTMAX / F3_SW;
-  static constexpr int THREADS = (2 + NMS) * COLS;  // NMS sets of maker waves (each takes every NMS-th 2-row batch)
+  static constexpr int THREADS = 3 * COLS;
   static_assert(FR_G * 2 * NSEGMAX <= COLS, "one solver thread per (row, half segment)");
-  static_assert(THREADS <= 1024 && (NMS == 1 || NMS == 2), "workgroup size");
+  static_assert(THREADS <= 1024, "workgroup size");
 };
 
-template <int NCW, int NMS, int MODE, int RB = 2>
-__global__ __launch_bounds__((FrGeom<NCW, NMS>::THREADS)) void k_flow_iter_roles(IterArgs a) {
-  typedef FrGeom<NCW, NMS> G;
-  constexpr int M = 7, W = 15;
-  static_assert(FR_G % (RB * NMS) == 0, "a step is a whole number of batches per maker set");
+template <int NCW, int MODE>
+__global__ __launch_bounds__((FrGeom<NCW>::THREADS)) void k_flow_iter_roles(IterArgs a) {
+  typedef FrGeom<NCW> G;
+  constexpr int M = 7, W = 15, RB = 2;
+  static_assert(FR_G % RB == 0, "a step is a whole number of batches");
   __shared__ float Mb[2][FR_G][5][G::COLS];
   __shared__ float Vs[3][FR_G][5][G::PADW];
   __shared__ double Ts[2][FR_G][2 * G::NSEGMAX][5];
   const int tid = threadIdx.x;
-  const int role = tid < NMS * G::COLS ? 0 : (tid < (NMS + 1) * G::COLS ? 1 : 2);  // wave-uniform
+  const int role = tid < G::COLS ? 0 : (tid < 2 * G::COLS ? 1 : 2);  // wave-uniform
   const int h = a.h, w = a.w;
   const int np = h * w;
   unsigned bx = blockIdx.x, by = blockIdx.y, bz = blockIdx.z;
@@ -2484,8 +2358,7 @@ __global__ __launch_bounds__((FrGeom<NCW, NMS>::THREADS)) void k_flow_iter_roles
 
   if (role == 0) {
     // ---------------- makers ----------------
-    const int mset = NMS == 1 ? 0 : tid / G::COLS;  // this wave's maker set
-    const int t = tid - mset * G::COLS;
+    const int t = tid;
     const int x = (int)bx * a.out_w - B2_HALO + t;
     // lanes beyond the strip's right halo (a strip may be narrower than the waves that march it) repeat its last column:
     // the same cache lines, no traffic of their own
@@ -2502,11 +2375,8 @@ __global__ __launch_bounds__((FrGeom<NCW, NMS>::THREADS)) void k_flow_iter_roles
     const float* __restrict__ fin = a.flow_in ? a.flow_in + (size_t)pr * 2 * (size_t)np : nullptr;
     const float* __restrict__ C = a.coarse ? a.coarse + (size_t)pr * 2 * (size_t)a.ch * a.cw : nullptr;
     const CoarseX cx = (MODE == FLOW_COARSE || MODE == FLOW_COARSE2) ? coarse_x(a, xc) : CoarseX{0, 1.f, 0.f, false};
-    // This set's n-th batch is rows k = KS n + RB mset + r, r < RB: with two sets a step's four rows are one batch of
-    // each set (twice the gathers in flight per compute unit: the makers are what a step waits for).
-    constexpr int KS = RB * NMS, NB = FR_G / KS;  // batch stride in rows, batches per step and set
+    constexpr int NB = FR_G / RB;  // batches per step
     auto rowk = [&](int k) { return d_clamp(y0 - 8 + k, 0, h - 1); };
-    const int kb = RB * mset;
     // software pipeline over the batches (as k_flow_iter3): gathers of the next batch in flight while this one is
     // finished, flows one batch further ahead, their loads one more
     float2 fcur[RB], fnext[RB];
@@ -2515,16 +2385,16 @@ __global__ __launch_bounds__((FrGeom<NCW, NMS>::THREADS)) void k_flow_iter_roles
     FlowRawN<RB> rawn;  // FLOW_COARSE2 (coarse level exactly half as tall): the batch's rows share three coarse rows
 #pragma unroll
     for (int r = 0; r < RB; ++r) {
-      fcur[r] = iter_flow_at<MODE>(a, fin, C, cx, xc, rowk(kb + r));
-      um_issue(R0, R1, np, h, w, xc, rowk(kb + r), fcur[r], L[r]);
+      fcur[r] = iter_flow_at<MODE>(a, fin, C, cx, xc, rowk(r));
+      um_issue(R0, R1, np, h, w, xc, rowk(r), fcur[r], L[r]);
     }
 #pragma unroll
-    for (int r = 0; r < RB; ++r) fnext[r] = iter_flow_at<MODE>(a, fin, C, cx, xc, rowk(kb + KS + r));
+    for (int r = 0; r < RB; ++r) fnext[r] = iter_flow_at<MODE>(a, fin, C, cx, xc, rowk(RB + r));
     if (MODE == FLOW_COARSE2) {
-      coarseN_issue<RB>(a, C, cx, rowk(kb + 2 * KS), rawn);
+      coarseN_issue<RB>(a, C, cx, rowk(2 * RB), rawn);
     } else {
 #pragma unroll
-      for (int r = 0; r < RB; ++r) flow_issue<MODE>(a, fin, C, cx, xc, rowk(kb + 2 * KS + r), raw[r]);
+      for (int r = 0; r < RB; ++r) flow_issue<MODE>(a, fin, C, cx, xc, rowk(2 * RB + r), raw[r]);
     }
     for (int sb = 0; sb < T; sb += 2) {
 #pragma unroll
@@ -2534,8 +2404,8 @@ __global__ __launch_bounds__((FrGeom<NCW, NMS>::THREADS)) void k_flow_iter_roles
           if (s < SM) {
 #pragma unroll
             for (int bb = 0; bb < NB; ++bb) {
-              const int k0 = FR_G * s + bb * KS + kb;   // first row of this batch
-              const int i0 = (NMS == 1 ? bb * RB : kb);  // its row within the step
+              const int k0 = FR_G * s + bb * RB;  // first row of this batch
+              const int i0 = bb * RB;             // its row within the step
 #pragma unroll
               for (int r = 0; r < RB; ++r) {
                 float m[5];
@@ -2543,19 +2413,19 @@ __global__ __launch_bounds__((FrGeom<NCW, NMS>::THREADS)) void k_flow_iter_roles
 #pragma unroll
                 for (int c = 0; c < 5; ++c) Mb[u][i0 + r][c][t] = m[c];
                 fcur[r] = fnext[r];
-                um_issue(R0, R1, np, h, w, xc, rowk(k0 + KS + r), fcur[r], L[r]);
+                um_issue(R0, R1, np, h, w, xc, rowk(k0 + RB + r), fcur[r], L[r]);
               }
               if (MODE == FLOW_COARSE2) {
                 int ysb[RB];
 #pragma unroll
-                for (int r = 0; r < RB; ++r) ysb[r] = rowk(k0 + 2 * KS + r);
+                for (int r = 0; r < RB; ++r) ysb[r] = rowk(k0 + 2 * RB + r);
                 coarse2_finish_batch<RB>(a, cx, ysb[0], ysb, rawn, fnext);
-                coarseN_issue<RB>(a, C, cx, rowk(k0 + 3 * KS), rawn);
+                coarseN_issue<RB>(a, C, cx, rowk(k0 + 3 * RB), rawn);
               } else {
 #pragma unroll
-                for (int r = 0; r < RB; ++r) fnext[r] = flow_finish<MODE>(a, fin, C, cx, rowk(k0 + 2 * KS + r), raw[MODE == FLOW_COARSE2 ? 0 : r]);
+                for (int r = 0; r < RB; ++r) fnext[r] = flow_finish<MODE>(a, fin, C, cx, rowk(k0 + 2 * RB + r), raw[MODE == FLOW_COARSE2 ? 0 : r]);
 #pragma unroll
-                for (int r = 0; r < RB; ++r) flow_issue<MODE>(a, fin, C, cx, xc, rowk(k0 + 3 * KS + r), raw[MODE == FLOW_COARSE2 ? 0 : r]);
+                for (int r = 0; r < RB; ++r) flow_issue<MODE>(a, fin, C, cx, xc, rowk(k0 + 3 * RB + r), raw[MODE == FLOW_COARSE2 ? 0 : r]);
               }
             }
           }
@@ -2565,7 +2435,7 @@ __global__ __launch_bounds__((FrGeom<NCW, NMS>::THREADS)) void k_flow_iter_roles
     }
   } else if (role == 1) {
     // ---------------- summers ----------------
-    const int t = tid - NMS * G::COLS;
+    const int t = tid - G::COLS;
     const int vpos = f3_pos(t);
     float ring[F3_RING][5];
     double vs[5];
@@ -2682,7 +2552,7 @@ __global__ __launch_bounds__((FrGeom<NCW, NMS>::THREADS)) void k_flow_iter_roles
     }
   } else {
     // ---------------- solvers ----------------
-    const int t = tid - (NMS + 1) * G::COLS;
+    const int t = tid - 2 * G::COLS;
     const int nq = 2 * nseg;
     const int r = t / nq, q = t - r * nq;
     const int sg = q >> 1, hf = q & 1;
@@ -2760,11 +2630,11 @@ __global__ __launch_bounds__((FrGeom<NCW, NMS>::THREADS)) void k_flow_iter_roles
 // 2.1x redundant UpdateMatrices work, but thousands of short independent workgroups instead of a
 // few dozen long ones: a level-3 launch drops from ~25 us to ~10 us.
 // ---------------------------------------------------------------------------------------------
-constexpr int FT_T = 32, FT_M = 7, FT_S = FT_T + 2 * FT_M;  // tile side, window radius, tile + apron
+constexpr int FT_T = 32, FT_M = 7, FT_S = FT_T + 2 * FT_M, FT_NT = 512;  // tile side, window radius, tile + apron, threads
 static_assert(FT_T == F3_ANCHOR && FT_T % F3_SW == 0 && B2_OUT % F3_SW == 0, "tile anchors must coincide with k_flow_iter3's");
 
-template <int MODE, int NT>
-__global__ __launch_bounds__(NT) void k_flow_iter_tile(IterArgs a) {
+template <int MODE>
+__global__ __launch_bounds__(FT_NT) void k_flow_iter_tile(IterArgs a) {
   constexpr int W = 2 * FT_M + 1;
   constexpr int NSEG = FT_T / F3_SW;  // 8-pixel segments per tile row
   __shared__ float Mt[5][FT_S][FT_S];            // M on the tile + apron; rows 0 .. 31 become the column sums in place
@@ -2790,13 +2660,13 @@ __global__ __launch_bounds__(NT) void k_flow_iter_tile(IterArgs a) {
   // ---- phase 1: M on the tile + apron (Mt row j = source row Y0 - 7 + j, clamped).  A thread has up to NI of the
   // 46 x 46 pixels.  Their flow vectors are requested together, then the expansions in chunks of up to three pixels: a few
   // memory round trips per tile instead of two per pixel -- these launches are latency-bound, so that is most of their time.
-  constexpr int NI = (FT_S * FT_S + NT - 1) / NT;
+  constexpr int NI = (FT_S * FT_S + FT_NT - 1) / FT_NT;
   int px[NI], py[NI];
   FlowRaw raw[NI];
   CoarseX cxs[NI];
 #pragma unroll
   for (int k = 0; k < NI; ++k) {
-    const int i = min(tid + NT * k, FT_S * FT_S - 1);  // the last, partial round recomputes the final pixel: harmless
+    const int i = min(tid + FT_NT * k, FT_S * FT_S - 1);  // the last, partial round recomputes the final pixel: harmless
     const int ty = i / FT_S, tx = i - ty * FT_S;
     px[k] = d_clamp(X0 - FT_M + tx, 0, w - 1);
     py[k] = d_clamp(Y0 - FT_M + ty, 0, h - 1);
@@ -2818,7 +2688,7 @@ __global__ __launch_bounds__(NT) void k_flow_iter_tile(IterArgs a) {
       if (k0 + j < NI) {
         float m[5];
         um_finish(L[j], h, w, px[k0 + j], py[k0 + j], fl[k0 + j], m);
-        const int i = tid + NT * (k0 + j);
+        const int i = tid + FT_NT * (k0 + j);
         if (i < FT_S * FT_S) {
           const int ty = i / FT_S, tx = i - ty * FT_S;
 #pragma unroll
@@ -2831,7 +2701,7 @@ __global__ __launch_bounds__(NT) void k_flow_iter_tile(IterArgs a) {
   __syncthreads();
   // ---- phase 2: column sums of the tile's 32 rows from the anchor at its first row; item = (channel, column).  The sum of
   // row j replaces M of row j (its last reader is this very step of this very thread).
-  for (int i = tid; i < 5 * FT_S; i += NT) {
+  for (int i = tid; i < 5 * FT_S; i += FT_NT) {
     const int c = i / FT_S, col = i - c * FT_S;
     // the column's 46 values first (one burst of LDS reads), then the serial chain on registers: read inside the chain, every
     // step would wait for an LDS round trip (the compiler cannot move the reads above the in-place stores)
@@ -2863,7 +2733,7 @@ __global__ __launch_bounds__(NT) void k_flow_iter_tile(IterArgs a) {
   __syncthreads();
   // ---- phase 3a: horizontal sums; item = (row, 8-pixel segment, channel), segments start at x = 8 i: the fresh 15-term sum
   // at the segment's first pixel and the four slides to its fifth (the longest serial chain of the tile, cut in two)
-  for (int i = tid; i < FT_T * NSEG * 5; i += NT) {
+  for (int i = tid; i < FT_T * NSEG * 5; i += FT_NT) {
     const int g = i % NSEG, rc = i / NSEG, c = rc % 5, r = rc / 5;
     const float* __restrict__ vp = &Mt[c][r][F3_SW * g];  // column j0 - 7 of the segment, j0 = FT_M + 8 g
     double acc = vp[0];
@@ -2876,7 +2746,7 @@ __global__ __launch_bounds__(NT) void k_flow_iter_tile(IterArgs a) {
   }
   __syncthreads();
   // ---- phase 3b: item = (row, half segment): three more slides, four solves
-  for (int i = tid; i < FT_T * 2 * NSEG; i += NT) {
+  for (int i = tid; i < FT_T * 2 * NSEG; i += FT_NT) {
     const int r = i / (2 * NSEG), q = i - r * (2 * NSEG);
     const int y = Y0 + r;
     if (y >= h) continue;
@@ -2942,8 +2812,7 @@ int rows_per_segment(st_ctx* ctx, int h, int strips, int batch, int halo) {
 // of a few frames is latency-bound (a workgroup marches its rows one barrier per 4 rows), so it is cut into many
 // short segments even though each re-reads 2N rows of context.
 int polyexp_rows(st_ctx* ctx, int h, int strips, int n, int poly_n) {
-  static const int env_min = getenv("ST_PE_MINROWS") ? atoi(getenv("ST_PE_MINROWS")) : 0;
-  const int min_rows = env_min > 0 ? (env_min + PE_RB - 1) / PE_RB * PE_RB : 12;  // measured at 1-8 pairs of 1080p: 12 rows +4 % over the former 44, nothing below
+  const int min_rows = 12;  // measured at 1-8 pairs of 1080p: 12 rows +4 % over the former 44, nothing below
   const long long target = (long long)ctx->num_cus * 8, per = (long long)strips * n;
   long long segs = (target + per - 1) / per;
   if (segs < 1) segs = 1;
@@ -2984,7 +2853,7 @@ int launch_pyr(st_ctx* ctx, const uint8_t* gray, int n, int h, int w, const Leve
   gaussian_kernel(g.ksize, g.sigma, a.taps);
   const double inv_sx = (double)g.lw / w, inv_sy = (double)g.lh / h;
   a.scale_x = 1. / inv_sx; a.scale_y = 1. / inv_sy;
-  if (g.lh == h && g.lw == w && g.ksize == 3 && h >= 2 && w >= 8 && !getenv("ST_PYR_GENERIC")) {
+  if (g.lh == h && g.lw == w && g.ksize == 3 && h >= 2 && w >= 8) {
     Pyr0Args z;
     z.gray = gray; z.img = img; z.h = h; z.w = w; z.k0 = a.taps[1]; z.k1 = a.taps[2];
     const int bx = ((w + 3) / 4 + 255) / 256;
@@ -3003,7 +2872,7 @@ int launch_pyr(st_ctx* ctx, const uint8_t* gray, int n, int h, int w, const Leve
     if (w == 2 * g.lw && h == 2 * g.lh && g.ksize == 3) S = 2;
     else if (w == 4 * g.lw && h == 4 * g.lh && g.ksize == 9) S = 4;
     else if (w == 8 * g.lw && h == 8 * g.lh && g.ksize == 19) S = 8;
-    if (S && !getenv("ST_PYR_GENERIC")) {
+    if (S) {
       PyrDecArgs z;
       z.gray = gray; z.img = img; z.sh = h; z.sw = w; z.dh = g.lh; z.dw = g.lw;
       memcpy(z.taps, a.taps, sizeof(z.taps));
@@ -3038,11 +2907,9 @@ int launch_pyr(st_ctx* ctx, const uint8_t* gray, int n, int h, int w, const Leve
 }
 
 // The one-pass pyramid applies to the reference's default geometry: four levels, each exactly half
-// the previous one (sides multiples of 8), kernel sizes 3/3/9/19.  ST_PYR_UNFUSED=1 forces the
-// per-level kernels (A/B runs).
+// the previous one (sides multiples of 8), kernel sizes 3/3/9/19.
 bool pyr_fused_ok(int h, int w, const st_fb_params& p) {
-  static const bool off = getenv("ST_PYR_UNFUSED") != nullptr || getenv("ST_PYR_GENERIC") != nullptr;
-  if (off || fb_levels(h, w, p) != 3 || (h & 7) || (w & 7)) return false;
+  if (fb_levels(h, w, p) != 3 || (h & 7) || (w & 7)) return false;
   static const int ks[4] = {3, 3, 9, 19};
   for (int k = 0; k <= 3; ++k) {
     const LevelGeom g = fb_level_geom(h, w, p, k);
@@ -3087,11 +2954,8 @@ int launch_pyr_fused(st_ctx* ctx, const uint8_t* gray, const uint8_t* const* fra
   rows = (rows + 7) / 8 * 8;
   // (a few frames only: down to 16-row segments -- twice the rows are read, but the launch is
   // latency-bound and needs the workgroups)
-  static const int env_min = getenv("ST_PYR_MINROWS") ? atoi(getenv("ST_PYR_MINROWS")) : 0;
-  const int min_rows = (long long)strips * n * ((h + 63) / 64) >= 2LL * ctx->num_cus ? 64 : (env_min > 0 ? (env_min + 7) / 8 * 8 : 16);
+  const int min_rows = (long long)strips * n * ((h + 63) / 64) >= 2LL * ctx->num_cus ? 64 : 16;
   if (rows < min_rows) rows = h < min_rows ? h : min_rows;
-  static const int force_rows = getenv("ST_PYR_SEGROWS") ? atoi(getenv("ST_PYR_SEGROWS")) : 0;  // experiments
-  if (force_rows >= 8) rows = (force_rows + 7) / 8 * 8;
   a.rows_per_seg = rows;
   st_timed t(ctx, ST_K_PYR);
   // role-split instance (k_pyr_roles) unless ST_PYR_ROLES=0 (read at st_ctx_create): 257 frames 1.23 against 1.50 ms, two frames 25 against 43 us
@@ -3183,7 +3047,7 @@ int launch_blur(st_ctx* ctx, BlurArgs a, int n_pairs) {
     a.rows_per_seg = rows;
     dim3 grid(strips, (a.h + rows - 1) / rows, n_pairs);
     st_timed t(ctx, ST_K_BLUR_UPDATE);
-    hipLaunchKernelGGL((k_blur_update_v2<7, true, 5, 2>), grid, dim3(B2_T), 0, ctx->stream, a);
+    hipLaunchKernelGGL((k_blur_update_v2<7>), grid, dim3(B2_T), 0, ctx->stream, a);
     ST_HIP(ctx, hipGetLastError());
     return ST_OK;
   }
@@ -3203,20 +3067,14 @@ int launch_flow_iter(st_ctx* ctx, IterArgs a, int n_pairs) {
   // the choice, like the segment height below, changes the schedule and not one bit of the result:
   // a pair's flow does not depend on how many pairs share the call.  ST_ITER_TILE=0 / 1 (read at
   // st_ctx_create) force the marching / the tile kernel (A/B runs, parity tests of each kernel).
-  const bool tile = ctx->tile_mode == 1 || (ctx->tile_mode != 0 && (long long)n_pairs * a.h * a.w <= ctx->tile_px);
+  constexpr long long kTilePx = 600000;
+  const bool tile = ctx->tile_mode == 1 || (ctx->tile_mode != 0 && (long long)n_pairs * a.h * a.w <= kTilePx);
   if (tile && (a.h + FT_T - 1) / FT_T <= 65535) {
     dim3 grid((a.w + FT_T - 1) / FT_T, (a.h + FT_T - 1) / FT_T, n_pairs);
     st_timed t(ctx, ST_K_BLUR_UPDATE);
-    static const int tile_nt = getenv("ST_TILE_NT") ? atoi(getenv("ST_TILE_NT")) : 512;  // threads per tile (256: A/B runs)
-    if (tile_nt == 256) {
-      if (a.coarse) hipLaunchKernelGGL((k_flow_iter_tile<FLOW_COARSE, 256>), grid, dim3(256), 0, ctx->stream, a);
-      else if (a.flow_in) hipLaunchKernelGGL((k_flow_iter_tile<FLOW_FIELD, 256>), grid, dim3(256), 0, ctx->stream, a);
-      else hipLaunchKernelGGL((k_flow_iter_tile<FLOW_ZERO, 256>), grid, dim3(256), 0, ctx->stream, a);
-    } else {
-      if (a.coarse) hipLaunchKernelGGL((k_flow_iter_tile<FLOW_COARSE, 512>), grid, dim3(512), 0, ctx->stream, a);
-      else if (a.flow_in) hipLaunchKernelGGL((k_flow_iter_tile<FLOW_FIELD, 512>), grid, dim3(512), 0, ctx->stream, a);
-      else hipLaunchKernelGGL((k_flow_iter_tile<FLOW_ZERO, 512>), grid, dim3(512), 0, ctx->stream, a);
-    }
+    if (a.coarse) hipLaunchKernelGGL((k_flow_iter_tile<FLOW_COARSE>), grid, dim3(FT_NT), 0, ctx->stream, a);
+    else if (a.flow_in) hipLaunchKernelGGL((k_flow_iter_tile<FLOW_FIELD>), grid, dim3(FT_NT), 0, ctx->stream, a);
+    else hipLaunchKernelGGL((k_flow_iter_tile<FLOW_ZERO>), grid, dim3(FT_NT), 0, ctx->stream, a);
     ST_HIP(ctx, hipGetLastError());
     return ST_OK;
   }
@@ -3249,7 +3107,7 @@ int launch_flow_iter(st_ctx* ctx, IterArgs a, int n_pairs) {
   // 1080p: K = 2: 4 210 -> 4 640 / 5 510 -> 5 740 frames/s, K = 4: 4 750 -> 5 180 / 5 770 -> 6 810, K = 8: 4 870 -> 5 310 /
   // 5 910 -> 6 870 (a lone instance: 3 540 -> 3 290, which is why the choice depends on it); profiles/r6_instances_modes.txt.
   const int roles_env = ctx->roles_mode == -1 && ctx->flow_concurrent ? 0 : ctx->roles_mode;
-  const int roles_ncw = ctx->roles_ncw, roles_rows = ctx->roles_rows;
+  const int roles_ncw = ctx->roles_ncw;
   // (the first iteration of a level -- coarse-flow source, expansions not yet in any cache -- is where the role kernel's single
   // maker wave per SIMD is weakest: 8 pairs, level 0: 264 us against k_flow_iter3's 226, while its field-source launches
   // win 183 : 195; it takes those launches only when k_flow_iter3 would leave more than a third of its slots empty)
@@ -3277,7 +3135,6 @@ int launch_flow_iter(st_ctx* ctx, IterArgs a, int n_pairs) {
         if (cost < bestr * 0.999) { bestr = cost; best_ncw = ncw; best_out = out_w; best_rows = r; }
       }
     }
-    if (roles_rows >= F3_ANCHOR && roles_rows % F3_ANCHOR == 0) best_rows = roles_rows;
     if (best_ncw) {
       a.rows_per_seg = best_rows;
       a.out_w = best_out;
@@ -3285,36 +3142,34 @@ int launch_flow_iter(st_ctx* ctx, IterArgs a, int n_pairs) {
       dim3 grid(rstrips, (a.h + best_rows - 1) / best_rows, n_pairs);
       st_timed t(ctx, ST_K_BLUR_UPDATE);
       const int mode = a.coarse ? (a.h == 2 * a.ch ? FLOW_COARSE2 : FLOW_COARSE) : (a.flow_in ? FLOW_FIELD : FLOW_ZERO);
-      // One maker set, two rows of gathers in flight per maker wave.  Measured and not kept (the template parameters remain):
+      // One maker set, two rows of gathers in flight per maker wave.  Measured and not kept:
       // two maker sets of the 4-column-wave instance (16 waves: 6.8 against 5.2 ms per 256-pair level-0 launch), four rows
       // in flight (163 registers; 8 pairs per call 1.37 against 1.23 ms).
       if (best_ncw == 5) {
-        const dim3 blk(FrGeom<5, 1>::THREADS);
-        if (mode == FLOW_COARSE2) hipLaunchKernelGGL((k_flow_iter_roles<5, 1, FLOW_COARSE2>), grid, blk, 0, ctx->stream, a);
-        else if (mode == FLOW_COARSE) hipLaunchKernelGGL((k_flow_iter_roles<5, 1, FLOW_COARSE>), grid, blk, 0, ctx->stream, a);
-        else if (mode == FLOW_FIELD) hipLaunchKernelGGL((k_flow_iter_roles<5, 1, FLOW_FIELD>), grid, blk, 0, ctx->stream, a);
-        else hipLaunchKernelGGL((k_flow_iter_roles<5, 1, FLOW_ZERO>), grid, blk, 0, ctx->stream, a);
+        const dim3 blk(FrGeom<5>::THREADS);
+        if (mode == FLOW_COARSE2) hipLaunchKernelGGL((k_flow_iter_roles<5, FLOW_COARSE2>), grid, blk, 0, ctx->stream, a);
+        else if (mode == FLOW_COARSE) hipLaunchKernelGGL((k_flow_iter_roles<5, FLOW_COARSE>), grid, blk, 0, ctx->stream, a);
+        else if (mode == FLOW_FIELD) hipLaunchKernelGGL((k_flow_iter_roles<5, FLOW_FIELD>), grid, blk, 0, ctx->stream, a);
+        else hipLaunchKernelGGL((k_flow_iter_roles<5, FLOW_ZERO>), grid, blk, 0, ctx->stream, a);
       } else {
-        const dim3 blk(FrGeom<4, 1>::THREADS);
-        if (mode == FLOW_COARSE2) hipLaunchKernelGGL((k_flow_iter_roles<4, 1, FLOW_COARSE2>), grid, blk, 0, ctx->stream, a);
-        else if (mode == FLOW_COARSE) hipLaunchKernelGGL((k_flow_iter_roles<4, 1, FLOW_COARSE>), grid, blk, 0, ctx->stream, a);
-        else if (mode == FLOW_FIELD) hipLaunchKernelGGL((k_flow_iter_roles<4, 1, FLOW_FIELD>), grid, blk, 0, ctx->stream, a);
-        else hipLaunchKernelGGL((k_flow_iter_roles<4, 1, FLOW_ZERO>), grid, blk, 0, ctx->stream, a);
+        const dim3 blk(FrGeom<4>::THREADS);
+        if (mode == FLOW_COARSE2) hipLaunchKernelGGL((k_flow_iter_roles<4, FLOW_COARSE2>), grid, blk, 0, ctx->stream, a);
+        else if (mode == FLOW_COARSE) hipLaunchKernelGGL((k_flow_iter_roles<4, FLOW_COARSE>), grid, blk, 0, ctx->stream, a);
+        else if (mode == FLOW_FIELD) hipLaunchKernelGGL((k_flow_iter_roles<4, FLOW_FIELD>), grid, blk, 0, ctx->stream, a);
+        else hipLaunchKernelGGL((k_flow_iter_roles<4, FLOW_ZERO>), grid, blk, 0, ctx->stream, a);
       }
       ST_HIP(ctx, hipGetLastError());
       return ST_OK;
     }
   }
-  static const int force_rows = getenv("ST_ITER_ROWS") ? atoi(getenv("ST_ITER_ROWS")) : 0;  // experiments
-  if (force_rows >= F3_ANCHOR && force_rows % F3_ANCHOR == 0 && force_rows < rows) rows = force_rows;
   a.rows_per_seg = rows;
   dim3 grid(strips, (a.h + rows - 1) / rows, n_pairs);
   st_timed t(ctx, ST_K_BLUR_UPDATE);
   const int mode = a.coarse ? (a.h == 2 * a.ch ? FLOW_COARSE2 : FLOW_COARSE) : (a.flow_in ? FLOW_FIELD : FLOW_ZERO);
-  if (mode == FLOW_COARSE2) hipLaunchKernelGGL((k_flow_iter3<7, 2, FLOW_COARSE2, ST_EXP_D>), grid, dim3(B2_T), 0, ctx->stream, a);
-  else if (mode == FLOW_COARSE) hipLaunchKernelGGL((k_flow_iter3<7, 2, FLOW_COARSE, ST_EXP_D>), grid, dim3(B2_T), 0, ctx->stream, a);
-  else if (mode == FLOW_FIELD) hipLaunchKernelGGL((k_flow_iter3<7, 2, FLOW_FIELD, ST_EXP_D>), grid, dim3(B2_T), 0, ctx->stream, a);
-  else hipLaunchKernelGGL((k_flow_iter3<7, 2, FLOW_ZERO, ST_EXP_D>), grid, dim3(B2_T), 0, ctx->stream, a);
+  if (mode == FLOW_COARSE2) hipLaunchKernelGGL((k_flow_iter3<FLOW_COARSE2>), grid, dim3(B2_T), 0, ctx->stream, a);
+  else if (mode == FLOW_COARSE) hipLaunchKernelGGL((k_flow_iter3<FLOW_COARSE>), grid, dim3(B2_T), 0, ctx->stream, a);
+  else if (mode == FLOW_FIELD) hipLaunchKernelGGL((k_flow_iter3<FLOW_FIELD>), grid, dim3(B2_T), 0, ctx->stream, a);
+  else hipLaunchKernelGGL((k_flow_iter3<FLOW_ZERO>), grid, dim3(B2_T), 0, ctx->stream, a);
   ST_HIP(ctx, hipGetLastError());
   return ST_OK;
 }
@@ -3322,7 +3177,7 @@ int launch_flow_iter(st_ctx* ctx, IterArgs a, int n_pairs) {
 // The fused iteration kernel applies to the reference's 15x15 window on frames whose pyramid
 // levels are at least 2x2; it needs two flow fields per pair instead of two matrix fields.
 bool fused_path(int h, int w, const st_fb_params& p) {
-  if (p.win_size != 15 || getenv("ST_UNFUSED")) return false;
+  if (p.win_size != 15) return false;
   const int levels = fb_levels(h, w, p);
   for (int k = 0; k <= levels; ++k) {
     LevelGeom g = fb_level_geom(h, w, p, k);
@@ -3421,8 +3276,7 @@ int farneback_pass(st_ctx* ctx, const uint8_t* const* frames, int nf, const int3
   }
   // Level 0 straight from the gray frames (ST_POLY_U8, read at st_ctx_create): the role-split pyramid leaves level 0 out and the
   // level-0 expansion evaluates the 3 x 3 blur itself -- large calls only (the single multi-level launch keeps its float source)
-  static const int single_max = getenv("ST_POLY_SINGLE_MAX") ? atoi(getenv("ST_POLY_SINGLE_MAX")) : 16;
-  const bool single = pyr1 && levels >= 1 && levels <= 3 && npairs <= single_max;
+  const bool single = pyr1 && levels >= 1 && levels <= 3 && npairs <= 16;
   const bool poly_u8 = pyr1 && !pyr_rgb && !single && ctx->poly_u8 && ctx->pyr_roles != 0 && geom[0].ksize == 3 && geom[0].sigma <= 0 &&
                        geom[0].lh == h && geom[0].lw == w && w >= 8;
   if (pyr1) ST_TRY(launch_pyr_fused(ctx, pyr_rgb ? nullptr : gray, d_frames, nf, h, w, p, imgs, poly_u8));
@@ -3430,8 +3284,7 @@ int farneback_pass(st_ctx* ctx, const uint8_t* const* frames, int nf, const int3
   // against the former arrangement -- level 0 on a second, low-priority stream beside the coarse levels' iterations --
   // at 1 / 2 / 4 / 8 pairs of 1080p per call: 292 / 444 / 731 / 1193 us per step against 308 / 458 / 744 / 1197: the
   // event record and wait of the second stream cost a launch's worth each, and the coarse iterations it overlapped with ran
-  // two to four times slower beside the level-0 expansion whatever the stream priority.  (ST_POLY_SINGLE_MAX: pairs up to
-  // which the single launch is used.)
+  // two to four times slower beside the level-0 expansion whatever the stream priority.  Up to 16 pairs per call.
   if (single) {
     int ks[4], nk = 0;
     for (int k = 0; k <= levels; ++k) ks[nk++] = k;

@@ -29,12 +29,11 @@ struct st_ctx {
   // -1 by total size (default), 0 never the tile kernel, 1 always.  The two kernels agree bit for
   // bit, so this is a scheduling switch only.
   int tile_mode = -1;
-  long long tile_px = 600000;
   bool poly_u8 = true;     // level-0 expansion straight from the gray frames (k_polyexp_u8), level 0 left out of the pyramid pass; ST_POLY_U8=0: float source
   bool fold_gray = false;  // ST_PYR_FOLD_GRAY=1: luma conversion inside the one-pass pyramid (slower; A/B switch)
   // role-split kernels (scheduling switches like tile_mode, read when the context is created; results do not depend on them):
   // ST_ITER_ROLES / ST_PYR_ROLES: -1 by launch size (default), 0 never, 1 always; ST_ROLES_NCW: 0 = by cost, 4 or 5 column waves
-  int roles_mode = -1, roles_ncw = 0, roles_rows = 0, pyr_roles = -1;
+  int roles_mode = -1, roles_ncw = 0, pyr_roles = -1;
   int conv_tile = -1;   // ST_CONV_TILE: 0 = bf16x3 convolutions always on the per-tap kernel (st_conv.hip)
   // Concurrent kernel instances (Scanner's pipeline_instances_per_node: K contexts of one process on one GPU, each call followed
   // by st_ctx_sync).  flow_busy: an OpticalFlow call of this context has been enqueued and not yet synchronised; flow_enter_ns:

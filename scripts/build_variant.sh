@@ -1,6 +1,6 @@
 #!/bin/bash
 # Experimental build of the HIP library with extra -D flags on st_farneback.hip:
-#   bash scripts/build_variant.sh <name> "-DST_EXP_NT=1 ..."   ->  scannertools_amd/lib_exp_<name>/libscannertools_hip.so
+#   bash scripts/build_variant.sh <name> "-DNAME=VALUE ..."   ->  scannertools_amd/lib_exp_<name>/libscannertools_hip.so
 # (select it with ST_HIP_LIB=<that path>; the directories are git-ignored and travel with gpurun)
 set -e
 name=$1; flags=$2

@@ -5,7 +5,7 @@ export GRAFT_REPO_ROOT="${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}"  
 cd "$GRAFT_REPO_ROOT"
 mkdir -p gpurun_out/abl
 # The .so files do not travel to the GPU box (.gpurunignore): the production library is built here first, and a variant given
-# as name=FLAGS (e.g. abl128=-DST_ABLATE=128) is built on the spot when its library is missing.
+# as name=FLAGS (e.g. trial=-DNAME=VALUE) is built on the spot when its library is missing.
 python -c "import __graft_entry__ as g; g.ensure_built()"
 for item in "$@"; do
   name="${item%%=*}"
