@@ -245,6 +245,25 @@ enum st_interpolation { ST_INTER_NEAREST = 0, ST_INTER_LINEAR = 1, ST_INTER_CUBI
 int st_resize_u8_batch(st_ctx* ctx, const uint8_t* const* frames_dev, int n, int h, int w, int channels,
                        int out_h, int out_w, int interpolation, uint8_t* const* out_dev);
 
+/* Montage: replaces the per-frame cv::resize(img, canvas(Rect(tw * x, th * y, tw, th)), Size(tw, th)) calls of
+ * MontageKernel::execute (scannertools_cpp/imgproc/montage_kernel_gpu.cpp; MontageArgs{num_frames = 1, target_width = 4,
+ * frames_per_row = 6}, scannertools_imgproc.proto).
+ * st_montage_geometry: MontageKernel::new_frame_info's geometry for frames of (frame_h, frame_w), evaluated as it does --
+ *   target_h = (i32)(target_width / (1.0 * frame_w) * frame_h), montage_w = frames_per_row * target_width,
+ *   montage_h = (i64)(ceil(num_frames / (1.0 * frames_per_row)) * target_h).  ST_ERR_INVALID for a non-positive argument,
+ *   a target_h below 1, a montage_w beyond int32 or a canvas (montage_h * montage_w * 3 bytes) beyond int64.  Host-only.
+ * st_montage_clear: zeroes a (montage_h, montage_w, 3) canvas on the context's stream (MontageKernel::reset).
+ * st_montage_u8c3_batch: resizes n dense (h, w, 3) U8 frames into tiles first_slot .. first_slot + n - 1 of a canvas whose
+ *   rows are 3 * montage_w bytes apart -- tile s at pixel ((s % frames_per_row) * target_w, (s / frames_per_row) * target_h)
+ *   -- in one launch, bit for bit what st_resize_u8_batch(..., ST_INTER_LINEAR, ...) gives for the same sizes (an equal
+ *   size is a copy, an exact 2 x 2 decimation the INTER_AREA mean).  Every other byte of the canvas is left as it is; the
+ *   caller sizes the canvas for the slots it names. */
+int st_montage_geometry(int frame_h, int frame_w, int64_t num_frames, int target_width, int frames_per_row, int* target_h,
+                        int64_t* montage_h, int* montage_w);
+int st_montage_clear(st_ctx* ctx, uint8_t* montage_dev, int64_t montage_h, int montage_w);
+int st_montage_u8c3_batch(st_ctx* ctx, const uint8_t* const* frames_dev, int n, int h, int w, uint8_t* montage_dev,
+                          int montage_w, int target_w, int target_h, int frames_per_row, int first_slot);
+
 /* ConvertColor: replaces the cv::cvtColor(img, out, code) call of ConvertColorKernel::execute
  * (scannertools_cpp/imgproc/convert_color_kernel.cpp:268-271) for U8 frames.  code takes
  * cv::ColorConversionCodes values; implemented: the ones below (the reference's name table at

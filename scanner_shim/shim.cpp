@@ -384,6 +384,16 @@ SHIM_EXPORT int stshim_op_info(const char* op, int* n_in, int* n_out, int* out_i
   return 0;
 }
 
+// The op's state declaration: unbounded_state() (every row depends on all earlier rows of the stream: a request for
+// any rows runs the stream from row 0) and bounded_state(warmup) (-1 when not declared).
+SHIM_EXPORT int stshim_op_state(const char* op, int* unbounded, int* bounded_warmup) {
+  const OpRegistration* o = find_op(op);
+  if (!o) return 1;
+  if (unbounded) *unbounded = o->unbounded_state;
+  if (bounded_warmup) *bounded_warmup = o->bounded_state;
+  return 0;
+}
+
 SHIM_EXPORT void* stshim_kernel_create(const char* op, int device_type, int device_id, const uint8_t* args,
                                        size_t n_args, char* err, size_t err_len) {
   const KernelRegistration* found = nullptr;

@@ -121,6 +121,9 @@ SIGNATURES = {
     "st_draw_flow_batch": (_i, [_vp, _c.POINTER(_vp), _c.POINTER(_vp), _i, _i, _i, _c.POINTER(_vp)]),
     "st_box_blur_u8c3_batch": (_i, [_vp, _c.POINTER(_vp), _i, _i, _i, _i, _c.POINTER(_vp)]),
     "st_resize_u8_batch": (_i, [_vp, _c.POINTER(_vp), _i, _i, _i, _i, _i, _i, _i, _c.POINTER(_vp)]),
+    "st_montage_geometry": (_i, [_i, _i, _c.c_int64, _i, _i, _c.POINTER(_i), _c.POINTER(_c.c_int64), _c.POINTER(_i)]),
+    "st_montage_clear": (_i, [_vp, _vp, _c.c_int64, _i]),
+    "st_montage_u8c3_batch": (_i, [_vp, _c.POINTER(_vp), _i, _i, _i, _vp, _i, _i, _i, _i, _i]),
     "st_cvt_color_out_channels": (_i, [_i, _i]),
     "st_cvt_color_out_shape": (_i, [_i, _i, _i, _i, _c.POINTER(_i), _c.POINTER(_i), _c.POINTER(_i)]),
     "st_cvt_color_u8_batch": (_i, [_vp, _c.POINTER(_vp), _i, _i, _i, _i, _i, _i, _c.POINTER(_vp)]),

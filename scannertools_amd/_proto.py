@@ -18,10 +18,10 @@ def _varint(v):
 
 
 def encode(fields):
-    """fields: iterable of (number, kind, value), kind in int32 / bool / float / string."""
+    """fields: iterable of (number, kind, value), kind in int32 / int64 / bool / float / string."""
     out = bytearray()
     for number, kind, value in fields:
-        if kind in ("int32", "bool"):
+        if kind in ("int32", "int64", "bool"):
             if int(value) == 0:
                 continue
             out += _varint(number << 3 | 0) + _varint(int(value))

@@ -15,12 +15,17 @@
 // INTER_AREA (integer cells, fractional cells in float, cell-aligned bilinear weights when enlarging); arithmetic as restated in
 // oracle/oracle.c (orc_resize_u8), one thread per output pixel, weights recomputed per thread.
 //
+// Montage replaces the per-frame cv::resize calls of MontageKernel::execute
+// (/root/reference/scannertools/scannertools_cpp/imgproc/montage_kernel_gpu.cpp): the frames of one execute() go into their
+// tiles of the canvas in one launch, through the INTER_LINEAR kernels of Resize with a tile origin and the canvas's pitch.
+//
 // ConvertColor replaces the cv::cvtColor call of ConvertColorKernel::execute
 // (/root/reference/scannertools/scannertools_cpp/imgproc/convert_color_kernel.cpp:268-271) for the
 // 8-bit codes BGR2RGB/RGB2BGR, BGR2GRAY, RGB2GRAY, GRAY2BGR/GRAY2RGB, BGR/RGB <-> YCrCb and BGR2HSV
 // (OpenCV's integer tables, oracle/oracle.c orc_cvt_color_u8).
 #include <cfloat>
 #include <cmath>
+#include <cstdint>
 #include <cstring>
 #include <vector>
 
@@ -221,6 +226,27 @@ struct ResizeArgsK {
   const int* xofs; const short* ialpha;
   const int* yofs; const short* ibeta;
 };
+
+// Montage: the destination of frame z is tile first_slot + z of one (montage_h, montage_w, 3) canvas -- tile (x, y) =
+// (slot % per_row, slot / per_row) at pixel (x * dw, y * dh), rows `pitch` = 3 * montage_w bytes apart -- instead of
+// dense (dh, dw, 3) frames.  The kernels that serve both take the argument type as a template parameter and address
+// their output through rs_dst_base / rs_dst_px, which for ResizeArgsK are the expressions they always used.
+struct ResizeTileArgsK : ResizeArgsK {
+  uint8_t* canvas;
+  size_t pitch;
+  int first_slot, per_row;
+};
+__device__ __forceinline__ uint8_t* rs_dst_base(const ResizeArgsK& a, unsigned z) { return st_gl(a.dst[z]); }
+__device__ __forceinline__ uint8_t* rs_dst_px(const ResizeArgsK& a, uint8_t* base, int dy, int dx) {
+  return base + ((size_t)dy * a.dw + dx) * 3;
+}
+__device__ __forceinline__ uint8_t* rs_dst_base(const ResizeTileArgsK& a, unsigned z) {
+  const int slot = a.first_slot + (int)z;
+  return st_gl(a.canvas) + (size_t)(slot / a.per_row) * a.dh * a.pitch + (size_t)(slot % a.per_row) * a.dw * 3;
+}
+__device__ __forceinline__ uint8_t* rs_dst_px(const ResizeTileArgsK& a, uint8_t* base, int dy, int dx) {
+  return base + (size_t)dy * a.pitch + (size_t)dx * 3;
+}
 
 // saturate_cast<short>(float): cvRound = round half to even, then saturation
 __device__ __forceinline__ int rs_coef(float v) {
@@ -424,13 +450,13 @@ __global__ __launch_bounds__(256) void k_resize_u8(ResizeArgsK a) {
 // (Rows of 3 * dw bytes start at any byte: the stores are unaligned dwords; a row's last, partial group goes out bytewise.)
 constexpr int RL_ROWS = 4;
 // AREA_UP: INTER_AREA when an axis is enlarged = the same two-tap filter with cell-aligned weights (RS_LINEAR_AREA)
-template <bool AREA_UP>
-__global__ __launch_bounds__(256) void k_resize_linear_c3_v4(ResizeArgsK a) {
+template <bool AREA_UP, class A>
+__global__ __launch_bounds__(256) void k_resize_linear_c3_v4(A a) {
   const int g = blockIdx.x * 256 + threadIdx.x;  // group of 4 output columns
   if (4 * g >= a.dw) return;
   const int npx = min(4, a.dw - 4 * g);          // the last group of a row may be partial
   const uint8_t* __restrict__ src = st_gl(a.src[blockIdx.z]);
-  unsigned* __restrict__ dst = reinterpret_cast<unsigned*>(st_gl(a.dst[blockIdx.z]));
+  unsigned* __restrict__ dst = reinterpret_cast<unsigned*>(rs_dst_base(a, blockIdx.z));
   const size_t srow = (size_t)a.sw * 3;
   int sxo[4], a0[4], a1[4];
   bool two[4], wide[4];
@@ -501,7 +527,7 @@ __global__ __launch_bounds__(256) void k_resize_linear_c3_v4(ResizeArgsK a) {
         out[(3 * p + c) >> 2] |= v << (8 * ((3 * p + c) & 3));
       }
     }
-    uint8_t* ob = reinterpret_cast<uint8_t*>(dst) + ((size_t)dy * a.dw + 4 * g) * 3;  // any byte when 3 * dw % 4 != 0
+    uint8_t* ob = rs_dst_px(a, reinterpret_cast<uint8_t*>(dst), dy, 4 * g);  // any byte when 3 * dw % 4 != 0
     if (npx == 4) {
       u32u* o = reinterpret_cast<u32u*>(ob);
       o[0] = out[0]; o[1] = out[1]; o[2] = out[2];
@@ -514,12 +540,13 @@ __global__ __launch_bounds__(256) void k_resize_linear_c3_v4(ResizeArgsK a) {
 // The exact 2 x 2 decimation (INTER_AREA, and INTER_LINEAR's reroute to it) on 3-channel frames: four output pixels per
 // thread = 24 contiguous source bytes in each of two rows (six unaligned dword loads per row instead of 24 byte loads),
 // twelve output bytes as three unaligned dword stores.  (v00 + v01 + v10 + v11 + 2) >> 2 as in k_resize_u8.
-__global__ __launch_bounds__(256) void k_resize_area2_c3_v4(ResizeArgsK a) {
+template <class A>
+__global__ __launch_bounds__(256) void k_resize_area2_c3_v4(A a) {
   typedef unsigned u32u __attribute__((aligned(1)));
   const int g = blockIdx.x * 256 + threadIdx.x, dy = blockIdx.y;
   if (4 * g >= a.dw) return;
   const uint8_t* __restrict__ src = st_gl(a.src[blockIdx.z]);
-  uint8_t* ob = st_gl(a.dst[blockIdx.z]) + ((size_t)dy * a.dw + 4 * g) * 3;
+  uint8_t* ob = rs_dst_px(a, rs_dst_base(a, blockIdx.z), dy, 4 * g);
   const size_t srow = (size_t)a.sw * 3;
   const uint8_t* S0 = src + (size_t)(2 * dy) * srow + (size_t)(8 * g) * 3;
   const uint8_t* S1 = S0 + srow;
@@ -544,6 +571,14 @@ __global__ __launch_bounds__(256) void k_resize_area2_c3_v4(ResizeArgsK a) {
       for (int c = 0; c < 3; ++c)
         ob[3 * p + c] = (uint8_t)((S0[6 * p + c] + S0[6 * p + 3 + c] + S1[6 * p + c] + S1[6 * p + 3 + c] + 2) >> 2);
   }
+}
+
+// Montage tile of a frame that already has the tile's size (cv::resize copies): one thread per byte of a tile row.
+__global__ __launch_bounds__(256) void k_montage_copy_c3(ResizeTileArgsK a) {
+  const int x = blockIdx.x * 256 + threadIdx.x, dy = blockIdx.y;
+  if (x >= 3 * a.dw) return;
+  const uint8_t* __restrict__ src = st_gl(a.src[blockIdx.z]);
+  rs_dst_px(a, rs_dst_base(a, blockIdx.z), dy, 0)[x] = src[(size_t)dy * a.sw * 3 + x];
 }
 
 // INTER_NEAREST and INTER_CUBIC on 3-channel frames with the same recipe as k_resize_linear_c3_v4: four output columns x
@@ -1387,6 +1422,25 @@ ST_EXPORT int st_box_blur_u8c3_batch(st_ctx* ctx, const uint8_t* const* frames_d
 }
 
 namespace {
+// cv::resize's scale factors for (h, w) -> (out_h, out_w) and the path it takes: an equal size is a copy, an exact 2 x 2
+// decimation under INTER_LINEAR or INTER_AREA the mean of four (st_resize_u8_batch and st_montage_u8c3_batch share this)
+void rs_plan(ResizeArgsK* a, int h, int w, int channels, int out_h, int out_w, int interpolation) {
+  a->sh = h; a->sw = w; a->dh = out_h; a->dw = out_w; a->cn = channels;
+  const double inv_sx = (double)out_w / w, inv_sy = (double)out_h / h;
+  a->scale_x = 1. / inv_sx; a->scale_y = 1. / inv_sy;
+  a->inv_scale_x = inv_sx; a->inv_scale_y = inv_sy;
+  a->iscale_x = (int)lrint(a->scale_x); a->iscale_y = (int)lrint(a->scale_y);
+  const bool area_fast = fabs(a->scale_x - a->iscale_x) < DBL_EPSILON && fabs(a->scale_y - a->iscale_y) < DBL_EPSILON;
+  if (h == out_h && w == out_w) a->mode = RS_COPY;
+  else if (interpolation == ST_INTER_NEAREST) a->mode = RS_NEAREST;
+  else if (interpolation == ST_INTER_CUBIC) a->mode = RS_CUBIC;
+  else if (interpolation == ST_INTER_LANCZOS4) a->mode = RS_LANCZOS4;
+  else if ((interpolation == ST_INTER_LINEAR || interpolation == ST_INTER_AREA) && area_fast && a->iscale_x == 2 && a->iscale_y == 2) a->mode = RS_AREA2;
+  else if (interpolation == ST_INTER_LINEAR) a->mode = RS_LINEAR;
+  else if (a->scale_x >= 1 && a->scale_y >= 1) a->mode = area_fast ? RS_AREA_INT : RS_AREA;
+  else a->mode = RS_LINEAR_AREA;
+}
+
 // cv::interpolateLanczos4 (imgproc/src/resize.cpp)
 void lanczos4_coeffs(float x, float* coeffs) {
   static const double s45 = 0.70710678118654752440084436210485;
@@ -1446,20 +1500,7 @@ ST_EXPORT int st_resize_u8_batch(st_ctx* ctx, const uint8_t* const* frames_dev, 
   ST_HIP(ctx, hipMemcpyAsync(d_dst, out_dev, sizeof(void*) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
   ResizeArgsK a;
   memset(&a, 0, sizeof(a));
-  a.sh = h; a.sw = w; a.dh = out_h; a.dw = out_w; a.cn = channels;
-  const double inv_sx = (double)out_w / w, inv_sy = (double)out_h / h;
-  a.scale_x = 1. / inv_sx; a.scale_y = 1. / inv_sy;
-  a.inv_scale_x = inv_sx; a.inv_scale_y = inv_sy;
-  a.iscale_x = (int)lrint(a.scale_x); a.iscale_y = (int)lrint(a.scale_y);
-  const bool area_fast = fabs(a.scale_x - a.iscale_x) < DBL_EPSILON && fabs(a.scale_y - a.iscale_y) < DBL_EPSILON;
-  if (h == out_h && w == out_w) a.mode = RS_COPY;
-  else if (interpolation == ST_INTER_NEAREST) a.mode = RS_NEAREST;
-  else if (interpolation == ST_INTER_CUBIC) a.mode = RS_CUBIC;
-  else if (interpolation == ST_INTER_LANCZOS4) a.mode = RS_LANCZOS4;
-  else if ((interpolation == ST_INTER_LINEAR || interpolation == ST_INTER_AREA) && area_fast && a.iscale_x == 2 && a.iscale_y == 2) a.mode = RS_AREA2;
-  else if (interpolation == ST_INTER_LINEAR) a.mode = RS_LINEAR;
-  else if (a.scale_x >= 1 && a.scale_y >= 1) a.mode = area_fast ? RS_AREA_INT : RS_AREA;
-  else a.mode = RS_LINEAR_AREA;
+  rs_plan(&a, h, w, channels, out_h, out_w, interpolation);
   std::vector<int> hx, hy;
   std::vector<short> ha, hb;
   if (a.mode == RS_LANCZOS4) {
@@ -1484,7 +1525,7 @@ ST_EXPORT int st_resize_u8_batch(st_ctx* ctx, const uint8_t* const* frames_dev, 
     st_timed t(ctx, ST_K_RESIZE);
     const bool fast = a.mode == RS_LINEAR && channels == 3;
     if (a.mode == RS_AREA2 && channels == 3)
-      hipLaunchKernelGGL(k_resize_area2_c3_v4, dim3(((out_w + 3) / 4 + 255) / 256, out_h, nf), dim3(256), 0, ctx->stream, a);
+      hipLaunchKernelGGL(k_resize_area2_c3_v4<ResizeArgsK>, dim3(((out_w + 3) / 4 + 255) / 256, out_h, nf), dim3(256), 0, ctx->stream, a);
     else if (a.mode == RS_AREA && channels == 3 && a.scale_x <= 6) {  // a cell spans at most scale + 2 source columns
       const dim3 gr(((out_w + 3) / 4 + 255) / 256, (out_h + RL_ROWS - 1) / RL_ROWS, nf);
       if (a.scale_x <= 2) hipLaunchKernelGGL(k_resize_area_c3_v4<4>, gr, dim3(256), 0, ctx->stream, a);
@@ -1503,11 +1544,78 @@ ST_EXPORT int st_resize_u8_batch(st_ctx* ctx, const uint8_t* const* frames_dev, 
     else if (a.mode == RS_CUBIC && channels == 3)
       hipLaunchKernelGGL(k_resize_cubic_c3_v4, dim3(((out_w + 3) / 4 + 255) / 256, (out_h + RL_ROWS - 1) / RL_ROWS, nf), dim3(256), 0, ctx->stream, a);
     else if (a.mode == RS_LINEAR_AREA && channels == 3)
-      hipLaunchKernelGGL(k_resize_linear_c3_v4<true>, dim3(((out_w + 3) / 4 + 255) / 256, (out_h + RL_ROWS - 1) / RL_ROWS, nf), dim3(256), 0, ctx->stream, a);
+      hipLaunchKernelGGL((k_resize_linear_c3_v4<true, ResizeArgsK>), dim3(((out_w + 3) / 4 + 255) / 256, (out_h + RL_ROWS - 1) / RL_ROWS, nf), dim3(256), 0, ctx->stream, a);
     else if (fast)
-      hipLaunchKernelGGL(k_resize_linear_c3_v4<false>, dim3(((out_w + 3) / 4 + 255) / 256, (out_h + RL_ROWS - 1) / RL_ROWS, nf), dim3(256), 0, ctx->stream, a);
+      hipLaunchKernelGGL((k_resize_linear_c3_v4<false, ResizeArgsK>), dim3(((out_w + 3) / 4 + 255) / 256, (out_h + RL_ROWS - 1) / RL_ROWS, nf), dim3(256), 0, ctx->stream, a);
     else
       hipLaunchKernelGGL(k_resize_u8, dim3((out_w + 255) / 256, out_h, nf), dim3(256), 0, ctx->stream, a);
+    ST_HIP(ctx, hipGetLastError());
+  }
+  return ST_OK;
+}
+
+ST_EXPORT int st_montage_geometry(int frame_h, int frame_w, int64_t num_frames, int target_width, int frames_per_row,
+                                  int* target_h, int64_t* montage_h, int* montage_w) {
+  if (frame_h < 1 || frame_w < 1 || num_frames < 1 || target_width < 1 || frames_per_row < 1) return ST_ERR_INVALID;
+  // MontageKernel::new_frame_info, in its order of double operations and truncations
+  const double th = target_width / (1.0 * frame_w) * frame_h;
+  if (!(th >= 1.0) || th >= 2147483648.0) return ST_ERR_INVALID;
+  const int th_i = (int)th;
+  const long long mw = (long long)frames_per_row * target_width;
+  if (mw > INT32_MAX) return ST_ERR_INVALID;
+  const double mh = std::ceil(num_frames / (1.0 * frames_per_row)) * th_i;
+  if (!(mh < 9223372036854775808.0)) return ST_ERR_INVALID;
+  const int64_t mh_i = (int64_t)mh;
+  if (mh_i > INT64_MAX / (3 * mw)) return ST_ERR_INVALID;  // the canvas's byte count must fit int64
+  if (target_h) *target_h = th_i;
+  if (montage_h) *montage_h = mh_i;
+  if (montage_w) *montage_w = (int)mw;
+  return ST_OK;
+}
+
+ST_EXPORT int st_montage_clear(st_ctx* ctx, uint8_t* montage_dev, int64_t montage_h, int montage_w) {
+  ST_TRY(st_enter(ctx));
+  if (!montage_dev || montage_h < 1 || montage_w < 1 || montage_h > INT64_MAX / (3 * (int64_t)montage_w))
+    return st_set_error(ctx, ST_ERR_INVALID, "montage: bad canvas (%lld x %d)", (long long)montage_h, montage_w);
+  ST_HIP(ctx, hipMemsetAsync(montage_dev, 0, (size_t)montage_h * montage_w * 3, ctx->stream));
+  return ST_OK;
+}
+
+ST_EXPORT int st_montage_u8c3_batch(st_ctx* ctx, const uint8_t* const* frames_dev, int n, int h, int w, uint8_t* montage_dev,
+                                    int montage_w, int target_w, int target_h, int frames_per_row, int first_slot) {
+  ST_TRY(st_enter(ctx));
+  if (n < 0 || h <= 0 || w <= 0 || target_w <= 0 || target_h <= 0 || frames_per_row < 1 || first_slot < 0 ||
+      (long long)h * w > 200000000LL || (long long)target_h * target_w > 200000000LL ||
+      (long long)frames_per_row * target_w > montage_w || (long long)first_slot + n > INT32_MAX)
+    return st_set_error(ctx, ST_ERR_INVALID, "montage: bad arguments (n=%d %dx%d -> %dx%d tiles, %d per row of %d px, slot %d)",
+                        n, h, w, target_h, target_w, frames_per_row, montage_w, first_slot);
+  if (target_h > 65535) return st_set_error(ctx, ST_ERR_UNSUPPORTED, "montage: tiles taller than 65535 rows");
+  if (n == 0) return ST_OK;
+  if (!frames_dev || !montage_dev) return st_set_error(ctx, ST_ERR_INVALID, "montage: null argument");
+  for (int i = 0; i < n; ++i)
+    if (!frames_dev[i]) return st_set_error(ctx, ST_ERR_INVALID, "montage: row %d is null", i);
+  const size_t tb = st_align_up(sizeof(void*) * (size_t)n);
+  ST_TRY(st_ws_reserve(ctx, tb));
+  const uint8_t** d_src = (const uint8_t**)st_ws_alloc(ctx, tb);
+  ST_HIP(ctx, hipMemcpyAsync(d_src, frames_dev, sizeof(void*) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+  ResizeTileArgsK a;
+  memset(&a, 0, sizeof(a));
+  rs_plan(&a, h, w, 3, target_h, target_w, ST_INTER_LINEAR);
+  a.canvas = montage_dev;
+  a.pitch = (size_t)montage_w * 3;
+  a.per_row = frames_per_row;
+  for (int f0 = 0; f0 < n; f0 += 65535) {  // one launch up to 65535 frames
+    const int nf = n - f0 < 65535 ? n - f0 : 65535;
+    a.src = d_src + f0;
+    a.first_slot = first_slot + f0;
+    st_timed t(ctx, ST_K_RESIZE);
+    if (a.mode == RS_COPY)
+      hipLaunchKernelGGL(k_montage_copy_c3, dim3((3 * target_w + 255) / 256, target_h, nf), dim3(256), 0, ctx->stream, a);
+    else if (a.mode == RS_AREA2)
+      hipLaunchKernelGGL(k_resize_area2_c3_v4<ResizeTileArgsK>, dim3(((target_w + 3) / 4 + 255) / 256, target_h, nf), dim3(256), 0, ctx->stream, a);
+    else
+      hipLaunchKernelGGL((k_resize_linear_c3_v4<false, ResizeTileArgsK>), dim3(((target_w + 3) / 4 + 255) / 256, (target_h + RL_ROWS - 1) / RL_ROWS, nf),
+                         dim3(256), 0, ctx->stream, a);
     ST_HIP(ctx, hipGetLastError());
   }
   return ST_OK;

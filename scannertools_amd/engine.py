@@ -12,12 +12,13 @@ installable here, so this module reproduces exactly that surface for in-memory f
     out = NamedStream(sc, 'hist'); sc.run(sc.io.Output(hist, [out]), PerfParams.estimate())
     next(out.load())
 
-C++ ops (``Histogram``, ``OpticalFlow``, ``FlowHistogram``, ``Blur``, ``Resize``, ``ConvertColor``) are looked up in the kernel registry of
+C++ ops (``Histogram``, ``OpticalFlow``, ``FlowHistogram``, ``Blur``, ``Resize``, ``ConvertColor``, ``Montage``) are looked up in the kernel registry of
 ``libscannertools_imgproc.so`` and executed by its mini engine (scanner_shim/shim.cpp): the same
 ``execute()`` bodies a real Scanner worker would call.  Python ops (``ShotBoundaries``, ``DrawFlow``) are the
 functions of this package.  What is deliberately absent: the database, video decode, the
 master/worker runtime, scheduling.
 """
+import copy
 import ctypes
 import os
 
@@ -76,6 +77,7 @@ def _load_op_library(path):
         L.stshim_kernel_info.argtypes = [ci, ctypes.c_char_p, ci, ctypes.POINTER(ci), ctypes.POINTER(ci), ctypes.POINTER(ci)]
         L.stshim_op_info.argtypes = [ctypes.c_char_p, ctypes.POINTER(ci), ctypes.POINTER(ci), ctypes.POINTER(ci),
                                      ctypes.POINTER(ci), ci, ctypes.POINTER(ci)]
+        L.stshim_op_state.argtypes = [ctypes.c_char_p, ctypes.POINTER(ci), ctypes.POINTER(ci)]
         L.stshim_kernel_create.restype = vp
         L.stshim_kernel_create.argtypes = [ctypes.c_char_p, ci, ci, ctypes.c_char_p, sz, ctypes.c_char_p, sz]
         L.stshim_kernel_destroy.argtypes = [vp]
@@ -151,8 +153,29 @@ def op_info(name):
     st = (ctypes.c_int * 16)()
     if L.stshim_op_info(name.encode(), ctypes.byref(n_in), ctypes.byref(n_out), ctypes.byref(isf), st, 16, ctypes.byref(ns)):
         return None
+    unbounded, warmup = ctypes.c_int(), ctypes.c_int()
+    if L.stshim_op_state(name.encode(), ctypes.byref(unbounded), ctypes.byref(warmup)):
+        return None
     return {"inputs": n_in.value, "outputs": n_out.value, "frame_output": bool(isf.value),
-            "stencil": list(st[:ns.value]) or [0]}
+            "stencil": list(st[:ns.value]) or [0], "unbounded_state": bool(unbounded.value)}
+
+
+def plan_runs(idx, unbounded=False):
+    """The engine streams that compute the requested rows `idx` (sorted) of an op: [(first, last)] output rows per
+    stream, each run on one kernel instance in order (a stencil only widens the input rows a stream reads, see
+    _CppOpNode.rows).  An op without state gets one stream per contiguous run of requested rows.  An op with unbounded
+    state (Montage) gets Scanner's semantics: every row depends on all rows before it, so any request runs rows
+    0 .. max(idx) as one stream."""
+    if not idx:
+        return []
+    if unbounded:
+        return [(0, max(idx))]
+    runs, start = [], 0
+    for i in range(1, len(idx) + 1):
+        if i == len(idx) or idx[i] != idx[i - 1] + 1:
+            runs.append((idx[start], idx[i - 1]))
+            start = i
+    return runs
 
 
 # ---------------------------------------------------------------------------------------------
@@ -208,6 +231,7 @@ class _CppOpNode(_Node):
         self.batch = int(batch) if batch else 1
         info = op_info(name)
         self.stencil = list(stencil) if stencil is not None else info["stencil"]
+        self.unbounded = info["unbounded_state"]
         self.args = args or b""
 
     def length(self):
@@ -227,13 +251,8 @@ class _CppOpNode(_Node):
         out = {}
         try:
             smin, smax = min(self.stencil + [0]), max(self.stencil + [0])
-            # contiguous runs of requested rows -> one engine stream each
-            runs, start = [], 0
-            for i in range(1, len(idx) + 1):
-                if i == len(idx) or idx[i] != idx[i - 1] + 1:
-                    runs.append((idx[start], idx[i - 1]))
-                    start = i
-            for a, b in runs:
+            wanted = set(idx)
+            for a, b in plan_runs(idx, self.unbounded):
                 # input rows this run touches; windows that reach outside the stream clamp to its
                 # edges, which is also what the engine does at the edges of the sub-stream
                 lo = max(0, a + smin)
@@ -265,8 +284,10 @@ class _CppOpNode(_Node):
                 try:
                     ncols = L.stshim_outputs_columns(res)
                     for r in range(a, b + 1):
+                        if r not in wanted:
+                            continue   # a row an op with state had to compute on the way
                         # ops with several output columns (CPM2) yield a tuple per row; _CppOpColumn picks one
-                        out[r] = self._fetch(L, res, r - lo) if ncols == 1 else tuple(self._fetch(L, res, r - lo, c) for c in range(ncols))
+                        out[r] = self._row(L, res, r - lo, r, ncols)
                 finally:
                     L.stshim_outputs_free(res)
             # what the kernel instance recorded through its Scanner Profiler (caffe_kernel.cpp:387, cpm2_input_kernel_gpu.cpp:154)
@@ -280,6 +301,10 @@ class _CppOpNode(_Node):
         finally:
             L.stshim_kernel_destroy(k)
         return [out[r] for r in idx]
+
+    def _row(self, L, res, i, r, ncols):
+        """Output row r (index i of the engine's outputs) on the host."""
+        return self._fetch(L, res, i) if ncols == 1 else tuple(self._fetch(L, res, i, c) for c in range(ncols))
 
     @staticmethod
     def _fetch(L, res, i, col=0):
@@ -298,6 +323,59 @@ class _CppOpNode(_Node):
         if L.stshim_output_copy_col(res, col, i, buf, size.value):
             raise RuntimeError("copying output row %d failed" % i)
         return buf.raw
+
+
+class _FramesNode(_Node):
+    """Rows fetched once, standing in for the node that produced them."""
+
+    def __init__(self, frames):
+        self.frames = frames
+
+    def length(self):
+        return len(self.frames)
+
+    def rows(self, idx):
+        return [self.frames[i] for i in idx]
+
+
+class _MontageNode(_CppOpNode):
+    """Montage (montage_kernel_gpu.cpp): an op with unbounded state.  What the kernel classes can only meet inside execute()
+    -- a stream longer than num_frames, frames that are not (h, w, 3) uint8, a tile height below 1 -- is a ValueError here,
+    before any kernel instance exists.  The rows before the last carry no canvas (their contents are unspecified in the
+    reference); they come back as a read-only zero view of the canvas's shape instead of one canvas-sized copy each."""
+
+    def __init__(self, client, parent, device, batch, num_frames, target_width, frames_per_row, args):
+        super().__init__(client, "Montage", parent, device, batch, None, args)
+        self.num_frames, self.target_width, self.frames_per_row = int(num_frames), int(target_width), int(frames_per_row)
+
+    def rows(self, idx):
+        import torch
+        if not idx:
+            return []
+        n = self.parent.length()
+        if n > self.num_frames:
+            raise ValueError("Montage: the input stream has %d rows, more than num_frames = %d" % (n, self.num_frames))
+        frames = self.parent.rows(list(range(max(idx) + 1)))
+        shape = tuple(frames[0].shape)
+        for i, f in enumerate(frames):
+            if len(f.shape) != 3 or f.shape[2] != 3 or f.dtype not in (np.uint8, torch.uint8):
+                raise ValueError("Montage: frame %d is %s %s, not (h, w, 3) uint8" % (i, tuple(f.shape), f.dtype))
+            if tuple(f.shape) != shape:
+                raise ValueError("Montage: frame %d is %s, frame 0 %s: one stream, one frame size" % (i, tuple(f.shape), shape))
+        h, w = shape[0], shape[1]
+        if int(self.target_width / (1.0 * w) * h) < 1:   # MontageKernel::new_frame_info's target_height
+            raise ValueError("Montage: %dx%d frames at target_width %d give tiles less than one row high" % (w, h, self.target_width))
+        node = copy.copy(self)
+        node.parent = _FramesNode(frames)
+        return _CppOpNode.rows(node, idx)
+
+    def _row(self, L, res, i, r, ncols):
+        if r == self.num_frames - 1:
+            return self._fetch(L, res, i)
+        shape = (ctypes.c_int * 3)()
+        if L.stshim_output_get_col(res, 0, i, None, None, None, shape, None):
+            raise RuntimeError("missing output row %d" % i)
+        return np.broadcast_to(np.zeros((), np.uint8), (shape[0], shape[1], shape[2]))
 
 
 class _CppOpColumn(_Node):
@@ -622,6 +700,15 @@ class _Ops:
         from . import _proto
         return _CppOpNode(self.sc, "ConvertColor", frame, device, batch, None, _proto.encode([(1, "string", conversion)]))
 
+    def Montage(self, frame, num_frames, target_width, frames_per_row, device=None, batch=None):
+        """sc.ops.Montage(frame=..., num_frames=..., target_width=..., frames_per_row=...): frame k of the stream resized to
+        target_width (height in proportion) into tile (k % frames_per_row, k / frames_per_row) of a zeroed canvas, which
+        the row of frame num_frames - 1 carries (MontageArgs, scannertools_imgproc.proto; montage_kernel_gpu.cpp).  A
+        shorter stream yields no canvas, as in the reference."""
+        from . import _proto
+        args = _proto.encode([(1, "int64", int(num_frames)), (4, "int32", int(target_width)), (6, "int32", int(frames_per_row))])
+        return _MontageNode(self.sc, frame, device, batch, num_frames, target_width, frames_per_row, args)
+
     def FlowHistogram(self, flow, device=None, batch=None):
         """db.ops.FlowHistogram(flow=flow, device=DeviceType.CPU) (old/histograms.py:74-77)."""
         node = _CppOpNode(self.sc, "FlowHistogram", flow, device, batch, None, b"")
@@ -731,6 +818,11 @@ class Client:
                 if s.name in self._tables and cache_mode == CacheMode.Ignore:
                     continue
                 self._tables[s.name] = (rows, reader)
+
+    def live_buffers(self):
+        """Buffers the engine holds on the host and on the devices (scanner_shim/shim.cpp new_buffer / delete_buffer)."""
+        L = _imgproc()
+        return L.stshim_live_buffers(DeviceType.CPU) + L.stshim_live_buffers(DeviceType.GPU)
 
     def live_device_buffers(self):
         return _imgproc().stshim_live_buffers(DeviceType.GPU)

@@ -258,6 +258,34 @@ class HipContext:
         self._check(self._L.st_resize_u8_batch(self._h, tf, n, h, w, c, int(height), int(width), int(interpolation), to))
         return out
 
+    def montage(self, frames, canvas, target_width, target_height, frames_per_row, first_slot=0):
+        """Montage op's tile writes (montage_kernel_gpu.cpp): (n,h,w,3) uint8 frames (a tensor or a list of (h,w,3) tensors)
+        resized INTER_LINEAR to (target_height, target_width) into tiles first_slot .. first_slot+n-1 of `canvas`, a
+        (montage_h, montage_w, 3) uint8 tensor, tile s at ((s % frames_per_row) * target_width, (s // frames_per_row) *
+        target_height).  One launch; the rest of the canvas is left as it is.  Returns canvas."""
+        self._bind()
+        fr = list(frames) if isinstance(frames, (list, tuple)) else list(frames.unbind(0))
+        _require_cuda(canvas, torch.uint8, "canvas", self.device)
+        if canvas.dim() != 3 or canvas.shape[2] != 3 or not canvas.is_contiguous():
+            raise ValueError("canvas must be a contiguous (montage_h, montage_w, 3) tensor")
+        n = len(fr)
+        if n == 0:
+            return canvas
+        h, w, c = fr[0].shape
+        for f in fr:
+            _require_cuda(f, torch.uint8, "frame", self.device)
+            if tuple(f.shape) != (h, w, 3):
+                raise ValueError("all frames must have the same (h,w,3) shape")
+        last = int(first_slot) + n - 1
+        if (frames_per_row * target_width > canvas.shape[1] or
+                (last // frames_per_row + 1) * target_height > canvas.shape[0]):
+            raise ValueError("tiles %d..%d of %dx%d do not fit a %dx%d canvas" % (first_slot, last, target_width, target_height,
+                                                                                  canvas.shape[1], canvas.shape[0]))
+        tf = (ctypes.c_void_p * n)(*[f.data_ptr() for f in fr])
+        self._check(self._L.st_montage_u8c3_batch(self._h, tf, n, h, w, canvas.data_ptr(), int(canvas.shape[1]), int(target_width),
+                                                  int(target_height), int(frames_per_row), int(first_slot)))
+        return canvas
+
     def cvt_color(self, frames, code, gray_bits=15, out=None):
         """ConvertColor op (convert_color_kernel.cpp:268-271): cv::cvtColor on (n,h,w,c) uint8 frames;
         ``code`` is a cv::ColorConversionCodes value or one of the names in _native.COLOR_CODES."""
