@@ -245,7 +245,8 @@ class HipContext:
         fr = list(frames) if isinstance(frames, (list, tuple)) else list(frames.unbind(0))
         n = len(fr)
         if n == 0:
-            return torch.zeros((0, height, width, 3), dtype=torch.uint8, device=self.device)
+            c = frames.shape[3] if isinstance(frames, torch.Tensor) and frames.dim() == 4 else 3
+            return torch.zeros((0, height, width, c), dtype=torch.uint8, device=self.device)
         h, w, c = fr[0].shape
         for f in fr:
             _require_cuda(f, torch.uint8, "frame", self.device)

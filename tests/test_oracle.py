@@ -367,21 +367,7 @@ def test_resize_oracle_against_torch_conventions():
         cub = oracle.resize_u8(img, dw, dh, oracle.INTER_CUBIC).astype(np.float32)
         ref = np.clip(tor("bicubic", (dh, dw), align_corners=False), 0, 255)
         assert np.abs(cub - ref)[2:-2, 2:-2].max() <= 1.5            # borders: replicate vs torch's clamp of the index
-    def box_average(a, dh, dw):
-        """Definition of area resampling: mean of the source over each destination cell, cells of
-        fractional extent weighted by their overlap (float64)."""
-        def weights(src, dst):
-            s = src / dst
-            wm = np.zeros((dst, src))
-            for d in range(dst):
-                lo, hi = d * s, min((d + 1) * s, src)
-                for i in range(int(np.floor(lo)), int(np.ceil(hi))):
-                    wm[d, i] = max(0.0, min(hi, i + 1) - max(lo, i))
-                wm[d] /= wm[d].sum()
-            return wm
-        wy, wx = weights(a.shape[0], dh), weights(a.shape[1], dw)
-        return np.einsum("yi,ijc,xj->yxc", wy, a.astype(np.float64), wx)
-
+    from ref_resize_np import box_average
     for (dh, dw) in ((48, 64), (32, 32), (24, 16), (37, 51), (95, 127), (13, 100 // 3)):
         area = oracle.resize_u8(img, dw, dh, oracle.INTER_AREA).astype(np.float64)
         assert np.abs(area - box_average(img, dh, dw)).max() <= 0.51
