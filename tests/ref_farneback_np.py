@@ -30,6 +30,30 @@ def levels_for(h, w, num_levels=3, pyr_scale=0.5, min_size=32):
     return k
 
 
+def level_shape(h, w, k, pyr_scale=0.5):
+    """(rows, columns) of pyramid level k: the full size scaled by pyr_scale^k, rounded half to even (Python's round,
+    as cvRound does)."""
+    scale = pyr_scale ** k
+    return int(round(h * scale)), int(round(w * scale))
+
+
+def _bilinear_taps(n_src, n_dst):
+    """Source index pairs and weights of half-pixel-centre bilinear resampling along one axis.  The sample position is
+    the one cv::resize uses: (d + 0.5) * scale - 0.5 evaluated in double and then stored as a float32, so at a ratio
+    that is not a power of two it is off the exact position by up to half a float32 ulp (3e-5 px at column 900 of a
+    1080p frame; times a gradient of 30 grey levels per pixel, 1e-3 in the pyramid image).  That rounding is part of
+    what the reference computes, so the derivation takes it over; the weights and the sums stay float64."""
+    scale = 1.0 / (n_dst / n_src)
+    pos = np.float32((np.arange(n_dst) + 0.5) * scale - 0.5).astype(np.float64)
+    i0 = np.floor(pos).astype(int)
+    a = pos - i0
+    a[i0 < 0] = 0.0
+    i0 = np.maximum(i0, 0)
+    a[i0 >= n_src - 1] = 0.0
+    i0 = np.minimum(i0, n_src - 1)
+    return i0, np.minimum(i0 + 1, n_src - 1), a
+
+
 def resize_bilinear(img, dh, dw):
     """Half-pixel-centre bilinear resampling of (h,w[,c]) float64 (exact 2x decimation = 2x2 mean,
     as cv::resize does)."""
@@ -39,12 +63,14 @@ def resize_bilinear(img, dh, dw):
     h, w, _ = a.shape
     if (h, w) == (dh, dw):
         return img.copy()
-    t = torch.from_numpy(np.ascontiguousarray(a)).permute(2, 0, 1)[None]
     if h == 2 * dh and w == 2 * dw:
-        o = F.avg_pool2d(t, 2)
+        t = torch.from_numpy(np.ascontiguousarray(a)).permute(2, 0, 1)[None]
+        o = F.avg_pool2d(t, 2)[0].permute(1, 2, 0).numpy()
     else:
-        o = F.interpolate(t, size=(dh, dw), mode="bilinear", align_corners=False)
-    o = o[0].permute(1, 2, 0).numpy()
+        y0, y1, ay = _bilinear_taps(h, dh)
+        x0, x1, ax = _bilinear_taps(w, dw)
+        r = (1 - ay)[:, None, None] * a[y0] + ay[:, None, None] * a[y1]
+        o = (1 - ax)[None, :, None] * r[:, x0] + ax[None, :, None] * r[:, x1]
     return o if img.ndim == 3 else o[..., 0]
 
 
@@ -57,7 +83,7 @@ def pyramid_image(gray, k, pyr_scale=0.5):
     f = gray.astype(np.float64)
     f = ndimage.correlate1d(f, taps, axis=1, mode="mirror")      # BORDER_REFLECT_101
     f = ndimage.correlate1d(f, taps, axis=0, mode="mirror")
-    return resize_bilinear(f, int(round(h * scale)), int(round(w * scale)))
+    return resize_bilinear(f, *level_shape(h, w, k, pyr_scale))
 
 
 def poly_expansion(img, n=5, sigma=1.2):

@@ -23,6 +23,7 @@ import torch
 import oracle
 from scannertools_amd.hip import default_params
 from util import interleaved5, planar5, random_frames, smooth_texture, texture_stream, translated_rgb_pair
+from util import torch_stream as _torch_stream
 
 pytestmark = pytest.mark.gpu
 
@@ -329,18 +330,6 @@ def test_flow_1080p_pair(flow_ctx):
     _check_flow(got, oracle.optical_flow_rgb(f0, f1))
     inner = got[100:-100, 100:-100]
     assert abs(np.median(inner[..., 0]) - 4) < 0.05 and abs(np.median(inner[..., 1]) - 3) < 0.05
-
-
-def _torch_stream(n, h, w, seed, step=2):
-    """n frames of a smooth texture under a steady translation, generated on the GPU (big sizes)."""
-    g = torch.Generator(device="cuda").manual_seed(seed)
-    m = step * n + 8
-    low = torch.rand((1, 3, (h + 2 * m) // 8 + 2, (w + 2 * m) // 8 + 2), device="cuda", generator=g)
-    tex = torch.nn.functional.interpolate(low, size=(h + 2 * m, w + 2 * m), mode="bicubic", align_corners=False)[0]
-    tex = ((tex - tex.amin()) / (tex.amax() - tex.amin()) * 235 + 10).permute(1, 2, 0)
-    fr = [tex[m + i:m + i + h, m - step * i:m - step * i + w] + torch.randint(-2, 3, (h, w, 3), device="cuda", generator=g)
-          for i in range(n)]
-    return torch.stack([f.clamp(0, 255).to(torch.uint8) for f in fr]).contiguous()
 
 
 def test_flow_1080p_batch_launch_geometry(mode_ctxs):
