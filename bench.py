@@ -16,9 +16,11 @@ torch.distributed (RCCL) is used only for the barriers and the max-over-ranks of
 parent touches the GPU; the parent relays rank 0's line and fails if any rank fails); under an
 external launcher (torch.distributed.run) WORLD_SIZE must equal --gpus.
 
-With more than one rank (N > 1) the line carries the headline fields, `roofline`, `flow_whole_path`, `histogram` and the multi-GPU
-evidence fields (`rccl_world_size`, `devices`, `distinct_devices`, `ms_per_step_by_rank`) only: `cpu_baseline`, `parity` and `extra`
-are single-GPU records (rank 0 at N = 1), so that a scaling run times nothing but the sharded step.
+A plain run sets up, warms up, times the steps, writes --dump-outputs and prints the line: the headline fields, `roofline`
+and `flow_whole_path` (both from the timed steps themselves) and the multi-GPU evidence fields (`rccl_world_size`, `devices`,
+`distinct_devices`, `ms_per_step_by_rank`).  Every record that needs work of its own (`histogram`, `cpu_baseline`, `parity`,
+`extra`) runs only with --full, after the headline; the --no-* options leave some of them out.  `cpu_baseline`, `parity` and
+`extra` are single-GPU records (rank 0 at N = 1), so that a scaling run times nothing but the sharded step.
 
 The JSON line also carries
   roofline     : for the dominant kernel (k_flow_iter3: UpdateMatrices + 15x15 box blur + 2x2
@@ -32,8 +34,8 @@ The JSON line also carries
                  really moved).  Steps of fewer than 32 pairs run without the event brackets (they cost
                  ~8 us per launch on the stream) and report no kernel roofline.
   parity       : the bench configuration's own output against the oracle (a 256-pair step taken
-                 outside the timed region; first pairs' flows, first frames' histograms).
-  histogram    : frames/s and roofline of the Histogram kernel alone (same run, own timed loop).
+                 outside the timed region; first pairs' flows, first frames' histograms; --full).
+  histogram    : frames/s and roofline of the Histogram kernel alone (same run, own timed loop; --full).
   cpu_baseline : the CPU oracle (oracle/oracle.c, a port of the OpenCV algorithms the reference
                  calls) on all host cores, median of >= 3 repetitions on a bounded sample.
   extra        : own timed loops after the headline: config 3 (10 000-frame shot detection on this GPU),
@@ -958,6 +960,49 @@ def extras(torch, ctx, _native, device, args, batches, hist_out):
     return out
 
 
+def histogram_alone(torch, ctx, _native, device, batches, B, bins, steps, rank, barrier, hist_out):
+    """The `histogram` record (--full): the Histogram kernel alone on the headline's frames, its own timed loop, then on
+    i.i.d. uniform bytes."""
+    _, h, w, _ = batches[0].shape
+    ctx.timing_enable([_native.K_HIST])
+    ctx.timing_reset()
+    barrier()
+    th0 = time.perf_counter()
+    for i in range(steps):
+        ctx.histogram(batches[i % len(batches)][:B], bins, out=hist_out)
+    torch.cuda.synchronize(device)
+    th = time.perf_counter() - th0
+    hist_launches, hist_ms = ctx.timing_read(_native.K_HIST)
+    ctx.timing_enable([])
+    hist_bytes = (3 * h * w + 3 * bins * 4) * B
+    hist_gbs = hist_bytes * steps / (hist_ms * 1e-3) / 1e9 if hist_ms > 0 else 0.0
+    # same kernel on i.i.d. uniform bytes (SURVEY.md 8d "random u8" input): the LDS-atomic-heavy case
+    g = torch.Generator(device=device).manual_seed(7 + rank)
+    rnd = torch.randint(0, 256, (B, h, w, 3), dtype=torch.uint8, device=device, generator=g)
+    ctx.histogram(rnd, bins, out=hist_out)
+    ctx.timing_enable([_native.K_HIST])
+    ctx.timing_reset()
+    for i in range(steps):
+        ctx.histogram(rnd, bins, out=hist_out)
+    rnd_launches, rnd_ms = ctx.timing_read(_native.K_HIST)
+    ctx.timing_enable([])
+    del rnd
+    rnd_gbs = hist_bytes * steps / (rnd_ms * 1e-3) / 1e9 if rnd_ms > 0 else 0.0
+    return {
+        "frames_per_s": B * steps / th,
+        "kernel": "k_hist_u8c3_v2",
+        "achieved": hist_gbs,
+        "peak": HBM_PEAK_GBS,
+        "unit": "GB/s",
+        "frac": hist_gbs / HBM_PEAK_GBS,
+        "frac_of_copy_ceiling": hist_gbs / HBM_COPY_CEILING_GBS,
+        "launches": hist_launches,
+        "avg_launch_ms": hist_ms / max(hist_launches, 1),
+        "uniform_random_frames": {"achieved": rnd_gbs, "frac": rnd_gbs / HBM_PEAK_GBS,
+                                  "frames_per_s": B * steps / (rnd_ms * 1e-3) if rnd_ms > 0 else 0.0},
+    }
+
+
 def run_rank(args):
     import torch
     import torch.distributed as dist
@@ -1068,32 +1113,8 @@ def run_rank(args):
         dist.all_gather(ones, one)
         rccl_world = int(sum(int(o_.item()) for o_ in ones))
 
-    # Histogram kernel alone (same data), its own timed loop
-    hist_steps = max(args.steps, 10)
-    ctx.timing_enable([_native.K_HIST])
-    ctx.timing_reset()
-    barrier()
-    th0 = time.perf_counter()
-    for i in range(hist_steps):
-        ctx.histogram(batches[i % n_batches][:B], args.bins, out=hist_out)
-    torch.cuda.synchronize(device)
-    th = time.perf_counter() - th0
-    hist_launches, hist_ms = ctx.timing_read(_native.K_HIST)
-    ctx.timing_enable([])
-    hist_bytes = (3 * h * w + 3 * args.bins * 4) * B
-    hist_gbs = hist_bytes * hist_steps / (hist_ms * 1e-3) / 1e9 if hist_ms > 0 else 0.0
-    # same kernel on i.i.d. uniform bytes (SURVEY.md 8d "random u8" input): the LDS-atomic-heavy case
-    g = torch.Generator(device=device).manual_seed(7 + rank)
-    rnd = torch.randint(0, 256, (B, h, w, 3), dtype=torch.uint8, device=device, generator=g)
-    ctx.histogram(rnd, args.bins, out=hist_out)
-    ctx.timing_enable([_native.K_HIST])
-    ctx.timing_reset()
-    for i in range(hist_steps):
-        ctx.histogram(rnd, args.bins, out=hist_out)
-    rnd_launches, rnd_ms = ctx.timing_read(_native.K_HIST)
-    ctx.timing_enable([])
-    del rnd
-    rnd_gbs = hist_bytes * hist_steps / (rnd_ms * 1e-3) / 1e9 if rnd_ms > 0 else 0.0
+    hist_rec = histogram_alone(torch, ctx, _native, device, batches, B, args.bins, max(args.steps, 10), rank, barrier,
+                               hist_out) if args.full else None
 
     # HBM bytes per k_flow_iter3 launch from the PMC counters of the committed profile of this same
     # command (scripts/profile_round.sh -> scripts/pmc_traffic.py -> profiles/traffic.json):
@@ -1191,21 +1212,9 @@ def run_rank(args):
                 "achieved_GBs": fps / world * flow_model_bytes / 1e9,
                 "frac_of_peak": fps / world * flow_model_bytes / 1e9 / HBM_PEAK_GBS,
             },
-            "histogram": {
-                "frames_per_s": B * hist_steps / th,
-                "kernel": "k_hist_u8c3_v2",
-                "achieved": hist_gbs,
-                "peak": HBM_PEAK_GBS,
-                "unit": "GB/s",
-                "frac": hist_gbs / HBM_PEAK_GBS,
-                "frac_of_copy_ceiling": hist_gbs / HBM_COPY_CEILING_GBS,
-                "launches": hist_launches,
-                "avg_launch_ms": hist_ms / max(hist_launches, 1),
-                "uniform_random_frames": {"achieved": rnd_gbs, "frac": rnd_gbs / HBM_PEAK_GBS,
-                                          "frames_per_s": B * hist_steps / (rnd_ms * 1e-3) if rnd_ms > 0 else 0.0},
-            },
+            **({"histogram": hist_rec} if hist_rec else {}),
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             # one more 256-pair step of the bench configuration outside the timed region: its output
             # is what the oracle results computed by the baseline leg are compared with
             ctx.histogram(batches[0][:B], args.bins, out=hist_out)
@@ -1249,7 +1258,7 @@ def run_rank(args):
                     "flow_tolerance": {"rel_l2": 1e-4, "max_abs_px": 5e-3},
                     "hist_bit_exact": bool(all((gpu_hist[i] == kept[i][0]).all() for i in idx)),
                 }
-        if world == 1 and not args.no_extras:
+        if args.full and world == 1 and not args.no_extras:
             del flow_out
             ctx.release_workspace()
             torch.cuda.empty_cache()
@@ -1272,6 +1281,10 @@ def main():
     ap.add_argument("--height", type=int, default=1080)
     ap.add_argument("--width", type=int, default=1920)
     ap.add_argument("--bins", type=int, default=256)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run the records that need work of their own: the Histogram kernel alone, "
+                         "the CPU baseline and parity (1 GPU) and the extra records (1 GPU); the --no-* options below leave "
+                         "some of them out")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extras", action="store_true", help="skip the extra records (4K, host-fed, small histogram batches)")
     ap.add_argument("--no-4k", action="store_true")

@@ -1,13 +1,16 @@
 #!/bin/bash
 export GRAFT_REPO_ROOT="${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}"   # the repo root when not run through gpurun
-# The round's committed bench line: bash scripts/final_bench.sh <tag>   (run on the GPU box; copy gpurun_out/bench_<tag>.json to profiles/<tag>_bench.json)
+# The round's committed bench line: bash scripts/final_bench.sh <tag> <output dir>   (on the GPU box; the line is
+# <output dir>/bench_<tag>.json, committed as profiles/<tag>_bench.json)
 cd "$GRAFT_REPO_ROOT"
-tag=${1:-final}
-python bench.py > gpurun_out/bench_$tag.json 2> gpurun_out/bench_$tag.err
-tail -1 gpurun_out/bench_$tag.err
-python - "$tag" <<'PY'
+tag=${1:?usage: final_bench.sh <tag> <output dir>}
+out=${2:?usage: final_bench.sh <tag> <output dir>}
+mkdir -p "$out"
+python bench.py --full > "$out/bench_$tag.json" 2> "$out/bench_$tag.err"
+tail -1 "$out/bench_$tag.err"
+python - "$out/bench_$tag.json" <<'PY'
 import json, sys
-d = json.load(open("gpurun_out/bench_%s.json" % sys.argv[1]))
+d = json.load(open(sys.argv[1]))
 print(d["value"], d["ms_per_step"], {k: d["roofline"][k] for k in ("frac", "frac_model_8d", "frac_traffic", "traffic", "l2_hit_rate")})
 e = d["extra"]
 for k, v in e["optical_flow_small_batches"].items():

@@ -10,7 +10,7 @@ mkdir -p $out
 BENCH_ARGS=("$@")
 rocprofv3 -L > $out/avail.txt 2>&1
 pass() { name=$1; shift
-  timeout 600 rocprofv3 --pmc "$@" --output-format csv -d $out/$name -o $name -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-extras "${BENCH_ARGS[@]}" > $out/$name.log 2>&1
+  timeout 600 rocprofv3 --pmc "$@" --output-format csv -d $out/$name -o $name -- python3 bench.py --steps 2 --warmup 1 --full --no-cpu-baseline --no-extras "${BENCH_ARGS[@]}" > $out/$name.log 2>&1
 }
 pass a SQ_INSTS_VMEM_RD SQ_INST_LEVEL_VMEM SQ_INST_CYCLES_VMEM_RD SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_VMEM SQ_WAIT_INST_ANY
 pass b TCP_TCC_READ_REQ_LATENCY_sum TCP_TCC_READ_REQ_sum TCP_TCP_LATENCY_sum TCP_TA_TCP_STATE_READ_sum

@@ -9,7 +9,7 @@ out=gpurun_out/ps_$b
 mkdir -p $out
 export ST_BENCH_NO_KERNEL_TIMING=1
 pass() { name=$1; shift
-  timeout 180 rocprofv3 --kernel-include-regex "$rx" --pmc "$@" --output-format csv -d $out/$name -o $name -- python3 bench.py --batch $b --steps 6 --warmup 2 --no-cpu-baseline --no-extras > $out/$name.log 2>&1
+  timeout 180 rocprofv3 --kernel-include-regex "$rx" --pmc "$@" --output-format csv -d $out/$name -o $name -- python3 bench.py --batch $b --steps 6 --warmup 2 --full --no-cpu-baseline --no-extras > $out/$name.log 2>&1
   echo "pass $name rc=$?"
 }
 pass p1 GRBM_GUI_ACTIVE SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_WAIT_INST_LDS SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_VMEM

@@ -4,7 +4,7 @@ set -u
 cd /tmp && export TMPDIR=/tmp; cd "$GRAFT_REPO_ROOT"
 out=gpurun_out/pmc_tlb; mkdir -p $out
 pass() { name=$1; shift
-  rocprofv3 --pmc "$@" --output-format csv -d $out/$name -o $name -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline > $out/$name.log 2>&1
+  rocprofv3 --pmc "$@" --output-format csv -d $out/$name -o $name -- python3 bench.py --steps 2 --warmup 1 --full --no-cpu-baseline > $out/$name.log 2>&1
 }
 pass tlb1 TCP_UTCL1_REQUEST_sum TCP_UTCL1_TRANSLATION_HIT_sum TCP_UTCL1_TRANSLATION_MISS_sum TCP_UTCL1_PERMISSION_MISS_sum
 pass tlb2 GRBM_GUI_ACTIVE GRBM_UTCL2_BUSY

@@ -8,13 +8,13 @@ tag=$1
 cd /tmp && export TMPDIR=/tmp; cd "$GRAFT_REPO_ROOT"
 out=gpurun_out/round_$tag
 mkdir -p $out
-python3 bench.py > $out/bench.json 2> $out/bench.err
+python3 bench.py --full > $out/bench.json 2> $out/bench.err
 # the headline region only (the CPU baseline and the extra records run other sizes / no kernels)
-rocprofv3 --kernel-trace --stats -d $out/trace -o trace -- python3 bench.py --no-cpu-baseline --no-extras > $out/trace.log 2>&1
+rocprofv3 --kernel-trace --stats -d $out/trace -o trace -- python3 bench.py --full --no-cpu-baseline --no-extras > $out/trace.log 2>&1
 pass() { name=$1; shift
   # only this library's kernels are instrumented (the input generator's thousands of torch launches would otherwise
   # dominate the run time of a counter pass)
-  rocprofv3 --kernel-include-regex "k_(flow_iter|polyexp|pyr|gray|hist)" --pmc "$@" --output-format csv -d $out/$name -o $name -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-extras > $out/$name.log 2>&1
+  rocprofv3 --kernel-include-regex "k_(flow_iter|polyexp|pyr|gray|hist)" --pmc "$@" --output-format csv -d $out/$name -o $name -- python3 bench.py --steps 3 --warmup 1 --full --no-cpu-baseline --no-extras > $out/$name.log 2>&1
 }
 pass fetch FETCH_SIZE
 pass write WRITE_SIZE

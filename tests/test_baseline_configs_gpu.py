@@ -3,7 +3,7 @@ counts and network geometry the configurations name, each against the oracle (or
 the pose network, whose parity target it is: DESIGN.md 4.8) on a sample, plus the size-independent properties.
 
   config 1  Histogram, 256 bins, 1000 host-resident 1080p frames through the DeviceType::CPU registration
-  config 2  (the headline: covered by bench.py's own `parity` block and tests/test_flow_gpu.py's 1080p cases)
+  config 2  (the headline: covered by the `parity` block of bench.py --full and tests/test_flow_gpu.py's 1080p cases)
   config 3  (10 000-frame shot pipeline: tests/test_shots_gpu.py, tests/test_engine_gpu.py)
   config 4  OpticalFlow at 3840x2160, 32 pairs (33 frames) in ONE call
   config 5  the pose network at its real 368x656 input: one convolution per distinct (map size, kernel size) of the

@@ -277,6 +277,38 @@ def test_bench_two_ranks_sharing_this_gpu(launcher):
 
 
 @pytest.mark.gpu
+def test_bench_plain_run_and_full_records():
+    """A plain bench.py run stops after its timed steps: the line carries the headline and what the timed steps give, none
+    of the records that need work of their own.  --full adds them (here, with --no-extras: the Histogram kernel alone, the
+    CPU baseline and the parity of one more step against the oracle)."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "ST_BENCH_SHARE_GPU")}
+    tail = [os.path.join(root, "bench.py"), "--steps", "2", "--warmup", "1", "--batch", "8", "--height", "270", "--width", "480"]
+    lines = {}
+    for mode, more in (("plain", []), ("full", ["--full", "--no-extras", "--cpu-reps", "1"])):
+        r = subprocess.run([sys.executable] + tail + more, env=env, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        out = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(out) == 1
+        lines[mode] = json.loads(out[0])
+    plain, full = lines["plain"], lines["full"]
+    for d in (plain, full):
+        assert d["n_gpus"] == 1 and d["steps"] == 2 and d["warmup"] == 1 and d["unit"] == "frames/s" and d["higher_is_better"] is True
+        assert d["value"] > 0 and abs(d["value"] - 8 / (d["ms_per_step"] * 1e-3)) < 1e-6 * d["value"]
+        assert {"roofline", "flow_whole_path", "dtype", "native_build"} <= set(d)
+    assert not {"histogram", "cpu_baseline", "parity", "extra"} & set(plain)
+    assert {"histogram", "cpu_baseline", "parity"} <= set(full) and "extra" not in full
+    assert full["histogram"]["frames_per_s"] > 0 and full["cpu_baseline"]["value"] > 0
+    p = full["parity"]
+    assert p["hist_bit_exact"] is True
+    assert p["flow_rel_l2"] <= p["flow_tolerance"]["rel_l2"] and p["flow_max_abs"] <= p["flow_tolerance"]["max_abs_px"]
+
+
+@pytest.mark.gpu
 def test_shot_pipeline_two_ranks_sharing_this_gpu():
     """Config 3's multi-rank path on real hardware (scripts/shot_pipeline.py --gpus 2, ranks sharing device 0, gloo): shards of a
     stream with planted cuts -> Histogram kernel per rank -> gather on rank 0 -> ShotBoundaries on the device, which the run itself
