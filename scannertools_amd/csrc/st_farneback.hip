@@ -2010,6 +2010,66 @@ __device__ __forceinline__ void coarse2_finish_batch(const IterArgs& a, const Co
   }
 }
 
+// k_flow_iter3's form of the same up-sampling: consecutive batches of 2 fine rows share all but one coarse row, so the
+// horizontally interpolated coarse rows u, u + 1 that the next batch reads are carried in registers from batch to batch,
+// and each batch loads and interpolates only the row u + 2 that enters (one 16-byte load per lane and batch instead of
+// three).  u is the coarse row of the batch's first fine row before the clamp to the frame; window slot v holds
+// coarse row d_clamp(u + v), so the clamped rows a fine row reads are the ones coarse2_finish_batch reads, and every
+// operand and operation per vector is the same.
+struct Coarse2Window {
+  float2 hx0, hx1;  // coarse rows u, u + 1, horizontally interpolated
+  f4u8 raw;         // coarse row u + 2, in flight
+};
+__device__ __forceinline__ void coarse2_row_issue(const IterArgs& a, const float* __restrict__ C, const CoarseX& cx, int u,
+                                                  f4u8& r) {
+  const int yy = d_clamp(u, 0, a.ch - 1);
+  if (cx.pair) {
+    r = *reinterpret_cast<const f4u8*>(reinterpret_cast<const char*>(C) + 8u * (unsigned)(yy * a.cw + cx.sx));
+  } else {
+    const float2 p = ld_flow(C, yy * a.cw + cx.sx);
+    r.x = p.x; r.y = p.y; r.z = 0.f; r.w = 0.f;
+  }
+}
+__device__ __forceinline__ float2 coarse2_row_hx(const CoarseX& cx, const f4u8& r) {
+  float2 hx;
+  if (cx.pair) {
+    hx.x = r.x * cx.a0 + r.z * cx.a1; hx.y = r.y * cx.a0 + r.w * cx.a1;
+  } else {
+    hx.x = r.x * 1.f; hx.y = r.y * 1.f;
+  }
+  return hx;
+}
+// fill for the batch whose first fine row is yu (unclamped)
+__device__ __forceinline__ void coarse2_window_start(const IterArgs& a, const float* __restrict__ C, const CoarseX& cx,
+                                                     int yu, Coarse2Window& win) {
+  const int u = coarse2_row(yu);
+  f4u8 r0, r1;
+  coarse2_row_issue(a, C, cx, u, r0);
+  coarse2_row_issue(a, C, cx, u + 1, r1);
+  coarse2_row_issue(a, C, cx, u + 2, win.raw);
+  win.hx0 = coarse2_row_hx(cx, r0);
+  win.hx1 = coarse2_row_hx(cx, r1);
+}
+// the flows of fine rows yu, yu + 1 (unclamped; the frame's rows d_clamp(yu + i, 0, h - 1)), then the window moves one
+// coarse row down and the row after it is requested
+__device__ __forceinline__ void coarse2_window_batch(const IterArgs& a, const float* __restrict__ C, const CoarseX& cx, int yu,
+                                                     Coarse2Window& win, float2 (&out)[2]) {
+  const int u = coarse2_row(yu);
+  const float2 hx2 = coarse2_row_hx(cx, win.raw);
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    const int y = min(yu + i, a.h - 1);          // yu >= 0
+    const bool second = coarse2_row(yu + i) > u;  // wave-uniform
+    const float fy = (y & 1) ? 0.25f : 0.75f;
+    const float b0 = 1.f - fy, b1 = fy;
+    const float2 ta = second ? win.hx1 : win.hx0, tb = second ? hx2 : win.hx1;
+    out[i] = make_float2((ta.x * b0 + tb.x * b1) * a.mul, (ta.y * b0 + tb.y * b1) * a.mul);
+  }
+  win.hx0 = win.hx1;
+  win.hx1 = hx2;
+  coarse2_row_issue(a, C, cx, u + 3, win.raw);
+}
+
 template <int RB>
 __device__ __forceinline__ float2 coarseN_finish(const IterArgs& a, const CoarseX& cx, int y0, int y, const FlowRawN<RB>& r) {
   float fy = (float)((y + 0.5) * a.scale_y - 0.5);
@@ -2153,10 +2213,11 @@ __global__ __launch_bounds__(B2_T, 2) void k_flow_iter3(IterArgs a) {
   }
 #pragma unroll
   for (int r = 0; r < RB; ++r) fnext[r] = iter_flow_at<MODE>(a, fin, C, cx, xc, d_clamp(y0 + RB + r + M + 1, 0, h - 1));
+  static_assert(RB == 2, "Coarse2Window moves one coarse row per batch of two fine rows");
   FlowRaw raw[MODE == FLOW_COARSE2 ? 1 : RB];
-  FlowRawN<RB> rawn;
+  Coarse2Window win;
   if (MODE == FLOW_COARSE2) {
-    coarseN_issue<RB>(a, C, cx, d_clamp(y0 + 2 * RB + M + 1, 0, h - 1), rawn);
+    coarse2_window_start(a, C, cx, y0 + 2 * RB + M + 1, win);
   } else {
 #pragma unroll
     for (int r = 0; r < RB; ++r) flow_issue<MODE>(a, fin, C, cx, xc, d_clamp(y0 + 2 * RB + r + M + 1, 0, h - 1), raw[r]);
@@ -2232,11 +2293,7 @@ __global__ __launch_bounds__(B2_T, 2) void k_flow_iter3(IterArgs a) {
         // flows: the loads requested one batch ago become vectors now and the next rows are requested --
         // never a wait on loads issued in the same batch
         if (MODE == FLOW_COARSE2) {
-          int ysb[RB];
-#pragma unroll
-          for (int r = 0; r < RB; ++r) ysb[r] = d_clamp(ybb + 2 * RB + r + M + 1, 0, h - 1);
-          coarse2_finish_batch<RB>(a, cx, ysb[0], ysb, rawn, fnext);
-          coarseN_issue<RB>(a, C, cx, d_clamp(ybb + 3 * RB + M + 1, 0, h - 1), rawn);
+          coarse2_window_batch(a, C, cx, ybb + 2 * RB + M + 1, win, fnext);
         } else {
 #pragma unroll
           for (int r = 0; r < RB; ++r) fnext[r] = flow_finish<MODE>(a, fin, C, cx, d_clamp(ybb + 2 * RB + r + M + 1, 0, h - 1), raw[MODE == FLOW_COARSE2 ? 0 : r]);
