@@ -98,7 +98,8 @@ enum st_kernel_id {
   ST_K_CONV = 13,       /* convolution / pooling launches of the pose network */
   ST_K_CPM2_RESIZE = 14,
   ST_K_CPM2_NMS = 15,
-  ST_K_COUNT = 16
+  ST_K_FRAME_STATS = 16, /* moments + finishing launches of the frame-statistics ops */
+  ST_K_COUNT = 17
 };
 int st_ctx_timing_enable(st_ctx* ctx, unsigned kernel_mask);
 int st_ctx_timing_reset(st_ctx* ctx);
@@ -118,6 +119,38 @@ int st_hist_u8c3_batch(st_ctx* ctx, const uint8_t* const* frames_dev, int n, int
 /* Same, frames at base_dev + i * frame_stride_bytes (a contiguous device-resident stream). */
 int st_hist_u8c3_strided(st_ctx* ctx, const uint8_t* base_dev, size_t frame_stride_bytes, int n,
                          int h, int w, int bins, int32_t* out_dev);
+
+/* ---- Frame statistics: BrightnessCPP / ContrastCPP / SharpnessCPP and Brightness / Contrast / Sharpness -------------------
+ * Replace the per-frame bodies of the legacy op library's BrightnessKernel, ContrastKernel and SharpnessKernel
+ * (scannertools/old/cpp_ops/imgproc.cpp:50-79 cv::cvtColor(RGB2YUV) + cv::mean; :81-131 the same + a float32 sum of squared
+ * deviations; :133-175 cv::Laplacian(CV_64F) + cv::meanStdDev + cv::pow) and of their Python twins (old/imgproc.py:11-37:
+ * np.mean of the Y plane, np.sqrt(np.mean((Y - mean)**2)), cv2.Laplacian(frame, CV_64F).var()) for a whole batch.
+ * Y = (R*4899 + G*9617 + B*1868 + 8192) >> 14 (cv::cvtColor COLOR_RGB2YUV); L_c = the reflect-101 4-neighbour Laplacian of
+ * channel c, an integer in [-1020, 1020] (the neighbour on an axis of length 1 is the pixel itself).
+ * st_frame_moments_u8c3_*: moments_dev receives n records of 8 int64, in the order ST_FM_SY .. ST_FM_Q_B: sum Y, sum Y^2,
+ *   sum L_R, sum L_G, sum L_B, sum L_R^2, sum L_G^2, sum L_B^2, exact.  what: ST_FM_LUMA and / or ST_FM_LAPLACIAN, the moments
+ *   to compute; the call zeroes all n * 8 values first, so those not asked for are 0.  Frames of up to 2^31 - 1 bytes;
+ *   ST_ERR_UNSUPPORTED for the Laplacian of rows wider than 19 786 pixels.
+ * st_frame_stats_finish: out_dev[i] = statistic `kind` (ST_FS_*) of record i for frames of h x w pixels: float for the
+ *   *_CPP kinds (the 4-byte element the reference's C++ op emits), double for the others (the value the Python op pickles).
+ *   Reads the moments the kind needs: SY, QY for brightness and contrast, the Laplacian moments for sharpness.
+ *   Formulas: scannertools_amd/csrc/st_framestats.hip, header comment. */
+enum st_frame_moment { ST_FM_SY = 0, ST_FM_QY = 1, ST_FM_S_R = 2, ST_FM_S_G = 3, ST_FM_S_B = 4, ST_FM_Q_R = 5, ST_FM_Q_G = 6, ST_FM_Q_B = 7 };
+enum st_frame_moment_mask { ST_FM_LUMA = 1, ST_FM_LAPLACIAN = 2 };
+enum st_frame_stat_kind {
+  ST_FS_BRIGHTNESS_CPP = 0, /* imgproc.cpp:61-75 */
+  ST_FS_CONTRAST_CPP = 1,   /* imgproc.cpp:92-126 (see the deviation noted in st_framestats.hip) */
+  ST_FS_SHARPNESS_CPP = 2,  /* imgproc.cpp:144-168 */
+  ST_FS_BRIGHTNESS = 3,     /* old/imgproc.py:11-17 */
+  ST_FS_CONTRAST = 4,       /* old/imgproc.py:20-30 */
+  ST_FS_SHARPNESS = 5       /* old/imgproc.py:33-36 */
+};
+int st_frame_moments_u8c3_batch(st_ctx* ctx, const uint8_t* const* frames_dev, int n, int h, int w, int what,
+                                int64_t* moments_dev);
+/* Same, frames at base_dev + i * frame_stride_bytes (a contiguous device-resident stream). */
+int st_frame_moments_u8c3_strided(st_ctx* ctx, const uint8_t* base_dev, size_t frame_stride_bytes, int n, int h, int w,
+                                  int what, int64_t* moments_dev);
+int st_frame_stats_finish(st_ctx* ctx, const int64_t* moments_dev, int n, int h, int w, int kind, void* out_dev);
 
 /* ---- ShotBoundaries (device-resident histograms) -------------------------------------------
  * Replaces the body of the ShotBoundaries python op, scannertools/shot_detection.py:12-28, for histograms that are

@@ -13,6 +13,9 @@ LIB_PATH = os.environ.get("ST_HIP_LIB") or os.path.join(_HERE, "lib", "libscanne
 CSRC = os.path.join(_HERE, "csrc")
 
 ST_OK, ST_ERR_INVALID, ST_ERR_HIP, ST_ERR_OOM, ST_ERR_UNSUPPORTED = range(5)
+FM_LUMA, FM_LAPLACIAN = 1, 2   # st_frame_moment_mask
+# st_frame_stat_kind: the six frame statistics (float32 for the *CPP kinds, float64 for the Python ops' values)
+FS_KINDS = {"BrightnessCPP": 0, "ContrastCPP": 1, "SharpnessCPP": 2, "Brightness": 3, "Contrast": 4, "Sharpness": 5}
 INTER_NEAREST, INTER_LINEAR, INTER_CUBIC, INTER_AREA, INTER_LANCZOS4 = 0, 1, 2, 3, 4  # cv::InterpolationFlags values the Resize op implements
 # cv::ColorConversionCodes values the ConvertColor op implements
 COLOR_CODES = {"COLOR_BGR2RGB": 4, "COLOR_RGB2BGR": 4, "COLOR_BGR2GRAY": 6, "COLOR_RGB2GRAY": 7,
@@ -52,8 +55,8 @@ COLOR_CODES = {"COLOR_BGR2RGB": 4, "COLOR_RGB2BGR": 4, "COLOR_BGR2GRAY": 6, "COL
                "COLOR_GRAY2BGR565": 20, "COLOR_BGR5652GRAY": 21, "COLOR_BGR2BGR555": 22, "COLOR_RGB2BGR555": 23,
                "COLOR_BGR5552BGR": 24, "COLOR_BGR5552RGB": 25, "COLOR_BGRA2BGR555": 26, "COLOR_RGBA2BGR555": 27,
                "COLOR_BGR5552BGRA": 28, "COLOR_BGR5552RGBA": 29, "COLOR_GRAY2BGR555": 30, "COLOR_BGR5552GRAY": 31}
-K_HIST, K_GRAY, K_PYR, K_POLYEXP, K_UPDATE_MATRICES, K_BLUR_UPDATE, K_FLOW_HIST, K_DRAW_FLOW, K_BLUR_OP, K_RESIZE, K_CVT_COLOR, K_CPM2_INPUT, K_CPM2_LIMBS, K_CONV, K_CPM2_RESIZE, K_CPM2_NMS, K_COUNT = range(17)
-KERNEL_NAMES = ["hist", "gray", "pyr", "polyexp", "update_matrices", "blur_update", "flow_hist", "draw_flow", "blur_op", "resize", "cvt_color", "cpm2_input", "cpm2_limbs", "conv", "cpm2_resize", "cpm2_nms"]
+K_HIST, K_GRAY, K_PYR, K_POLYEXP, K_UPDATE_MATRICES, K_BLUR_UPDATE, K_FLOW_HIST, K_DRAW_FLOW, K_BLUR_OP, K_RESIZE, K_CVT_COLOR, K_CPM2_INPUT, K_CPM2_LIMBS, K_CONV, K_CPM2_RESIZE, K_CPM2_NMS, K_FRAME_STATS, K_COUNT = range(18)
+KERNEL_NAMES = ["hist", "gray", "pyr", "polyexp", "update_matrices", "blur_update", "flow_hist", "draw_flow", "blur_op", "resize", "cvt_color", "cpm2_input", "cpm2_limbs", "conv", "cpm2_resize", "cpm2_nms", "frame_stats"]
 assert len(KERNEL_NAMES) == K_COUNT
 
 
@@ -103,6 +106,9 @@ SIGNATURES = {
     "st_ctx_timing_read": (_i, [_vp, _i, _c.POINTER(_i), _c.POINTER(_d)]),
     "st_hist_u8c3_batch": (_i, [_vp, _c.POINTER(_vp), _i, _i, _i, _i, _vp]),
     "st_hist_u8c3_strided": (_i, [_vp, _vp, _sz, _i, _i, _i, _i, _vp]),
+    "st_frame_moments_u8c3_batch": (_i, [_vp, _c.POINTER(_vp), _i, _i, _i, _i, _vp]),
+    "st_frame_moments_u8c3_strided": (_i, [_vp, _vp, _sz, _i, _i, _i, _i, _vp]),
+    "st_frame_stats_finish": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
     "st_shot_boundaries": (_i, [_vp, _vp, _i, _i, _i, _d, _vp, _vp]),
     "st_fb_params_default": (None, [_c.POINTER(FbParams)]),
     "st_farneback_pairs": (_i, [_vp, _c.POINTER(_vp), _i, _c.POINTER(_c.c_int32), _i, _i, _i,
@@ -164,7 +170,7 @@ def source_hash():
     st_build_info() of a library built from THIS tree reports."""
     import hashlib
     srcs = ["st_context.hip", "st_hist.hip", "st_farneback.hip", "st_flowvis.hip", "st_imgproc.hip", "st_pose.hip", "st_conv.hip",
-            "st_conv_tile_bf16x3.hip", "st_conv_tile_f32.hip", "st_internal.h", "st_conv_tile.h",
+            "st_conv_tile_bf16x3.hip", "st_conv_tile_f32.hip", "st_framestats.hip", "st_internal.h", "st_conv_tile.h",
             os.path.join("..", "..", "include", "scannertools_hip.h"), "Makefile"]
     hsh = hashlib.sha256()
     for f in srcs:

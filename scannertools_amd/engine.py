@@ -12,9 +12,11 @@ installable here, so this module reproduces exactly that surface for in-memory f
     out = NamedStream(sc, 'hist'); sc.run(sc.io.Output(hist, [out]), PerfParams.estimate())
     next(out.load())
 
-C++ ops (``Histogram``, ``OpticalFlow``, ``FlowHistogram``, ``Blur``, ``Resize``, ``ConvertColor``, ``Montage``) are looked up in the kernel registry of
+C++ ops (``Histogram``, ``OpticalFlow``, ``FlowHistogram``, ``Blur``, ``Resize``, ``ConvertColor``, ``Montage``, ``BrightnessCPP``,
+``ContrastCPP``, ``SharpnessCPP``) are looked up in the kernel registry of
 ``libscannertools_imgproc.so`` and executed by its mini engine (scanner_shim/shim.cpp): the same
-``execute()`` bodies a real Scanner worker would call.  Python ops (``ShotBoundaries``, ``DrawFlow``) are the
+``execute()`` bodies a real Scanner worker would call.  Python ops (``ShotBoundaries``, ``DrawFlow``, ``Brightness``,
+``Contrast``, ``Sharpness``) are the
 functions of this package.  What is deliberately absent: the database, video decode, the
 master/worker runtime, scheduling.
 """
@@ -78,6 +80,7 @@ def _load_op_library(path):
         L.stshim_op_info.argtypes = [ctypes.c_char_p, ctypes.POINTER(ci), ctypes.POINTER(ci), ctypes.POINTER(ci),
                                      ctypes.POINTER(ci), ci, ctypes.POINTER(ci)]
         L.stshim_op_state.argtypes = [ctypes.c_char_p, ctypes.POINTER(ci), ctypes.POINTER(ci)]
+        L.stshim_op_output_name.argtypes = [ctypes.c_char_p, ci, ctypes.c_char_p, ci]
         L.stshim_kernel_create.restype = vp
         L.stshim_kernel_create.argtypes = [ctypes.c_char_p, ci, ci, ctypes.c_char_p, sz, ctypes.c_char_p, sz]
         L.stshim_kernel_destroy.argtypes = [vp]
@@ -156,8 +159,13 @@ def op_info(name):
     unbounded, warmup = ctypes.c_int(), ctypes.c_int()
     if L.stshim_op_state(name.encode(), ctypes.byref(unbounded), ctypes.byref(warmup)):
         return None
+    names = []
+    for i in range(n_out.value):
+        buf = ctypes.create_string_buffer(64)
+        if L.stshim_op_output_name(name.encode(), i, buf, 64) == 0:
+            names.append(buf.value.decode())
     return {"inputs": n_in.value, "outputs": n_out.value, "frame_output": bool(isf.value),
-            "stencil": list(st[:ns.value]) or [0], "unbounded_state": bool(unbounded.value)}
+            "stencil": list(st[:ns.value]) or [0], "unbounded_state": bool(unbounded.value), "output_names": names}
 
 
 def plan_runs(idx, unbounded=False):
@@ -376,6 +384,34 @@ class _MontageNode(_CppOpNode):
         if L.stshim_output_get_col(res, 0, i, None, None, None, shape, None):
             raise RuntimeError("missing output row %d" % i)
         return np.broadcast_to(np.zeros((), np.uint8), (shape[0], shape[1], shape[2]))
+
+
+class _RowsNode(_Node):
+    """Rows fetched once, by absolute row index, standing in for the node that produced them."""
+
+    def __init__(self, rows, n):
+        self._rows, self._n = rows, n
+
+    def length(self):
+        return self._n
+
+    def rows(self, idx):
+        return [self._rows[i] for i in idx]
+
+
+class _FrameStatNode(_CppOpNode):
+    """BrightnessCPP / ContrastCPP / SharpnessCPP (old/cpp_ops/imgproc.cpp:50-175): frames that are not (h, w, 3) uint8 are a
+    ValueError here, before any kernel instance exists."""
+
+    def rows(self, idx):
+        from . import frame_stats as _fs
+        if not idx:
+            return []
+        frames = self.parent.rows(idx)
+        _fs.check_frames(self.name, frames)
+        node = copy.copy(self)
+        node.parent = _RowsNode(dict(zip(idx, frames)), self.parent.length())
+        return _CppOpNode.rows(node, idx)
 
 
 class _CppOpColumn(_Node):
@@ -721,6 +757,46 @@ class _Ops:
         from . import vis as _vis
         dev = self.sc.device_id
         return _PyMapNode(lambda frames, flows: _vis.draw_flow_rows(frames, flows, device=dev), [frame, flow])
+
+    def _frame_stat_cpp(self, name, frame, device, batch, width, height):
+        from . import _proto
+        node = _FrameStatNode(self.sc, name, frame, device, batch, None,
+                              _proto.encode([(1, "int32", int(width)), (2, "int32", int(height))]))   # ImgProcArgs (ignored)
+        node.reader = _types.frame_stat
+        return node
+
+    def BrightnessCPP(self, frame, device=None, batch=None, width=0, height=0):
+        """db.ops.BrightnessCPP(frame=...) (old/imgproc.py:76): mean COLOR_RGB2YUV luma, one float per row."""
+        return self._frame_stat_cpp("BrightnessCPP", frame, device, batch, width, height)
+
+    def ContrastCPP(self, frame, device=None, batch=None, width=0, height=0):
+        """db.ops.ContrastCPP(frame=...) (old/imgproc.py:109): standard deviation of the luma, one float per row."""
+        return self._frame_stat_cpp("ContrastCPP", frame, device, batch, width, height)
+
+    def SharpnessCPP(self, frame, device=None, batch=None, width=0, height=0):
+        """db.ops.SharpnessCPP(frame=...) (old/imgproc.py:135): mean over the channels of the Laplacian's variance, one float
+        per row."""
+        return self._frame_stat_cpp("SharpnessCPP", frame, device, batch, width, height)
+
+    def _frame_stat_py(self, name, frame):
+        from . import frame_stats as _fs
+        dev = self.sc.device_id
+        node = _PyMapNode(lambda frames: _fs.stat_rows(name, frames, device=dev), [frame])
+        node.reader = _types.pickled
+        return node
+
+    def Brightness(self, frame):
+        """sc.ops.Brightness(frame=frame): the python op of old/imgproc.py:11-17 (a pickled np.float64 per row), computed on
+        the GPU (scannertools_amd.frame_stats)."""
+        return self._frame_stat_py("Brightness", frame)
+
+    def Contrast(self, frame):
+        """sc.ops.Contrast(frame=frame): the python op of old/imgproc.py:20-30, computed on the GPU."""
+        return self._frame_stat_py("Contrast", frame)
+
+    def Sharpness(self, frame):
+        """sc.ops.Sharpness(frame=frame): the python op of old/imgproc.py:33-36, computed on the GPU."""
+        return self._frame_stat_py("Sharpness", frame)
 
     def InfoFromFrame(self, frame):
         """sc.ops.InfoFromFrame(frame=frame): the frame's FrameInfo as a bytes column."""

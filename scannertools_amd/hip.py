@@ -140,6 +140,60 @@ class HipContext:
                                                  bins, ctypes.c_void_p(out.data_ptr())))
         return out
 
+    # -- frame statistics -------------------------------------------------------------------
+    def frame_moments(self, frames, luma=True, laplacian=True, out=None):
+        """Exact moments of U8 RGB frames (st_frame_moments_u8c3_*): int64 (n, 8), row i = [sum Y, sum Y^2, sum L_R, sum L_G,
+        sum L_B, sum L_R^2, sum L_G^2, sum L_B^2] of frame i, Y the COLOR_RGB2YUV luma byte and L_c the reflect-101 Laplacian of
+        channel c.  ``luma`` / ``laplacian`` pick the moments computed (the others are 0).  frames: CUDA uint8 tensor
+        (n,h,w,3) or a list of (h,w,3) tensors of one shape."""
+        self._bind()
+        what = (_native.FM_LUMA if luma else 0) | (_native.FM_LAPLACIAN if laplacian else 0)
+        if isinstance(frames, (list, tuple)):
+            n = len(frames)
+            if n == 0:
+                return torch.zeros((0, 8), dtype=torch.int64, device=self.device)
+            for f in frames:
+                _require_cuda(f, torch.uint8, "frame", self.device)
+            if frames[0].dim() != 3 or frames[0].shape[2] != 3:
+                raise ValueError("frames must be (h,w,3)")
+            h, w, _ = frames[0].shape
+            if any(tuple(f.shape) != (h, w, 3) for f in frames):
+                raise ValueError("all frames must be (h,w,3) with equal shape")
+            out = (torch.empty((n, 8), dtype=torch.int64, device=self.device) if out is None
+                   else _check_out(out, (n, 8), torch.int64, self.device))
+            table = (ctypes.c_void_p * n)(*[f.data_ptr() for f in frames])
+            self._check(self._L.st_frame_moments_u8c3_batch(self._h, table, n, h, w, what, ctypes.c_void_p(out.data_ptr())))
+            return out
+        _require_cuda(frames, torch.uint8, "frames", self.device)
+        if frames.dim() != 4 or frames.shape[3] != 3:
+            raise ValueError("frames must be (n,h,w,3)")
+        n, h, w, _ = frames.shape
+        out = (torch.empty((n, 8), dtype=torch.int64, device=self.device) if out is None
+               else _check_out(out, (n, 8), torch.int64, self.device))
+        if n == 0:
+            return out
+        self._check(self._L.st_frame_moments_u8c3_strided(self._h, ctypes.c_void_p(frames.data_ptr()), 3 * h * w, n, h, w, what,
+                                                          ctypes.c_void_p(out.data_ptr())))
+        return out
+
+    def frame_stats(self, frames, kind):
+        """One frame statistic per frame (st_frame_stats_finish over st_frame_moments_u8c3_*): ``kind`` is a name of
+        _native.FS_KINDS or its value.  BrightnessCPP / ContrastCPP / SharpnessCPP give float32 (the element of the legacy C++
+        ops, old/cpp_ops/imgproc.cpp:50-175), Brightness / Contrast / Sharpness float64 (the value their Python twins
+        pickle, old/imgproc.py:11-37).  frames as for frame_moments."""
+        k = _native.FS_KINDS[kind] if isinstance(kind, str) else int(kind)
+        if k not in _native.FS_KINDS.values():
+            raise ValueError("unknown frame statistic %r" % (kind,))
+        sharp = k in (_native.FS_KINDS["SharpnessCPP"], _native.FS_KINDS["Sharpness"])
+        m = self.frame_moments(frames, luma=not sharp, laplacian=sharp)
+        n = m.shape[0]
+        out = torch.empty((n,), dtype=torch.float32 if k < 3 else torch.float64, device=self.device)
+        if n == 0:
+            return out
+        h, w = (frames[0].shape[0], frames[0].shape[1]) if isinstance(frames, (list, tuple)) else (frames.shape[1], frames.shape[2])
+        self._check(self._L.st_frame_stats_finish(self._h, ctypes.c_void_p(m.data_ptr()), n, h, w, k, ctypes.c_void_p(out.data_ptr())))
+        return out
+
     # -- flow consumers ---------------------------------------------------------------------
     def shot_boundaries(self, hist, window=500, k_std=2.5, return_diffs=False):
         """ShotBoundaries on device-resident histograms (shot_detection.py:12-28): hist = CUDA int32 (n, 3, bins) as

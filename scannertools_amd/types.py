@@ -28,6 +28,23 @@ def flow_histograms(buf, protobufs=None):
     return np.split(np.frombuffer(buf, dtype=np.dtype(np.int32)), 2)
 
 
+def frame_stat(buf, protobufs=None):
+    """One BrightnessCPP / ContrastCPP / SharpnessCPP element: a 4-byte float (the reference runners' parser,
+    ``struct.unpack('f', buf)[0]``, scannertools/old/imgproc.py:64,84,104)."""
+    if buf is None:
+        return None
+    import struct
+    return struct.unpack("f", buf)[0]
+
+
+def pickled(buf, protobufs=None):
+    """One Brightness / Contrast / Sharpness element: a pickled np.float64 (``pickle.loads``, old/imgproc.py:54,74,94)."""
+    if buf is None:
+        return None
+    import pickle
+    return pickle.loads(buf)
+
+
 def poses(buf, protobufs=None):
     """Reader of the CPM2Output op's element (cpm2_output_kernel_cpu.cpp:177-180:
     serialize_proto_vector_of_vectors<scanner::Point>): u64 people; per person u64 joints; per joint
