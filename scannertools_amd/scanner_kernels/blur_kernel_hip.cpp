@@ -15,7 +15,7 @@
 #include "scanner/util/memory.h"
 #include "proto_lite.h"
 #include "scannertools_hip.h"
-#include "stage.h"
+#include "kernel_core.h"
 
 namespace scanner {
 namespace {
@@ -36,60 +36,40 @@ bool parse_blur_args(const std::vector<u8>& args, i32* kernel_size, f32* sigma) 
 template <bool STAGED>
 class BlurKernelHIPImpl : public BatchedKernel, public VideoKernel {
  public:
-  BlurKernelHIPImpl(const KernelConfig& config)
-    : BatchedKernel(config), device_(config.devices[0]), gpu_(STAGED ? staging_device_id() : config.devices[0].id),
-      stage_(gpu_) {
+  BlurKernelHIPImpl(const KernelConfig& config) : BatchedKernel(config), core_(config, STAGED), stage_(core_.gpu) {
     // blur_kernel_cpu.cpp:29-33: an empty or unparsable BlurArgs invalidates the kernel
     if (!parse_blur_args(config.args, &kernel_size_, &sigma_)) {
-      RESULT_ERROR(&valid_, "Could not parse BlurArgs");
-      return;
+      RESULT_ERROR(&core_.valid, "Could not parse BlurArgs");
+    } else if (kernel_size_ < 1 || kernel_size_ > 31) {
+      RESULT_ERROR(&core_.valid, "Blur kernel_size must be in [1, 31], got %d", kernel_size_);
+    } else {
+      core_.open("BlurKernelHIP");
     }
-    if (!STAGED && device_.type != DeviceType::GPU) {
-      RESULT_ERROR(&valid_, "BlurKernelHIP runs on DeviceType::GPU only");
-      return;
-    }
-    if (kernel_size_ < 1 || kernel_size_ > 31) {
-      RESULT_ERROR(&valid_, "Blur kernel_size must be in [1, 31], got %d", kernel_size_);
-      return;
-    }
-    int st = st_ctx_create(gpu_, &ctx_);
-    if (st != ST_OK) RESULT_ERROR(&valid_, "st_ctx_create(%d) failed: %s (no CPU fallback exists)", gpu_, st_status_string(st));
   }
-  ~BlurKernelHIPImpl() {
-    if (ctx_) st_ctx_destroy(ctx_);
-  }
-  void validate(Result* result) override {
-    result->set_msg(valid_.msg());
-    result->set_success(valid_.success());
-  }
+  void validate(Result* result) override { core_.validate(result); }
 
   void execute(const BatchedElements& input_columns, BatchedElements& output_columns) override {
     auto& frame_col = input_columns[0];
     i32 input_count = (i32)num_rows(frame_col);
     if (input_count == 0) return;
-    check_frame(device_, frame_col[0]);
+    check_frame(core_.device, frame_col[0]);
     LOG_IF(FATAL, frame_info_.channels() != 3 || frame_info_.type != FrameType::U8)
         << "Blur expects U8 frames with 3 channels";
     const i32 h = frame_info_.height(), w = frame_info_.width();
     FrameInfo info = frame_col[0].as_const_frame()->as_frame_info();  // blur_kernel_cpu.cpp:58
-    std::vector<Frame*> output_frames = new_frames(device_, info, input_count);
-    src_.resize(input_count);
-    dst_.resize(input_count);
+    std::vector<Frame*> output_frames = new_frames(core_.device, info, input_count);
     if (STAGED) {
+      // device layout: [input_count frames][input_count blurred frames]
       const size_t frame_bytes = frame_info_.size(), stride = DeviceStage::align(frame_bytes);
-      u8* dev = stage_.reserve(2 * stride * input_count);
-      for (i32 i = 0; i < input_count; ++i) {
-        stage_.upload(dev + stride * i, frame_col[i].as_const_frame()->data, frame_bytes);
-        src_[i] = dev + stride * i;
-        dst_[i] = dev + stride * (input_count + i);
-      }
+      u8* dev = stage_.reserve(2 * stride * input_count), *dev_out = dev + stride * input_count;
+      stage_.upload_frames(dev, stride, frame_col, frame_bytes);
+      strided_ptrs(src_, input_count, dev, stride);
+      strided_ptrs(dst_, input_count, dev_out, stride);
       run(input_count, h, w);
-      for (i32 i = 0; i < input_count; ++i) stage_.download(output_frames[i]->data, dst_[i], frame_bytes);
+      stage_.download_frames(output_frames, dev_out, stride, frame_bytes);
     } else {
-      for (i32 i = 0; i < input_count; ++i) {
-        src_[i] = frame_col[i].as_const_frame()->data;
-        dst_[i] = output_frames[i]->data;
-      }
+      input_ptrs(src_, frame_col);
+      output_ptrs(dst_, output_frames);
       run(input_count, h, w);
     }
     for (i32 i = 0; i < input_count; ++i) insert_frame(output_columns[0], output_frames[i]);
@@ -97,19 +77,14 @@ class BlurKernelHIPImpl : public BatchedKernel, public VideoKernel {
 
  private:
   void run(i32 n, i32 h, i32 w) {
-    int st = st_box_blur_u8c3_batch(ctx_, src_.data(), n, h, w, kernel_size_, dst_.data());
-    LOG_IF(FATAL, st != ST_OK) << "st_box_blur_u8c3_batch: " << st_ctx_last_error(ctx_);
-    st = st_ctx_sync(ctx_);
-    LOG_IF(FATAL, st != ST_OK) << "st_ctx_sync: " << st_ctx_last_error(ctx_);
+    ST_CHECK(core_.ctx, st_box_blur_u8c3_batch(core_.ctx, src_.data(), n, h, w, kernel_size_, dst_.data()));
+    core_.sync();
   }
 
-  DeviceHandle device_;
-  int gpu_;
+  KernelCore core_;
   DeviceStage stage_;
   i32 kernel_size_ = 0;
   f32 sigma_ = 0.f;
-  Result valid_;
-  st_ctx* ctx_ = nullptr;
   std::vector<const uint8_t*> src_;
   std::vector<uint8_t*> dst_;
 };

@@ -23,7 +23,7 @@
 #include "scanner/util/memory.h"
 #include "proto_lite.h"
 #include "scannertools_hip.h"
-#include "stage.h"
+#include "kernel_core.h"
 
 namespace scanner {
 namespace {
@@ -136,26 +136,12 @@ const std::map<std::string, int> COLOR_CONVERSION_TYPES = {
 template <bool STAGED>
 class ConvertColorKernelHIPImpl : public BatchedKernel {
  public:
-  ConvertColorKernelHIPImpl(const KernelConfig& config)
-    : BatchedKernel(config), device_(config.devices[0]), gpu_(STAGED ? staging_device_id() : config.devices[0].id),
-      stage_(gpu_) {
-    valid_.set_success(true);
+  ConvertColorKernelHIPImpl(const KernelConfig& config) : BatchedKernel(config), core_(config, STAGED), stage_(core_.gpu) {
     const char* gb = getenv("SCANNERTOOLS_GRAY_BITS");
     gray_bits_ = gb && atoi(gb) == 14 ? 14 : 15;
-    if (!STAGED && device_.type != DeviceType::GPU) {
-      RESULT_ERROR(&valid_, "ConvertColorKernelHIP runs on DeviceType::GPU only");
-      return;
-    }
-    int st = st_ctx_create(gpu_, &ctx_);
-    if (st != ST_OK) RESULT_ERROR(&valid_, "st_ctx_create(%d) failed: %s (no CPU fallback exists)", gpu_, st_status_string(st));
+    core_.open("ConvertColorKernelHIP");
   }
-  ~ConvertColorKernelHIPImpl() {
-    if (ctx_) st_ctx_destroy(ctx_);
-  }
-  void validate(Result* result) override {
-    result->set_msg(valid_.msg());
-    result->set_success(valid_.success());
-  }
+  void validate(Result* result) override { core_.validate(result); }
 
   void new_stream(const std::vector<u8>& args) override {
     std::vector<proto_lite::Field> fields;
@@ -168,7 +154,7 @@ class ConvertColorKernelHIPImpl : public BatchedKernel {
     } else {
       // convert_color_kernel.cpp:231-236
       std::string err = "ConvertColor: invalid color conversion argument provided: " + conversion;
-      RESULT_ERROR(&valid_, "%s", err.c_str());
+      RESULT_ERROR(&core_.valid, "%s", err.c_str());
       code_ = -1;
     }
   }
@@ -177,7 +163,7 @@ class ConvertColorKernelHIPImpl : public BatchedKernel {
     auto& frame_col = input_columns[0];
     i32 input_count = (i32)num_rows(frame_col);
     if (input_count == 0) return;
-    LOG_IF(FATAL, code_ < 0) << valid_.msg();
+    LOG_IF(FATAL, code_ < 0) << core_.valid.msg();
     const Frame* frame = frame_col[0].as_const_frame();
     LOG_IF(FATAL, frame->type != FrameType::U8) << "ConvertColor expects U8 frames";
     int out_h = 0, out_w = 0, out_channels = 0;
@@ -185,42 +171,33 @@ class ConvertColorKernelHIPImpl : public BatchedKernel {
         << "ConvertColor: conversion " << code_ << " does not apply to " << frame->width() << "x" << frame->height() << " frames of "
         << frame->channels() << " channel(s)";
     FrameInfo info(out_h, out_w, out_channels, FrameType::U8);
-    std::vector<Frame*> output_frames = new_frames(device_, info, input_count);
-    src_.resize(input_count);
-    dst_.resize(input_count);
+    std::vector<Frame*> output_frames = new_frames(core_.device, info, input_count);
     const size_t in_bytes = frame->size(), out_bytes = info.size();
+    const size_t in_stride = DeviceStage::align(in_bytes), out_stride = DeviceStage::align(out_bytes);
+    u8* dev_out = nullptr;
     if (STAGED) {
-      const size_t in_stride = DeviceStage::align(in_bytes), out_stride = DeviceStage::align(out_bytes);
+      // device layout: [input_count frames][input_count converted frames]
       u8* dev = stage_.reserve((in_stride + out_stride) * input_count);
-      for (i32 i = 0; i < input_count; ++i) {
-        stage_.upload(dev + in_stride * i, frame_col[i].as_const_frame()->data, in_bytes);
-        src_[i] = dev + in_stride * i;
-        dst_[i] = dev + in_stride * input_count + out_stride * i;
-      }
+      dev_out = dev + in_stride * input_count;
+      stage_.upload_frames(dev, in_stride, frame_col, in_bytes);
+      strided_ptrs(src_, input_count, dev, in_stride);
+      strided_ptrs(dst_, input_count, dev_out, out_stride);
     } else {
-      for (i32 i = 0; i < input_count; ++i) {
-        src_[i] = frame_col[i].as_const_frame()->data;
-        dst_[i] = output_frames[i]->data;
-      }
+      input_ptrs(src_, frame_col);
+      output_ptrs(dst_, output_frames);
     }
-    int st = st_cvt_color_u8_batch(ctx_, src_.data(), input_count, frame->height(), frame->width(), frame->channels(),
-                                   code_, gray_bits_, dst_.data());
-    LOG_IF(FATAL, st != ST_OK) << "st_cvt_color_u8_batch: " << st_ctx_last_error(ctx_);
-    st = st_ctx_sync(ctx_);
-    LOG_IF(FATAL, st != ST_OK) << "st_ctx_sync: " << st_ctx_last_error(ctx_);
-    if (STAGED)
-      for (i32 i = 0; i < input_count; ++i) stage_.download(output_frames[i]->data, dst_[i], out_bytes);
+    ST_CHECK(core_.ctx, st_cvt_color_u8_batch(core_.ctx, src_.data(), input_count, frame->height(), frame->width(), frame->channels(),
+                                              code_, gray_bits_, dst_.data()));
+    core_.sync();
+    if (STAGED) stage_.download_frames(output_frames, dev_out, out_stride, out_bytes);
     for (i32 i = 0; i < input_count; ++i) insert_frame(output_columns[0], output_frames[i]);
   }
 
  private:
-  DeviceHandle device_;
-  int gpu_;
+  KernelCore core_;
   DeviceStage stage_;
   int code_ = -1;
   int gray_bits_ = 15;
-  Result valid_;
-  st_ctx* ctx_ = nullptr;
   std::vector<const uint8_t*> src_;
   std::vector<uint8_t*> dst_;
 };

@@ -21,7 +21,7 @@
 #include "pose_net.h"
 #include "proto_lite.h"
 #include "scannertools_hip.h"
-#include "stage.h"
+#include "kernel_core.h"
 
 namespace scanner {
 namespace {
@@ -47,87 +47,65 @@ bool parse_weights_path(const std::vector<u8>& args, std::string* path, std::str
 template <bool STAGED>
 class CPM2KernelHIPImpl : public BatchedKernel, public VideoKernel {
  public:
-  CPM2KernelHIPImpl(const KernelConfig& config)
-    : BatchedKernel(config), device_(config.devices[0]), gpu_(STAGED ? staging_device_id() : config.devices[0].id),
-      stage_(gpu_) {
+  CPM2KernelHIPImpl(const KernelConfig& config) : BatchedKernel(config), core_(config, STAGED), stage_(core_.gpu) {
     std::string path, prototxt;
     if (!parse_weights_path(config.args, &path, &prototxt)) {
-      RESULT_ERROR(&valid_, "Could not parse CPM2Args");
+      RESULT_ERROR(&core_.valid, "Could not parse CPM2Args");
       return;
     }
     if (path.empty()) {
-      RESULT_ERROR(&valid_, "CPM2: CPM2Args.caffe_args.net_descriptor.model_weights_path is empty");
+      RESULT_ERROR(&core_.valid, "CPM2: CPM2Args.caffe_args.net_descriptor.model_weights_path is empty");
       return;
     }
-    if (!STAGED && device_.type != DeviceType::GPU) {
-      RESULT_ERROR(&valid_, "CPM2KernelHIP runs on DeviceType::GPU only");
-      return;
-    }
-    int st = st_ctx_create(gpu_, &ctx_);
-    if (st != ST_OK) {
-      RESULT_ERROR(&valid_, "st_ctx_create(%d) failed: %s (no CPU fallback exists)", gpu_, st_status_string(st));
-      return;
-    }
-    if (hipSetDevice(gpu_) != hipSuccess) {
-      RESULT_ERROR(&valid_, "CPM2: hipSetDevice(%d) failed", gpu_);
+    if (!core_.open("CPM2KernelHIP")) return;
+    if (hipSetDevice(core_.gpu) != hipSuccess) {
+      RESULT_ERROR(&core_.valid, "CPM2: hipSetDevice(%d) failed", core_.gpu);
       return;
     }
     std::string err;
-    if (!net_.load(path, &err, prototxt)) RESULT_ERROR(&valid_, "CPM2: %s", err.c_str());
+    if (!net_.load(path, &err, prototxt)) RESULT_ERROR(&core_.valid, "CPM2: %s", err.c_str());
     for (int c = 0; c < 57; ++c) chan_[c] = c < pose::kHeat ? pose::kOffHeat + c : pose::kOffPaf + (c - pose::kHeat);
   }
   ~CPM2KernelHIPImpl() {
-    (void)hipSetDevice(gpu_);  // the network's buffers are freed by its destructor, on their device
-    if (ctx_) st_ctx_destroy(ctx_);
+    (void)hipSetDevice(core_.gpu);  // the network's buffers are freed by its destructor, on their device
   }
-  void validate(Result* result) override {
-    result->set_msg(valid_.msg());
-    result->set_success(valid_.success());
-  }
+  void validate(Result* result) override { core_.validate(result); }
 
   void execute(const BatchedElements& input_columns, BatchedElements& output_columns) override {
     auto& in_col = input_columns[0];
     const i32 n = (i32)num_rows(in_col);
     if (n == 0) return;
-    check_frame(device_, in_col[0]);
+    check_frame(core_.device, in_col[0]);
     // the input frame is CPM2Input's: FrameInfo(3, H, W, F32) (cpm2_input_kernel_gpu.cpp:112-113)
     LOG_IF(FATAL, frame_info_.shape[0] != 3 || frame_info_.type != FrameType::F32) << "CPM2 expects planar (3, H, W) F32 frames";
     const int H = frame_info_.shape[1], W = frame_info_.shape[2];
     LOG_IF(FATAL, H % 8 || W % 8) << "CPM2: the network input must be padded to a multiple of 8 (CPM2Input does)";
-    HIP_CHECK(hipSetDevice(gpu_));
+    check_batch_shape(in_col, frame_info_, "CPM2");
+    HIP_CHECK(hipSetDevice(core_.gpu));
     FrameInfo map_info(57, H, W, FrameType::F32), joint_info(pose::kHeat - 1, kMaxPeaks + 1, 3, FrameType::F32);
-    std::vector<Frame*> maps = new_frames(device_, map_info, n), joints = new_frames(device_, joint_info, n);
+    std::vector<Frame*> maps = new_frames(core_.device, map_info, n), joints = new_frames(core_.device, joint_info, n);
     const size_t in_bytes = frame_info_.size(), map_bytes = map_info.size(), joint_bytes = joint_info.size();
-    src_.resize(n); map_ptr_.resize(n); joint_ptr_.resize(n);
     if (STAGED) {
+      // device layout: [n inputs][n map stacks][n joint tables]
       const size_t is = DeviceStage::align(in_bytes), ms = DeviceStage::align(map_bytes), js = DeviceStage::align(joint_bytes);
       u8* dev = stage_.reserve((is + ms + js) * n);
-      for (i32 i = 0; i < n; ++i) {
-        LOG_IF(FATAL, in_col[i].as_const_frame()->as_frame_info() != frame_info_) << "CPM2: frame shape changes inside a batch";
-        stage_.upload(dev + is * i, in_col[i].as_const_frame()->data, in_bytes);
-        src_[i] = (const float*)(dev + is * i);
-        map_ptr_[i] = (float*)(dev + is * n + ms * i);
-        joint_ptr_[i] = (float*)(dev + (is + ms) * n + js * i);
-      }
+      stage_.upload_frames(dev, is, in_col, in_bytes);
+      strided_ptrs(src_, n, dev, is);
+      strided_ptrs(map_ptr_, n, dev + is * n, ms);
+      strided_ptrs(joint_ptr_, n, dev + (is + ms) * n, js);
     } else {
-      for (i32 i = 0; i < n; ++i) {
-        LOG_IF(FATAL, in_col[i].as_const_frame()->as_frame_info() != frame_info_) << "CPM2: frame shape changes inside a batch";
-        src_[i] = (const float*)in_col[i].as_const_frame()->data;
-        map_ptr_[i] = (float*)maps[i]->data;
-        joint_ptr_[i] = (float*)joints[i]->data;
-      }
+      input_ptrs(src_, in_col);
+      output_ptrs(map_ptr_, maps);
+      output_ptrs(joint_ptr_, joints);
     }
     std::string err;
     const auto net_start = now();  // caffe_kernel.cpp:381
-    const float* final_maps = net_.forward(ctx_, src_.data(), n, H, W, &err);
+    const float* final_maps = net_.forward(core_.ctx, src_.data(), n, H, W, &err);
     LOG_IF(FATAL, !final_maps) << "CPM2: " << err;
-    int st = st_cpm2_resize_maps(ctx_, final_maps, n, H / 8, W / 8, pose::kCatPad, chan_, 57, H, W, map_ptr_.data());
-    LOG_IF(FATAL, st != ST_OK) << "st_cpm2_resize_maps: " << st_ctx_last_error(ctx_);
+    ST_CHECK(core_.ctx, st_cpm2_resize_maps(core_.ctx, final_maps, n, H / 8, W / 8, pose::kCatPad, chan_, 57, H, W, map_ptr_.data()));
     cmap_ptr_.assign(map_ptr_.begin(), map_ptr_.end());
-    st = st_cpm2_nms(ctx_, cmap_ptr_.data(), n, H, W, pose::kHeat - 1, kMaxPeaks, kNmsThreshold, joint_ptr_.data());
-    LOG_IF(FATAL, st != ST_OK) << "st_cpm2_nms: " << st_ctx_last_error(ctx_);
-    st = st_ctx_sync(ctx_);
-    LOG_IF(FATAL, st != ST_OK) << "st_ctx_sync: " << st_ctx_last_error(ctx_);
+    ST_CHECK(core_.ctx, st_cpm2_nms(core_.ctx, cmap_ptr_.data(), n, H, W, pose::kHeat - 1, kMaxPeaks, kNmsThreshold, joint_ptr_.data()));
+    core_.sync();
     // the network + its resize / nms layers, complete on the device (the reference brackets net->Forward() the same way and
     // notes that the interval is only meaningful with a synchronisation, caffe_kernel.cpp:384-387)
     if (profiler_) profiler_->add_interval("caffe:net", net_start, now());
@@ -143,11 +121,8 @@ class CPM2KernelHIPImpl : public BatchedKernel, public VideoKernel {
   }
 
  private:
-  DeviceHandle device_;
-  int gpu_;
+  KernelCore core_;
   DeviceStage stage_;
-  Result valid_;
-  st_ctx* ctx_ = nullptr;
   pose::Net net_;
   int chan_[57];
   std::vector<const float*> src_, cmap_ptr_;

@@ -20,48 +20,35 @@
 #include "cpm2_parse.h"
 #include "proto_lite.h"
 #include "scannertools_hip.h"
-#include "stage.h"
+#include "kernel_core.h"
 
 namespace scanner {
 
 template <bool ON_GPU>
 class CPM2OutputKernelHIPImpl : public BatchedKernel, public VideoKernel {
  public:
-  CPM2OutputKernelHIPImpl(const KernelConfig& config)
-    : BatchedKernel(config), device_(config.devices[0]), stage_(ON_GPU ? config.devices[0].id : 0) {
+  // the host class is "staged" only in that it is registered on DeviceType::CPU: it opens no context and stages nothing
+  CPM2OutputKernelHIPImpl(const KernelConfig& config) : BatchedKernel(config), core_(config, !ON_GPU), stage_(core_.gpu) {
     std::vector<proto_lite::Field> fields;
     if (!proto_lite::parse(config.args.data(), config.args.size(), &fields)) {
-      RESULT_ERROR(&valid_, "Could not parse CPM2Args");
+      RESULT_ERROR(&core_.valid, "Could not parse CPM2Args");
       return;
     }
     for (auto& f : fields)
       if (f.number == 2 && f.wire == 5) scale_ = proto_lite::as_float(f);
     if (!(scale_ > 0.f)) {
-      RESULT_ERROR(&valid_, "CPM2Output: scale must be positive, got %f", scale_);
+      RESULT_ERROR(&core_.valid, "CPM2Output: scale must be positive, got %f", scale_);
       return;
     }
-    if (ON_GPU) {
-      if (device_.type != DeviceType::GPU) {
-        RESULT_ERROR(&valid_, "CPM2OutputKernelHIP runs on DeviceType::GPU only");
-        return;
-      }
-      int st = st_ctx_create(device_.id, &ctx_);
-      if (st != ST_OK) RESULT_ERROR(&valid_, "st_ctx_create(%d) failed: %s", device_.id, st_status_string(st));
-    }
+    if (ON_GPU) core_.open("CPM2OutputKernelHIP");
   }
-  ~CPM2OutputKernelHIPImpl() {
-    if (ctx_) st_ctx_destroy(ctx_);
-  }
-  void validate(Result* result) override {
-    result->set_msg(valid_.msg());
-    result->set_success(valid_.success());
-  }
+  void validate(Result* result) override { core_.validate(result); }
 
   void new_frame_info() override {
     // cpm2_output_kernel_cpu.cpp:123-137; frame_info_ is the ORIGINAL frame's (third input column)
     int rh, rw;
-    int st = st_cpm2_geometry(frame_info_.height(), frame_info_.width(), scale_, &rh, &rw, &net_input_height_, &net_input_width_);
-    LOG_IF(FATAL, st != ST_OK) << "CPM2Output: bad original frame info";
+    const bool ok = st_cpm2_geometry(frame_info_.height(), frame_info_.width(), scale_, &rh, &rw, &net_input_height_, &net_input_width_) == ST_OK;
+    LOG_IF(FATAL, !ok) << "CPM2Output: bad original frame info";
   }
 
   void execute(const BatchedElements& input_columns, BatchedElements& output_columns) override {
@@ -82,16 +69,13 @@ class CPM2OutputKernelHIPImpl : public BatchedKernel, public VideoKernel {
     scores_.resize(score_floats * input_count);
     peaks_.resize(peak_floats * input_count);
     if (ON_GPU) {
-      std::vector<const float*> hm(input_count), pk(input_count);
-      for (i32 b = 0; b < input_count; ++b) {
-        hm[b] = (const float*)input_columns[heatmap_idx][b].as_const_frame()->data;
-        pk[b] = (const float*)input_columns[joints_idx][b].as_const_frame()->data;
-      }
+      std::vector<const float*> hm, pk;
+      input_ptrs(hm, input_columns[heatmap_idx]);
+      input_ptrs(pk, input_columns[joints_idx]);
       float* dev_scores = (float*)stage_.reserve(score_floats * sizeof(f32) * input_count);
-      int st = st_cpm2_limb_scores(ctx_, hm.data(), pk.data(), input_count, H, W, mp, params_.inter_threshold,
-                                   params_.inter_min_above, dev_scores);
-      LOG_IF(FATAL, st != ST_OK) << "st_cpm2_limb_scores: " << st_ctx_last_error(ctx_);
-      LOG_IF(FATAL, st_ctx_sync(ctx_) != ST_OK) << "st_ctx_sync: " << st_ctx_last_error(ctx_);
+      ST_CHECK(core_.ctx, st_cpm2_limb_scores(core_.ctx, hm.data(), pk.data(), input_count, H, W, mp, params_.inter_threshold,
+                                              params_.inter_min_above, dev_scores));
+      core_.sync();
       stage_.download((u8*)scores_.data(), (const u8*)dev_scores, score_floats * sizeof(f32) * input_count);
       for (i32 b = 0; b < input_count; ++b)
         stage_.download((u8*)(peaks_.data() + peak_floats * b), (const u8*)pk[b], peak_floats * sizeof(f32));
@@ -108,20 +92,18 @@ class CPM2OutputKernelHIPImpl : public BatchedKernel, public VideoKernel {
       const int people = cpm2::assemble(scores_.data() + score_floats * b, peaks_.data() + peak_floats * b, frame_info_.height(),
                                         frame_info_.width(), H, W, params_, &joints);
       cpm2::serialize_people(joints, people, &bytes);
-      u8* buffer = new_buffer(device_, bytes.size());
-      memcpy_buffer(buffer, device_, bytes.data(), CPU_DEVICE, bytes.size());
+      u8* buffer = new_buffer(core_.device, bytes.size());
+      memcpy_buffer(buffer, core_.device, bytes.data(), CPU_DEVICE, bytes.size());
       insert_element(output_columns[0], buffer, bytes.size());
     }
   }
 
  private:
-  DeviceHandle device_;
+  KernelCore core_;
   DeviceStage stage_;
   f32 scale_ = 0.f;
   int net_input_width_ = 0, net_input_height_ = 0;
   cpm2::Params params_;
-  Result valid_;
-  st_ctx* ctx_ = nullptr;
   std::vector<float> scores_, peaks_;
 };
 

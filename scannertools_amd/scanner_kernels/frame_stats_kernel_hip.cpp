@@ -17,7 +17,7 @@
 #include "scanner/util/memory.h"
 #include "proto_lite.h"
 #include "scannertools_hip.h"
-#include "stage.h"
+#include "kernel_core.h"
 
 namespace scanner {
 namespace {
@@ -28,6 +28,7 @@ bool parse_imgproc_args(const std::vector<u8>& args) {
 }
 
 const char* const kOpNames[] = {"BrightnessCPP", "ContrastCPP", "SharpnessCPP"};
+const char* const kClassNames[] = {"BrightnessKernelHIP", "ContrastKernelHIP", "SharpnessKernelHIP"};
 }  // namespace
 
 // KIND: ST_FS_BRIGHTNESS_CPP, ST_FS_CONTRAST_CPP or ST_FS_SHARPNESS_CPP.  STAGED: registered on DeviceType::CPU (host frames
@@ -35,74 +36,51 @@ const char* const kOpNames[] = {"BrightnessCPP", "ContrastCPP", "SharpnessCPP"};
 template <int KIND, bool STAGED>
 class FrameStatsKernelHIP : public BatchedKernel, public VideoKernel {
  public:
-  FrameStatsKernelHIP(const KernelConfig& config)
-    : BatchedKernel(config), device_(config.devices[0]), gpu_(STAGED ? staging_device_id() : config.devices[0].id), stage_(gpu_) {
-    if (!parse_imgproc_args(config.args)) {
-      RESULT_ERROR(&valid_, "%s: could not parse ImgProcArgs", kOpNames[KIND]);
-    } else if (!STAGED && device_.type != DeviceType::GPU) {
-      RESULT_ERROR(&valid_, "%s: the GPU kernel class runs on DeviceType::GPU only", kOpNames[KIND]);
-    } else {
-      int st = st_ctx_create(gpu_, &ctx_);
-      if (st != ST_OK) RESULT_ERROR(&valid_, "st_ctx_create(%d) failed: %s (no CPU fallback exists)", gpu_, st_status_string(st));
-    }
+  FrameStatsKernelHIP(const KernelConfig& config) : BatchedKernel(config), core_(config, STAGED), stage_(core_.gpu) {
+    if (!parse_imgproc_args(config.args)) RESULT_ERROR(&core_.valid, "%s: could not parse ImgProcArgs", kOpNames[KIND]);
+    else core_.open(kClassNames[KIND]);
   }
-  ~FrameStatsKernelHIP() {
-    if (ctx_) st_ctx_destroy(ctx_);
-  }
-  void validate(Result* result) override {
-    result->set_msg(valid_.msg());
-    result->set_success(valid_.success());
-  }
+  void validate(Result* result) override { core_.validate(result); }
 
   void execute(const BatchedElements& input_columns, BatchedElements& output_columns) override {
     auto& frame_col = input_columns[0];
     const i32 n = (i32)num_rows(frame_col);
     if (n == 0) return;
-    check_frame(device_, frame_col[0]);
+    check_frame(core_.device, frame_col[0]);
     LOG_IF(FATAL, frame_info_.channels() != 3 || frame_info_.type != FrameType::U8) << kOpNames[KIND] << " expects U8 frames with 3 channels";
-    for (i32 i = 0; i < n; ++i)
-      LOG_IF(FATAL, frame_col[i].as_const_frame()->as_frame_info() != frame_info_)
-          << kOpNames[KIND] << ": frame " << i << " changes shape inside a batch";
+    check_batch_shape(frame_col, frame_info_, kOpNames[KIND]);
     const i32 h = frame_info_.height(), w = frame_info_.width();
     const int what = KIND == ST_FS_SHARPNESS_CPP ? ST_FM_LAPLACIAN : ST_FM_LUMA;   // brightness and contrast skip the Laplacian
     const size_t frame_bytes = frame_info_.size(), stride = DeviceStage::align(frame_bytes);
     const size_t moments_bytes = DeviceStage::align(sizeof(int64_t) * 8 * (size_t)n);
-    int st;
+    st_ctx* ctx = core_.ctx;
     if (STAGED) {
+      // device layout: [n frames][moments][n results]
       u8* dev = stage_.reserve(stride * n + moments_bytes + sizeof(float) * (size_t)n);
-      for (i32 i = 0; i < n; ++i) stage_.upload(dev + stride * i, frame_col[i].as_const_frame()->data, frame_bytes);
+      stage_.upload_frames(dev, stride, frame_col, frame_bytes);
       int64_t* moments = (int64_t*)(dev + stride * n);
       float* out = (float*)(dev + stride * n + moments_bytes);
-      st = st_frame_moments_u8c3_strided(ctx_, dev, stride, n, h, w, what, moments);
-      LOG_IF(FATAL, st != ST_OK) << "st_frame_moments_u8c3_strided: " << st_ctx_last_error(ctx_);
-      st = st_frame_stats_finish(ctx_, moments, n, h, w, KIND, out);
-      LOG_IF(FATAL, st != ST_OK) << "st_frame_stats_finish: " << st_ctx_last_error(ctx_);
-      LOG_IF(FATAL, st_ctx_sync(ctx_) != ST_OK) << "st_ctx_sync: " << st_ctx_last_error(ctx_);
-      u8* output_block = new_block_buffer_size(device_, sizeof(float), n);
+      ST_CHECK(ctx, st_frame_moments_u8c3_strided(ctx, dev, stride, n, h, w, what, moments));
+      ST_CHECK(ctx, st_frame_stats_finish(ctx, moments, n, h, w, KIND, out));
+      core_.sync();
+      u8* output_block = new_block_buffer_size(core_.device, sizeof(float), n);
       stage_.download(output_block, (const u8*)out, sizeof(float) * (size_t)n);
       for (i32 i = 0; i < n; ++i) insert_element(output_columns[0], output_block + i * sizeof(float), sizeof(float));
     } else {
       int64_t* moments = (int64_t*)stage_.reserve(moments_bytes);
-      frames_.resize(n);
-      for (i32 i = 0; i < n; ++i) frames_[i] = frame_col[i].as_const_frame()->data;
+      input_ptrs(frames_, frame_col);
       // one device block for the whole batch, one reference per output element
-      u8* output_block = new_block_buffer(device_, sizeof(float) * (size_t)n, n);
-      st = st_frame_moments_u8c3_batch(ctx_, frames_.data(), n, h, w, what, moments);
-      LOG_IF(FATAL, st != ST_OK) << "st_frame_moments_u8c3_batch: " << st_ctx_last_error(ctx_);
-      st = st_frame_stats_finish(ctx_, moments, n, h, w, KIND, output_block);
-      LOG_IF(FATAL, st != ST_OK) << "st_frame_stats_finish: " << st_ctx_last_error(ctx_);
-      st = st_ctx_sync(ctx_);  // the engine may read the elements from another stream
-      LOG_IF(FATAL, st != ST_OK) << "st_ctx_sync: " << st_ctx_last_error(ctx_);
+      u8* output_block = new_block_buffer(core_.device, sizeof(float) * (size_t)n, n);
+      ST_CHECK(ctx, st_frame_moments_u8c3_batch(ctx, frames_.data(), n, h, w, what, moments));
+      ST_CHECK(ctx, st_frame_stats_finish(ctx, moments, n, h, w, KIND, output_block));
+      core_.sync();  // the engine may read the elements from another stream
       for (i32 i = 0; i < n; ++i) insert_element(output_columns[0], output_block + i * sizeof(float), sizeof(float));
     }
   }
 
  private:
-  DeviceHandle device_;
-  int gpu_;
+  KernelCore core_;
   DeviceStage stage_;   // staged: frames + moments + results; GPU: the moments record
-  Result valid_;
-  st_ctx* ctx_ = nullptr;
   std::vector<const uint8_t*> frames_;
 };
 

@@ -21,7 +21,7 @@
 #include "scanner/util/memory.h"
 #include "proto_lite.h"
 #include "scannertools_hip.h"
-#include "stage.h"
+#include "kernel_core.h"
 
 namespace scanner {
 namespace {
@@ -41,61 +41,41 @@ bool parse_histogram_args(const std::vector<u8>& args, i32* bins) {
 
 class HistogramKernelHIP : public BatchedKernel, public VideoKernel {
  public:
-  HistogramKernelHIP(const KernelConfig& config)
-    : BatchedKernel(config), device_(config.devices[0]), bins_(BINS) {
+  HistogramKernelHIP(const KernelConfig& config) : BatchedKernel(config), core_(config, false), bins_(BINS) {
     if (!parse_histogram_args(config.args, &bins_)) {
-      RESULT_ERROR(&valid_, "Could not parse HistogramArgs");
-    } else if (device_.type != DeviceType::GPU) {
-      RESULT_ERROR(&valid_, "HistogramKernelHIP runs on DeviceType::GPU only");
+      RESULT_ERROR(&core_.valid, "Could not parse HistogramArgs");
     } else if (bins_ < 1 || bins_ > 256) {
-      RESULT_ERROR(&valid_, "Histogram bins must be in [1, 256], got %d", bins_);
+      RESULT_ERROR(&core_.valid, "Histogram bins must be in [1, 256], got %d", bins_);
     } else {
-      int st = st_ctx_create(device_.id, &ctx_);
-      if (st != ST_OK) RESULT_ERROR(&valid_, "st_ctx_create(%d) failed: %s", device_.id, st_status_string(st));
+      core_.open("HistogramKernelHIP");
     }
   }
-
-  ~HistogramKernelHIP() {
-    if (ctx_) st_ctx_destroy(ctx_);
-  }
-
-  void validate(Result* result) override {
-    result->set_msg(valid_.msg());
-    result->set_success(valid_.success());
-  }
+  void validate(Result* result) override { core_.validate(result); }
 
   void execute(const BatchedElements& input_columns, BatchedElements& output_columns) override {
     auto& frame_col = input_columns[0];
     i32 input_count = (i32)num_rows(frame_col);
     if (input_count == 0) return;
-    check_frame(device_, frame_col[0]);
+    check_frame(core_.device, frame_col[0]);
     LOG_IF(FATAL, frame_info_.channels() != 3 || frame_info_.type != FrameType::U8)
         << "Histogram expects U8 frames with 3 channels";
+    check_batch_shape(frame_col, frame_info_, "Histogram");
 
     size_t hist_size = bins_ * 3 * sizeof(i32);
     // one device block for the whole batch, one reference per output element
-    u8* output_block = new_block_buffer(device_, hist_size * input_count, input_count);
+    u8* output_block = new_block_buffer(core_.device, hist_size * input_count, input_count);
 
-    frames_.resize(input_count);
-    for (i32 i = 0; i < input_count; ++i) {
-      const Frame* f = frame_col[i].as_const_frame();
-      LOG_IF(FATAL, f->as_frame_info() != frame_info_) << "Histogram: frame " << i << " changes shape inside a batch";
-      frames_[i] = f->data;
-    }
-    int st = st_hist_u8c3_batch(ctx_, frames_.data(), input_count, frame_info_.height(), frame_info_.width(), bins_,
-                                (int32_t*)output_block);
-    LOG_IF(FATAL, st != ST_OK) << "st_hist_u8c3_batch: " << st_ctx_last_error(ctx_);
-    st = st_ctx_sync(ctx_);  // the engine may read the elements from another stream
-    LOG_IF(FATAL, st != ST_OK) << "st_ctx_sync: " << st_ctx_last_error(ctx_);
+    input_ptrs(frames_, frame_col);
+    ST_CHECK(core_.ctx, st_hist_u8c3_batch(core_.ctx, frames_.data(), input_count, frame_info_.height(), frame_info_.width(), bins_,
+                                           (int32_t*)output_block));
+    core_.sync();  // the engine may read the elements from another stream
 
     for (i32 i = 0; i < input_count; ++i) insert_element(output_columns[0], output_block + i * hist_size, hist_size);
   }
 
  private:
-  DeviceHandle device_;
+  KernelCore core_;
   i32 bins_;
-  Result valid_;
-  st_ctx* ctx_ = nullptr;
   std::vector<const uint8_t*> frames_;
 };
 
@@ -108,41 +88,25 @@ class HistogramKernelHIP : public BatchedKernel, public VideoKernel {
 class HistogramKernelHIPStaged : public BatchedKernel, public VideoKernel {
  public:
   HistogramKernelHIPStaged(const KernelConfig& config)
-    : BatchedKernel(config), device_(config.devices[0]), bins_(BINS), gpu_(staging_device_id()), pipe_(gpu_), out_stage_(gpu_) {
-    const char* e = getenv("SCANNERTOOLS_HIST_SUBBATCH");
-    sub_ = e ? atoi(e) : 8;
-    if (sub_ < 1) sub_ = 1;
+    : BatchedKernel(config), core_(config, true), bins_(BINS), sub_(env_int("SCANNERTOOLS_HIST_SUBBATCH", 8, 1)), out_stage_(core_.gpu) {
     if (!parse_histogram_args(config.args, &bins_)) {
-      RESULT_ERROR(&valid_, "Could not parse HistogramArgs");
+      RESULT_ERROR(&core_.valid, "Could not parse HistogramArgs");
     } else if (bins_ < 1 || bins_ > 256) {
-      RESULT_ERROR(&valid_, "Histogram bins must be in [1, 256], got %d", bins_);
-    } else {
-      int st = st_ctx_create(gpu_, &ctx_);
-      if (st != ST_OK) {
-        RESULT_ERROR(&valid_, "st_ctx_create(%d) failed: %s (no CPU fallback exists)", gpu_, st_status_string(st));
-      } else if (!pipe_.init() || st_ctx_set_stream(ctx_, pipe_.compute_stream()) != ST_OK) {
-        RESULT_ERROR(&valid_, "cannot create the upload pipeline on device %d", gpu_);
-      }
+      RESULT_ERROR(&core_.valid, "Histogram bins must be in [1, 256], got %d", bins_);
+    } else if (core_.open("HistogramKernelHIPStaged")) {
+      core_.bind(&pipe_);
     }
   }
-  ~HistogramKernelHIPStaged() {
-    if (ctx_) st_ctx_destroy(ctx_);
-  }
-  void validate(Result* result) override {
-    result->set_msg(valid_.msg());
-    result->set_success(valid_.success());
-  }
+  void validate(Result* result) override { core_.validate(result); }
 
   void execute(const BatchedElements& input_columns, BatchedElements& output_columns) override {
     auto& frame_col = input_columns[0];
     i32 input_count = (i32)num_rows(frame_col);
     if (input_count == 0) return;
-    check_frame(device_, frame_col[0]);
+    check_frame(core_.device, frame_col[0]);
     LOG_IF(FATAL, frame_info_.channels() != 3 || frame_info_.type != FrameType::U8)
         << "Histogram expects U8 frames with 3 channels";
-    for (i32 i = 0; i < input_count; ++i)
-      LOG_IF(FATAL, frame_col[i].as_const_frame()->as_frame_info() != frame_info_)
-          << "Histogram: frame " << i << " changes shape inside a batch";
+    check_batch_shape(frame_col, frame_info_, "Histogram");
     const size_t hist_size = bins_ * 3 * sizeof(i32);
     const size_t frame_bytes = frame_info_.size(), stride = DeviceStage::align(frame_bytes);
     const i32 h = frame_info_.height(), w = frame_info_.width();
@@ -150,24 +114,20 @@ class HistogramKernelHIPStaged : public BatchedKernel, public VideoKernel {
     pipe_.run(input_count, sub_, frame_bytes, stride,
               [&](i32 i) { return (const u8*)frame_col[i].as_const_frame()->data; },
               [&](u8* dev, i32 first, i32 nb) {
-                int st = st_hist_u8c3_strided(ctx_, dev, stride, nb, h, w, bins_, (int32_t*)(dev_out + hist_size * first));
-                LOG_IF(FATAL, st != ST_OK) << "st_hist_u8c3_strided: " << st_ctx_last_error(ctx_);
+                ST_CHECK(core_.ctx, st_hist_u8c3_strided(core_.ctx, dev, stride, nb, h, w, bins_, (int32_t*)(dev_out + hist_size * first)));
               });
-    u8* output_block = new_block_buffer_size(device_, hist_size, input_count);
+    u8* output_block = new_block_buffer_size(core_.device, hist_size, input_count);
     HIP_CHECK(hipMemcpyAsync(output_block, dev_out, hist_size * input_count, hipMemcpyDeviceToHost, pipe_.compute_stream()));
     pipe_.drain();
     for (i32 i = 0; i < input_count; ++i) insert_element(output_columns[0], output_block + i * hist_size, hist_size);
   }
 
  private:
-  DeviceHandle device_;
+  UploadPipeline pipe_;  // before core_: the context leaves the pipeline's stream before the stream is destroyed
+  KernelCore core_;
   i32 bins_;
-  int gpu_;
-  int sub_ = 8;
-  UploadPipeline pipe_;
+  int sub_;
   DeviceStage out_stage_;
-  Result valid_;
-  st_ctx* ctx_ = nullptr;
 };
 
 REGISTER_OP(Histogram).frame_input("frame").output("histogram", ColumnType::Bytes, "Histogram").protobuf_name("HistogramArgs");

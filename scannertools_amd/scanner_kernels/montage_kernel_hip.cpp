@@ -17,7 +17,7 @@
 #include "scanner/util/memory.h"
 #include "proto_lite.h"
 #include "scannertools_hip.h"
-#include "stage.h"
+#include "kernel_core.h"
 
 namespace scanner {
 namespace {
@@ -45,63 +45,42 @@ template <bool STAGED>
 class MontageKernelHIPImpl : public BatchedKernel, public VideoKernel {
  public:
   MontageKernelHIPImpl(const KernelConfig& config)
-    : BatchedKernel(config), device_(config.devices[0]), gpu_(STAGED ? staging_device_id() : config.devices[0].id),
-      canvas_device_{DeviceType::GPU, gpu_}, pipe_(gpu_) {
-    if (!STAGED && device_.type != DeviceType::GPU) {
-      RESULT_ERROR(&valid_, "MontageKernelHIP runs on DeviceType::GPU only");
-      return;
-    }
+    : BatchedKernel(config), core_(config, STAGED), canvas_device_{DeviceType::GPU, core_.gpu} {
     if (!parse_montage_args(config.args, &args_)) {
-      RESULT_ERROR(&valid_, "Montage: could not parse MontageArgs");
-      return;
-    }
-    if (args_.num_frames < 1) {
-      RESULT_ERROR(&valid_, "Montage: num_frames must be at least 1 (got %lld)", (long long)args_.num_frames);
-      return;
-    }
-    if (args_.frames_per_row < 1) {
-      RESULT_ERROR(&valid_, "Montage: frames_per_row must be at least 1 (got %d)", args_.frames_per_row);
-      return;
-    }
-    if (args_.target_width < 1) {
-      RESULT_ERROR(&valid_, "Montage: target_width must be at least 1 (got %d)", args_.target_width);
-      return;
-    }
-    int st = st_ctx_create(gpu_, &ctx_);
-    if (st != ST_OK) {
-      RESULT_ERROR(&valid_, "st_ctx_create(%d) failed: %s (no CPU fallback exists)", gpu_, st_status_string(st));
-    } else if (STAGED && (!pipe_.init() || st_ctx_set_stream(ctx_, pipe_.compute_stream()) != ST_OK)) {
-      RESULT_ERROR(&valid_, "cannot create the upload pipeline on device %d", gpu_);
+      RESULT_ERROR(&core_.valid, "Montage: could not parse MontageArgs");
+    } else if (args_.num_frames < 1) {
+      RESULT_ERROR(&core_.valid, "Montage: num_frames must be at least 1 (got %lld)", (long long)args_.num_frames);
+    } else if (args_.frames_per_row < 1) {
+      RESULT_ERROR(&core_.valid, "Montage: frames_per_row must be at least 1 (got %d)", args_.frames_per_row);
+    } else if (args_.target_width < 1) {
+      RESULT_ERROR(&core_.valid, "Montage: target_width must be at least 1 (got %d)", args_.target_width);
+    } else if (core_.open("MontageKernelHIP") && STAGED) {
+      core_.bind(&pipe_);
     }
   }
   ~MontageKernelHIPImpl() {
     // every execute() ends synchronised, so an unfinished canvas has no work in flight
     if (canvas_) delete_buffer(canvas_device_, canvas_);
-    if (placeholder_) delete_buffer(device_, placeholder_);  // the rows handed out keep their own references
-    if (ctx_) st_ctx_destroy(ctx_);
+    if (placeholder_) delete_buffer(core_.device, placeholder_);  // the rows handed out keep their own references
   }
-  void validate(Result* result) override {
-    result->set_msg(valid_.msg());
-    result->set_success(valid_.success());
-  }
+  void validate(Result* result) override { core_.validate(result); }
 
   // a fresh zeroed canvas; nothing before the first frame has fixed the geometry
   void reset() override {
     if (montage_w_ == 0) return;
     if (canvas_) delete_buffer(canvas_device_, canvas_);
     canvas_ = new_buffer(canvas_device_, canvas_bytes());
-    int st = st_montage_clear(ctx_, canvas_, montage_h_, montage_w_);
-    LOG_IF(FATAL, st != ST_OK) << "st_montage_clear: " << st_ctx_last_error(ctx_);
+    ST_CHECK(core_.ctx, st_montage_clear(core_.ctx, canvas_, montage_h_, montage_w_));
     frames_seen_ = 0;
   }
 
   void new_frame_info() override {
-    int st = st_montage_geometry(frame_info_.height(), frame_info_.width(), args_.num_frames, args_.target_width,
-                                 args_.frames_per_row, &target_h_, &montage_h_, &montage_w_);
-    LOG_IF(FATAL, st != ST_OK) << "Montage: no canvas for " << frame_info_.width() << "x" << frame_info_.height()
+    const bool ok = st_montage_geometry(frame_info_.height(), frame_info_.width(), args_.num_frames, args_.target_width,
+                                        args_.frames_per_row, &target_h_, &montage_h_, &montage_w_) == ST_OK;
+    LOG_IF(FATAL, !ok) << "Montage: no canvas for " << frame_info_.width() << "x" << frame_info_.height()
                                << " frames at target_width " << args_.target_width << " (tile height below 1 or canvas too large)";
     LOG_IF(FATAL, montage_h_ > INT32_MAX) << "Montage: a canvas of " << montage_h_ << " rows is taller than a frame can be";
-    if (placeholder_) delete_buffer(device_, placeholder_);
+    if (placeholder_) delete_buffer(core_.device, placeholder_);
     placeholder_ = nullptr;
     reset();
   }
@@ -112,9 +91,8 @@ class MontageKernelHIPImpl : public BatchedKernel, public VideoKernel {
     if (input_count == 0) return;
     const Frame* frame = frame_col[0].as_const_frame();
     LOG_IF(FATAL, frame->type != FrameType::U8 || frame->channels() != 3) << "Montage expects U8 frames of 3 channels";
-    check_frame(device_, frame_col[0]);
-    for (i32 i = 1; i < input_count; ++i)
-      LOG_IF(FATAL, frame_col[i].as_const_frame()->as_frame_info() != frame_info_) << "Montage: frame " << i << " changes shape inside a batch";
+    check_frame(core_.device, frame_col[0]);
+    check_batch_shape(frame_col, frame_info_, "Montage");
     LOG_IF(FATAL, canvas_ == nullptr || frames_seen_ + input_count > args_.num_frames)
         << "Montage: row " << frames_seen_ + input_count - 1 << " is beyond num_frames = " << args_.num_frames;
 
@@ -123,9 +101,8 @@ class MontageKernelHIPImpl : public BatchedKernel, public VideoKernel {
     const int first_slot = (int)frames_seen_;
     src_.resize(input_count);
     auto launch = [&](const uint8_t* const* src, i32 first, i32 nb) {
-      int st = st_montage_u8c3_batch(ctx_, src, nb, fh, fw, canvas_, montage_w_, args_.target_width, target_h_,
-                                     args_.frames_per_row, first_slot + first);
-      LOG_IF(FATAL, st != ST_OK) << "st_montage_u8c3_batch: " << st_ctx_last_error(ctx_);
+      ST_CHECK(core_.ctx, st_montage_u8c3_batch(core_.ctx, src, nb, fh, fw, canvas_, montage_w_, args_.target_width, target_h_,
+                                                args_.frames_per_row, first_slot + first));
     };
     frames_seen_ += input_count;
     const bool finished = frames_seen_ == args_.num_frames;
@@ -140,7 +117,7 @@ class MontageKernelHIPImpl : public BatchedKernel, public VideoKernel {
                   launch(src_.data() + first, first, nb);
                 });
       if (finished) {
-        handed = new_buffer(device_, canvas_bytes());
+        handed = new_buffer(core_.device, canvas_bytes());
         HIP_CHECK(hipMemcpyAsync(handed, canvas_, canvas_bytes(), hipMemcpyDeviceToHost, pipe_.compute_stream()));
       }
       pipe_.drain();
@@ -149,10 +126,9 @@ class MontageKernelHIPImpl : public BatchedKernel, public VideoKernel {
         canvas_ = nullptr;
       }
     } else {
-      for (i32 i = 0; i < input_count; ++i) src_[i] = frame_col[i].as_const_frame()->data;
+      input_ptrs(src_, frame_col);
       launch(src_.data(), 0, input_count);
-      int st = st_ctx_sync(ctx_);
-      LOG_IF(FATAL, st != ST_OK) << "st_ctx_sync: " << st_ctx_last_error(ctx_);
+      core_.sync();
       if (finished) {
         handed = canvas_;  // now Scanner's
         canvas_ = nullptr;
@@ -164,8 +140,8 @@ class MontageKernelHIPImpl : public BatchedKernel, public VideoKernel {
     FrameInfo info((int)montage_h_, montage_w_, 3, FrameType::U8);
     const i32 n_other = input_count - (finished ? 1 : 0);
     if (n_other > 0) {
-      if (!placeholder_) placeholder_ = new_buffer(device_, canvas_bytes());
-      add_buffer_refs(device_, placeholder_, (size_t)n_other);
+      if (!placeholder_) placeholder_ = new_buffer(core_.device, canvas_bytes());
+      add_buffer_refs(core_.device, placeholder_, (size_t)n_other);
     }
     for (i32 i = 0; i < input_count; ++i) {
       const bool last = finished && i == input_count - 1;
@@ -176,13 +152,10 @@ class MontageKernelHIPImpl : public BatchedKernel, public VideoKernel {
  private:
   size_t canvas_bytes() const { return (size_t)montage_h_ * (size_t)montage_w_ * 3; }
 
-  DeviceHandle device_;
-  int gpu_;
+  UploadPipeline pipe_;  // before core_: the context leaves the pipeline's stream before the stream is destroyed
+  KernelCore core_;
   DeviceHandle canvas_device_;
-  UploadPipeline pipe_;
   MontageArgsLite args_;
-  Result valid_;
-  st_ctx* ctx_ = nullptr;
   int target_h_ = 0, montage_w_ = 0;
   int64_t montage_h_ = 0;
   u8* canvas_ = nullptr;

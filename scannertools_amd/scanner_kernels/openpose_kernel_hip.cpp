@@ -25,7 +25,7 @@
 #include "pose_net.h"
 #include "proto_lite.h"
 #include "scannertools_hip.h"
-#include "stage.h"
+#include "kernel_core.h"
 
 namespace scanner {
 namespace {
@@ -58,38 +58,28 @@ bool parse_args(const std::vector<u8>& bytes, OpenPoseArgs* a) {
 template <bool STAGED>
 class OpenPoseKernelHIPImpl : public BatchedKernel, public VideoKernel {
  public:
-  OpenPoseKernelHIPImpl(const KernelConfig& config)
-    : BatchedKernel(config), device_(config.devices[0]), gpu_(STAGED ? staging_device_id() : config.devices[0].id),
-      stage_(gpu_) {
+  OpenPoseKernelHIPImpl(const KernelConfig& config) : BatchedKernel(config), core_(config, STAGED), stage_(core_.gpu) {
     if (!parse_args(config.args, &args_)) {
-      RESULT_ERROR(&valid_, "Could not parse OpenPoseArgs");
+      RESULT_ERROR(&core_.valid, "Could not parse OpenPoseArgs");
       return;
     }
     if (args_.compute_hands || args_.compute_face) {
-      RESULT_ERROR(&valid_, "OpenPose: compute_hands / compute_face need the hand and face networks, which this build does not have");
+      RESULT_ERROR(&core_.valid, "OpenPose: compute_hands / compute_face need the hand and face networks, which this build does not have");
       return;
     }
     scales_ = args_.pose_num_scales < 1 ? 1 : args_.pose_num_scales;  // proto3 default 0 = one scale
     if (scales_ > 8 || !(args_.pose_scale_gap >= 0.f) || (scales_ > 1 && !(1.f - (scales_ - 1) * args_.pose_scale_gap > 0.05f))) {
-      RESULT_ERROR(&valid_, "OpenPose: pose_num_scales = %d with pose_scale_gap = %f is outside what is supported (<= 8 scales, smallest above 0.05)",
+      RESULT_ERROR(&core_.valid, "OpenPose: pose_num_scales = %d with pose_scale_gap = %f is outside what is supported (<= 8 scales, smallest above 0.05)",
                    scales_, args_.pose_scale_gap);
       return;
     }
     if (args_.model_directory.empty()) {
-      RESULT_ERROR(&valid_, "OpenPose: OpenPoseArgs.model_directory is empty (the reference downloads the model there; this build does not)");
+      RESULT_ERROR(&core_.valid, "OpenPose: OpenPoseArgs.model_directory is empty (the reference downloads the model there; this build does not)");
       return;
     }
-    if (!STAGED && device_.type != DeviceType::GPU) {
-      RESULT_ERROR(&valid_, "OpenPoseKernelHIP runs on DeviceType::GPU only");
-      return;
-    }
-    int st = st_ctx_create(gpu_, &ctx_);
-    if (st != ST_OK) {
-      RESULT_ERROR(&valid_, "st_ctx_create(%d) failed: %s (no CPU fallback exists)", gpu_, st_status_string(st));
-      return;
-    }
-    if (hipSetDevice(gpu_) != hipSuccess) {
-      RESULT_ERROR(&valid_, "OpenPose: hipSetDevice(%d) failed", gpu_);
+    if (!core_.open("OpenPoseKernelHIP")) return;
+    if (hipSetDevice(core_.gpu) != hipSuccess) {
+      RESULT_ERROR(&core_.valid, "OpenPose: hipSetDevice(%d) failed", core_.gpu);
       return;
     }
     std::string err;
@@ -110,17 +100,13 @@ class OpenPoseKernelHIPImpl : public BatchedKernel, public VideoKernel {
       }
     }
     const bool loaded = net_.load(model, &err, proto);
-    if (!loaded) RESULT_ERROR(&valid_, "OpenPose: %s", err.c_str());
+    if (!loaded) RESULT_ERROR(&core_.valid, "OpenPose: %s", err.c_str());
     for (int c = 0; c < 57; ++c) chan_[c] = c < pose::kHeat ? pose::kOffHeat + c : pose::kOffPaf + (c - pose::kHeat);
   }
   ~OpenPoseKernelHIPImpl() {
-    (void)hipSetDevice(gpu_);
-    if (ctx_) st_ctx_destroy(ctx_);
+    (void)hipSetDevice(core_.gpu);  // the network's buffers are freed by its destructor, on their device
   }
-  void validate(Result* result) override {
-    result->set_msg(valid_.msg());
-    result->set_success(valid_.success());
-  }
+  void validate(Result* result) override { core_.validate(result); }
 
   void new_frame_info() override {
     const int H = frame_info_.height(), W = frame_info_.width();
@@ -142,9 +128,11 @@ class OpenPoseKernelHIPImpl : public BatchedKernel, public VideoKernel {
     auto& frame_col = input_columns[0];
     const i32 n = (i32)num_rows(frame_col);
     if (n == 0) return;
-    check_frame(device_, frame_col[0]);
+    check_frame(core_.device, frame_col[0]);
     LOG_IF(FATAL, frame_info_.channels() != 3 || frame_info_.type != FrameType::U8) << "OpenPose expects U8 frames with 3 channels";
-    HIP_CHECK(hipSetDevice(gpu_));
+    check_batch_shape(frame_col, frame_info_, "OpenPose");
+    HIP_CHECK(hipSetDevice(core_.gpu));
+    st_ctx* ctx = core_.ctx;
     const int H = frame_info_.height(), W = frame_info_.width(), mp = params_.max_peaks;
     const Geom& g0 = geom_[0];
     // device scratch: [staged frames][network inputs of the current scale][merged maps][joints][limb scores]
@@ -156,22 +144,19 @@ class OpenPoseKernelHIPImpl : public BatchedKernel, public VideoKernel {
     const size_t joint_bytes = DeviceStage::align(peak_floats * sizeof(f32)), score_bytes = DeviceStage::align(score_floats * sizeof(f32) * n);
     u8* dev = stage_.reserve(((STAGED ? frame_bytes : 0) + in_bytes + map_bytes + joint_bytes) * n + score_bytes);
     u8* p = dev;
-    frames_.resize(n);
-    for (i32 i = 0; i < n; ++i) {
-      LOG_IF(FATAL, frame_col[i].as_const_frame()->as_frame_info() != frame_info_) << "OpenPose: frame shape changes inside a batch";
-      if (STAGED) {
-        stage_.upload(p, frame_col[i].as_const_frame()->data, frame_info_.size());
-        frames_[i] = p;
-        p += frame_bytes;
-      } else {
-        frames_[i] = frame_col[i].as_const_frame()->data;
-      }
+    if (STAGED) {
+      stage_.upload_frames(p, frame_bytes, frame_col, frame_info_.size());
+      strided_ptrs(frames_, n, p, frame_bytes);
+      p += frame_bytes * n;
+    } else {
+      input_ptrs(frames_, frame_col);
     }
-    net_in_.resize(n); maps_.resize(n); joints_.resize(n);
-    for (i32 i = 0; i < n; ++i) { net_in_[i] = (float*)p; p += in_bytes; }
-    for (i32 i = 0; i < n; ++i) { maps_[i] = (float*)p; p += map_bytes; }
-    for (i32 i = 0; i < n; ++i) { joints_[i] = (float*)p; p += joint_bytes; }
-    float* dev_scores = (float*)p;
+    strided_ptrs(net_in_, n, p, in_bytes);
+    p += in_bytes * n;
+    strided_ptrs(maps_, n, p, map_bytes);
+    p += map_bytes * n;
+    strided_ptrs(joints_, n, p, joint_bytes);
+    float* dev_scores = (float*)(p + joint_bytes * n);
 
     // every scale: input transform + network; the stage buffers of scale s stay alive in slot s until the merge
     std::vector<const float*> srcs(scales_);
@@ -180,26 +165,23 @@ class OpenPoseKernelHIPImpl : public BatchedKernel, public VideoKernel {
     std::string err;
     for (int s = 0; s < scales_; ++s) {
       const Geom& g = geom_[s];
-      int st = st_cpm2_input_batch(ctx_, frames_.data(), n, H, W, g.scale, net_in_.data());
-      LOG_IF(FATAL, st != ST_OK) << "st_cpm2_input_batch: " << st_ctx_last_error(ctx_);
+      ST_CHECK(ctx, st_cpm2_input_batch(ctx, frames_.data(), n, H, W, g.scale, net_in_.data()));
       cin_.assign(net_in_.begin(), net_in_.end());
-      srcs[s] = net_.forward(ctx_, cin_.data(), n, g.nh, g.nw, &err, s);
+      srcs[s] = net_.forward(ctx, cin_.data(), n, g.nh, g.nw, &err, s);
       LOG_IF(FATAL, !srcs[s]) << "OpenPose: " << err;
       sh[s] = g.nh / 8; sw[s] = g.nw / 8;
       // the part of scale s's maps that shows the frame, stretched over the part of the output that shows it
       eh[s] = s == 0 ? (float)sh[0] : (float)sh[0] * ((float)g.rh / (float)g0.rh);
       ew[s] = s == 0 ? (float)sw[0] : (float)sw[0] * ((float)g.rw / (float)g0.rw);
     }
-    int st = st_cpm2_resize_merge_maps(ctx_, srcs.data(), sh.data(), sw.data(), eh.data(), ew.data(), scales_, n, pose::kCatPad, chan_, 57,
-                                       g0.nh, g0.nw, maps_.data());
-    LOG_IF(FATAL, st != ST_OK) << "st_cpm2_resize_merge_maps: " << st_ctx_last_error(ctx_);
+    ST_CHECK(ctx, st_cpm2_resize_merge_maps(ctx, srcs.data(), sh.data(), sw.data(), eh.data(), ew.data(), scales_, n, pose::kCatPad, chan_, 57,
+                                            g0.nh, g0.nw, maps_.data()));
     cmaps_.assign(maps_.begin(), maps_.end());
-    st = st_cpm2_nms(ctx_, cmaps_.data(), n, g0.nh, g0.nw, cpm2::kParts, mp, kNmsThreshold, joints_.data());
-    LOG_IF(FATAL, st != ST_OK) << "st_cpm2_nms: " << st_ctx_last_error(ctx_);
+    ST_CHECK(ctx, st_cpm2_nms(ctx, cmaps_.data(), n, g0.nh, g0.nw, cpm2::kParts, mp, kNmsThreshold, joints_.data()));
     cjoints_.assign(joints_.begin(), joints_.end());
-    st = st_cpm2_limb_scores(ctx_, cmaps_.data(), cjoints_.data(), n, g0.nh, g0.nw, mp, params_.inter_threshold, params_.inter_min_above, dev_scores);
-    LOG_IF(FATAL, st != ST_OK) << "st_cpm2_limb_scores: " << st_ctx_last_error(ctx_);
-    LOG_IF(FATAL, st_ctx_sync(ctx_) != ST_OK) << "st_ctx_sync: " << st_ctx_last_error(ctx_);
+    ST_CHECK(ctx, st_cpm2_limb_scores(ctx, cmaps_.data(), cjoints_.data(), n, g0.nh, g0.nw, mp, params_.inter_threshold, params_.inter_min_above,
+                                      dev_scores));
+    core_.sync();
     scores_.resize(score_floats * n);
     peaks_.resize(peak_floats * n);
     stage_.download((u8*)scores_.data(), (const u8*)dev_scores, score_floats * sizeof(f32) * n);
@@ -218,8 +200,8 @@ class OpenPoseKernelHIPImpl : public BatchedKernel, public VideoKernel {
         memcpy(out + POSE_SCORES, kp.data() + (size_t)q * POSE_KEYPOINTS * 3, sizeof(float) * POSE_KEYPOINTS * 3);
       }
       const size_t size = row.size() * sizeof(float);
-      u8* buffer = new_buffer(device_, size);
-      memcpy_buffer(buffer, device_, (const u8*)row.data(), CPU_DEVICE, size);
+      u8* buffer = new_buffer(core_.device, size);
+      memcpy_buffer(buffer, core_.device, (const u8*)row.data(), CPU_DEVICE, size);
       insert_element(output_columns[0], buffer, size);
     }
   }
@@ -229,13 +211,10 @@ class OpenPoseKernelHIPImpl : public BatchedKernel, public VideoKernel {
     float scale;
     int rh, rw, nh, nw;
   };
-  DeviceHandle device_;
-  int gpu_;
+  KernelCore core_;
   DeviceStage stage_;
-  Result valid_;
   OpenPoseArgs args_;
   int scales_ = 1;
-  st_ctx* ctx_ = nullptr;
   pose::Net net_;
   cpm2::Params params_;
   int chan_[57];

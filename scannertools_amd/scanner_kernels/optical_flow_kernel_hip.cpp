@@ -14,42 +14,37 @@
 #include <algorithm>
 #include <memory>
 #include <string>
-#include <unordered_map>
 
 #include "scanner/api/kernel.h"
 #include "scanner/api/op.h"
 #include "scanner/util/hip.h"
 #include "scanner/util/memory.h"
 #include "scannertools_hip.h"
-#include "stage.h"
+#include "kernel_core.h"
 
 namespace scanner {
 
+namespace {
+// every row is a window of two frames of the stream's shape
+void check_windows(const std::vector<Elements>& col, const FrameInfo& info) {
+  for (auto& window : col) {
+    LOG_IF(FATAL, window.size() != 2) << "OpticalFlow needs a 2-element stencil, got " << window.size();
+    check_batch_shape(window, info, "OpticalFlow stencil");
+  }
+}
+}  // namespace
+
 class OpticalFlowKernelHIP : public StenciledBatchedKernel, public VideoKernel {
  public:
-  OpticalFlowKernelHIP(const KernelConfig& config)
-    : StenciledBatchedKernel(config), device_(config.devices[0]) {
+  OpticalFlowKernelHIP(const KernelConfig& config) : StenciledBatchedKernel(config), core_(config, false) {
     st_fb_params_default(&params_);  // (3, 0.5, false, 15, 3, 5, 1.2, 0): optical_flow_kernel_cpu.cpp:16
-    if (device_.type != DeviceType::GPU) {
-      RESULT_ERROR(&valid_, "OpticalFlowKernelHIP runs on DeviceType::GPU only");
-    } else {
-      int st = st_ctx_create(device_.id, &ctx_);
-      if (st != ST_OK) RESULT_ERROR(&valid_, "st_ctx_create(%d) failed: %s", device_.id, st_status_string(st));
-    }
+    core_.open("OpticalFlowKernelHIP");
   }
-
-  ~OpticalFlowKernelHIP() {
-    if (ctx_) st_ctx_destroy(ctx_);
-  }
-
-  void validate(Result* result) override {
-    result->set_msg(valid_.msg());
-    result->set_success(valid_.success());
-  }
+  void validate(Result* result) override { core_.validate(result); }
 
   void new_frame_info() override {
     // scratch is sized for the new geometry on the next call; drop the old one now
-    if (ctx_) st_ctx_release_workspace(ctx_);
+    if (core_.ctx) st_ctx_release_workspace(core_.ctx);
   }
 
   void reset() override {}
@@ -58,46 +53,25 @@ class OpticalFlowKernelHIP : public StenciledBatchedKernel, public VideoKernel {
     auto& frame_col = input_columns[0];
     i32 input_count = (i32)frame_col.size();
     if (input_count == 0) return;
-    check_frame(device_, frame_col[0][0]);
+    check_frame(core_.device, frame_col[0][0]);
     LOG_IF(FATAL, frame_info_.channels() != 3 || frame_info_.type != FrameType::U8)
         << "OpticalFlow expects U8 frames with 3 channels";
-
-    // distinct frames of the batch (by buffer) and the (from, to) index pair of every row
-    frames_.clear();
-    pairs_.clear();
-    std::unordered_map<const u8*, i32> slot;
-    for (i32 i = 0; i < input_count; ++i) {
-      LOG_IF(FATAL, frame_col[i].size() != 2) << "OpticalFlow needs a 2-element stencil, got " << frame_col[i].size();
-      for (i32 s = 0; s < 2; ++s) {
-        const Frame* f = frame_col[i][s].as_const_frame();
-        LOG_IF(FATAL, f->as_frame_info() != frame_info_) << "OpticalFlow: frame shape changes inside a batch";
-        auto it = slot.find(f->data);
-        if (it == slot.end()) {
-          it = slot.emplace(f->data, (i32)frames_.size()).first;
-          frames_.push_back(f->data);
-        }
-        pairs_.push_back(it->second);
-      }
-    }
+    check_windows(frame_col, frame_info_);
+    pair_table(frame_col, 0, input_count, &frames_, &pairs_);
 
     FrameInfo out_frame_info(frame_info_.height(), frame_info_.width(), 2, FrameType::F32);
-    std::vector<Frame*> output_frames = new_frames(device_, out_frame_info, input_count);
-    outs_.resize(input_count);
-    for (i32 i = 0; i < input_count; ++i) outs_[i] = (float*)output_frames[i]->data;
+    std::vector<Frame*> output_frames = new_frames(core_.device, out_frame_info, input_count);
+    output_ptrs(outs_, output_frames);
 
-    int st = st_farneback_pairs(ctx_, frames_.data(), (int)frames_.size(), pairs_.data(), input_count,
-                                frame_info_.height(), frame_info_.width(), &params_, outs_.data());
-    LOG_IF(FATAL, st != ST_OK) << "st_farneback_pairs: " << st_ctx_last_error(ctx_);
-    st = st_ctx_sync(ctx_);
-    LOG_IF(FATAL, st != ST_OK) << "st_ctx_sync: " << st_ctx_last_error(ctx_);
+    ST_CHECK(core_.ctx, st_farneback_pairs(core_.ctx, frames_.data(), (int)frames_.size(), pairs_.data(), input_count,
+                                           frame_info_.height(), frame_info_.width(), &params_, outs_.data()));
+    core_.sync();
 
     for (i32 i = 0; i < input_count; ++i) insert_frame(output_columns[0], output_frames[i]);
   }
 
  private:
-  DeviceHandle device_;
-  Result valid_;
-  st_ctx* ctx_ = nullptr;
+  KernelCore core_;
   st_fb_params params_;
   std::vector<const uint8_t*> frames_;
   std::vector<int32_t> pairs_;
@@ -116,25 +90,17 @@ class OpticalFlowKernelHIP : public StenciledBatchedKernel, public VideoKernel {
 // the path is PCIe-bound; overlapping the three stages is what this structure buys.
 class OpticalFlowKernelHIPStaged : public StenciledBatchedKernel, public VideoKernel {
  public:
-  OpticalFlowKernelHIPStaged(const KernelConfig& config)
-    : StenciledBatchedKernel(config), device_(config.devices[0]), gpu_(staging_device_id()) {
+  OpticalFlowKernelHIPStaged(const KernelConfig& config) : StenciledBatchedKernel(config), core_(config, true) {
     st_fb_params_default(&params_);
-    const char* e = getenv("SCANNERTOOLS_FLOW_SUBBATCH");
-    sub_fixed_ = e != nullptr;
-    sub_ = e ? atoi(e) : 8;
-    if (sub_ < 1) sub_ = 1;
-    for (int l = 0; l < 2 && valid_.success(); ++l) {
-      lanes_[l].stage.reset(new DeviceStage(gpu_));
-      int st = st_ctx_create(gpu_, &lanes_[l].ctx);
-      if (st != ST_OK) {
-        RESULT_ERROR(&valid_, "st_ctx_create(%d) failed: %s (no CPU fallback exists)", gpu_, st_status_string(st));
-        break;
-      }
+    sub_ = env_int("SCANNERTOOLS_FLOW_SUBBATCH", 8, 1, &sub_fixed_);
+    for (int l = 0; l < 2 && core_.valid.success(); ++l) {
+      lanes_[l].stage.reset(new DeviceStage(core_.gpu));
+      if (!core_.open(&lanes_[l].ctx)) break;
       if (hipStreamCreateWithFlags(&lanes_[l].stream, hipStreamNonBlocking) != hipSuccess ||
           st_ctx_set_stream(lanes_[l].ctx, lanes_[l].stream) != ST_OK ||
           hipEventCreateWithFlags(&lanes_[l].up_done, hipEventDisableTiming) != hipSuccess ||
           hipEventCreateWithFlags(&lanes_[l].comp_done, hipEventDisableTiming) != hipSuccess)
-        RESULT_ERROR(&valid_, "cannot create a HIP stream on device %d", gpu_);
+        RESULT_ERROR(&core_.valid, "cannot create a HIP stream on device %d", core_.gpu);
     }
     // SCANNERTOOLS_FLOW_COPIES=overlap: every lane copies on its own stream (uploads of one lane run beside the other's
     // copy-back); default "serial": ALL copies of both lanes on one stream, so that an upload and a copy-back are never in
@@ -142,22 +108,19 @@ class OpticalFlowKernelHIPStaged : public StenciledBatchedKernel, public VideoKe
     // the flow fields going back are 2.7x the frames coming in
     const char* cm = getenv("SCANNERTOOLS_FLOW_COPIES");
     serial_copies_ = !(cm && std::string(cm) == "overlap");
-    if (valid_.success() && hipStreamCreateWithFlags(&copy_, hipStreamNonBlocking) != hipSuccess)
-      RESULT_ERROR(&valid_, "cannot create a HIP stream on device %d", gpu_);
+    if (core_.valid.success() && hipStreamCreateWithFlags(&copy_, hipStreamNonBlocking) != hipSuccess)
+      RESULT_ERROR(&core_.valid, "cannot create a HIP stream on device %d", core_.gpu);
   }
   ~OpticalFlowKernelHIPStaged() {
     if (copy_) { (void)hipStreamSynchronize(copy_); (void)hipStreamDestroy(copy_); }
     for (auto& l : lanes_) {
       if (l.up_done) (void)hipEventDestroy(l.up_done);
       if (l.comp_done) (void)hipEventDestroy(l.comp_done);
-      if (l.ctx) st_ctx_destroy(l.ctx);
+      core_.close(&l.ctx);
       if (l.stream) (void)hipStreamDestroy(l.stream);
     }
   }
-  void validate(Result* result) override {
-    result->set_msg(valid_.msg());
-    result->set_success(valid_.success());
-  }
+  void validate(Result* result) override { core_.validate(result); }
   void new_frame_info() override {
     for (auto& l : lanes_) if (l.ctx) st_ctx_release_workspace(l.ctx);
   }
@@ -166,20 +129,17 @@ class OpticalFlowKernelHIPStaged : public StenciledBatchedKernel, public VideoKe
     auto& frame_col = input_columns[0];
     i32 input_count = (i32)frame_col.size();
     if (input_count == 0) return;
-    check_frame(device_, frame_col[0][0]);
+    check_frame(core_.device, frame_col[0][0]);
     LOG_IF(FATAL, frame_info_.channels() != 3 || frame_info_.type != FrameType::U8)
         << "OpticalFlow expects U8 frames with 3 channels";
-    for (i32 i = 0; i < input_count; ++i) {
-      LOG_IF(FATAL, frame_col[i].size() != 2) << "OpticalFlow needs a 2-element stencil, got " << frame_col[i].size();
-      for (i32 s = 0; s < 2; ++s)
-        LOG_IF(FATAL, frame_col[i][s].as_const_frame()->as_frame_info() != frame_info_)
-            << "OpticalFlow: frame shape changes inside a batch";
-    }
+    check_windows(frame_col, frame_info_);
     FrameInfo out_info(frame_info_.height(), frame_info_.width(), 2, FrameType::F32);
     const size_t frame_bytes = frame_info_.size(), fstride = DeviceStage::align(frame_bytes);
     const size_t out_bytes = out_info.size(), ostride = DeviceStage::align(out_bytes);
-    std::vector<Frame*> output_frames = new_frames(device_, out_info, input_count);
-    HIP_CHECK(hipSetDevice(gpu_));
+    std::vector<Frame*> output_frames = new_frames(core_.device, out_info, input_count);
+    std::vector<u8*> host_outs;
+    output_ptrs(host_outs, output_frames);
+    HIP_CHECK(hipSetDevice(core_.gpu));
 
     // Sub-batch size: SCANNERTOOLS_FLOW_SUBBATCH when set; otherwise by bytes -- about 64 MB of frames + flow fields per
     // sub-batch, at least 8 rows (1080p: 8 rows = 180 MB), so that small frames (the legacy pipeline's 426x240: 1.1 MB per
@@ -200,12 +160,7 @@ class OpticalFlowKernelHIPStaged : public StenciledBatchedKernel, public VideoKe
       Pending& P = pending[li];
       if (!P.any) return;
       HIP_CHECK(hipStreamWaitEvent(copy_, lanes_[li].comp_done, 0));
-      for (i32 i = 0; i < P.nb;) {
-        i32 j = i + 1;
-        while (ostride == out_bytes && j < P.nb && output_frames[P.r0 + j]->data == output_frames[P.r0 + j - 1]->data + out_bytes) ++j;
-        HIP_CHECK(hipMemcpyAsync(output_frames[P.r0 + i]->data, P.dev_outs[i], out_bytes * (size_t)(j - i), hipMemcpyDeviceToHost, copy_));
-        i = j;
-      }
+      copy_runs(hipMemcpyDeviceToHost, host_outs.data() + P.r0, P.dev_outs.data(), P.nb, out_bytes, copy_);
       P.any = false;
     };
     int lane_idx = 0;
@@ -217,42 +172,26 @@ class OpticalFlowKernelHIPStaged : public StenciledBatchedKernel, public VideoKe
       // overlap mode; in serial mode its copy-back goes first on the copy stream, and this sub-batch's compute waits for
       // the upload behind it
       if (serial_copies_) copy_back(lane_idx);
-      else LOG_IF(FATAL, st_ctx_sync(L.ctx) != ST_OK) << "st_ctx_sync: " << st_ctx_last_error(L.ctx);
-      // distinct frames of this sub-batch
-      std::vector<const u8*> host_frames;
+      else st_sync(L.ctx);
+      // distinct frames of this sub-batch; device layout: [frames][nb flow fields]
+      std::vector<const u8*> host_frames, dev_frames;
       std::vector<int32_t> pairs;
-      std::unordered_map<const u8*, i32> slot;
-      for (i32 i = r0; i < r0 + nb; ++i)
-        for (i32 s = 0; s < 2; ++s) {
-          const u8* d = frame_col[i][s].as_const_frame()->data;
-          auto it = slot.find(d);
-          if (it == slot.end()) {
-            it = slot.emplace(d, (i32)host_frames.size()).first;
-            host_frames.push_back(d);
-          }
-          pairs.push_back(it->second);
-        }
+      pair_table(frame_col, r0, nb, &host_frames, &pairs);
       u8* dev = L.stage->reserve(fstride * host_frames.size() + ostride * nb);
-      std::vector<const uint8_t*> dev_frames(host_frames.size());
+      strided_ptrs(dev_frames, (i32)host_frames.size(), dev, fstride);
       // One copy per RUN of frames that are adjacent in host memory (Scanner hands out a batch's frames from block
-      // allocations): a PCIe copy of one 6 MB frame carries ~0.2 ms of fixed cost, a third of its duration.
+      // allocations) when a frame is a multiple of the staging alignment.
       // (Pageable sources: the call returns when the data is on its way; the other lane keeps computing.)
-      for (size_t i = 0; i < host_frames.size();) {
-        size_t j = i + 1;
-        while (fstride == frame_bytes && j < host_frames.size() && host_frames[j] == host_frames[j - 1] + frame_bytes) ++j;
-        HIP_CHECK(hipMemcpyAsync(dev + fstride * i, host_frames[i], frame_bytes * (j - i), hipMemcpyHostToDevice, up_stream));
-        for (; i < j; ++i) dev_frames[i] = dev + fstride * i;
-      }
+      copy_runs(hipMemcpyHostToDevice, host_frames.data(), dev_frames.data(), host_frames.size(), frame_bytes, up_stream);
       if (serial_copies_) {
         HIP_CHECK(hipEventRecord(L.up_done, copy_));
         HIP_CHECK(hipStreamWaitEvent(L.stream, L.up_done, 0));
         copy_back(lane_idx ^ 1);  // the other lane's finished sub-batch comes back behind this upload
       }
-      std::vector<float*> dev_outs(nb);
-      for (i32 i = 0; i < nb; ++i) dev_outs[i] = (float*)(dev + fstride * host_frames.size() + ostride * i);
-      int st = st_farneback_pairs(L.ctx, dev_frames.data(), (int)dev_frames.size(), pairs.data(), nb,
-                                  frame_info_.height(), frame_info_.width(), &params_, dev_outs.data());
-      LOG_IF(FATAL, st != ST_OK) << "st_farneback_pairs: " << st_ctx_last_error(L.ctx);
+      std::vector<float*> dev_outs;
+      strided_ptrs(dev_outs, nb, dev + fstride * host_frames.size(), ostride);
+      ST_CHECK(L.ctx, st_farneback_pairs(L.ctx, dev_frames.data(), (int)dev_frames.size(), pairs.data(), nb,
+                                         frame_info_.height(), frame_info_.width(), &params_, dev_outs.data()));
       if (serial_copies_) {
         HIP_CHECK(hipEventRecord(L.comp_done, L.stream));
         pending[lane_idx].any = true; pending[lane_idx].r0 = r0; pending[lane_idx].nb = nb; pending[lane_idx].dev_outs = dev_outs;
@@ -261,12 +200,7 @@ class OpticalFlowKernelHIPStaged : public StenciledBatchedKernel, public VideoKe
       // the output frames of a batch are one host block (new_frames) and the staged flows are adjacent on the device
       // whenever a flow field is a multiple of the staging alignment: then the whole sub-batch comes back in ONE copy
       // (16.6 MB copies reach 33 GB/s on this host, a 133 MB copy 57)
-      for (i32 i = 0; i < nb;) {
-        i32 j = i + 1;
-        while (ostride == out_bytes && j < nb && output_frames[r0 + j]->data == output_frames[r0 + j - 1]->data + out_bytes) ++j;
-        HIP_CHECK(hipMemcpyAsync(output_frames[r0 + i]->data, dev_outs[i], out_bytes * (size_t)(j - i), hipMemcpyDeviceToHost, L.stream));
-        i = j;
-      }
+      copy_runs(hipMemcpyDeviceToHost, host_outs.data() + r0, dev_outs.data(), nb, out_bytes, L.stream);
     }
     if (serial_copies_) {
       // the last two sub-batches, oldest first
@@ -274,7 +208,7 @@ class OpticalFlowKernelHIPStaged : public StenciledBatchedKernel, public VideoKe
       copy_back(lane_idx ^ 1);
       HIP_CHECK(hipStreamSynchronize(copy_));
     }
-    for (auto& l : lanes_) LOG_IF(FATAL, st_ctx_sync(l.ctx) != ST_OK) << "st_ctx_sync: " << st_ctx_last_error(l.ctx);
+    for (auto& l : lanes_) st_sync(l.ctx);
     for (i32 i = 0; i < input_count; ++i) insert_frame(output_columns[0], output_frames[i]);
   }
 
@@ -287,12 +221,10 @@ class OpticalFlowKernelHIPStaged : public StenciledBatchedKernel, public VideoKe
   };
   hipStream_t copy_ = nullptr;
   bool serial_copies_ = true;
-  DeviceHandle device_;
-  int gpu_;
+  KernelCore core_;  // the GPU and the result; the two contexts are the lanes'
   int sub_ = 8;
   bool sub_fixed_ = false;
   Lane lanes_[2];
-  Result valid_;
   st_fb_params params_;
 };
 

@@ -19,7 +19,7 @@
 #include "scanner/util/memory.h"
 #include "proto_lite.h"
 #include "scannertools_hip.h"
-#include "stage.h"
+#include "kernel_core.h"
 
 namespace scanner {
 namespace {
@@ -53,27 +53,10 @@ bool parse_resize_args(const std::vector<u8>& args, ResizeArgsLite* out) {
 template <bool STAGED>
 class ResizeKernelHIPImpl : public BatchedKernel {
  public:
-  ResizeKernelHIPImpl(const KernelConfig& config)
-    : BatchedKernel(config), device_(config.devices[0]), gpu_(STAGED ? staging_device_id() : config.devices[0].id),
-      stage_(gpu_), pipe_(gpu_) {
-    if (!STAGED && device_.type != DeviceType::GPU) {
-      RESULT_ERROR(&valid_, "ResizeKernelHIP runs on DeviceType::GPU only");
-      return;
-    }
-    int st = st_ctx_create(gpu_, &ctx_);
-    if (st != ST_OK) {
-      RESULT_ERROR(&valid_, "st_ctx_create(%d) failed: %s (no CPU fallback exists)", gpu_, st_status_string(st));
-    } else if (STAGED && (!pipe_.init() || st_ctx_set_stream(ctx_, pipe_.compute_stream()) != ST_OK)) {
-      RESULT_ERROR(&valid_, "cannot create the upload pipeline on device %d", gpu_);
-    }
+  ResizeKernelHIPImpl(const KernelConfig& config) : BatchedKernel(config), core_(config, STAGED), stage_(core_.gpu) {
+    if (core_.open("ResizeKernelHIP") && STAGED) core_.bind(&pipe_);
   }
-  ~ResizeKernelHIPImpl() {
-    if (ctx_) st_ctx_destroy(ctx_);
-  }
-  void validate(Result* result) override {
-    result->set_msg(valid_.msg());
-    result->set_success(valid_.success());
-  }
+  void validate(Result* result) override { core_.validate(result); }
 
   void new_stream(const std::vector<u8>& args) override {
     LOG_IF(FATAL, !parse_resize_args(args, &args_)) << "Resize: could not parse ResizeArgs";
@@ -110,10 +93,9 @@ class ResizeKernelHIPImpl : public BatchedKernel {
     LOG_IF(FATAL, target_width <= 0 || target_height <= 0) << "Resize: empty target size";
 
     FrameInfo info(target_height, target_width, frame->channels(), frame->type);
-    std::vector<Frame*> output_frames = new_frames(device_, info, input_count);
-    src_.resize(input_count);
-    dst_.resize(input_count);
+    std::vector<Frame*> output_frames = new_frames(core_.device, info, input_count);
     const size_t in_bytes = frame->size(), out_bytes = info.size();
+    const i32 fh = frame->height(), fw = frame->width(), fc = frame->channels();
     if (STAGED) {
       // Host frames: the uploads are the work (a 1080p frame is 110 us of PCIe for a few us of kernel), so they run back to
       // back on a copy stream in sub-batches that alternate between two device slots while the compute stream resizes the
@@ -121,57 +103,39 @@ class ResizeKernelHIPImpl : public BatchedKernel {
       // packed on the device and come back in one copy.  (Was: one synchronous copy per frame each way, 0.73 of the H2D rate.)
       const size_t in_stride = DeviceStage::align(in_bytes);
       u8* dev_out = stage_.reserve(out_bytes * (size_t)input_count + 256);
-      const i32 fh = frame->height(), fw = frame->width(), fc = frame->channels();
       for (i32 i = 0; i < input_count; ++i)
         LOG_IF(FATAL, frame_col[i].as_const_frame()->size() != in_bytes) << "Resize: frame " << i << " changes shape inside a batch";
+      src_.resize(input_count);
+      strided_ptrs(dst_, input_count, dev_out, out_bytes);
       pipe_.run(input_count, 8, in_bytes, in_stride,
                 [&](i32 i) { return (const u8*)frame_col[i].as_const_frame()->data; },
                 [&](u8* dev, i32 first, i32 nb) {
-                  for (i32 i = 0; i < nb; ++i) {
-                    src_[first + i] = dev + in_stride * i;
-                    dst_[first + i] = dev_out + out_bytes * (size_t)(first + i);
-                  }
-                  int st2 = st_resize_u8_batch(ctx_, src_.data() + first, nb, fh, fw, fc, target_height, target_width, interp_type_,
-                                               dst_.data() + first);
-                  LOG_IF(FATAL, st2 != ST_OK) << "st_resize_u8_batch: " << st_ctx_last_error(ctx_);
+                  for (i32 i = 0; i < nb; ++i) src_[first + i] = dev + in_stride * i;
+                  ST_CHECK(core_.ctx, st_resize_u8_batch(core_.ctx, src_.data() + first, nb, fh, fw, fc, target_height, target_width,
+                                                         interp_type_, dst_.data() + first));
                 });
-      // one copy when the output frames are one host block (new_frames), else frame by frame
-      bool packed = true;
-      for (i32 i = 1; i < input_count; ++i) packed = packed && output_frames[i]->data == output_frames[i - 1]->data + out_bytes;
-      if (packed) {
-        HIP_CHECK(hipMemcpyAsync(output_frames[0]->data, dev_out, out_bytes * (size_t)input_count, hipMemcpyDeviceToHost, pipe_.compute_stream()));
-      } else {
-        for (i32 i = 0; i < input_count; ++i)
-          HIP_CHECK(hipMemcpyAsync(output_frames[i]->data, dst_[i], out_bytes, hipMemcpyDeviceToHost, pipe_.compute_stream()));
-      }
+      // one copy, the output frames being one host block (new_frames); a copy per run of adjacent frames otherwise
+      output_ptrs(host_out_, output_frames);
+      copy_runs(hipMemcpyDeviceToHost, host_out_.data(), dst_.data(), input_count, out_bytes, pipe_.compute_stream());
       pipe_.drain();
-      for (i32 i = 0; i < input_count; ++i) insert_frame(output_columns[0], output_frames[i]);
-      return;
     } else {
-      for (i32 i = 0; i < input_count; ++i) {
-        src_[i] = frame_col[i].as_const_frame()->data;
-        dst_[i] = output_frames[i]->data;
-      }
+      input_ptrs(src_, frame_col);
+      output_ptrs(dst_, output_frames);
+      ST_CHECK(core_.ctx, st_resize_u8_batch(core_.ctx, src_.data(), input_count, fh, fw, fc, target_height, target_width, interp_type_,
+                                             dst_.data()));
+      core_.sync();
     }
-    int st = st_resize_u8_batch(ctx_, src_.data(), input_count, frame->height(), frame->width(), frame->channels(),
-                                target_height, target_width, interp_type_, dst_.data());
-    LOG_IF(FATAL, st != ST_OK) << "st_resize_u8_batch: " << st_ctx_last_error(ctx_);
-    st = st_ctx_sync(ctx_);
-    LOG_IF(FATAL, st != ST_OK) << "st_ctx_sync: " << st_ctx_last_error(ctx_);
     for (i32 i = 0; i < input_count; ++i) insert_frame(output_columns[0], output_frames[i]);
   }
 
  private:
-  DeviceHandle device_;
-  int gpu_;
+  UploadPipeline pipe_;  // before core_: the context leaves the pipeline's stream before the stream is destroyed
+  KernelCore core_;
   DeviceStage stage_;
-  UploadPipeline pipe_;
   ResizeArgsLite args_;
   int interp_type_ = 1;
-  Result valid_;
-  st_ctx* ctx_ = nullptr;
   std::vector<const uint8_t*> src_;
-  std::vector<uint8_t*> dst_;
+  std::vector<uint8_t*> dst_, host_out_;
 };
 
 using ResizeKernelHIP = ResizeKernelHIPImpl<false>;

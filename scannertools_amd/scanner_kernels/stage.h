@@ -6,6 +6,7 @@
 #include <algorithm>
 #include <cstring>
 
+#include "scanner/api/kernel.h"
 #include "scanner/util/hip.h"
 
 namespace scanner {
@@ -29,6 +30,13 @@ class DeviceStage {
   }
   void upload(u8* dst_dev, const u8* src_host, size_t n) { HIP_CHECK(hipMemcpy(dst_dev, src_host, n, hipMemcpyHostToDevice)); }
   void download(u8* dst_host, const u8* src_dev, size_t n) { HIP_CHECK(hipMemcpy(dst_host, src_dev, n, hipMemcpyDeviceToHost)); }
+  // the frames of a host column to dev, dev + stride, ...; `bytes` of each device block back into newly allocated frames
+  void upload_frames(u8* dev, size_t stride, const Elements& col, size_t bytes) {
+    for (size_t i = 0; i < col.size(); ++i) upload(dev + stride * i, col[i].as_const_frame()->data, bytes);
+  }
+  void download_frames(const std::vector<Frame*>& out, const u8* dev, size_t stride, size_t bytes) {
+    for (size_t i = 0; i < out.size(); ++i) download(out[i]->data, dev + stride * i, bytes);
+  }
   static size_t align(size_t v) { return (v + 255) / 256 * 256; }
 
  private:
@@ -49,8 +57,8 @@ class DeviceStage {
 // kernel receiving device frames directly (frame_to_gpu_mat, histogram_kernel_gpu.cpp:48).
 class UploadPipeline {
  public:
-  explicit UploadPipeline(int device_id) : device_id_(device_id) {}
   ~UploadPipeline() {
+    if (device_id_ < 0) return;
     (void)hipSetDevice(device_id_);
     for (int s = 0; s < 2; ++s) {
       if (dev_[s]) (void)hipFree(dev_[s]);
@@ -62,7 +70,8 @@ class UploadPipeline {
     if (comp_) (void)hipStreamDestroy(comp_);
   }
   // false if the streams / events cannot be created
-  bool init() {
+  bool init(int device_id) {
+    device_id_ = device_id;
     if (hipSetDevice(device_id_) != hipSuccess) return false;
     if (hipStreamCreateWithFlags(&copy_, hipStreamNonBlocking) != hipSuccess) return false;
     if (hipStreamCreateWithFlags(&comp_, hipStreamNonBlocking) != hipSuccess) return false;
@@ -126,7 +135,7 @@ class UploadPipeline {
   }
 
  private:
-  int device_id_;
+  int device_id_ = -1;  // none before init(): a pipeline that was never set up owns nothing
   hipStream_t copy_ = nullptr, comp_ = nullptr;
   hipEvent_t up_[2] = {nullptr, nullptr}, done_[2] = {nullptr, nullptr};
   u8* dev_[2] = {nullptr, nullptr};
