@@ -152,6 +152,35 @@ int st_frame_moments_u8c3_strided(st_ctx* ctx, const uint8_t* base_dev, size_t f
                                   int what, int64_t* moments_dev);
 int st_frame_stats_finish(st_ctx* ctx, const int64_t* moments_dev, int n, int h, int w, int kind, void* out_dev);
 
+/* ---- SharpnessBBoxCPP / SharpnessBBox: sharpness of boxes of a frame ---------------------------------------------------------
+ * Replace the per-box bodies of the legacy op library's SharpnessBBoxKernel (scannertools/old/cpp_ops/imgproc.cpp:177-234:
+ * cv::resize of the box to 200 x 200 at INTER_LINEAR, cv::Laplacian(CV_64F), cv::meanStdDev) and of its Python twin
+ * (old/imgproc.py:44-54) for all boxes of all frames of a call, in ONE moments launch (a call with fewer boxes than the GPU has
+ * CUs cuts each box into bands of rows and adds a small second launch that sums them): a box is gathered from its frame, resized with
+ * the Resize op's arithmetic (the region an image of its own: taps clamp inside it; an exactly 200 x 200 box is copied, an
+ * exactly 400 x 400 box is the rounded mean of its 2 x 2 cells) and reduced to its six Laplacian moments without the resized
+ * image leaving the chip.
+ * boxes_host: m records of 5 int32 {frame index, x1, y1, x2, y2} in HOST memory, coordinates already truncated to pixels; the
+ *   region is rows y1 .. y2-1, columns x1 .. x2-1.  Every record is validated before anything is launched: ST_ERR_INVALID
+ *   (the message names the box) unless 0 <= frame < n, 0 <= x1 < x2 <= w and 0 <= y1 < y2 <= h.  The records are copied during
+ *   the call; any order, any overlap, a frame without a box and a box listed twice are all fine.
+ * st_bbox_moments_u8c3_*: moments_dev receives m records of 8 int64 in the ST_FM_* layout of the ST_BBOX_SIDE x ST_BBOX_SIDE
+ *   image of box i (SY = QY = 0), exact, so that st_frame_stats_finish(ctx, moments_dev, m, ST_BBOX_SIDE, ST_BBOX_SIDE,
+ *   ST_FS_SHARPNESS_CPP or ST_FS_SHARPNESS, out) finishes them.  A box's record does not depend on what else is in the call.
+ * st_bbox_sharpness_u8c3_*: the same launch with the finishing formula fused: out_dev[i] = statistic `kind`
+ *   (ST_FS_SHARPNESS_CPP: float, ST_FS_SHARPNESS: double) of box i, bit for bit what the two calls above give.
+ * Frames of up to 2^31 - 1 bytes at any byte alignment; m = 0 is a successful no-op; m above 2^31 - 1 is ST_ERR_UNSUPPORTED.
+ * No host synchronisation (the scratch allocation may grow, as in every entry point). */
+#define ST_BBOX_SIDE 200
+int st_bbox_moments_u8c3_batch(st_ctx* ctx, const uint8_t* const* frames_dev, int n, int h, int w, const int32_t* boxes_host,
+                               int64_t m, int64_t* moments_dev);
+int st_bbox_moments_u8c3_strided(st_ctx* ctx, const uint8_t* base_dev, size_t frame_stride_bytes, int n, int h, int w,
+                                 const int32_t* boxes_host, int64_t m, int64_t* moments_dev);
+int st_bbox_sharpness_u8c3_batch(st_ctx* ctx, const uint8_t* const* frames_dev, int n, int h, int w, const int32_t* boxes_host,
+                                 int64_t m, int kind, void* out_dev);
+int st_bbox_sharpness_u8c3_strided(st_ctx* ctx, const uint8_t* base_dev, size_t frame_stride_bytes, int n, int h, int w,
+                                   const int32_t* boxes_host, int64_t m, int kind, void* out_dev);
+
 /* ---- ShotBoundaries (device-resident histograms) -------------------------------------------
  * Replaces the body of the ShotBoundaries python op, scannertools/shot_detection.py:12-28, for histograms that are
  * already on the GPU (the op itself stays host code in the reference; with resident frames its 10 000-window loop is

@@ -402,6 +402,13 @@ SHIM_EXPORT int stshim_op_output_name(const char* op, int i, char* name, int nam
   return 0;
 }
 
+SHIM_EXPORT int stshim_op_input_name(const char* op, int i, char* name, int name_len) {
+  const OpRegistration* o = find_op(op);
+  if (!o || i < 0 || i >= (int)o->inputs.size()) return 1;
+  if (name && name_len > 0) { strncpy(name, o->inputs[i].name.c_str(), name_len - 1); name[name_len - 1] = 0; }
+  return 0;
+}
+
 SHIM_EXPORT void* stshim_kernel_create(const char* op, int device_type, int device_id, const uint8_t* args,
                                        size_t n_args, char* err, size_t err_len) {
   const KernelRegistration* found = nullptr;

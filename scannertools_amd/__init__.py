@@ -8,7 +8,7 @@
 ``scannertools_amd.optical_flow``   compute_flow (mirror of scannertools/old/optical_flow.py)
 ``scannertools_amd.histograms``     compute_histograms / _hsv_ / _flow_ (mirror of old/histograms.py)
 ``scannertools_amd.vis``            the DrawFlow python op (mirror of scannertools/vis.py)
-``scannertools_amd.frame_stats``    Brightness / Contrast / Sharpness ops and runners (mirror of scannertools/old/imgproc.py)
+``scannertools_amd.frame_stats``    Brightness / Contrast / Sharpness / SharpnessBBox ops and runners (mirror of scannertools/old/imgproc.py)
 """
 from .shot_detection import shot_boundaries, WINDOW_SIZE, BOUNDARY_BATCH  # noqa: F401
 

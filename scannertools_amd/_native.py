@@ -16,6 +16,7 @@ ST_OK, ST_ERR_INVALID, ST_ERR_HIP, ST_ERR_OOM, ST_ERR_UNSUPPORTED = range(5)
 FM_LUMA, FM_LAPLACIAN = 1, 2   # st_frame_moment_mask
 # st_frame_stat_kind: the six frame statistics (float32 for the *CPP kinds, float64 for the Python ops' values)
 FS_KINDS = {"BrightnessCPP": 0, "ContrastCPP": 1, "SharpnessCPP": 2, "Brightness": 3, "Contrast": 4, "Sharpness": 5}
+BBOX_SIDE = 200   # ST_BBOX_SIDE: the SharpnessBBox ops resize every box to BBOX_SIDE x BBOX_SIDE
 INTER_NEAREST, INTER_LINEAR, INTER_CUBIC, INTER_AREA, INTER_LANCZOS4 = 0, 1, 2, 3, 4  # cv::InterpolationFlags values the Resize op implements
 # cv::ColorConversionCodes values the ConvertColor op implements
 COLOR_CODES = {"COLOR_BGR2RGB": 4, "COLOR_RGB2BGR": 4, "COLOR_BGR2GRAY": 6, "COLOR_RGB2GRAY": 7,
@@ -109,6 +110,10 @@ SIGNATURES = {
     "st_frame_moments_u8c3_batch": (_i, [_vp, _c.POINTER(_vp), _i, _i, _i, _i, _vp]),
     "st_frame_moments_u8c3_strided": (_i, [_vp, _vp, _sz, _i, _i, _i, _i, _vp]),
     "st_frame_stats_finish": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
+    "st_bbox_moments_u8c3_batch": (_i, [_vp, _c.POINTER(_vp), _i, _i, _i, _c.POINTER(_c.c_int32), _c.c_int64, _vp]),
+    "st_bbox_moments_u8c3_strided": (_i, [_vp, _vp, _sz, _i, _i, _i, _c.POINTER(_c.c_int32), _c.c_int64, _vp]),
+    "st_bbox_sharpness_u8c3_batch": (_i, [_vp, _c.POINTER(_vp), _i, _i, _i, _c.POINTER(_c.c_int32), _c.c_int64, _i, _vp]),
+    "st_bbox_sharpness_u8c3_strided": (_i, [_vp, _vp, _sz, _i, _i, _i, _c.POINTER(_c.c_int32), _c.c_int64, _i, _vp]),
     "st_shot_boundaries": (_i, [_vp, _vp, _i, _i, _i, _d, _vp, _vp]),
     "st_fb_params_default": (None, [_c.POINTER(FbParams)]),
     "st_farneback_pairs": (_i, [_vp, _c.POINTER(_vp), _i, _c.POINTER(_c.c_int32), _i, _i, _i,

@@ -244,10 +244,8 @@ __device__ double exact_diff_of_products(unsigned long long a, unsigned long lon
   return u128_to_double(hi, lo);
 }
 
-__global__ __launch_bounds__(256) void k_frame_stats_finish(const long long* __restrict__ m, int n, long long N, int kind, void* out) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
-  const long long* r = m + (size_t)i * 8;
+// statistic `kind` (ST_FS_*) of one moments record r for frames of N pixels, as a double (the *_CPP kinds are then rounded to float)
+__device__ double fs_value(const long long* r, long long N, int kind) {
   const double dN = (double)N;
   double v = 0.0;
   switch (kind) {
@@ -283,8 +281,219 @@ __global__ __launch_bounds__(256) void k_frame_stats_finish(const long long* __r
       break;
     }
   }
+  return v;
+}
+__device__ __forceinline__ void fs_store(void* out, size_t i, int kind, double v) {
   if (kind <= ST_FS_SHARPNESS_CPP) reinterpret_cast<float*>(out)[i] = (float)v;
   else reinterpret_cast<double*>(out)[i] = v;
+}
+
+__global__ __launch_bounds__(256) void k_frame_stats_finish(const long long* __restrict__ m, int n, long long N, int kind, void* out) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  fs_store(out, (size_t)i, kind, fs_value(m + (size_t)i * 8, N, kind));
+}
+
+// ---- SharpnessBBox: boxes of a frame, resized to ST_BBOX_SIDE x ST_BBOX_SIDE, to Laplacian moments -----------------------------
+// Contract (imgproc.cpp:177-234, old/imgproc.py:44-54): per box, the region frame[y1:y2, x1:x2] treated as an image of its own
+// is resized to 200 x 200 at INTER_LINEAR with the Resize op's arithmetic (the device functions of st_internal.h: an equal size
+// is a copy, an exact 2 x 2 decimation the rounded mean of four, else 11-bit fixed-point two-tap rows and columns whose taps
+// clamp inside the region), and the moments S_c, Q_c of the reflect-101 Laplacian of that image are the record.
+//
+// Kernel.  One workgroup of 1024 threads per box.  The resized image is 120 000 bytes and is built in LDS (rows 640 bytes
+// apart), never in HBM; after a barrier the same workgroup takes the Laplacian out of LDS, reduces per-lane 32-bit partials
+// (at most 40 values of L^2 <= 1020^2 per lane and channel) to 64 bits and writes the box's record, and, if asked, the
+// finished statistic: one writer per record, no atomics, no zeroing pass.  128 KB of LDS means one workgroup per CU, and a
+// whole box keeps one CU busy for about 50 us (the pass is bound by that CU's vector ALU), so a call with fewer boxes than
+// CUs cuts every box into up to 10 bands of rows, one workgroup each (its band plus a halo row on each side), which write
+// their six sums to scratch; a second, tiny launch (k_bbox_finish) adds them up and finishes.  Measured on 1080p frames
+// (DESIGN.md 4.11): one box 50.9 us as one workgroup, against 38.3 us for the composed older entry points; banded, see there.
+//   copy (200 x 200 box): a row is fetched with 16-byte loads at the source's own alignment and lands in its LDS row at the
+//     same offset modulo 16, so no byte is shifted on the way in; the Laplacian pass adds the row's offset instead.
+//   2 x 2 mean (400 x 400): four output pixels per step, 24 contiguous bytes of two rows as unaligned dwords (the Resize kernel's).
+//   linear (everything else): per-column and per-row taps and weights are computed once per box into LDS, then four output
+//     pixels per step, each tap pair as two unaligned dwords (the Resize kernel's); a 1080p-wide box reads 6 bytes in 29.
+// The host has checked every box against the frame (bb_plan) before the launch; the kernel trusts its table.
+constexpr int BB_T = 1024;
+constexpr int BB_S = ST_BBOX_SIDE;
+constexpr int BB_ROW = 3 * BB_S;        // bytes of an image row
+constexpr int BB_PITCH = 640;           // LDS row pitch: the row + up to 15 bytes of source misalignment, a multiple of 16
+constexpr int BB_G = BB_S / 4;          // groups of four pixels per row
+constexpr int BB_MAX_BANDS = 10;        // a box is cut into at most this many bands of rows (calls with few boxes)
+constexpr int BB_VEC = (BB_ROW + 15 + 15) / 16;   // 16-byte vectors that can hold bytes of one misaligned row: 39
+static_assert(BB_S % 4 == 0 && BB_PITCH % 16 == 0 && BB_VEC * 16 <= BB_PITCH, "SharpnessBBox LDS layout");
+
+struct BoxK {
+  int frame, x1, y1, bw, bh, mode;   // mode: RS_COPY, RS_AREA2 or RS_LINEAR (st_rs_linear_mode on the host)
+  double scale_x, scale_y;           // cv::resize's source / destination ratios (st_rs_plan_scales on the host)
+};
+
+// bands == 1: the workgroup owns the whole image and writes the record (out) and / or the statistic (stat_out).  bands > 1
+// (calls with fewer boxes than CUs): workgroup box * bands + j builds rows j * band_rows - 1 .. (j + 1) * band_rows of the image
+// (its band and a halo row on each side) and writes its six sums to part[box * bands + j]; k_bbox_finish adds them up.
+__global__ __launch_bounds__(BB_T) void k_bbox_moments(FrameSrc src, int h, int w, const BoxK* __restrict__ boxes, int bands, int band_rows,
+                                                       unsigned long long* __restrict__ part, unsigned long long* __restrict__ out, int kind,
+                                                       void* stat_out) {
+  __shared__ uint4 img4[1 + BB_S * BB_PITCH / 16 + 1];   // 16 bytes of slack before and after: windows reach 3 bytes outside a row
+  __shared__ int tx_ofs[BB_S], ty_y0[BB_S], ty_y1[BB_S];
+  __shared__ unsigned tx_a[BB_S], ty_b[BB_S];            // a0 | a1 << 16, b0 | b1 << 16 (weights are 0 .. 2048)
+  __shared__ unsigned char tx_flags[BB_S];               // 1: two taps, 2: 8 bytes from the first tap stay inside the region row
+  __shared__ unsigned long long red[BB_T / 64][6];
+  unsigned* img = reinterpret_cast<unsigned*>(img4 + 1);
+  const int tid = threadIdx.x;
+  const size_t box = blockIdx.x / (unsigned)bands;
+  const int r0 = (int)(blockIdx.x % (unsigned)bands) * band_rows, r1 = min(r0 + band_rows, BB_S);   // rows this workgroup sums
+  const int fa = max(r0 - 1, 0), fb = min(r1 + 1, BB_S);   // rows it builds: reflect-101 keeps the neighbours of rows 0 and 199 inside
+  const BoxK b = boxes[box];
+  const uint8_t* p = src.ptrs ? src.ptrs[b.frame] : src.base + (size_t)b.frame * src.stride;
+  p = st_gl(p);
+  const long long frow = 3LL * w, N3 = frow * h;
+  const long long i0 = ((long long)b.y1 * w + b.x1) * 3;   // frame index of the region's first byte
+  const uint8_t* reg = p + i0;
+  // copy path: LDS row r starts (sa + r * ss) & 15 bytes into its pitch, the source row's own offset in its 16-byte block
+  const unsigned fs = (unsigned)((uintptr_t)p & 15);
+  const unsigned sa = b.mode == RS_COPY ? (unsigned)((i0 + fs) & 15) : 0u, ss = b.mode == RS_COPY ? (unsigned)(frow & 15) : 0u;
+
+  if (b.mode == RS_COPY) {
+    for (int idx = tid; idx < (fb - fa) * BB_VEC; idx += BB_T) {
+      const int r = fa + idx / BB_VEC, k = idx % BB_VEC;
+      const long long ir = i0 + r * frow;                       // frame index of the row's first byte
+      const long long v0 = ((ir + fs) & ~15LL) - fs + 16 * k;   // frame index of this vector's first byte (may be negative)
+      if (v0 >= ir + BB_ROW) continue;                          // past the row
+      uint4 q;
+      if (v0 >= 0 && v0 + 16 <= N3) {
+        const u4nt t = *reinterpret_cast<const u4nt*>(p + v0);
+        q = make_uint4(t.x, t.y, t.z, t.w);
+      } else {   // the vector holds bytes outside the frame: those stay unread
+        unsigned d[4] = {0, 0, 0, 0};
+        for (int j = 0; j < 16; ++j)
+          if (v0 + j >= 0 && v0 + j < N3) d[j >> 2] |= (unsigned)p[v0 + j] << (8 * (j & 3));
+        q = make_uint4(d[0], d[1], d[2], d[3]);
+      }
+      img4[1 + r * (BB_PITCH / 16) + k] = q;
+    }
+  } else if (b.mode == RS_AREA2) {
+    for (int idx = tid; idx < (fb - fa) * BB_G; idx += BB_T) {
+      const int r = fa + idx / BB_G, g = idx % BB_G;
+      const uint8_t* S0 = reg + (size_t)(2 * r) * frow + 24 * g;
+      unsigned o[3];
+      rs_area2_4px_c3(S0, S0 + frow, o);
+      unsigned* d = img + r * (BB_PITCH / 4) + 3 * g;
+      d[0] = o[0]; d[1] = o[1]; d[2] = o[2];
+    }
+  } else {
+    if (tid < BB_S) {
+      int sx;
+      const float fx = rs_linear_coord(tid, b.scale_x, &sx);
+      const RsTapX t = rs_linear_tap_x(sx, fx, b.bw);
+      tx_ofs[tid] = t.sx * 3;
+      tx_a[tid] = (unsigned)t.a0 | (unsigned)t.a1 << 16;
+      tx_flags[tid] = (unsigned char)((t.two ? 1 : 0) | ((long long)t.sx * 3 + 8 <= 3LL * b.bw ? 2 : 0));
+    } else if (tid >= 256 && tid < 256 + BB_S) {
+      const int dy = tid - 256;
+      int sy;
+      const float fy = rs_linear_coord(dy, b.scale_y, &sy);
+      const RsTapY t = rs_linear_tap_y(sy, fy, b.bh);
+      ty_y0[dy] = t.y0; ty_y1[dy] = t.y1;
+      ty_b[dy] = (unsigned)t.b0 | (unsigned)t.b1 << 16;
+    }
+    __syncthreads();
+    for (int idx = tid; idx < (fb - fa) * BB_G; idx += BB_T) {
+      const int r = fa + idx / BB_G, g = idx % BB_G;
+      const uint8_t* __restrict__ R0 = reg + (size_t)ty_y0[r] * frow;
+      const uint8_t* __restrict__ R1 = reg + (size_t)ty_y1[r] * frow;
+      const int b0 = (int)(ty_b[r] & 0xffffu), b1 = (int)(ty_b[r] >> 16);
+      unsigned o[3] = {0u, 0u, 0u};
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const int c = 4 * g + q;
+        const unsigned a = tx_a[c], fl = tx_flags[c];
+        rs_linear_px_c3(R0, R1, tx_ofs[c], (int)(a & 0xffffu), (int)(a >> 16), fl & 1, fl & 2, b0, b1, q, o);
+      }
+      unsigned* d = img + r * (BB_PITCH / 4) + 3 * g;
+      d[0] = o[0]; d[1] = o[1]; d[2] = o[2];
+    }
+  }
+  __syncthreads();
+
+  // Laplacian of the image in LDS, 12 bytes (four pixels) per step: a group starts at a multiple of 3, so byte j has channel j % 3
+  int s_c[3] = {0, 0, 0};
+  unsigned q_c[3] = {0, 0, 0};
+  for (int idx = tid; idx < (r1 - r0) * BB_G; idx += BB_T) {
+    const int r = r0 + idx / BB_G, g = idx % BB_G;
+    const int ru = r == 0 ? 1 : r - 1, rd = r == BB_S - 1 ? BB_S - 2 : r + 1;   // reflect-101
+    const int oc = r * BB_PITCH + (int)((sa + r * ss) & 15u) + 12 * g - 3;     // bytes -3 .. 14 of the group, this row
+    const int ou = ru * BB_PITCH + (int)((sa + ru * ss) & 15u) + 12 * g;
+    const int od = rd * BB_PITCH + (int)((sa + rd * ss) & 15u) + 12 * g;
+    unsigned c[5], u[3], d[3];
+    {
+      unsigned rc[6], rr[4];
+      const unsigned* wc = img + (oc >> 2);
+#pragma unroll
+      for (int k = 0; k < 6; ++k) rc[k] = wc[k];
+#pragma unroll
+      for (int k = 0; k < 5; ++k) c[k] = __builtin_amdgcn_alignbyte(rc[k + 1], rc[k], (unsigned)(oc & 3));
+      const unsigned* wu = img + (ou >> 2);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) rr[k] = wu[k];
+#pragma unroll
+      for (int k = 0; k < 3; ++k) u[k] = __builtin_amdgcn_alignbyte(rr[k + 1], rr[k], (unsigned)(ou & 3));
+      const unsigned* wd = img + (od >> 2);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) rr[k] = wd[k];
+#pragma unroll
+      for (int k = 0; k < 3; ++k) d[k] = __builtin_amdgcn_alignbyte(rr[k + 1], rr[k], (unsigned)(od & 3));
+    }
+#pragma unroll
+    for (int j = 0; j < 12; ++j) {
+      const unsigned cc = byte_of(c, j + 3);
+      unsigned lf = byte_of(c, j), rt = byte_of(c, j + 6);
+      if (j < 3 && g == 0) lf = rt;                 // column 0: reflect-101
+      if (j >= 9 && g == BB_G - 1) rt = lf;         // column 199
+      const int l = (int)(lf + rt + byte_of(u, j) + byte_of(d, j)) - 4 * (int)cc;
+      s_c[j % 3] += l;
+      q_c[j % 3] += (unsigned)(l * l);
+    }
+  }
+
+  long long acc[6];
+#pragma unroll
+  for (int ch = 0; ch < 3; ++ch) { acc[ch] = s_c[ch]; acc[3 + ch] = (long long)q_c[ch]; }
+#pragma unroll
+  for (int k = 0; k < 6; ++k)
+    for (int off = 32; off > 0; off >>= 1) acc[k] += __shfl_down(acc[k], off, 64);
+  if ((tid & 63) == 0)
+    for (int k = 0; k < 6; ++k) red[tid >> 6][k] = (unsigned long long)acc[k];
+  __syncthreads();
+  if (tid == 0) {
+    long long rec[8];
+    rec[ST_FM_SY] = 0; rec[ST_FM_QY] = 0;
+    for (int k = 0; k < 6; ++k) {
+      unsigned long long t = 0;
+      for (int wv = 0; wv < BB_T / 64; ++wv) t += red[wv][k];
+      rec[ST_FM_S_R + k] = (long long)t;
+    }
+    if (bands > 1) {
+      for (int k = 0; k < 6; ++k) part[(size_t)blockIdx.x * 6 + k] = (unsigned long long)rec[ST_FM_S_R + k];
+      return;
+    }
+    if (out)
+      for (int k = 0; k < 8; ++k) out[box * 8 + k] = (unsigned long long)rec[k];
+    if (stat_out) fs_store(stat_out, box, kind, fs_value(rec, (long long)BB_S * BB_S, kind));
+  }
+}
+
+// the banded launch's second half: one thread per box adds its bands' sums and writes the record and / or the statistic
+__global__ __launch_bounds__(256) void k_bbox_finish(const unsigned long long* __restrict__ part, int bands, int m,
+                                                     unsigned long long* __restrict__ out, int kind, void* stat_out) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= m) return;
+  long long rec[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  for (int j = 0; j < bands; ++j)
+    for (int k = 0; k < 6; ++k) rec[ST_FM_S_R + k] += (long long)part[((size_t)i * bands + j) * 6 + k];
+  if (out)
+    for (int k = 0; k < 8; ++k) out[(size_t)i * 8 + k] = (unsigned long long)rec[k];
+  if (stat_out) fs_store(stat_out, (size_t)i, kind, fs_value(rec, (long long)BB_S * BB_S, kind));
 }
 
 // Rows per band: about four workgroups per CU over the call, at least 4 rows (halo rows are re-read), and few enough steps
@@ -350,6 +559,94 @@ int fm_launch(st_ctx* ctx, FrameSrc src, int n, int h, int w, int what, int64_t*
   return ST_OK;
 }
 
+// Checks every box of a call and plans its resize; nothing has been enqueued when this fails
+int bb_plan(st_ctx* ctx, int n, int h, int w, const int32_t* boxes_host, int64_t m, const void* out, std::vector<BoxK>* plan) {
+  if (n < 0 || h <= 0 || w <= 0 || m < 0 || (m > 0 && (!boxes_host || !out)))
+    return st_set_error(ctx, ST_ERR_INVALID, "bbox moments: bad arguments (n=%d h=%d w=%d m=%lld)", n, h, w, (long long)m);
+  if (3LL * h * w > 0x7fffffffLL)
+    return st_set_error(ctx, ST_ERR_INVALID, "bbox moments: %dx%d frames exceed 2^31 - 1 bytes", h, w);
+  if (m > 0x7fffffffLL) return st_set_error(ctx, ST_ERR_UNSUPPORTED, "bbox moments: more than 2^31 - 1 boxes in one call");
+  plan->resize((size_t)m);
+  for (int64_t i = 0; i < m; ++i) {
+    const int32_t* r = boxes_host + 5 * i;
+    if (r[0] < 0 || r[0] >= n || r[1] < 0 || r[1] >= r[3] || r[3] > w || r[2] < 0 || r[2] >= r[4] || r[4] > h)
+      return st_set_error(ctx, ST_ERR_INVALID, "bbox moments: box %lld {frame %d, x %d..%d, y %d..%d} is not inside one of %d frames of %dx%d",
+                          (long long)i, r[0], r[1], r[3], r[2], r[4], n, w, h);
+    BoxK& b = (*plan)[(size_t)i];
+    b.frame = r[0]; b.x1 = r[1]; b.y1 = r[2]; b.bw = r[3] - r[1]; b.bh = r[4] - r[2];
+    const st_rs_scales s = st_rs_plan_scales(b.bh, b.bw, BB_S, BB_S);
+    b.mode = st_rs_linear_mode(b.bh, b.bw, BB_S, BB_S, s);
+    b.scale_x = s.scale_x; b.scale_y = s.scale_y;
+  }
+  return ST_OK;
+}
+
+// frames_host: the caller's pointer table (uploaded here) or null for a strided stream
+int bb_run(st_ctx* ctx, const uint8_t* const* frames_host, FrameSrc src, int n, int h, int w, const int32_t* boxes_host, int64_t m,
+           int64_t* moments_dev, int kind, void* stat_dev) {
+  std::vector<BoxK> plan;
+  ST_TRY(bb_plan(ctx, n, h, w, boxes_host, m, moments_dev ? (const void*)moments_dev : stat_dev, &plan));
+  if (m == 0) return ST_OK;
+  // A workgroup fills one CU (its LDS) and a whole box keeps it busy for about 50 us: a call with fewer boxes than CUs cuts
+  // every box into up to BB_MAX_BANDS bands of rows.  Integer sums: the record is the same bit for bit for any cut.
+  int bands = (int)(ctx->num_cus / m);
+  bands = bands < 1 ? 1 : (bands > BB_MAX_BANDS ? BB_MAX_BANDS : bands);
+  const int band_rows = (BB_S + bands - 1) / bands;
+  bands = (BB_S + band_rows - 1) / band_rows;
+  const size_t tb = frames_host ? st_align_up(sizeof(void*) * (size_t)n) : 0, bb = st_align_up(sizeof(BoxK) * (size_t)m);
+  const size_t pb = bands > 1 ? st_align_up(sizeof(unsigned long long) * 6 * (size_t)m * bands) : 0;
+  ST_TRY(st_ws_reserve(ctx, tb + bb + pb));
+  if (frames_host) {
+    const uint8_t** table = (const uint8_t**)st_ws_alloc(ctx, tb);
+    ST_HIP(ctx, hipMemcpyAsync(table, frames_host, sizeof(void*) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+    src.ptrs = table;
+  }
+  BoxK* boxes = (BoxK*)st_ws_alloc(ctx, bb);
+  unsigned long long* part = bands > 1 ? (unsigned long long*)st_ws_alloc(ctx, pb) : nullptr;
+  if (!boxes || (bands > 1 && !part)) return st_set_error(ctx, ST_ERR_OOM, "bbox moments: scratch plan exhausted");
+  // a pageable source: hipMemcpyAsync returns once the runtime has staged it, so the vector may go
+  ST_HIP(ctx, hipMemcpyAsync(boxes, plan.data(), sizeof(BoxK) * (size_t)m, hipMemcpyHostToDevice, ctx->stream));
+  hipEvent_t e0, e1;
+  ST_TRY(st_time_dispatch(ctx, ST_K_FRAME_STATS, &e0, &e1));
+  // boxes on grid.x, which reaches 2^31 - 1: one moments launch per call
+  hipExtLaunchKernelGGL(k_bbox_moments, dim3((unsigned)(m * bands)), dim3(BB_T), 0, ctx->stream, e0, e1, 0, src, h, w, (const BoxK*)boxes,
+                        bands, band_rows, part, reinterpret_cast<unsigned long long*>(moments_dev), kind, stat_dev);
+  ST_HIP(ctx, hipGetLastError());
+  if (bands > 1) {
+    ST_TRY(st_time_dispatch(ctx, ST_K_FRAME_STATS, &e0, &e1));
+    hipExtLaunchKernelGGL(k_bbox_finish, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, ctx->stream, e0, e1, 0,
+                          (const unsigned long long*)part, bands, (int)m, reinterpret_cast<unsigned long long*>(moments_dev), kind, stat_dev);
+    ST_HIP(ctx, hipGetLastError());
+  }
+  return ST_OK;
+}
+
+int bb_batch(st_ctx* ctx, const uint8_t* const* frames_dev, int n, int h, int w, const int32_t* boxes_host, int64_t m, int64_t* moments_dev,
+             int kind, void* stat_dev) {
+  ST_TRY(st_enter(ctx));
+  if (n > 0 && m > 0) {
+    if (!frames_dev) return st_set_error(ctx, ST_ERR_INVALID, "bbox moments: null frame table");
+    for (int i = 0; i < n; ++i)
+      if (!frames_dev[i]) return st_set_error(ctx, ST_ERR_INVALID, "bbox moments: frame %d is null", i);
+  }
+  return bb_run(ctx, frames_dev, FrameSrc{nullptr, nullptr, 0}, n, h, w, boxes_host, m, moments_dev, kind, stat_dev);
+}
+
+int bb_strided(st_ctx* ctx, const uint8_t* base_dev, size_t stride, int n, int h, int w, const int32_t* boxes_host, int64_t m,
+               int64_t* moments_dev, int kind, void* stat_dev) {
+  ST_TRY(st_enter(ctx));
+  if (n > 0 && m > 0 && h > 0 && w > 0 && (!base_dev || stride < (size_t)3 * h * w))
+    return st_set_error(ctx, ST_ERR_INVALID, "bbox moments: bad base/stride");
+  return bb_run(ctx, nullptr, FrameSrc{nullptr, base_dev, stride}, n, h, w, boxes_host, m, moments_dev, kind, stat_dev);
+}
+
+int bb_kind_check(st_ctx* ctx, int kind) {
+  ST_TRY(st_enter(ctx));
+  if (kind != ST_FS_SHARPNESS_CPP && kind != ST_FS_SHARPNESS)
+    return st_set_error(ctx, ST_ERR_INVALID, "bbox sharpness: kind %d is neither ST_FS_SHARPNESS_CPP nor ST_FS_SHARPNESS", kind);
+  return ST_OK;
+}
+
 }  // namespace
 
 ST_EXPORT int st_frame_moments_u8c3_batch(st_ctx* ctx, const uint8_t* const* frames_dev, int n, int h, int w, int what,
@@ -387,4 +684,26 @@ ST_EXPORT int st_frame_stats_finish(st_ctx* ctx, const int64_t* moments_dev, int
                         (long long)h * w, kind, out_dev);
   ST_HIP(ctx, hipGetLastError());
   return ST_OK;
+}
+
+ST_EXPORT int st_bbox_moments_u8c3_batch(st_ctx* ctx, const uint8_t* const* frames_dev, int n, int h, int w, const int32_t* boxes_host,
+                                         int64_t m, int64_t* moments_dev) {
+  return bb_batch(ctx, frames_dev, n, h, w, boxes_host, m, moments_dev, 0, nullptr);
+}
+
+ST_EXPORT int st_bbox_moments_u8c3_strided(st_ctx* ctx, const uint8_t* base_dev, size_t frame_stride_bytes, int n, int h, int w,
+                                           const int32_t* boxes_host, int64_t m, int64_t* moments_dev) {
+  return bb_strided(ctx, base_dev, frame_stride_bytes, n, h, w, boxes_host, m, moments_dev, 0, nullptr);
+}
+
+ST_EXPORT int st_bbox_sharpness_u8c3_batch(st_ctx* ctx, const uint8_t* const* frames_dev, int n, int h, int w, const int32_t* boxes_host,
+                                           int64_t m, int kind, void* out_dev) {
+  ST_TRY(bb_kind_check(ctx, kind));
+  return bb_batch(ctx, frames_dev, n, h, w, boxes_host, m, nullptr, kind, out_dev);
+}
+
+ST_EXPORT int st_bbox_sharpness_u8c3_strided(st_ctx* ctx, const uint8_t* base_dev, size_t frame_stride_bytes, int n, int h, int w,
+                                             const int32_t* boxes_host, int64_t m, int kind, void* out_dev) {
+  ST_TRY(bb_kind_check(ctx, kind));
+  return bb_strided(ctx, base_dev, frame_stride_bytes, n, h, w, boxes_host, m, nullptr, kind, out_dev);
 }

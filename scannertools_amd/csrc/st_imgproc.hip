@@ -211,8 +211,7 @@ __global__ __launch_bounds__(BL_T) void k_box_blur_u8c3(BlurArgsK a) {
 }
 
 // ---- Resize -------------------------------------------------------------------------------------
-enum { RS_NEAREST = 0, RS_LINEAR = 1, RS_AREA2 = 2, RS_COPY = 3, RS_CUBIC = 4, RS_AREA_INT = 5, RS_AREA = 6, RS_LINEAR_AREA = 7, RS_LANCZOS4 = 8 };
-
+// (the RS_* modes and the INTER_LINEAR / 2 x 2 device functions live in st_internal.h: the SharpnessBBox kernel shares them)
 struct ResizeArgsK {
   const uint8_t* const* src;
   uint8_t* const* dst;
@@ -246,12 +245,6 @@ __device__ __forceinline__ uint8_t* rs_dst_base(const ResizeTileArgsK& a, unsign
 }
 __device__ __forceinline__ uint8_t* rs_dst_px(const ResizeTileArgsK& a, uint8_t* base, int dy, int dx) {
   return base + (size_t)dy * a.pitch + (size_t)dx * 3;
-}
-
-// saturate_cast<short>(float): cvRound = round half to even, then saturation
-__device__ __forceinline__ int rs_coef(float v) {
-  const float r = rintf(v);
-  return r < -32768.f ? -32768 : (r > 32767.f ? 32767 : (int)r);
 }
 
 // cv::interpolateCubic, A = -0.75
@@ -419,26 +412,17 @@ __global__ __launch_bounds__(256) void k_resize_u8(ResizeArgsK a) {
       fy = (float)((dy + 1) - (sy + 1) * a.inv_scale_y);
       fy = fy <= 0 ? 0.f : fy - floorf(fy);
     } else {
-      fx = (float)((dx + 0.5) * a.scale_x - 0.5);
-      sx = (int)floorf(fx);
-      fx -= sx;
-      fy = (float)((dy + 0.5) * a.scale_y - 0.5);
-      sy = (int)floorf(fy);
-      fy -= sy;
+      fx = rs_linear_coord(dx, a.scale_x, &sx);
+      fy = rs_linear_coord(dy, a.scale_y, &sy);
     }
-    if (sx < 0) { fx = 0; sx = 0; }
-    if (sx >= a.sw - 1) { fx = 0; sx = a.sw - 1; }
-    const int a0 = rs_coef((1.f - fx) * 2048), a1 = rs_coef(fx * 2048);
-    const int b0 = rs_coef((1.f - fy) * 2048), b1 = rs_coef(fy * 2048);
-    const int y0 = sy < 0 ? 0 : (sy > a.sh - 1 ? a.sh - 1 : sy);
-    const int y1 = sy + 1 < 0 ? 0 : (sy + 1 > a.sh - 1 ? a.sh - 1 : sy + 1);
-    const uint8_t* S0 = src + (size_t)y0 * srow + (size_t)sx * cn;
-    const uint8_t* S1 = src + (size_t)y1 * srow + (size_t)sx * cn;
-    const bool two = sx + 1 < a.sw;  // the right edge takes a single tap * 2048
+    const RsTapX tx = rs_linear_tap_x(sx, fx, a.sw);   // the right edge takes a single tap * 2048
+    const RsTapY ty = rs_linear_tap_y(sy, fy, a.sh);
+    const uint8_t* S0 = src + (size_t)ty.y0 * srow + (size_t)tx.sx * cn;
+    const uint8_t* S1 = src + (size_t)ty.y1 * srow + (size_t)tx.sx * cn;
     for (int c = 0; c < cn; ++c) {
-      const int r0 = two ? S0[c] * a0 + S0[cn + c] * a1 : S0[c] * 2048;
-      const int r1 = two ? S1[c] * a0 + S1[cn + c] * a1 : S1[c] * 2048;
-      D[c] = (uint8_t)((((b0 * (r0 >> 4)) >> 16) + ((b1 * (r1 >> 4)) >> 16) + 2) >> 2);
+      const int r0 = rs_linear_h(S0[c], tx.two ? S0[cn + c] : 0, tx.a0, tx.a1, tx.two);
+      const int r1 = rs_linear_h(S1[c], tx.two ? S1[cn + c] : 0, tx.a0, tx.a1, tx.two);
+      D[c] = (uint8_t)rs_linear_v(r0, r1, ty.b0, ty.b1);
     }
   }
 }
@@ -470,16 +454,13 @@ __global__ __launch_bounds__(256) void k_resize_linear_c3_v4(A a) {
       fx = (float)((dx + 1) - (sx + 1) * a.inv_scale_x);
       fx = fx <= 0 ? 0.f : fx - floorf(fx);
     } else {
-      fx = (float)((dx + 0.5) * a.scale_x - 0.5);
-      sx = (int)floorf(fx);
-      fx -= sx;
+      fx = rs_linear_coord(dx, a.scale_x, &sx);
     }
-    if (sx < 0) { fx = 0; sx = 0; }
-    if (sx >= a.sw - 1) { fx = 0; sx = a.sw - 1; }
-    a0[p] = rs_coef((1.f - fx) * 2048); a1[p] = rs_coef(fx * 2048);
-    two[p] = sx + 1 < a.sw;  // the right edge takes a single tap * 2048
-    sxo[p] = sx * 3;
-    wide[p] = (size_t)sx * 3 + 8 <= srow;
+    const RsTapX t = rs_linear_tap_x(sx, fx, a.sw);
+    a0[p] = t.a0; a1[p] = t.a1;
+    two[p] = t.two;  // the right edge takes a single tap * 2048
+    sxo[p] = t.sx * 3;
+    wide[p] = (size_t)t.sx * 3 + 8 <= srow;
   }
   const int dy0 = blockIdx.y * RL_ROWS;
   for (int dy = dy0; dy < min(a.dh, dy0 + RL_ROWS); ++dy) {
@@ -490,43 +471,18 @@ __global__ __launch_bounds__(256) void k_resize_linear_c3_v4(A a) {
       fy = (float)((dy + 1) - (sy + 1) * a.inv_scale_y);
       fy = fy <= 0 ? 0.f : fy - floorf(fy);
     } else {
-      fy = (float)((dy + 0.5) * a.scale_y - 0.5);
-      sy = (int)floorf(fy);
-      fy -= sy;
+      fy = rs_linear_coord(dy, a.scale_y, &sy);
     }
-    const int b0 = rs_coef((1.f - fy) * 2048), b1 = rs_coef(fy * 2048);
-    const int y0 = sy < 0 ? 0 : (sy > a.sh - 1 ? a.sh - 1 : sy);
-    const int y1 = sy + 1 < 0 ? 0 : (sy + 1 > a.sh - 1 ? a.sh - 1 : sy + 1);
-    const uint8_t* __restrict__ R0 = src + (size_t)y0 * srow;
-    const uint8_t* __restrict__ R1 = src + (size_t)y1 * srow;
+    const RsTapY ty = rs_linear_tap_y(sy, fy, a.sh);
+    const uint8_t* __restrict__ R0 = src + (size_t)ty.y0 * srow;
+    const uint8_t* __restrict__ R1 = src + (size_t)ty.y1 * srow;
     unsigned out[3] = {0u, 0u, 0u};
     typedef unsigned u32u __attribute__((aligned(1)));
+    // the two source pixels of a row are 6 contiguous bytes at any byte offset: two unaligned dword loads instead of
+    // six byte loads (vector-memory instructions are what this kernel is short of), except where 8 bytes would run
+    // past the end of the row (rs_linear_px_c3, st_internal.h)
 #pragma unroll
-    for (int p = 0; p < 4; ++p) {
-      // the two source pixels of a row are 6 contiguous bytes at any byte offset: two unaligned dword loads instead of
-      // six byte loads (vector-memory instructions are what this kernel is short of), except where 8 bytes would run
-      // past the end of the row
-      int t0[6], t1[6];
-      if (wide[p]) {
-        const unsigned l0 = *reinterpret_cast<const u32u*>(R0 + sxo[p]), h0 = *reinterpret_cast<const u32u*>(R0 + sxo[p] + 4);
-        const unsigned l1 = *reinterpret_cast<const u32u*>(R1 + sxo[p]), h1 = *reinterpret_cast<const u32u*>(R1 + sxo[p] + 4);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) { t0[k] = (l0 >> (8 * k)) & 0xff; t1[k] = (l1 >> (8 * k)) & 0xff; }
-        t0[4] = h0 & 0xff; t0[5] = (h0 >> 8) & 0xff; t1[4] = h1 & 0xff; t1[5] = (h1 >> 8) & 0xff;
-      } else {
-#pragma unroll
-        for (int k = 0; k < 3; ++k) { t0[k] = R0[sxo[p] + k]; t1[k] = R1[sxo[p] + k]; }
-#pragma unroll
-        for (int k = 3; k < 6; ++k) { t0[k] = two[p] ? R0[sxo[p] + k] : 0; t1[k] = two[p] ? R1[sxo[p] + k] : 0; }
-      }
-#pragma unroll
-      for (int c = 0; c < 3; ++c) {
-        const int r0 = two[p] ? t0[c] * a0[p] + t0[3 + c] * a1[p] : t0[c] * 2048;
-        const int r1 = two[p] ? t1[c] * a0[p] + t1[3 + c] * a1[p] : t1[c] * 2048;
-        const unsigned v = (unsigned)((((b0 * (r0 >> 4)) >> 16) + ((b1 * (r1 >> 4)) >> 16) + 2) >> 2) & 0xffu;
-        out[(3 * p + c) >> 2] |= v << (8 * ((3 * p + c) & 3));
-      }
-    }
+    for (int p = 0; p < 4; ++p) rs_linear_px_c3(R0, R1, sxo[p], a0[p], a1[p], two[p], wide[p], ty.b0, ty.b1, p, out);
     uint8_t* ob = rs_dst_px(a, reinterpret_cast<uint8_t*>(dst), dy, 4 * g);  // any byte when 3 * dw % 4 != 0
     if (npx == 4) {
       u32u* o = reinterpret_cast<u32u*>(ob);
@@ -551,19 +507,8 @@ __global__ __launch_bounds__(256) void k_resize_area2_c3_v4(A a) {
   const uint8_t* S0 = src + (size_t)(2 * dy) * srow + (size_t)(8 * g) * 3;
   const uint8_t* S1 = S0 + srow;
   if (4 * g + 4 <= a.dw) {
-    unsigned w0[6], w1[6];
-#pragma unroll
-    for (int k = 0; k < 6; ++k) { w0[k] = reinterpret_cast<const u32u*>(S0)[k]; w1[k] = reinterpret_cast<const u32u*>(S1)[k]; }
-    unsigned out[3] = {0u, 0u, 0u};
-#pragma unroll
-    for (int p = 0; p < 4; ++p)
-#pragma unroll
-      for (int c = 0; c < 3; ++c) {
-        const int i0 = 6 * p + c, i1 = 6 * p + 3 + c;  // bytes of the two source columns
-        const unsigned v = (((w0[i0 >> 2] >> (8 * (i0 & 3))) & 0xffu) + ((w0[i1 >> 2] >> (8 * (i1 & 3))) & 0xffu) +
-                            ((w1[i0 >> 2] >> (8 * (i0 & 3))) & 0xffu) + ((w1[i1 >> 2] >> (8 * (i1 & 3))) & 0xffu) + 2u) >> 2;
-        out[(3 * p + c) >> 2] |= v << (8 * ((3 * p + c) & 3));
-      }
+    unsigned out[3];
+    rs_area2_4px_c3(S0, S1, out);
     u32u* o = reinterpret_cast<u32u*>(ob);
     o[0] = out[0]; o[1] = out[1]; o[2] = out[2];
   } else {
@@ -1421,22 +1366,34 @@ ST_EXPORT int st_box_blur_u8c3_batch(st_ctx* ctx, const uint8_t* const* frames_d
   return ST_OK;
 }
 
+// cv::resize's scale factors for (h, w) -> (out_h, out_w) (st_internal.h)
+st_rs_scales st_rs_plan_scales(int h, int w, int out_h, int out_w) {
+  st_rs_scales s;
+  const double inv_sx = (double)out_w / w, inv_sy = (double)out_h / h;
+  s.scale_x = 1. / inv_sx; s.scale_y = 1. / inv_sy;
+  s.inv_scale_x = inv_sx; s.inv_scale_y = inv_sy;
+  s.iscale_x = (int)lrint(s.scale_x); s.iscale_y = (int)lrint(s.scale_y);
+  s.area_fast = fabs(s.scale_x - s.iscale_x) < DBL_EPSILON && fabs(s.scale_y - s.iscale_y) < DBL_EPSILON;
+  return s;
+}
+
 namespace {
-// cv::resize's scale factors for (h, w) -> (out_h, out_w) and the path it takes: an equal size is a copy, an exact 2 x 2
-// decimation under INTER_LINEAR or INTER_AREA the mean of four (st_resize_u8_batch and st_montage_u8c3_batch share this)
+// The path cv::resize takes: an equal size is a copy, an exact 2 x 2 decimation under INTER_LINEAR or INTER_AREA the mean
+// of four (st_resize_u8_batch and st_montage_u8c3_batch share this; INTER_LINEAR's choice is st_rs_linear_mode, which the
+// SharpnessBBox kernel takes per box)
 void rs_plan(ResizeArgsK* a, int h, int w, int channels, int out_h, int out_w, int interpolation) {
   a->sh = h; a->sw = w; a->dh = out_h; a->dw = out_w; a->cn = channels;
-  const double inv_sx = (double)out_w / w, inv_sy = (double)out_h / h;
-  a->scale_x = 1. / inv_sx; a->scale_y = 1. / inv_sy;
-  a->inv_scale_x = inv_sx; a->inv_scale_y = inv_sy;
-  a->iscale_x = (int)lrint(a->scale_x); a->iscale_y = (int)lrint(a->scale_y);
-  const bool area_fast = fabs(a->scale_x - a->iscale_x) < DBL_EPSILON && fabs(a->scale_y - a->iscale_y) < DBL_EPSILON;
+  const st_rs_scales s = st_rs_plan_scales(h, w, out_h, out_w);
+  a->scale_x = s.scale_x; a->scale_y = s.scale_y;
+  a->inv_scale_x = s.inv_scale_x; a->inv_scale_y = s.inv_scale_y;
+  a->iscale_x = s.iscale_x; a->iscale_y = s.iscale_y;
+  const bool area_fast = s.area_fast;
   if (h == out_h && w == out_w) a->mode = RS_COPY;
   else if (interpolation == ST_INTER_NEAREST) a->mode = RS_NEAREST;
   else if (interpolation == ST_INTER_CUBIC) a->mode = RS_CUBIC;
   else if (interpolation == ST_INTER_LANCZOS4) a->mode = RS_LANCZOS4;
-  else if ((interpolation == ST_INTER_LINEAR || interpolation == ST_INTER_AREA) && area_fast && a->iscale_x == 2 && a->iscale_y == 2) a->mode = RS_AREA2;
-  else if (interpolation == ST_INTER_LINEAR) a->mode = RS_LINEAR;
+  else if (interpolation == ST_INTER_LINEAR) a->mode = st_rs_linear_mode(h, w, out_h, out_w, s);
+  else if (interpolation == ST_INTER_AREA && area_fast && a->iscale_x == 2 && a->iscale_y == 2) a->mode = RS_AREA2;
   else if (a->scale_x >= 1 && a->scale_y >= 1) a->mode = area_fast ? RS_AREA_INT : RS_AREA;
   else a->mode = RS_LINEAR_AREA;
 }

@@ -111,4 +111,109 @@ __device__ __forceinline__ T* st_gl(T* p) {
 }
 #endif
 
+// ---- cv::resize's INTER_LINEAR arithmetic for 8-bit data, shared by the Resize / Montage kernels (st_imgproc.hip) and the
+// SharpnessBBox kernel (st_framestats.hip), so that a box resized inside the statistics kernel cannot drift from the op.
+enum { RS_NEAREST = 0, RS_LINEAR = 1, RS_AREA2 = 2, RS_COPY = 3, RS_CUBIC = 4, RS_AREA_INT = 5, RS_AREA = 6, RS_LINEAR_AREA = 7, RS_LANCZOS4 = 8 };
+
+// cv::resize's scale factors for (h, w) -> (out_h, out_w), computed on the host, and the path INTER_LINEAR takes: an equal
+// size is a copy (RS_COPY), an exact 2 x 2 decimation the mean of four (RS_AREA2, INTER_AREA's fast path), else RS_LINEAR
+struct st_rs_scales {
+  double scale_x, scale_y, inv_scale_x, inv_scale_y;
+  int iscale_x, iscale_y;
+  bool area_fast;   // both ratios are integers
+};
+st_rs_scales st_rs_plan_scales(int h, int w, int out_h, int out_w);
+inline int st_rs_linear_mode(int h, int w, int out_h, int out_w, const st_rs_scales& s) {
+  if (h == out_h && w == out_w) return RS_COPY;
+  if (s.area_fast && s.iscale_x == 2 && s.iscale_y == 2) return RS_AREA2;
+  return RS_LINEAR;
+}
+
+#ifdef __HIPCC__
+// saturate_cast<short>(float): cvRound = round half to even, then saturation
+__device__ __forceinline__ int rs_coef(float v) {
+  const float r = rintf(v);
+  return r < -32768.f ? -32768 : (r > 32767.f ? 32767 : (int)r);
+}
+
+// INTER_LINEAR's source coordinate of destination index d: the first tap's index and the fraction towards the second
+__device__ __forceinline__ float rs_linear_coord(int d, double scale, int* s) {
+  const float f = (float)((d + 0.5) * scale - 0.5);
+  *s = (int)floorf(f);
+  return f - *s;
+}
+
+// Horizontal taps of one destination column: the column is clamped into the row (a single tap * 2048 at the right edge),
+// 11-bit weights.  sx: the first tap's column; two: a second tap exists at sx + 1.
+struct RsTapX { int sx, a0, a1; bool two; };
+__device__ __forceinline__ RsTapX rs_linear_tap_x(int sx, float fx, int sw) {
+  RsTapX t;
+  if (sx < 0) { fx = 0; sx = 0; }
+  if (sx >= sw - 1) { fx = 0; sx = sw - 1; }
+  t.a0 = rs_coef((1.f - fx) * 2048); t.a1 = rs_coef(fx * 2048);
+  t.two = sx + 1 < sw;
+  t.sx = sx;
+  return t;
+}
+// Vertical taps of one destination row: both rows clamped into the image
+struct RsTapY { int y0, y1, b0, b1; };
+__device__ __forceinline__ RsTapY rs_linear_tap_y(int sy, float fy, int sh) {
+  RsTapY t;
+  t.b0 = rs_coef((1.f - fy) * 2048); t.b1 = rs_coef(fy * 2048);
+  t.y0 = sy < 0 ? 0 : (sy > sh - 1 ? sh - 1 : sy);
+  t.y1 = sy + 1 < 0 ? 0 : (sy + 1 > sh - 1 ? sh - 1 : sy + 1);
+  return t;
+}
+// HResizeLinear for one channel of one row (v0, v1: the two taps' bytes) and VResizeLinear<uchar> of the two row values
+__device__ __forceinline__ int rs_linear_h(int v0, int v1, int a0, int a1, bool two) { return two ? v0 * a0 + v1 * a1 : v0 * 2048; }
+__device__ __forceinline__ int rs_linear_v(int r0, int r1, int b0, int b1) { return (((b0 * (r0 >> 4)) >> 16) + ((b1 * (r1 >> 4)) >> 16) + 2) >> 2; }
+
+// One output pixel of the 3-channel INTER_LINEAR kernels: the two source pixels of a row are 6 contiguous bytes at R + sxo,
+// read as two unaligned dwords when `wide` (8 bytes from sxo stay inside the row), bytewise otherwise.  The three output
+// bytes go into bytes 3p .. 3p + 2 of out[0..2] (which the caller zeroed).
+__device__ __forceinline__ void rs_linear_px_c3(const uint8_t* __restrict__ R0, const uint8_t* __restrict__ R1, int sxo, int a0, int a1, bool two,
+                                                bool wide, int b0, int b1, int p, unsigned* out) {
+  typedef unsigned u32u __attribute__((aligned(1)));
+  int t0[6], t1[6];
+  if (wide) {
+    const unsigned l0 = *reinterpret_cast<const u32u*>(R0 + sxo), h0 = *reinterpret_cast<const u32u*>(R0 + sxo + 4);
+    const unsigned l1 = *reinterpret_cast<const u32u*>(R1 + sxo), h1 = *reinterpret_cast<const u32u*>(R1 + sxo + 4);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) { t0[k] = (l0 >> (8 * k)) & 0xff; t1[k] = (l1 >> (8 * k)) & 0xff; }
+    t0[4] = h0 & 0xff; t0[5] = (h0 >> 8) & 0xff; t1[4] = h1 & 0xff; t1[5] = (h1 >> 8) & 0xff;
+  } else {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) { t0[k] = R0[sxo + k]; t1[k] = R1[sxo + k]; }
+#pragma unroll
+    for (int k = 3; k < 6; ++k) { t0[k] = two ? R0[sxo + k] : 0; t1[k] = two ? R1[sxo + k] : 0; }
+  }
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const int r0 = rs_linear_h(t0[c], t0[3 + c], a0, a1, two);
+    const int r1 = rs_linear_h(t1[c], t1[3 + c], a0, a1, two);
+    const unsigned v = (unsigned)rs_linear_v(r0, r1, b0, b1) & 0xffu;
+    out[(3 * p + c) >> 2] |= v << (8 * ((3 * p + c) & 3));
+  }
+}
+
+// The exact 2 x 2 decimation of four output pixels of a 3-channel image: 24 contiguous source bytes in each of two rows
+// (six unaligned dword loads per row), (v00 + v01 + v10 + v11 + 2) >> 2, twelve output bytes in out[0..2].
+__device__ __forceinline__ void rs_area2_4px_c3(const uint8_t* __restrict__ S0, const uint8_t* __restrict__ S1, unsigned* out) {
+  typedef unsigned u32u __attribute__((aligned(1)));
+  unsigned w0[6], w1[6];
+#pragma unroll
+  for (int k = 0; k < 6; ++k) { w0[k] = reinterpret_cast<const u32u*>(S0)[k]; w1[k] = reinterpret_cast<const u32u*>(S1)[k]; }
+  out[0] = out[1] = out[2] = 0u;
+#pragma unroll
+  for (int p = 0; p < 4; ++p)
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      const int i0 = 6 * p + c, i1 = 6 * p + 3 + c;  // bytes of the two source columns
+      const unsigned v = (((w0[i0 >> 2] >> (8 * (i0 & 3))) & 0xffu) + ((w0[i1 >> 2] >> (8 * (i1 & 3))) & 0xffu) +
+                          ((w1[i0 >> 2] >> (8 * (i0 & 3))) & 0xffu) + ((w1[i1 >> 2] >> (8 * (i1 & 3))) & 0xffu) + 2u) >> 2;
+      out[(3 * p + c) >> 2] |= v << (8 * ((3 * p + c) & 3));
+    }
+}
+#endif
+
 #endif  // ST_INTERNAL_H_

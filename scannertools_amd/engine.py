@@ -81,6 +81,7 @@ def _load_op_library(path):
                                      ctypes.POINTER(ci), ci, ctypes.POINTER(ci)]
         L.stshim_op_state.argtypes = [ctypes.c_char_p, ctypes.POINTER(ci), ctypes.POINTER(ci)]
         L.stshim_op_output_name.argtypes = [ctypes.c_char_p, ci, ctypes.c_char_p, ci]
+        L.stshim_op_input_name.argtypes = [ctypes.c_char_p, ci, ctypes.c_char_p, ci]
         L.stshim_kernel_create.restype = vp
         L.stshim_kernel_create.argtypes = [ctypes.c_char_p, ci, ci, ctypes.c_char_p, sz, ctypes.c_char_p, sz]
         L.stshim_kernel_destroy.argtypes = [vp]
@@ -164,8 +165,14 @@ def op_info(name):
         buf = ctypes.create_string_buffer(64)
         if L.stshim_op_output_name(name.encode(), i, buf, 64) == 0:
             names.append(buf.value.decode())
+    in_names = []
+    for i in range(n_in.value):
+        buf = ctypes.create_string_buffer(64)
+        if L.stshim_op_input_name(name.encode(), i, buf, 64) == 0:
+            in_names.append(buf.value.decode())
     return {"inputs": n_in.value, "outputs": n_out.value, "frame_output": bool(isf.value),
-            "stencil": list(st[:ns.value]) or [0], "unbounded_state": bool(unbounded.value), "output_names": names}
+            "stencil": list(st[:ns.value]) or [0], "unbounded_state": bool(unbounded.value), "output_names": names,
+            "input_names": in_names}
 
 
 def plan_runs(idx, unbounded=False):
@@ -572,6 +579,23 @@ class _CppMultiOpNode(_Node):
             L.stshim_kernel_destroy(k)
 
 
+class _SharpnessBBoxNode(_CppMultiOpNode):
+    """SharpnessBBoxCPP (old/cpp_ops/imgproc.cpp:177-234): frames that are not (h, w, 3) uint8, malformed ``bboxes`` bytes and
+    boxes that are empty or not inside their frame are a ValueError here, naming row and box, before any kernel instance
+    exists (the kernel class can only abort)."""
+
+    def rows(self, idx):
+        from . import frame_stats as _fs
+        if not idx:
+            return []
+        frames, boxes = self.parents[0].rows(idx), self.parents[1].rows(idx)
+        _fs.bbox_records(self.name, frames, boxes, row_ids=idx)
+        node = copy.copy(self)
+        n = self.length()
+        node.parents = [_RowsNode(dict(zip(idx, frames)), n), _RowsNode(dict(zip(idx, boxes)), n)]
+        return _CppMultiOpNode.rows(node, idx)
+
+
 class _PyOpNode(_Node):
     """A batched python op over one input column (ShotBoundaries: batch = whole stream)."""
 
@@ -648,8 +672,12 @@ class NamedStream:
 
     def _rows(self):
         if self.name not in self.sc._tables:
-            raise KeyError("stream %r has not been written (run the graph first)" % self.name)
+            raise KeyError("stream %r has not been written (run the graph first, or Client.ingest_rows)" % self.name)
         return self.sc._tables[self.name]
+
+    def _frames(self):
+        """The stream as the input of a graph (sc.io.Input): its rows as they are stored."""
+        return self._rows()[0]
 
     def len(self):
         return len(self._rows()[0])
@@ -798,6 +826,24 @@ class _Ops:
         """sc.ops.Sharpness(frame=frame): the python op of old/imgproc.py:33-36, computed on the GPU."""
         return self._frame_stat_py("Sharpness", frame)
 
+    def SharpnessBBoxCPP(self, frame, bboxes, device=None, batch=None, width=0, height=0):
+        """db.ops.SharpnessBBoxCPP(frame=..., bboxes=...) (old/imgproc.py:156, with the column it forgets): per box of the row's
+        ``bboxes`` element the SharpnessCPP value of the box resized to 200 x 200, 4 bytes per box."""
+        from . import _proto
+        node = _SharpnessBBoxNode(self.sc, "SharpnessBBoxCPP", [frame, bboxes], device, batch,
+                                  _proto.encode([(1, "int32", int(width)), (2, "int32", int(height))]))   # ImgProcArgs (ignored)
+        node.reader = _types.sharpness_bbox
+        return node
+
+    def SharpnessBBox(self, frame, bboxes):
+        """sc.ops.SharpnessBBox(frame=frame, bboxes=bboxes): the python op of old/imgproc.py:44-54 (a pickled list of
+        np.float64 per row), computed on the GPU (scannertools_amd.frame_stats)."""
+        from . import frame_stats as _fs
+        dev = self.sc.device_id
+        node = _PyMapNode(lambda frames, boxes: _fs.bbox_rows_py(frames, boxes, device=dev), [frame, bboxes])
+        node.reader = _types.pickled
+        return node
+
     def InfoFromFrame(self, frame):
         """sc.ops.InfoFromFrame(frame=frame): the frame's FrameInfo as a bytes column."""
         return _FrameInfoNode(frame)
@@ -879,6 +925,12 @@ class Client:
         """Register decoded RGB frames (n,h,w,3) uint8 -- numpy or a CUDA torch tensor -- as a
         named video stream (stands in for ingest_videos + the H.264 decoder)."""
         self._videos[name] = frames
+
+    def ingest_rows(self, name, rows, reader=None):
+        """Register a stream of byte rows (e.g. a detector's ``bboxes`` elements, scannertools_amd.types.write_bboxes) under
+        ``name``: ``sc.io.Input([NamedStream(sc, name)])`` feeds it to an op beside a video stream.  ``reader`` is what
+        NamedStream.load applies to a row."""
+        self._tables[name] = ([bytes(r) for r in rows], reader)
 
     def run(self, outputs, perf_params=None, cache_mode=CacheMode.Error, show_progress=False, **_kw):
         outputs = outputs if isinstance(outputs, (list, tuple)) else [outputs]

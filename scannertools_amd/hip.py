@@ -194,6 +194,75 @@ class HipContext:
         self._check(self._L.st_frame_stats_finish(self._h, ctypes.c_void_p(m.data_ptr()), n, h, w, k, ctypes.c_void_p(out.data_ptr())))
         return out
 
+    def _bbox_args(self, frames, boxes):
+        """(list-of-frames?, n, h, w, frame argument, int32 (m, 5) box records) of a bbox_* call.  Every box is checked
+        here, against the frame count and size, before the library is entered."""
+        boxes = np.ascontiguousarray(np.asarray(boxes, dtype=np.int64).reshape(-1, 5))
+        if isinstance(frames, (list, tuple)):
+            n = len(frames)
+            for f in frames:
+                _require_cuda(f, torch.uint8, "frame", self.device)
+            if n and (frames[0].dim() != 3 or frames[0].shape[2] != 3):
+                raise ValueError("frames must be (h,w,3)")
+            h, w = (int(frames[0].shape[0]), int(frames[0].shape[1])) if n else (1, 1)
+            if any(tuple(f.shape) != (h, w, 3) for f in frames):
+                raise ValueError("all frames must be (h,w,3) with equal shape")
+            arg = (ctypes.c_void_p * max(n, 1))(*[f.data_ptr() for f in frames])
+        else:
+            _require_cuda(frames, torch.uint8, "frames", self.device)
+            if frames.dim() != 4 or frames.shape[3] != 3:
+                raise ValueError("frames must be (n,h,w,3)")
+            n, h, w = int(frames.shape[0]), int(frames.shape[1]), int(frames.shape[2])
+            arg = ctypes.c_void_p(frames.data_ptr())
+        f, x1, y1, x2, y2 = boxes.T
+        bad = ~((0 <= f) & (f < n) & (0 <= x1) & (x1 < x2) & (x2 <= w) & (0 <= y1) & (y1 < y2) & (y2 <= h))
+        if bad.any():
+            i = int(np.argmax(bad))
+            raise ValueError("box %d {frame %d, x %d..%d, y %d..%d} is empty or not inside one of %d frames of %dx%d"
+                             % ((i,) + tuple(boxes[i].tolist()[k] for k in (0, 1, 3, 2, 4)) + (n, w, h)))
+        return isinstance(frames, (list, tuple)), n, h, w, arg, np.ascontiguousarray(boxes.astype(np.int32))
+
+    def bbox_moments(self, frames, boxes, out=None):
+        """Exact Laplacian moments of boxes of U8 RGB frames, each box resized to 200 x 200 with the Resize op's INTER_LINEAR
+        arithmetic (st_bbox_moments_u8c3_*; the SharpnessBBox ops, old/cpp_ops/imgproc.cpp:177-234): int64 (m, 8) in the
+        layout of frame_moments, row i = [0, 0, sum L_R, sum L_G, sum L_B, sum L_R^2, sum L_G^2, sum L_B^2] of box i.
+        frames: CUDA uint8 tensor (n,h,w,3) or a list of (h,w,3) tensors of one shape.  boxes: (m, 5) integers
+        [frame index, x1, y1, x2, y2], the region being rows y1 .. y2-1 and columns x1 .. x2-1 of that frame; a box that is
+        empty or not inside its frame is a ValueError and nothing is launched.  One launch for all boxes."""
+        self._bind()
+        is_list, n, h, w, arg, rec = self._bbox_args(frames, boxes)
+        m = rec.shape[0]
+        out = (torch.empty((m, 8), dtype=torch.int64, device=self.device) if out is None
+               else _check_out(out, (m, 8), torch.int64, self.device))
+        if m == 0:
+            return out
+        bp = rec.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))
+        if is_list:
+            self._check(self._L.st_bbox_moments_u8c3_batch(self._h, arg, n, h, w, bp, m, ctypes.c_void_p(out.data_ptr())))
+        else:
+            self._check(self._L.st_bbox_moments_u8c3_strided(self._h, arg, 3 * h * w, n, h, w, bp, m, ctypes.c_void_p(out.data_ptr())))
+        return out
+
+    def bbox_sharpness(self, frames, boxes, kind):
+        """One sharpness value per box (st_bbox_sharpness_u8c3_*: the moments launch with the finishing formula fused):
+        ``kind`` "SharpnessCPP" gives float32, the element of SharpnessBBoxCPP (imgproc.cpp:210-226), "Sharpness" float64, the
+        value SharpnessBBox pickles (old/imgproc.py:44-54).  frames and boxes as for bbox_moments."""
+        k = _native.FS_KINDS[kind] if isinstance(kind, str) else int(kind)
+        if k not in (_native.FS_KINDS["SharpnessCPP"], _native.FS_KINDS["Sharpness"]):
+            raise ValueError("bbox_sharpness: kind must be SharpnessCPP or Sharpness, not %r" % (kind,))
+        self._bind()
+        is_list, n, h, w, arg, rec = self._bbox_args(frames, boxes)
+        m = rec.shape[0]
+        out = torch.empty((m,), dtype=torch.float32 if k < 3 else torch.float64, device=self.device)
+        if m == 0:
+            return out
+        bp = rec.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))
+        if is_list:
+            self._check(self._L.st_bbox_sharpness_u8c3_batch(self._h, arg, n, h, w, bp, m, k, ctypes.c_void_p(out.data_ptr())))
+        else:
+            self._check(self._L.st_bbox_sharpness_u8c3_strided(self._h, arg, 3 * h * w, n, h, w, bp, m, k, ctypes.c_void_p(out.data_ptr())))
+        return out
+
     # -- flow consumers ---------------------------------------------------------------------
     def shot_boundaries(self, hist, window=500, k_std=2.5, return_diffs=False):
         """ShotBoundaries on device-resident histograms (shot_detection.py:12-28): hist = CUDA int32 (n, 3, bins) as

@@ -2,7 +2,7 @@
 (`_register_module(<pkg dir>, "scannertools_imgproc")`, /root/reference/scannertools/scannertools/
 imgproc/__init__.py:1-3).  Importing this module makes the ops Histogram, OpticalFlow,
 FlowHistogram, Blur, Resize, ConvertColor, Montage (a contact sheet: frame k resized into tile k of one canvas) and the
-legacy library's BrightnessCPP, ContrastCPP and SharpnessCPP
+legacy library's BrightnessCPP, ContrastCPP, SharpnessCPP and SharpnessBBoxCPP
 available: inside a Scanner deployment through
 ``scannertools_infra._register_module`` (Scanner then dlopens libscannertools_imgproc.so, whose
 static initialisers run REGISTER_OP / REGISTER_KERNEL); standalone through the in-process engine
