@@ -198,8 +198,21 @@ int st_shot_boundaries(st_ctx* ctx, const int32_t* hist_dev, int n, int bins, in
  * numIters, polyN, polySigma, flags); st_fb_params_default() gives the reference's
  * (3, 0.5, false, 15, 3, 5, 1.2, 0) (optical_flow_kernel_cpu.cpp:15-16).  Implemented:
  * flags == 0 (box filter, no initial flow), fast_pyramids == 0, poly_n in {5, 7},
- * odd win_size <= 63.  gray_bits selects cv::cvtColor's 8-bit luma table: 15 (OpenCV 4.x)
- * or 14 (OpenCV <= 3.4.2). */
+ * odd win_size in 3...63, num_iters >= 1, num_levels >= 0, pyr_scale in (0, 1).  gray_bits
+ * selects cv::cvtColor's 8-bit luma table: 15 (OpenCV 4.x) or 14 (OpenCV <= 3.4.2).
+ * win_size == 1 is refused (ST_ERR_UNSUPPORTED): at a window radius of 0 the reference's
+ * running sums count row 0 and column 0 twice, so every "box sum" it forms is M[y] + M[0]; what
+ * it returns there is an artefact of that initialisation, not a flow, and is not reproduced.
+ * Two limits on the pyramid, both checked for every level before anything is launched
+ * (ST_ERR_UNSUPPORTED, nothing written): the Gaussian of a level, cvRound(5 * sigma) | 1 taps
+ * with sigma = (1 / pyr_scale^k - 1) / 2, has at most 31 taps (pyr_scale^k above 0.0735); and a
+ * level that is not an exact 2 / 4 / 8 decimation with the reference's 3 / 9 / 19 taps is built
+ * in tiles of 8 x 32 pixels whose source rows and columns, Gaussian apron included, must fit
+ * 64 KiB of LDS: with s = 1 / pyr_scale^k and r = taps / 2,
+ *   rows = ceil(7 s) + 2 r + 4, cols = (ceil(31 s) + 2 r + 4) rounded up to 4, 256 rows + rows cols <= 65536
+ * (at 1080p the deepest level that can be built: pyr_scale 0.3: 1, 0.45: 2, 0.5: 3, 0.6: 4,
+ * 0.7: 6, 0.75: 8, 0.8: 10; num_levels beyond it is refused where the frame is large enough to
+ * reach that level). */
 typedef struct st_fb_params {
   int num_levels;
   double pyr_scale;
@@ -251,7 +264,8 @@ int st_fb_update_matrices(st_ctx* ctx, const float* r0_dev, const float* r1_dev,
                           const float* coarse_flow_dev, int ch, int cw, double pyr_scale, int h, int w,
                           float* m_dev /* (5,h,w) */);
 /* One FarnebackUpdateFlow_Blur pass: flow_out = solve(box(M)); if update != 0 additionally
- * m_out = UpdateMatrices(R0, R1, flow_out).  m_out must not alias m_in. */
+ * m_out = UpdateMatrices(R0, R1, flow_out).  m_out must not alias m_in.  block_size: odd, 3...63
+ * (1 is refused as win_size 1 is). */
 int st_fb_update_flow_blur(st_ctx* ctx, const float* r0_dev, const float* r1_dev, const float* m_in_dev,
                            int h, int w, int block_size, int update, float* flow_out_dev,
                            float* m_out_dev);

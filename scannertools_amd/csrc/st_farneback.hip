@@ -2831,21 +2831,62 @@ __global__ __launch_bounds__(FT_NT) void k_flow_iter_tile(IterArgs a) {
 // ---------------------------------------------------------------------------------------------
 // host orchestration
 // ---------------------------------------------------------------------------------------------
+// Which kernel builds one pyramid level (launch_pyr), and the dynamic LDS the general one (k_pyr) needs for its tile:
+// PYR_OH x PYR_OW outputs, the source rows and columns under them at the level's ratio, and the Gaussian's apron.
+struct PyrPlan {
+  int kind;              // 0: k_pyr0 (level 0 streamed), 2 / 4 / 8: k_pyr_dec, 1: k_pyr
+  int mode, max_rows, max_cols;
+  size_t lds;
+};
+constexpr size_t kPyrLdsMax = 64 * 1024;
+
+PyrPlan pyr_plan(int h, int w, const LevelGeom& g) {
+  PyrPlan q;
+  memset(&q, 0, sizeof(q));
+  if (g.lh == h && g.lw == w && g.ksize == 3 && h >= 2 && w >= 8) return q;
+  if (w == 2 * g.lw && h == 2 * g.lh && g.ksize == 3) q.kind = 2;
+  else if (w == 4 * g.lw && h == 4 * g.lh && g.ksize == 9) q.kind = 4;
+  else if (w == 8 * g.lw && h == 8 * g.lh && g.ksize == 19) q.kind = 8;
+  if (q.kind) return q;
+  q.kind = 1;
+  if (g.lh == h && g.lw == w) q.mode = PYR_COPY;
+  else if (w == 2 * g.lw && h == 2 * g.lh) q.mode = PYR_AREA2;
+  else q.mode = PYR_LINEAR;
+  const double scale_x = 1. / ((double)g.lw / w), scale_y = 1. / ((double)g.lh / h);
+  const int r = g.ksize / 2;
+  q.max_rows = (int)std::ceil((PYR_OH - 1) * scale_y) + 3 + 2 * r + 1;
+  q.max_cols = ((int)std::ceil((PYR_OW - 1) * scale_x) + 3 + 2 * r + 1 + 3) / 4 * 4;
+  q.lds = sizeof(float) * (size_t)q.max_rows * 2 * PYR_OW + (size_t)q.max_rows * q.max_cols;
+  return q;
+}
+
+// A level the library cannot build: Gaussian above kMaxTaps - 1 taps, or a k_pyr tile above 64 KiB of LDS
+int check_pyr_level(st_ctx* ctx, int h, int w, const LevelGeom& g, int k) {
+  if (g.ksize > kMaxTaps - 1)
+    return st_set_error(ctx, ST_ERR_UNSUPPORTED, "farneback: pyramid level %d: kernel size %d too large (at most %d)", k, g.ksize, kMaxTaps - 1);
+  if (g.lh < 1 || g.lw < 1) return ST_OK;   // the callers report an empty level themselves
+  const PyrPlan q = pyr_plan(h, w, g);
+  if (q.lds > kPyrLdsMax)
+    return st_set_error(ctx, ST_ERR_UNSUPPORTED, "farneback: pyramid level %d (kernel size %d) needs a tile of %zu B of LDS (at most %zu)", k,
+                        g.ksize, q.lds, kPyrLdsMax);
+  return ST_OK;
+}
+
 int check_params(st_ctx* ctx, const st_fb_params& p, int h, int w) {
   if (h <= 0 || w <= 0) return st_set_error(ctx, ST_ERR_INVALID, "farneback: bad frame size %dx%d", w, h);
   if (p.flags != 0) return st_set_error(ctx, ST_ERR_UNSUPPORTED, "farneback: flags=%d (only 0 implemented)", p.flags);
   if (p.fast_pyramids) return st_set_error(ctx, ST_ERR_UNSUPPORTED, "farneback: fastPyramids not implemented");
   if (!(p.pyr_scale > 0 && p.pyr_scale < 1)) return st_set_error(ctx, ST_ERR_INVALID, "farneback: pyr_scale must be in (0,1)");
   if (p.poly_n != 5 && p.poly_n != 7) return st_set_error(ctx, ST_ERR_UNSUPPORTED, "farneback: poly_n=%d (5 or 7)", p.poly_n);
-  if (p.win_size < 1 || p.win_size > 63 || !(p.win_size & 1))
-    return st_set_error(ctx, ST_ERR_UNSUPPORTED, "farneback: win_size=%d (odd, <= 63)", p.win_size);
+  if (p.win_size < 3 || p.win_size > 63 || !(p.win_size & 1))
+    return st_set_error(ctx, ST_ERR_UNSUPPORTED, "farneback: win_size=%d (odd, 3...63)", p.win_size);
   if (p.num_iters < 1 || p.num_levels < 0) return st_set_error(ctx, ST_ERR_INVALID, "farneback: bad iteration/level count");
   if (p.gray_bits != 14 && p.gray_bits != 15) return st_set_error(ctx, ST_ERR_INVALID, "farneback: gray_bits must be 14 or 15");
   if ((long long)h * w > 200000000LL) return st_set_error(ctx, ST_ERR_UNSUPPORTED, "farneback: frames above 200 Mpx are not supported (32-bit plane offsets)");
   int levels = fb_levels(h, w, p);
   for (int k = 0; k <= levels; ++k) {
     LevelGeom g = fb_level_geom(h, w, p, k);
-    if (g.ksize > kMaxTaps - 1) return st_set_error(ctx, ST_ERR_UNSUPPORTED, "farneback: pyramid kernel size %d too large", g.ksize);
+    ST_TRY(check_pyr_level(ctx, h, w, g, k));
     if (g.lh < 1 || g.lw < 1) return st_set_error(ctx, ST_ERR_INVALID, "farneback: empty pyramid level");
   }
   return ST_OK;
@@ -2910,7 +2951,8 @@ int launch_pyr(st_ctx* ctx, const uint8_t* gray, int n, int h, int w, const Leve
   gaussian_kernel(g.ksize, g.sigma, a.taps);
   const double inv_sx = (double)g.lw / w, inv_sy = (double)g.lh / h;
   a.scale_x = 1. / inv_sx; a.scale_y = 1. / inv_sy;
-  if (g.lh == h && g.lw == w && g.ksize == 3 && h >= 2 && w >= 8) {
+  const PyrPlan q = pyr_plan(h, w, g);   // the one place that picks the kernel
+  if (q.kind == 0) {
     Pyr0Args z;
     z.gray = gray; z.img = img; z.h = h; z.w = w; z.k0 = a.taps[1]; z.k1 = a.taps[2];
     const int bx = ((w + 3) / 4 + 255) / 256;
@@ -2923,39 +2965,30 @@ int launch_pyr(st_ctx* ctx, const uint8_t* gray, int n, int h, int w, const Leve
     ST_HIP(ctx, hipGetLastError());
     return ST_OK;
   }
-  {
+  if (q.kind != 1) {
     // exact power-of-two decimation with the reference's kernel sizes: dedicated marching kernel
-    int S = 0;
-    if (w == 2 * g.lw && h == 2 * g.lh && g.ksize == 3) S = 2;
-    else if (w == 4 * g.lw && h == 4 * g.lh && g.ksize == 9) S = 4;
-    else if (w == 8 * g.lw && h == 8 * g.lh && g.ksize == 19) S = 8;
-    if (S) {
-      PyrDecArgs z;
-      z.gray = gray; z.img = img; z.sh = h; z.sw = w; z.dh = g.lh; z.dw = g.lw;
-      memcpy(z.taps, a.taps, sizeof(z.taps));
-      const int bx = (g.lw + 255) / 256;
-      long long segs = ((long long)ctx->num_cus * 8 + (long long)bx * n - 1) / ((long long)bx * n);
-      int rows = (int)((g.lh + segs - 1) / segs);
-      const int min_rows = S == 8 ? 4 : 8;
-      if (rows < min_rows) rows = g.lh < min_rows ? g.lh : min_rows;
-      z.rows_per_seg = rows;
-      dim3 grid(bx, (g.lh + rows - 1) / rows, n);
-      st_timed t(ctx, ST_K_PYR);
-      if (S == 2) hipLaunchKernelGGL((k_pyr_dec<2, 3>), grid, dim3(256), 0, ctx->stream, z);
-      else if (S == 4) hipLaunchKernelGGL((k_pyr_dec<4, 9>), grid, dim3(256), 0, ctx->stream, z);
-      else hipLaunchKernelGGL((k_pyr_dec<8, 19>), grid, dim3(256), 0, ctx->stream, z);
-      ST_HIP(ctx, hipGetLastError());
-      return ST_OK;
-    }
+    const int S = q.kind;
+    PyrDecArgs z;
+    z.gray = gray; z.img = img; z.sh = h; z.sw = w; z.dh = g.lh; z.dw = g.lw;
+    memcpy(z.taps, a.taps, sizeof(z.taps));
+    const int bx = (g.lw + 255) / 256;
+    long long segs = ((long long)ctx->num_cus * 8 + (long long)bx * n - 1) / ((long long)bx * n);
+    int rows = (int)((g.lh + segs - 1) / segs);
+    const int min_rows = S == 8 ? 4 : 8;
+    if (rows < min_rows) rows = g.lh < min_rows ? g.lh : min_rows;
+    z.rows_per_seg = rows;
+    dim3 grid(bx, (g.lh + rows - 1) / rows, n);
+    st_timed t(ctx, ST_K_PYR);
+    if (S == 2) hipLaunchKernelGGL((k_pyr_dec<2, 3>), grid, dim3(256), 0, ctx->stream, z);
+    else if (S == 4) hipLaunchKernelGGL((k_pyr_dec<4, 9>), grid, dim3(256), 0, ctx->stream, z);
+    else hipLaunchKernelGGL((k_pyr_dec<8, 19>), grid, dim3(256), 0, ctx->stream, z);
+    ST_HIP(ctx, hipGetLastError());
+    return ST_OK;
   }
-  if (g.lh == h && g.lw == w) a.mode = PYR_COPY;
-  else if (w == 2 * g.lw && h == 2 * g.lh) a.mode = PYR_AREA2;
-  else a.mode = PYR_LINEAR;
-  const int r = g.ksize / 2;
-  a.max_rows = (int)std::ceil((PYR_OH - 1) * a.scale_y) + 3 + 2 * r + 1;
-  a.max_cols = ((int)std::ceil((PYR_OW - 1) * a.scale_x) + 3 + 2 * r + 1 + 3) / 4 * 4;
-  size_t lds = sizeof(float) * (size_t)a.max_rows * 2 * PYR_OW + (size_t)a.max_rows * a.max_cols;
-  if (lds > 64 * 1024) return st_set_error(ctx, ST_ERR_UNSUPPORTED, "farneback: pyramid tile needs %zu B of LDS", lds);
+  // (check_params and st_fb_pyr_image refuse a level whose tile does not fit before anything is launched; this is the backstop)
+  a.mode = q.mode; a.max_rows = q.max_rows; a.max_cols = q.max_cols;
+  const size_t lds = q.lds;
+  if (lds > kPyrLdsMax) return st_set_error(ctx, ST_ERR_UNSUPPORTED, "farneback: pyramid tile needs %zu B of LDS", lds);
   dim3 grid((g.lw + PYR_OW - 1) / PYR_OW, (g.lh + PYR_OH - 1) / PYR_OH, n);
   st_timed t(ctx, ST_K_PYR);
   hipLaunchKernelGGL(k_pyr, grid, dim3(256), lds, ctx->stream, a);
@@ -3514,7 +3547,8 @@ ST_EXPORT int st_fb_pyr_image(st_ctx* ctx, const uint8_t* gray_dev, int h, int w
   if (!gray_dev || !img_dev || level < 0) return st_set_error(ctx, ST_ERR_INVALID, "pyr: bad arguments");
   ST_TRY(check_params(ctx, p, h, w));
   LevelGeom g = fb_level_geom(h, w, p, level);
-  if (g.ksize > kMaxTaps - 1 || g.lh < 1 || g.lw < 1) return st_set_error(ctx, ST_ERR_UNSUPPORTED, "pyr: level %d unsupported", level);
+  ST_TRY(check_pyr_level(ctx, h, w, g, level));   // (a level beyond those check_params walked)
+  if (g.lh < 1 || g.lw < 1) return st_set_error(ctx, ST_ERR_UNSUPPORTED, "pyr: level %d is empty", level);
   if (pyr_fused_ok(h, w, p) && level <= 3) {
     // the production path builds all four levels in one pass; run exactly that and hand out one
     const size_t np0 = (size_t)h * w;
@@ -3587,7 +3621,8 @@ ST_EXPORT int st_fb_update_flow_blur(st_ctx* ctx, const float* r0_dev, const flo
                                      int w, int block_size, int update, float* flow_out_dev, float* m_out_dev) {
   ST_TRY(st_enter(ctx));
   if (!m_in_dev || !flow_out_dev || h <= 0 || w <= 0) return st_set_error(ctx, ST_ERR_INVALID, "update_flow_blur: bad arguments");
-  if (block_size < 1 || block_size > 63 || !(block_size & 1)) return st_set_error(ctx, ST_ERR_UNSUPPORTED, "update_flow_blur: block_size=%d", block_size);
+  if (block_size < 3 || block_size > 63 || !(block_size & 1))
+    return st_set_error(ctx, ST_ERR_UNSUPPORTED, "update_flow_blur: block_size=%d (odd, 3...63)", block_size);
   if (update && (!r0_dev || !r1_dev || !m_out_dev || m_out_dev == m_in_dev))
     return st_set_error(ctx, ST_ERR_INVALID, "update_flow_blur: update needs R0, R1 and a distinct m_out");
   BlurArgs b;

@@ -49,23 +49,44 @@ def calls(h, w):
 
 
 # ---------------------------------------------------------------- restated host predicates
-def levels(h, w):
-    return oracle.fb_levels(h, w)                            # fb_levels :49
+# Every predicate takes an optional `params`: a dict of st_fb_params fields that differ from st_fb_params_default()
+# (tests/test_flow_params.py walks that axis); None is the reference's (3, 0.5, 15, 3, 5, 1.2), gray_bits 15.
+DEFAULT_PARAMS = dict(num_levels=3, pyr_scale=0.5, win_size=15, num_iters=3, poly_n=5, poly_sigma=1.2, gray_bits=15)
 
 
-def geom(h, w, k):
-    return oracle.fb_level_geom(h, w, k)                     # fb_level_geom :59 -> (lh, lw, sigma, ksize)
+def param(params, name):
+    return (params or {}).get(name, DEFAULT_PARAMS[name])
 
 
-def pyr_fused_ok(h, w):
-    """:2911-2919: exactly 3 levels, sides multiples of 8, every level exactly halved, kernel sizes 3 / 3 / 9 / 19."""
-    if levels(h, w) != 3 or h & 7 or w & 7:
+def _op(params):
+    return oracle.default_params(**params) if params else None
+
+
+def levels(h, w, params=None):
+    return oracle.fb_levels(h, w, _op(params))               # fb_levels :49
+
+
+def geom(h, w, k, params=None):
+    return oracle.fb_level_geom(h, w, k, _op(params))        # fb_level_geom :59 -> (lh, lw, sigma, ksize)
+
+
+def pyr_fused_ok(h, w, params=None):
+    """pyr_fused_ok: exactly 3 levels, sides multiples of 8, every level exactly halved, kernel sizes 3 / 3 / 9 / 19."""
+    if levels(h, w, params) != 3 or h & 7 or w & 7:
         return False
     for k, ks in enumerate((3, 3, 9, 19)):
-        lh, lw, _, ksize = geom(h, w, k)
+        lh, lw, _, ksize = geom(h, w, k, params)
         if lh != h >> k or lw != w >> k or ksize != ks:
             return False
     return True
+
+
+def fused_path(h, w, params=None):
+    """fused_path: the fused iteration kernels take the 15 x 15 window on frames whose every level is at least 2 x 2;
+    every other window goes through k_update_matrices + the blur kernel with materialised M."""
+    if param(params, "win_size") != 15:
+        return False
+    return all(min(geom(h, w, k, params)[:2]) >= 2 for k in range(levels(h, w, params) + 1))
 
 
 def pyr_strip_w(w):
@@ -74,17 +95,17 @@ def pyr_strip_w(w):
     return strips, ((w + strips - 1) // strips + 7) // 8 * 8
 
 
-def single(h, w, npairs):
+def single(h, w, npairs, params=None):
     """:3279: all levels' expansions in one launch (one-pass pyramid, up to 16 pairs)."""
-    return pyr_fused_ok(h, w) and 1 <= levels(h, w) <= 3 and npairs <= 16
+    return pyr_fused_ok(h, w, params) and 1 <= levels(h, w, params) <= 3 and npairs <= 16
 
 
-def poly_u8(h, w, npairs):
+def poly_u8(h, w, npairs, params=None):
     """:3280-3281 in the default context (ST_POLY_U8 on, role-split pyramid on, gray not folded): level 0 expanded from
     the gray frames."""
     pyr_rgb = False                                          # :3270, fold_gray is off by default
-    lh, lw, sigma, ksize = geom(h, w, 0)
-    return (pyr_fused_ok(h, w) and not pyr_rgb and not single(h, w, npairs) and ksize == 3 and sigma <= 0
+    lh, lw, sigma, ksize = geom(h, w, 0, params)
+    return (pyr_fused_ok(h, w, params) and not pyr_rgb and not single(h, w, npairs, params) and ksize == 3 and sigma <= 0
             and (lh, lw) == (h, w) and w >= 8)
 
 
@@ -130,45 +151,63 @@ def iter_kernel(h, w, n_pairs, coarse, num_cus=NUM_CUS):
     return "iter3"
 
 
-def iter_launches(h, w, npairs):
-    """Every launch_flow_iter of one pass (fused path, 3 iterations per level, coarse to fine): (level, kernel, source),
-    source as the instance is chosen at :3144 / :3168 (the tile kernel has one coarse instance, FLOW_COARSE)."""
-    L = levels(h, w)
+def iter_plan(h, w, npairs, params=None):
+    """Every launch_flow_iter of one pass (fused path, num_iters iterations per level, coarse to fine), as
+    farneback_pass's loop issues them: a dict per launch with the level `k`, the iteration `it`, the kernel `kern`, the
+    source instance `src` (as chosen in launch_flow_iter; the tile kernel has one coarse instance, FLOW_COARSE), the
+    buffer it reads (`reads`: None, "cflow<i>" or "fbuf<i>"), the buffer it writes (`writes`: "fbuf<i>", "cflow<i>" or
+    "flow_ptrs", the caller's output frames) and, for a coarse source, the upsampling `ratio` (rows over coarse rows)."""
+    L = levels(h, w, params)
+    iters = param(params, "num_iters")
     out = []
+    cur = 0                                                  # cflow[cur] holds the coarser level's flow
     for k in range(L, -1, -1):
-        lh, lw, _, _ = geom(h, w, k)
-        for it in range(3):
+        lh, lw, _, _ = geom(h, w, k, params)
+        for it in range(iters):
             coarse = it == 0 and k < L
+            last = it == iters - 1
             kern = iter_kernel(lh, lw, npairs, coarse)
+            ratio = None
             if coarse:
-                src = "FLOW_COARSE" if kern == "tile" or lh != 2 * geom(h, w, k + 1)[0] else "FLOW_COARSE2"
+                ch = geom(h, w, k + 1, params)[0]
+                src = "FLOW_COARSE" if kern == "tile" or lh != 2 * ch else "FLOW_COARSE2"
+                reads, ratio = "cflow%d" % cur, lh / ch
+            elif it > 0:
+                src, reads = "FLOW_FIELD", "fbuf%d" % ((it - 1) & 1)
             else:
-                src = "FLOW_FIELD" if it > 0 else "FLOW_ZERO"
-            out.append((k, kern, src))
+                src, reads = "FLOW_ZERO", None
+            writes = ("flow_ptrs" if k == 0 else "cflow%d" % (cur ^ 1)) if last else "fbuf%d" % (it & 1)
+            out.append(dict(k=k, it=it, kern=kern, src=src, reads=reads, writes=writes, ratio=ratio))
+        cur ^= 1
     return out
+
+
+def iter_launches(h, w, npairs, params=None):
+    """(level, kernel, source) of every launch of iter_plan."""
+    return [(q["k"], q["kern"], q["src"]) for q in iter_plan(h, w, npairs, params)]
 
 
 def align_up(v, a=256):
     return (v + a - 1) // a * a
 
 
-def pass_bytes(h, w, nf, npairs):
-    """:3190-3210 (the fused iteration path: every level of these geometries is at least 2 x 2)."""
-    L = levels(h, w)
+def pass_bytes(h, w, nf, npairs, params=None):
+    """pass_bytes: two flow fields per pair on the fused iteration path, two five-plane M fields on the unfused one."""
+    L = levels(h, w, params)
     np0 = h * w
-    npk = [geom(h, w, k)[0] * geom(h, w, k)[1] for k in range(L + 1)]
+    npk = [geom(h, w, k, params)[0] * geom(h, w, k, params)[1] for k in range(L + 1)]
     max_coarse = max(npk[1:], default=0)
     b = align_up(np0 * nf) + align_up(4 * np0 * nf)
-    if pyr_fused_ok(h, w):
+    if pyr_fused_ok(h, w, params):
         b += sum(align_up(4 * (np0 >> (2 * k)) * nf) for k in (1, 2, 3))
     b += sum(align_up(4 * 5 * n * nf) for n in npk)
-    b += 2 * align_up(4 * 2 * np0 * npairs)
+    b += 2 * align_up(4 * (2 if fused_path(h, w, params) else 5) * np0 * npairs)
     b += 2 * align_up(4 * 2 * (max_coarse or 1) * npairs)
     b += align_up(8 * nf) + align_up(4 * 2 * npairs) + align_up(8 * npairs)
     return b + 4096
 
 
-def plan_passes(h, w, pairs, ws_limit=DEFAULT_WS_LIMIT):
+def plan_passes(h, w, pairs, ws_limit=DEFAULT_WS_LIMIT, params=None):
     """st_farneback_pairs :3413-3437: runs of pairs halved until one pass fits the limit; returns, per pass, the
     distinct frame indices it touches (in slot order) and its pair count."""
     passes, start, n = [], 0, len(pairs)
@@ -180,7 +219,7 @@ def plan_passes(h, w, pairs, ws_limit=DEFAULT_WS_LIMIT):
                 for f in (a, b):
                     if f not in frames:
                         frames.append(f)
-            if pass_bytes(h, w, len(frames), count) <= ws_limit or count == 1:
+            if pass_bytes(h, w, len(frames), count, params) <= ws_limit or count == 1:
                 break
             count = (count + 1) // 2
         passes.append((frames, count))
@@ -195,16 +234,16 @@ def split_limit(h, w):
     return int(8 * per_pair)
 
 
-def paths(h, w, pairs, ws_limit=DEFAULT_WS_LIMIT):
-    """The set of paths one call takes."""
+def paths(h, w, pairs, ws_limit=DEFAULT_WS_LIMIT, params=None):
+    """The set of paths one call takes (the iteration launches: on the fused path only)."""
     got = set()
-    for frames, npairs in plan_passes(h, w, pairs, ws_limit):
+    for frames, npairs in plan_passes(h, w, pairs, ws_limit, params):
         al = aligned4(h, w, frames)
-        got.add("pyr_fused" if pyr_fused_ok(h, w) else "pyr_per_level")
-        got.add("polyexp_single" if single(h, w, npairs) else "polyexp_per_level")
-        got.add("poly_u8" if poly_u8(h, w, npairs) else "poly_f32")
+        got.add("pyr_fused" if pyr_fused_ok(h, w, params) else "pyr_per_level")
+        got.add("polyexp_single" if single(h, w, npairs, params) else "polyexp_per_level")
+        got.add("poly_u8" if poly_u8(h, w, npairs, params) else "poly_f32")
         got.add("aligned" if al else "unaligned")
-        for k, kern, src in iter_launches(h, w, npairs):
+        for k, kern, src in (iter_launches(h, w, npairs, params) if fused_path(h, w, params) else []):
             if k == 0:
                 got.add("L0:" + kern)
             if kern != "tile":

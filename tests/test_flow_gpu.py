@@ -380,7 +380,9 @@ def test_flow_tiny_frames(hip_ctx, h, w):
 def test_flow_rejects_unsupported(hip_ctx):
     from scannertools_amd.hip import StError
     f = torch.zeros((2, 64, 64, 3), dtype=torch.uint8, device="cuda")
-    for kw in (dict(flags=256), dict(fast_pyramids=1), dict(poly_n=6), dict(win_size=14), dict(pyr_scale=1.5)):
+    for kw in (dict(flags=256), dict(fast_pyramids=1), dict(poly_n=6), dict(win_size=14), dict(pyr_scale=1.5),
+               dict(num_iters=0), dict(num_levels=-1), dict(gray_bits=13), dict(pyr_scale=0.0), dict(pyr_scale=1.0),
+               dict(win_size=65), dict(win_size=1)):
         with pytest.raises(StError):
             hip_ctx.optical_flow(f, params=default_params(**kw))
     with pytest.raises(StError):

@@ -187,7 +187,30 @@ def cvt_source(rng, code, h, w):
     return rng.integers(0, 256, (h, w, cin), dtype=np.uint8)
 
 
-def assert_flow_close(got, ref, frame_a, frame_b, what=""):
+def float64_flow(frame_a, frame_b, params=None):
+    """The independent float64 derivation's flow between two RGB frames; params: a dict of st_fb_params fields that differ
+    from the defaults (None: the reference's parameters)."""
+    import oracle
+    import ref_farneback_np as exact
+    p = dict(params or {})
+    bits = p.get("gray_bits", 15)
+    return exact.farneback(oracle.gray_u8(frame_a, bits), oracle.gray_u8(frame_b, bits), num_levels=p.get("num_levels", 3),
+                           pyr_scale=p.get("pyr_scale", 0.5), win=p.get("win_size", 15), iters=p.get("num_iters", 3),
+                           poly_n=p.get("poly_n", 5), poly_sigma=p.get("poly_sigma", 1.2))
+
+
+def within_half_again(got, ref, f64, size=45):
+    """The second tier-2 rule of assert_flow_close: the kernel is as close to exact arithmetic as the oracle is, within half
+    again -- every pixel against the oracle's worst distance within its size x size neighbourhood, and in L2 over the field."""
+    from scipy import ndimage as _ndi
+    noise = np.abs(ref - f64).max(-1)
+    eg = np.abs(got - f64).max(-1)
+    local = _ndi.maximum_filter(noise, size=size, mode="nearest")
+    return bool((eg <= 1.5 * local + 5e-3).all() and
+                np.linalg.norm(got - f64) <= 1.5 * np.linalg.norm(ref - f64) + 1e-4 * np.linalg.norm(f64) + 1e-6)
+
+
+def assert_flow_close(got, ref, frame_a, frame_b, what="", params=None):
     """Flow of the HIP path against the oracle: max-abs <= 5e-3 px and relative L2 <= 1e-4 -- tier 1, what all but a few
     in ten thousand fuzz pairs (and every benchmark-sized, textured pair) meet.
 
@@ -209,6 +232,10 @@ def assert_flow_close(got, ref, frame_a, frame_b, what=""):
               border or where the float64 normal equations have det + 1e-3 <= 0.05 (textured 8-bit images: 1e2..1e4),
               none is beyond 0.1 px, relative L2 <= 1e-4 over the other pixels and <= 1e-3 (the north-star bound)
               over the whole field (fields below 20 000 pixels: 1e-3 x sqrt(20 000 / n), the footprint of a flip being fixed).
+    params: a dict of the st_fb_params fields that differ from the defaults, when `ref` was computed with other parameters
+    than the reference's: the float64 arbitration then runs with the same parameters, and the neighbourhood of the
+    half-again rule is 3 x win_size instead of the fixed 45 (three box filters of win_size carry one pixel's rounding
+    residue that far).
     Returns the tier that passed (1, 2 or 3)."""
     d = np.abs(got - ref).max(-1)
     nref = max(float(np.linalg.norm(ref)), 1e-30)
@@ -216,8 +243,10 @@ def assert_flow_close(got, ref, frame_a, frame_b, what=""):
         return 1
     import oracle
     import ref_farneback_np as exact
-    g0, g1 = oracle.gray_u8(frame_a), oracle.gray_u8(frame_b)
-    f64 = exact.farneback(g0, g1)
+    prm = dict(params or {})
+    win = prm.get("win_size", 15)
+    g0, g1 = oracle.gray_u8(frame_a, prm.get("gray_bits", 15)), oracle.gray_u8(frame_b, prm.get("gray_bits", 15))
+    f64 = float64_flow(frame_a, frame_b, prm)
     noise = np.abs(ref - f64).max(-1)
     out = d > 5e-3
 
@@ -234,10 +263,7 @@ def assert_flow_close(got, ref, frame_a, frame_b, what=""):
     # oracle's own distance in the pixel's neighbourhood (45 x 45: three iterations of the 15 x 15 box filter carry one pixel's
     # rounding residue that far), not against the worst pixel of the field, so that one noisy pixel in a corner cannot excuse
     # an error somewhere else
-    from scipy import ndimage as _ndi
-    eg = np.abs(got - f64).max(-1)
-    local = _ndi.maximum_filter(noise, size=45, mode="nearest")
-    if (eg <= 1.5 * local + 5e-3).all() and np.linalg.norm(got - f64) <= 1.5 * np.linalg.norm(ref - f64) + 1e-4 * np.linalg.norm(f64) + 1e-6:
+    if within_half_again(got, ref, f64, 3 * win):
         return 2
     # tier 3: where are the outliers?
     # one flipped pixel moves its whole 15 x 15 box window: on frames of a few thousand pixels two windows are more than 0.75 %
@@ -247,8 +273,9 @@ def assert_flow_close(got, ref, frame_a, frame_b, what=""):
     h, w = d.shape
     yy, xx = np.mgrid[0:h, 0:w]
     near_border = (yy < 24) | (yy >= h - 24) | (xx < 24) | (xx >= w - 24)
-    R0, R1 = exact.poly_expansion(exact.pyramid_image(g0, 0)), exact.poly_expansion(exact.pyramid_image(g1, 0))
-    B = np.stack([ndimage.uniform_filter(exact.update_matrices(R0, R1, f64)[..., c], size=15, mode="nearest") for c in range(3)], -1)
+    pn, ps = prm.get("poly_n", 5), prm.get("poly_sigma", 1.2)
+    R0, R1 = exact.poly_expansion(exact.pyramid_image(g0, 0), pn, ps), exact.poly_expansion(exact.pyramid_image(g1, 0), pn, ps)
+    B = np.stack([ndimage.uniform_filter(exact.update_matrices(R0, R1, f64)[..., c], size=win, mode="nearest") for c in range(3)], -1)
     flat = B[..., 0] * B[..., 2] - B[..., 1] * B[..., 1] + 1e-3 <= 0.05
     bad = out & ~(near_border | flat)
     assert not bad.any(), (what, "pixels beyond 5e-3 px in the textured interior", int(bad.sum()), float(d[bad].max()))
