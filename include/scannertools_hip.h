@@ -99,7 +99,8 @@ enum st_kernel_id {
   ST_K_CPM2_RESIZE = 14,
   ST_K_CPM2_NMS = 15,
   ST_K_FRAME_STATS = 16, /* moments + finishing launches of the frame-statistics ops */
-  ST_K_COUNT = 17
+  ST_K_JPEG = 17,        /* inverse DCT + upsample / colour launches of the ImageDecoder op */
+  ST_K_COUNT = 18
 };
 int st_ctx_timing_enable(st_ctx* ctx, unsigned kernel_mask);
 int st_ctx_timing_reset(st_ctx* ctx);
@@ -498,6 +499,47 @@ int st_cpm2_resize_merge_maps(st_ctx* ctx, const float* const* src_dev, const in
  * cpm2_output_kernel_cpu.cpp:481-499 reads. */
 int st_cpm2_nms(st_ctx* ctx, const float* const* maps_dev, int n, int h, int w, int parts, int max_peaks, float threshold,
                 float* const* joints_dev);
+
+/* ---- ImageDecoder: baseline JPEG ------------------------------------------------------------
+ * Replaces the reference's ImageDecoder kernels (scannertools_cpp/imgproc/image_decoder_kernel_cpu.cpp: cv::imdecode(
+ * IMREAD_UNCHANGED) + BGR->RGB on a thread pool; image_decoder_kernel_gpu.cpp: cv::cudacodec, JPEG only).  Entropy decoding
+ * runs on host threads, dequantisation / inverse DCT / chroma upsampling / colour conversion in HIP kernels; the result is
+ * bit-exact to libjpeg(-turbo) at its defaults (JDCT_ISLOW, fancy upsampling, RGB output), which is what cv::imdecode calls.
+ * Supported: SOF0 (baseline sequential Huffman, 8-bit samples, 8-bit quantisation tables), one scan, with 1 component or with
+ * 3 YCbCr components at luma sampling 1x1 (4:4:4), 2x1 (4:2:2) or 2x2 (4:2:0) and chroma 1x1; restart intervals, APPn / COM
+ * segments and fill bytes are handled, EXIF orientation is not applied (IMREAD_UNCHANGED does not).  ST_ERR_UNSUPPORTED:
+ * progressive, extended, lossless, hierarchical and arithmetic-coded streams, other precisions, 16-bit quantisation tables,
+ * 4 components, an Adobe transform other than YCbCr, any other sampling, several scans.  ST_ERR_INVALID: anything malformed,
+ * truncated or not a JPEG.  Known deviation on corrupt input only: samples are clamped to 0..255 where libjpeg's range table
+ * wraps (dequantised coefficients no encoder produces). */
+typedef struct st_jpeg_info {
+  int h, w, channels;   /* channels: 1 or 3 = the decoded frame's (h, w, channels) */
+  int h_samp, v_samp;   /* luma sampling factors: 1,1 (4:4:4 and one-component streams), 2,1 (4:2:2), 2,2 (4:2:0) */
+  int restart_interval; /* MCUs between RSTn markers; 0: none */
+  char message[160];    /* what is wrong with the stream when the status is not ST_OK; empty otherwise */
+} st_jpeg_info;
+/* Host only (no context, no GPU): parses the markers up to the scan.  Re-entrant. */
+int st_jpeg_probe(const uint8_t* buf, size_t size, st_jpeg_info* info);
+/* Host only: stage 1 alone (marker parser + Huffman decoder), for tests and tools.  coef receives int16 coefficients as
+ * stored in the stream (not dequantised), 64 per 8 x 8 block in natural (row-major) order; the blocks of component 0 first,
+ * then component 1, then 2, each component's blocks in raster order of its block-padded plane: ceil(w / (8 H)) H_c blocks
+ * per row and ceil(h / (8 V)) V_c block rows, (H, V) the luma sampling and (H_c, V_c) the component's (a one-component
+ * stream: ceil(w / 8) x ceil(h / 8)).  cap: the number of int16 behind coef; too few is ST_ERR_INVALID with nothing decoded.
+ * quant (may be null): channels x 64 uint16, each component's quantisation table in natural order.  info (may be null)
+ * receives the probe's fields and the message. */
+int st_jpeg_coefficients(const uint8_t* buf, size_t size, int16_t* coef, size_t cap, uint16_t* quant, st_jpeg_info* info);
+/* n streams in HOST memory -> n dense (h, w, channels) uint8 frames in DEVICE memory (out_dev: host array of n device
+ * pointers), R, G, B order (the reference's BGR->RGB after imdecode) or one channel.  Every stream is probed first: one that
+ * is refused, malformed, or of another shape than (h, w, channels) fails the call -- the message names the stream -- before
+ * anything is launched or written.  Then the streams are entropy-decoded on min(n, ST_JPEG_THREADS) host threads (read at
+ * each call; default min(16, hardware threads)) into page-locked memory, in sub-batches that alternate between two slots:
+ * each sub-batch's coefficients are copied and its two kernels enqueued on the context's stream while the next one is being
+ * decoded.  The only host synchronisation is the wait for a slot's previous copy before the slot is refilled.  Subsampling
+ * may differ between the streams of a call.  A stream whose entropy-coded data turns out to be corrupt or truncated also
+ * fails the call with ST_ERR_INVALID; the frames of its sub-batch and of later ones are then not written, those of
+ * sub-batches already enqueued are (a call of at most ST_JPEG_THREADS streams is one sub-batch: nothing is written). */
+int st_jpeg_decode_batch(st_ctx* ctx, const uint8_t* const* bufs_host, const size_t* sizes, int n, int h, int w, int channels,
+                         uint8_t* const* out_dev);
 
 #ifdef __cplusplus
 }

@@ -100,3 +100,25 @@ def fields(buf):
 def message(number, payload):
     """A length-delimited field (sub-message, bytes, packed repeated) with the given serialized payload."""
     return _varint(number << 3 | 2) + _varint(len(payload)) + bytes(payload)
+
+
+IMAGE_TYPES = {"PNG": 0, "JPEG": 1, "ANY": 2}   # ImageDecoderArgs.ImageType
+
+
+def image_decoder_args(image_type=None):
+    """A serialised ImageDecoderArgs.  None: the empty message (the op then decodes JPEG).  A named or numeric type is
+    written explicitly, PNG = 0 too (proto3 would omit it, and the kernel could not tell it from an absent field)."""
+    if image_type is None:
+        return b""
+    v = IMAGE_TYPES[image_type] if isinstance(image_type, str) else int(image_type)
+    return _varint(1 << 3 | 0) + _varint(v)
+
+
+def parse_image_decoder_args(buf):
+    """{'image_type': name or number} of a serialised ImageDecoderArgs; {} when the field is absent."""
+    names = {v: k for k, v in IMAGE_TYPES.items()}
+    out = {}
+    for number, wt, value in fields(buf):
+        if number == 1 and wt == 0:
+            out["image_type"] = names.get(value, value)
+    return out

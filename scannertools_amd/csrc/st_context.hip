@@ -144,6 +144,7 @@ ST_EXPORT int st_ctx_destroy(st_ctx* ctx) {
     for (auto e : t.stops) (void)hipEventDestroy(e);
   }
   if (ctx->ws) (void)hipFree(ctx->ws);
+  st_jpeg_release(ctx);
   if (ctx->own_stream) (void)hipStreamDestroy(ctx->own_stream);
   delete ctx;
   return ST_OK;

@@ -52,7 +52,9 @@ struct st_ctx {
   st_timing_slot timing[ST_K_COUNT];
   std::string last_error;
   int num_cus = 256;
+  struct st_jpeg_state* jpeg = nullptr;   // page-locked slots of st_jpeg_decode_batch (st_jpeg.hip), made at its first call
 };
+void st_jpeg_release(st_ctx* ctx);   // frees ctx->jpeg (st_ctx_destroy)
 
 int st_set_error(st_ctx* ctx, int status, const char* fmt, ...);
 

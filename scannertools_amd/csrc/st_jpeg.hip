@@ -1,0 +1,477 @@
+// ImageDecoder op, baseline JPEG: st_jpeg_decode_batch and its two kernels.
+//
+// Stage 1 (st_jpeg_parse.cpp, host threads) turns each stream into int16 coefficient blocks; this file uploads them and runs
+//   k_jpeg_idct   dequantisation + libjpeg's "islow" inverse DCT, one lane per block row, into block-tiled component planes
+//   k_jpeg_color  chroma upsampling ("fancy" triangle filter, or replication for planes at most 2 samples wide) + YCbCr -> RGB
+//                 into the dense output frames
+// Two launches per sub-batch (the unfused form; DESIGN.md 4.12 has the byte model).  The arithmetic is libjpeg's at its
+// defaults (JDCT_ISLOW, fancy upsampling), restated in include/scannertools_hip.h's terms and DESIGN.md 4.12; the one known
+// deviation is that samples are clamped where libjpeg's range table wraps (corrupt input only).
+//
+// Device layout of a sub-batch of nf frames (the page-locked slot holds the same bytes, one copy moves them):
+//   [nf x JpegFrameHdr (512 B)] [coefficients: frame 0's blocks, frame 1's, ...]   128 B per block, natural order
+// and the planes buffer holds 64 B per block in the SAME block order (component planes are block-tiled: sample (y, x) of a
+// component is byte (y & 7) * 8 + (x & 7) of block (y >> 3) * blocks_per_row + (x >> 3)), so the IDCT kernel needs no plane
+// geometry and a wave's eight blocks are 1 KiB of contiguous loads and 512 B of contiguous stores.
+#include <algorithm>
+#include <atomic>
+#include <climits>
+#include <condition_variable>
+#include <cstdlib>
+#include <cstring>
+#include <mutex>
+#include <thread>
+
+#include "st_internal.h"
+#include "st_jpeg_parse.h"
+
+namespace {
+
+struct alignas(16) JpegFrameHdr {
+  uint8_t* out;          // the frame's dense (h, w, channels) output
+  int blk_off;           // the frame's first block within the sub-batch
+  int nblk_y, nblk_c;    // blocks of the luma plane / of each chroma plane (0 for a one-component stream)
+  int bw_y, bw_c;        // blocks per row of them
+  int mode;              // ST_JPEG_*
+  int dw, dh;            // the chroma planes' real extent in samples
+  int fancy;             // 1: triangle filter; 0: replication (dw <= 2)
+  int pad0[5];
+  uint16_t quant[3][64];
+  uint8_t pad1[64];
+};
+static_assert(sizeof(JpegFrameHdr) == 512, "one header is 512 bytes");
+
+struct JpegArgsK {
+  const uint8_t* slot;   // headers, then coefficients
+  uint8_t* planes;
+  int nf, h, w, channels;
+};
+
+typedef short short8 __attribute__((ext_vector_type(8)));
+typedef unsigned short ushort8 __attribute__((ext_vector_type(8)));
+
+// One pass of jidctint's 8-point inverse DCT (CONST_BITS 13): out = DESCALE(..., n), arithmetic shifts.
+__device__ __forceinline__ void idct_pass(const int* i, int* o, int n) {
+  int z1 = (i[2] + i[6]) * 4433;
+  const int t2 = z1 - i[6] * 15137, t3 = z1 + i[2] * 6270;
+  const int t0 = (i[0] + i[4]) * 8192, t1 = (i[0] - i[4]) * 8192;
+  const int t10 = t0 + t3, t13 = t0 - t3, t11 = t1 + t2, t12 = t1 - t2;
+  int a = i[7], b = i[5], c = i[3], d = i[1];
+  z1 = a + d;
+  int z2 = b + c, z3 = a + c, z4 = b + d;
+  const int z5 = (z3 + z4) * 9633;
+  a *= 2446; b *= 16819; c *= 25172; d *= 12299;
+  z1 *= -7373; z2 *= -20995;
+  z3 = z3 * -16069 + z5; z4 = z4 * -3196 + z5;
+  a += z1 + z3; b += z2 + z4; c += z2 + z3; d += z1 + z4;
+  const int r = 1 << (n - 1);
+  o[0] = (t10 + d + r) >> n; o[7] = (t10 - d + r) >> n;
+  o[1] = (t11 + c + r) >> n; o[6] = (t11 - c + r) >> n;
+  o[2] = (t12 + b + r) >> n; o[5] = (t12 - b + r) >> n;
+  o[3] = (t13 + a + r) >> n; o[4] = (t13 - a + r) >> n;
+}
+
+__device__ __forceinline__ int clamp255(int v) { return v < 0 ? 0 : (v > 255 ? 255 : v); }
+
+// Lane = one row of one block: 16 B of coefficients in, 8 B of samples out; 32 blocks per workgroup, 8 per wave.  The two
+// transposes (rows -> columns for pass 1, back for pass 2) go through LDS, 72 dwords per block: lanes (block, c) of a
+// 32-lane half then touch 32 distinct banks on the strided side.
+constexpr int kIdctBlocks = 32, kLdsBlock = 72;
+__global__ __launch_bounds__(256) void k_jpeg_idct(JpegArgsK a) {
+  __shared__ int lds[kIdctBlocks * kLdsBlock];
+  const JpegFrameHdr* __restrict__ hdr = reinterpret_cast<const JpegFrameHdr*>(a.slot) + blockIdx.y;
+  const int ny = hdr->nblk_y, nc = hdr->nblk_c;
+  const int total = ny + 2 * nc;
+  const int lb = threadIdx.x >> 3, r = threadIdx.x & 7;
+  const int b = blockIdx.x * kIdctBlocks + lb;
+  const bool live = b < total;
+  const size_t blk = (size_t)hdr->blk_off + (size_t)(live ? b : 0);
+  int v[8], t[8];
+#pragma unroll
+  for (int k = 0; k < 8; ++k) v[k] = 0;
+  if (live) {
+    const int comp = (b >= ny) + (b >= ny + nc);
+    const short8 c = *reinterpret_cast<const short8*>(a.slot + (size_t)a.nf * sizeof(JpegFrameHdr) + blk * 128 + (size_t)r * 16);
+    const ushort8 q = *reinterpret_cast<const ushort8*>(&hdr->quant[comp][r * 8]);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) v[k] = (int)c[k] * (int)q[k];
+  }
+  int* L = lds + lb * kLdsBlock;
+#pragma unroll
+  for (int k = 0; k < 8; ++k) L[r * 8 + k] = v[k];
+  __syncthreads();
+#pragma unroll
+  for (int k = 0; k < 8; ++k) v[k] = L[k * 8 + r];   // column r
+  idct_pass(v, t, 11);
+  __syncthreads();
+#pragma unroll
+  for (int k = 0; k < 8; ++k) L[k * 8 + r] = t[k];
+  __syncthreads();
+#pragma unroll
+  for (int k = 0; k < 8; ++k) v[k] = L[r * 8 + k];   // row r of the pass-1 result
+  idct_pass(v, t, 18);
+  if (live) {
+    unsigned lo = 0, hi = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      lo |= (unsigned)clamp255(t[k] + 128) << (8 * k);
+      hi |= (unsigned)clamp255(t[4 + k] + 128) << (8 * k);
+    }
+    *reinterpret_cast<uint2*>(a.planes + blk * 64 + (size_t)r * 8) = make_uint2(lo, hi);
+  }
+}
+
+// ---- upsampling + colour ----------------------------------------------------------------------------------------------------
+__device__ __forceinline__ size_t smp_at(int bw, int y, int x) { return ((size_t)(y >> 3) * bw + (size_t)(x >> 3)) * 64 + (size_t)((y & 7) * 8 + (x & 7)); }
+
+struct ChromaGeom { int bw, mode, fancy, dw, dh; };
+
+// One chroma sample at full resolution.  Fancy h2v1: (3 p[i] + p[i -/+ 1] + 1 / 2) >> 2; fancy h2v2: t = 3 p[r] + p[r -/+ 1]
+// vertically, then (3 t[i] + t[i -/+ 1] + 8 / 7) >> 4; the neighbour index clamped into the plane gives libjpeg's edge
+// columns and rows, the neighbour replaced by the sample itself gives its plain replication.
+__device__ __forceinline__ int chroma_at(const uint8_t* __restrict__ P, const ChromaGeom& g, int y, int x) {
+  if (g.mode == ST_JPEG_444) return P[smp_at(g.bw, y, x)];
+  const int i = x >> 1;
+  int j = i + ((x & 1) ? 1 : -1);
+  j = j < 0 ? 0 : (j > g.dw - 1 ? g.dw - 1 : j);
+  if (!g.fancy) j = i;
+  if (g.mode == ST_JPEG_H2V1) return (3 * P[smp_at(g.bw, y, i)] + P[smp_at(g.bw, y, j)] + ((x & 1) ? 2 : 1)) >> 2;
+  const int r = y >> 1;
+  int r2 = r + ((y & 1) ? 1 : -1);
+  r2 = r2 < 0 ? 0 : (r2 > g.dh - 1 ? g.dh - 1 : r2);
+  if (!g.fancy) r2 = r;
+  const int ti = 3 * P[smp_at(g.bw, r, i)] + P[smp_at(g.bw, r2, i)];
+  const int tj = 3 * P[smp_at(g.bw, r, j)] + P[smp_at(g.bw, r2, j)];
+  return (3 * ti + tj + ((x & 1) ? 7 : 8)) >> 4;
+}
+
+__device__ __forceinline__ void unpack8(uint2 v, int* o) {
+#pragma unroll
+  for (int k = 0; k < 4; ++k) { o[k] = (v.x >> (8 * k)) & 0xff; o[4 + k] = (v.y >> (8 * k)) & 0xff; }
+}
+
+// 16 chroma samples of output columns x0 .. x0 + 15 (x0 a multiple of 16, the row 16-sample aligned: w % 16 == 0, so dw is a
+// multiple of 8 above 2 and the filter is always the fancy one): per source row one 8-byte block row and its two neighbours.
+__device__ __forceinline__ void chroma16(const uint8_t* __restrict__ P, const ChromaGeom& g, int y, int x0, int* o) {
+  if (g.mode == ST_JPEG_444) {
+    unpack8(*reinterpret_cast<const uint2*>(P + smp_at(g.bw, y, x0)), o);
+    unpack8(*reinterpret_cast<const uint2*>(P + smp_at(g.bw, y, x0 + 8)), o + 8);
+    return;
+  }
+  const int i0 = x0 >> 1;
+  const int il = i0 > 0 ? i0 - 1 : 0, ir = i0 + 8 < g.dw ? i0 + 8 : g.dw - 1;
+  int s[10];
+  if (g.mode == ST_JPEG_H2V1) {
+    unpack8(*reinterpret_cast<const uint2*>(P + smp_at(g.bw, y, i0)), s + 1);
+    s[0] = P[smp_at(g.bw, y, il)];
+    s[9] = P[smp_at(g.bw, y, ir)];
+#pragma unroll
+    for (int p = 0; p < 16; ++p) o[p] = (3 * s[1 + (p >> 1)] + s[1 + (p >> 1) + ((p & 1) ? 1 : -1)] + ((p & 1) ? 2 : 1)) >> 2;
+    return;
+  }
+  const int r = y >> 1;
+  int r2 = r + ((y & 1) ? 1 : -1);
+  r2 = r2 < 0 ? 0 : (r2 > g.dh - 1 ? g.dh - 1 : r2);
+  int u[10];
+  unpack8(*reinterpret_cast<const uint2*>(P + smp_at(g.bw, r, i0)), s + 1);
+  s[0] = P[smp_at(g.bw, r, il)];
+  s[9] = P[smp_at(g.bw, r, ir)];
+  unpack8(*reinterpret_cast<const uint2*>(P + smp_at(g.bw, r2, i0)), u + 1);
+  u[0] = P[smp_at(g.bw, r2, il)];
+  u[9] = P[smp_at(g.bw, r2, ir)];
+#pragma unroll
+  for (int k = 0; k < 10; ++k) s[k] = 3 * s[k] + u[k];
+#pragma unroll
+  for (int p = 0; p < 16; ++p) o[p] = (3 * s[1 + (p >> 1)] + s[1 + (p >> 1) + ((p & 1) ? 1 : -1)] + ((p & 1) ? 7 : 8)) >> 4;
+}
+
+// jdcolor's YCbCr -> RGB in 16 fractional bits
+__device__ __forceinline__ void ycc_rgb(int Y, int Cb, int Cr, int* rgb) {
+  const int cb = Cb - 128, cr = Cr - 128;
+  rgb[0] = clamp255(Y + ((91881 * cr + 32768) >> 16));
+  rgb[1] = clamp255(Y + ((-22554 * cb - 46802 * cr + 32768) >> 16));
+  rgb[2] = clamp255(Y + ((116130 * cb + 32768) >> 16));
+}
+
+// PX pixels of one row per thread.  PX = 16: w % 16 == 0 and 16-byte aligned frames, whole 16-byte stores (three per thread, one
+// for a one-component frame); PX = 4: w % 4 == 0 and 4-byte aligned frames, dword stores; PX = 1: anything, byte stores.
+template <int PX>
+__global__ __launch_bounds__(256) void k_jpeg_color(JpegArgsK a) {
+  const JpegFrameHdr* __restrict__ hdr = reinterpret_cast<const JpegFrameHdr*>(a.slot) + blockIdx.y;
+  const uint8_t* __restrict__ PY = a.planes + (size_t)hdr->blk_off * 64;
+  const uint8_t* __restrict__ PB = PY + (size_t)hdr->nblk_y * 64;
+  const uint8_t* __restrict__ PR = PB + (size_t)hdr->nblk_c * 64;
+  const int bwy = hdr->bw_y;
+  ChromaGeom g;
+  g.bw = hdr->bw_c; g.mode = hdr->mode; g.fancy = hdr->fancy; g.dw = hdr->dw; g.dh = hdr->dh;
+  uint8_t* __restrict__ out = st_gl(hdr->out);
+  const int w = a.w, cn = a.channels;
+  const long long groups = (long long)a.h * w / PX;
+  for (long long gi = (long long)blockIdx.x * 256 + threadIdx.x; gi < groups; gi += (long long)gridDim.x * 256) {
+    const long long pix = gi * PX;
+    const int y = (int)(pix / w), x0 = (int)(pix % w);
+    int Y[PX], Cb[PX], Cr[PX];
+    if constexpr (PX == 16) {
+      unpack8(*reinterpret_cast<const uint2*>(PY + smp_at(bwy, y, x0)), Y);
+      unpack8(*reinterpret_cast<const uint2*>(PY + smp_at(bwy, y, x0 + 8)), Y + 8);
+      if (cn == 3) {
+        chroma16(PB, g, y, x0, Cb);
+        chroma16(PR, g, y, x0, Cr);
+      }
+    } else {
+#pragma unroll
+      for (int p = 0; p < PX; ++p) {
+        Y[p] = PY[smp_at(bwy, y, x0 + p)];
+        if (cn == 3) {
+          Cb[p] = chroma_at(PB, g, y, x0 + p);
+          Cr[p] = chroma_at(PR, g, y, x0 + p);
+        }
+      }
+    }
+    if constexpr (PX == 1) {
+      if (cn == 1) {
+        out[pix] = (uint8_t)Y[0];
+      } else {
+        int rgb[3];
+        ycc_rgb(Y[0], Cb[0], Cr[0], rgb);
+        out[3 * pix] = (uint8_t)rgb[0]; out[3 * pix + 1] = (uint8_t)rgb[1]; out[3 * pix + 2] = (uint8_t)rgb[2];
+      }
+    } else if (cn == 1) {
+      unsigned o[PX / 4];
+#pragma unroll
+      for (int k = 0; k < PX / 4; ++k) o[k] = 0;
+#pragma unroll
+      for (int p = 0; p < PX; ++p) o[p >> 2] |= (unsigned)Y[p] << (8 * (p & 3));
+      if constexpr (PX == 16) *reinterpret_cast<uint4*>(out + pix) = make_uint4(o[0], o[1], o[2], o[3]);
+      else *reinterpret_cast<unsigned*>(out + pix) = o[0];
+    } else {
+      constexpr int NO = 3 * PX / 4;
+      unsigned o[NO];
+#pragma unroll
+      for (int k = 0; k < NO; ++k) o[k] = 0;
+#pragma unroll
+      for (int p = 0; p < PX; ++p) {
+        int rgb[3];
+        ycc_rgb(Y[p], Cb[p], Cr[p], rgb);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) o[(3 * p + k) >> 2] |= (unsigned)rgb[k] << (8 * ((3 * p + k) & 3));
+      }
+      unsigned* d = reinterpret_cast<unsigned*>(out + 3 * pix);
+      if constexpr (PX == 16) {
+#pragma unroll
+        for (int k = 0; k < NO / 4; ++k) reinterpret_cast<uint4*>(d)[k] = make_uint4(o[4 * k], o[4 * k + 1], o[4 * k + 2], o[4 * k + 3]);
+      } else {
+#pragma unroll
+        for (int k = 0; k < NO; ++k) d[k] = o[k];
+      }
+    }
+  }
+}
+
+// ---- host ---------------------------------------------------------------------------------------------------------------
+struct SubBatch { int first, count; size_t blocks; };
+
+int jpeg_threads(int n) {
+  int t = (int)std::min(16u, std::max(1u, std::thread::hardware_concurrency()));
+  if (const char* e = getenv("ST_JPEG_THREADS")) t = atoi(e);
+  return std::max(1, std::min(std::min(t, 64), n));
+}
+
+constexpr size_t kSlotCoefBytes = (size_t)64 << 20;   // coefficients of one sub-batch, unless a single frame has more
+
+}  // namespace
+
+struct st_jpeg_state {
+  uint8_t* pin[2] = {nullptr, nullptr};
+  size_t cap[2] = {0, 0};
+  hipEvent_t copied[2] = {nullptr, nullptr};   // the slot's last copy has left host memory
+  bool busy[2] = {false, false};
+};
+
+void st_jpeg_release(st_ctx* ctx) {
+  if (!ctx->jpeg) return;
+  for (int s = 0; s < 2; ++s) {
+    if (ctx->jpeg->copied[s]) (void)hipEventDestroy(ctx->jpeg->copied[s]);
+    if (ctx->jpeg->pin[s]) (void)hipHostFree(ctx->jpeg->pin[s]);
+  }
+  delete ctx->jpeg;
+  ctx->jpeg = nullptr;
+}
+
+ST_EXPORT int st_jpeg_decode_batch(st_ctx* ctx, const uint8_t* const* bufs_host, const size_t* sizes, int n, int h, int w, int channels,
+                                   uint8_t* const* out_dev) {
+  ST_TRY(st_enter(ctx));
+  if (n < 0 || h <= 0 || w <= 0 || h > 65535 || w > 65535 || (channels != 1 && channels != 3))
+    return st_set_error(ctx, ST_ERR_INVALID, "jpeg: bad arguments (n=%d h=%d w=%d channels=%d)", n, h, w, channels);
+  if (n == 0) return ST_OK;
+  if (!bufs_host || !sizes || !out_dev) return st_set_error(ctx, ST_ERR_INVALID, "jpeg: null argument");
+  // every stream's markers first: nothing is launched or written unless all of them are streams this decodes, of one shape
+  std::vector<StJpegHeader> hds((size_t)n);
+  for (int i = 0; i < n; ++i) {
+    char msg[160];
+    if (!out_dev[i]) return st_set_error(ctx, ST_ERR_INVALID, "jpeg: stream %d has no output frame", i);
+    const int st = st_jpeg_parse_header(bufs_host[i], sizes[i], &hds[i], msg, sizeof msg);
+    if (st != ST_OK) return st_set_error(ctx, st, "jpeg: stream %d: %s", i, msg);
+    if (hds[i].h != h || hds[i].w != w || hds[i].ncomp != channels)
+      return st_set_error(ctx, ST_ERR_INVALID, "jpeg: stream %d is %dx%d with %d channel(s), the call decodes %dx%d with %d", i, hds[i].w, hds[i].h,
+                          hds[i].ncomp, w, h, channels);
+  }
+  const int T = jpeg_threads(n);
+  std::vector<SubBatch> sbs;
+  std::vector<int> sb_of((size_t)n), blk_off((size_t)n);
+  for (int i = 0; i < n; ++i) {
+    const size_t nb = st_jpeg_blocks(hds[i]);
+    if (sbs.empty() || sbs.back().count >= T || (sbs.back().blocks + nb) * 128 > kSlotCoefBytes) sbs.push_back(SubBatch{i, 0, 0});
+    sb_of[i] = (int)sbs.size() - 1;
+    blk_off[i] = (int)sbs.back().blocks;
+    sbs.back().count++;
+    sbs.back().blocks += nb;
+  }
+  const int nsb = (int)sbs.size();
+  size_t slot_bytes = 0, plane_bytes = 0;
+  for (const SubBatch& sb : sbs) {
+    slot_bytes = std::max(slot_bytes, (size_t)sb.count * sizeof(JpegFrameHdr) + sb.blocks * 128);
+    plane_bytes = std::max(plane_bytes, sb.blocks * 64);
+  }
+  if (!ctx->jpeg) {
+    ctx->jpeg = new (std::nothrow) st_jpeg_state();
+    if (!ctx->jpeg) return st_set_error(ctx, ST_ERR_OOM, "jpeg: out of host memory");
+  }
+  st_jpeg_state* js = ctx->jpeg;
+  for (int s = 0; s < std::min(2, nsb); ++s) {
+    if (!js->copied[s]) ST_HIP(ctx, hipEventCreateWithFlags(&js->copied[s], hipEventDisableTiming));
+    // a slot is refilled only after its previous copy (of this call or an earlier one) has read it
+    if (js->busy[s]) { ST_HIP(ctx, hipEventSynchronize(js->copied[s])); js->busy[s] = false; }
+    if (slot_bytes > js->cap[s]) {
+      if (js->pin[s]) ST_HIP(ctx, hipHostFree(js->pin[s]));
+      js->pin[s] = nullptr;
+      js->cap[s] = 0;
+      if (hipHostMalloc((void**)&js->pin[s], slot_bytes, hipHostMallocDefault) != hipSuccess) {
+        (void)hipGetLastError();
+        js->pin[s] = nullptr;
+        return st_set_error(ctx, ST_ERR_OOM, "jpeg: cannot page-lock %zu bytes for the coefficients", slot_bytes);
+      }
+      js->cap[s] = slot_bytes;
+    }
+  }
+  ST_TRY(st_ws_reserve(ctx, st_align_up(slot_bytes) + st_align_up(plane_bytes)));
+  uint8_t* d_slot = (uint8_t*)st_ws_alloc(ctx, slot_bytes);
+  uint8_t* d_planes = (uint8_t*)st_ws_alloc(ctx, plane_bytes);
+  if (!d_slot || !d_planes) return st_set_error(ctx, ST_ERR_OOM, "jpeg: workspace exhausted");
+
+  // workers take streams in order; sub-batch k may be filled once `allowed` > k
+  struct Shared {
+    std::mutex mu;
+    std::condition_variable cv;
+    int allowed = 2;
+    std::vector<int> remaining;
+    bool failed = false;
+    int fail_status = ST_OK, fail_stream = -1;
+    char fail_msg[160];
+  } sh;
+  sh.remaining.resize((size_t)nsb);
+  for (int k = 0; k < nsb; ++k) sh.remaining[k] = sbs[k].count;
+  std::atomic<int> next{0};
+  auto work = [&]() {
+    for (;;) {
+      const int i = next.fetch_add(1);
+      if (i >= n) return;
+      const int k = sb_of[i];
+      bool skip;
+      {
+        std::unique_lock<std::mutex> lk(sh.mu);
+        sh.cv.wait(lk, [&] { return sh.allowed > k; });
+        skip = sh.failed;
+      }
+      int st = ST_OK;
+      char msg[160];
+      msg[0] = 0;
+      if (!skip) {
+        const StJpegHeader& hd = hds[i];
+        uint8_t* slot = js->pin[k & 1];
+        JpegFrameHdr* fh = reinterpret_cast<JpegFrameHdr*>(slot) + (i - sbs[k].first);
+        memset(fh, 0, sizeof *fh);
+        fh->out = out_dev[i];
+        fh->blk_off = blk_off[i];
+        fh->nblk_y = (int)st_jpeg_comp_blocks(hd, 0);
+        fh->nblk_c = hd.ncomp == 3 ? (int)st_jpeg_comp_blocks(hd, 1) : 0;
+        fh->bw_y = hd.bw[0];
+        fh->bw_c = hd.ncomp == 3 ? hd.bw[1] : 0;
+        fh->mode = hd.mode;
+        fh->dw = (hd.w + hd.hs[0] - 1) / hd.hs[0];
+        fh->dh = (hd.h + hd.vs[0] - 1) / hd.vs[0];
+        fh->fancy = fh->dw > 2 ? 1 : 0;
+        for (int c = 0; c < hd.ncomp; ++c) memcpy(fh->quant[c], hd.quant[hd.tq[c]], 128);
+        int16_t* coef = reinterpret_cast<int16_t*>(slot + (size_t)sbs[k].count * sizeof(JpegFrameHdr) + (size_t)blk_off[i] * 128);
+        st = st_jpeg_decode_scan(bufs_host[i], sizes[i], hd, coef, msg, sizeof msg);
+      }
+      std::lock_guard<std::mutex> lk(sh.mu);
+      if (st != ST_OK && (!sh.failed || i < sh.fail_stream)) {
+        sh.failed = true;
+        sh.fail_status = st;
+        sh.fail_stream = i;
+        memcpy(sh.fail_msg, msg, sizeof msg);
+      }
+      --sh.remaining[k];
+      sh.cv.notify_all();
+    }
+  };
+  std::vector<std::thread> pool;
+  pool.reserve((size_t)T);
+  for (int t = 0; t < T; ++t) pool.emplace_back(work);
+
+  const unsigned align = [&] {
+    unsigned a = 0;
+    for (int i = 0; i < n; ++i) a |= (unsigned)(uintptr_t)out_dev[i];
+    return a;
+  }();
+  const int px = (w % 16 == 0 && (align & 15) == 0) ? 16 : ((w % 4 == 0 && (align & 3) == 0) ? 4 : 1);
+  auto issue = [&]() -> int {
+    for (int k = 0; k < nsb; ++k) {
+      {
+        std::unique_lock<std::mutex> lk(sh.mu);
+        sh.cv.wait(lk, [&] { return sh.remaining[k] == 0; });
+        if (sh.failed) return st_set_error(ctx, sh.fail_status, "jpeg: stream %d: %s", sh.fail_stream, sh.fail_msg);
+      }
+      const SubBatch& sb = sbs[k];
+      const int s = k & 1;
+      const size_t bytes = (size_t)sb.count * sizeof(JpegFrameHdr) + sb.blocks * 128;
+      ST_HIP(ctx, hipMemcpyAsync(d_slot, js->pin[s], bytes, hipMemcpyHostToDevice, ctx->stream));
+      ST_HIP(ctx, hipEventRecord(js->copied[s], ctx->stream));
+      js->busy[s] = true;
+      JpegArgsK a;
+      a.slot = d_slot; a.planes = d_planes; a.nf = sb.count; a.h = h; a.w = w; a.channels = channels;
+      size_t most = 0;
+      for (int i = sb.first; i < sb.first + sb.count; ++i) most = std::max(most, st_jpeg_blocks(hds[i]));
+      {
+        st_timed t(ctx, ST_K_JPEG);
+        hipLaunchKernelGGL(k_jpeg_idct, dim3((unsigned)((most + kIdctBlocks - 1) / kIdctBlocks), sb.count), dim3(256), 0, ctx->stream, a);
+        long long bx = ((long long)h * w / px + 255) / 256;
+        if (bx > 8192) bx = 8192;
+        const dim3 grid((unsigned)bx, sb.count);
+        if (px == 16) hipLaunchKernelGGL(k_jpeg_color<16>, grid, dim3(256), 0, ctx->stream, a);
+        else if (px == 4) hipLaunchKernelGGL(k_jpeg_color<4>, grid, dim3(256), 0, ctx->stream, a);
+        else hipLaunchKernelGGL(k_jpeg_color<1>, grid, dim3(256), 0, ctx->stream, a);
+      }
+      ST_HIP(ctx, hipGetLastError());
+      if (k + 2 < nsb) {
+        ST_HIP(ctx, hipEventSynchronize(js->copied[s]));
+        js->busy[s] = false;
+        std::lock_guard<std::mutex> lk(sh.mu);
+        sh.allowed = k + 3;
+        sh.cv.notify_all();
+      }
+    }
+    return ST_OK;
+  };
+  const int status = issue();
+  {
+    // on an error the workers run out of streams without decoding them
+    std::lock_guard<std::mutex> lk(sh.mu);
+    if (status != ST_OK) sh.failed = true;
+    sh.allowed = INT_MAX;
+    sh.cv.notify_all();
+  }
+  for (std::thread& t : pool) t.join();
+  return status;
+}

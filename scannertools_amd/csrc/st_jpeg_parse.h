@@ -1,0 +1,47 @@
+// Host side of the ImageDecoder op: marker parser and Huffman (entropy) decoder of baseline JPEG streams.
+// Plain C++ (no HIP): st_jpeg_parse.cpp also compiles on its own under a host sanitizer.  Re-entrant: everything a call
+// needs lives in its StJpegHeader; nothing is kept between calls.
+#ifndef ST_JPEG_PARSE_H_
+#define ST_JPEG_PARSE_H_
+
+#include <stddef.h>
+#include <stdint.h>
+
+// One Huffman table: a 9-bit lookahead for the short codes, the canonical max-code walk for the longer ones.
+struct StJpegHuff {
+  uint16_t look[512];   // (code length << 8) | symbol of the code that prefixes these 9 bits; 0: longer than 9 bits
+  int32_t maxcode[18];  // largest code of each length (-1: none); [17] ends the walk
+  int32_t valoff[17];   // index into vals of the first code of each length, minus that code
+  uint8_t vals[256];
+};
+
+enum { ST_JPEG_444 = 0, ST_JPEG_H2V1 = 1, ST_JPEG_H2V2 = 2, ST_JPEG_GRAY = 3 };
+
+struct StJpegHeader {
+  int h, w, ncomp;
+  int hs[3], vs[3];            // sampling factors as the scan uses them (1 x 1 for a one-component stream)
+  int tq[3], td[3], ta[3];     // table selectors per component
+  int restart_interval;
+  int mode;                    // ST_JPEG_*
+  int mcux, mcuy;              // MCUs per row / column
+  int bw[3], bh[3];            // blocks per row / column of each component's block-padded plane
+  size_t scan_pos;             // first entropy-coded byte
+  bool have_q[4], have_dc[4], have_ac[4];
+  uint16_t quant[4][64];       // natural (row-major) order
+  StJpegHuff dc[4], ac[4];
+};
+
+// Number of 8 x 8 blocks of component c / of the whole frame (component planes in SOF order, each in raster order).
+inline size_t st_jpeg_comp_blocks(const StJpegHeader& hd, int c) { return (size_t)hd.bw[c] * hd.bh[c]; }
+inline size_t st_jpeg_blocks(const StJpegHeader& hd) {
+  size_t n = 0;
+  for (int c = 0; c < hd.ncomp; ++c) n += st_jpeg_comp_blocks(hd, c);
+  return n;
+}
+
+// Markers up to and including SOS.  Returns an st_status; `msg` (msg_len > 0) names the cause of anything but ST_OK.
+int st_jpeg_parse_header(const uint8_t* buf, size_t size, StJpegHeader* hd, char* msg, size_t msg_len);
+// The scan of a parsed stream into st_jpeg_blocks(hd) * 64 coefficients (the layout of st_jpeg_coefficients).
+int st_jpeg_decode_scan(const uint8_t* buf, size_t size, const StJpegHeader& hd, int16_t* coef, char* msg, size_t msg_len);
+
+#endif  // ST_JPEG_PARSE_H_

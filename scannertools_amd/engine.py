@@ -12,8 +12,8 @@ installable here, so this module reproduces exactly that surface for in-memory f
     out = NamedStream(sc, 'hist'); sc.run(sc.io.Output(hist, [out]), PerfParams.estimate())
     next(out.load())
 
-C++ ops (``Histogram``, ``OpticalFlow``, ``FlowHistogram``, ``Blur``, ``Resize``, ``ConvertColor``, ``Montage``, ``BrightnessCPP``,
-``ContrastCPP``, ``SharpnessCPP``) are looked up in the kernel registry of
+C++ ops (``Histogram``, ``OpticalFlow``, ``FlowHistogram``, ``Blur``, ``Resize``, ``ConvertColor``, ``Montage``, ``ImageDecoder``,
+``BrightnessCPP``, ``ContrastCPP``, ``SharpnessCPP``) are looked up in the kernel registry of
 ``libscannertools_imgproc.so`` and executed by its mini engine (scanner_shim/shim.cpp): the same
 ``execute()`` bodies a real Scanner worker would call.  Python ops (``ShotBoundaries``, ``DrawFlow``, ``Brightness``,
 ``Contrast``, ``Sharpness``) are the
@@ -596,6 +596,34 @@ class _SharpnessBBoxNode(_CppMultiOpNode):
         return _CppMultiOpNode.rows(node, idx)
 
 
+class _ImageDecoderNode(_CppMultiOpNode):
+    """ImageDecoder (image_decoder_kernel_cpu.cpp / _gpu.cpp): a bytes column in, frames out.  Every requested row is probed
+    on the host first (st_jpeg_probe): a row that is not a JPEG this library decodes, or whose shape differs from the first
+    row's, is a ValueError naming the row and the cause, before any kernel instance exists (the kernel class can only abort)."""
+
+    def rows(self, idx):
+        if not idx:
+            return []
+        streams = self.parents[0].rows(idx)
+        L = _native.lib()
+        first = None
+        for r, data in zip(idx, streams):
+            if not isinstance(data, (bytes, bytearray)):
+                raise ValueError("%s: row %d is %s, not the bytes of an encoded image" % (self.name, r, type(data).__name__))
+            info = _native.JpegInfo()
+            if L.st_jpeg_probe(bytes(data), len(data), ctypes.byref(info)) != 0:
+                raise ValueError("%s: row %d: %s" % (self.name, r, info.message.decode()))
+            shape = (info.h, info.w, info.channels)
+            if first is None:
+                first = shape
+            # the kernel takes the frame shape of an execute() from its first element: one stream, one shape
+            if shape != first:
+                raise ValueError("%s: row %d changes shape inside a batch: %s after %s" % (self.name, r, shape, first))
+        node = copy.copy(self)
+        node.parents = [_RowsNode(dict(zip(idx, streams)), self.length())]
+        return _CppMultiOpNode.rows(node, idx)
+
+
 class _PyOpNode(_Node):
     """A batched python op over one input column (ShotBoundaries: batch = whole stream)."""
 
@@ -843,6 +871,16 @@ class _Ops:
         node = _PyMapNode(lambda frames, boxes: _fs.bbox_rows_py(frames, boxes, device=dev), [frame, bboxes])
         node.reader = _types.pickled
         return node
+
+    def ImageDecoder(self, img, device=None, batch=None, args=None):
+        """sc.ops.ImageDecoder(img=..., device=..., batch=..., args={'image_type': 'JPEG'}): the bytes of one baseline JPEG per
+        row (Client.ingest_rows) -> the decoded (h, w, 3) RGB or (h, w, 1) uint8 frame (image_decoder_kernel_cpu.cpp:57,
+        ImageDecoderArgs of scannertools_imgproc.proto:41-49).  ``args``: None, a dict with image_type "JPEG" / "PNG" / "ANY"
+        (the last two fail validation: JPEG only), or serialised bytes."""
+        from . import _proto
+        if isinstance(args, dict):
+            args = _proto.image_decoder_args(args.get("image_type"))
+        return _ImageDecoderNode(self.sc, "ImageDecoder", [img], device, batch, args or b"")
 
     def InfoFromFrame(self, frame):
         """sc.ops.InfoFromFrame(frame=frame): the frame's FrameInfo as a bytes column."""

@@ -437,6 +437,25 @@ class HipContext:
         self._check(self._L.st_cvt_color_u8_batch(self._h, tf, n, h, w, c, int(code), int(gray_bits), to))
         return out
 
+    def decode_jpeg(self, streams, out=None):
+        """ImageDecoder op (image_decoder_kernel_cpu.cpp:16-29): a list of baseline JPEG streams (bytes) of one shape ->
+        (n, h, w, c) uint8 CUDA tensor, c = 3 in R, G, B order or 1; bit-exact to libjpeg's defaults.  The shape is the first
+        stream's; a stream of another shape, or one that is refused or malformed, raises StError naming it, and nothing is
+        written.  Entropy decoding runs on host threads (ST_JPEG_THREADS), the rest in HIP kernels on the current stream."""
+        self._bind()
+        streams = [bytes(s) for s in streams]
+        n = len(streams)
+        if n == 0:
+            return torch.zeros((0, 0, 0, 3), dtype=torch.uint8, device=self.device)
+        info = probe_jpeg(streams[0])
+        shape = (n, info["h"], info["w"], info["channels"])
+        out = torch.empty(shape, dtype=torch.uint8, device=self.device) if out is None else _check_out(out, shape, torch.uint8, self.device)
+        bufs = (ctypes.c_void_p * n)(*[ctypes.cast(ctypes.c_char_p(s), ctypes.c_void_p).value for s in streams])
+        sizes = (ctypes.c_size_t * n)(*[len(s) for s in streams])
+        to = (ctypes.c_void_p * n)(*[out[i].data_ptr() for i in range(n)])
+        self._check(self._L.st_jpeg_decode_batch(self._h, bufs, sizes, n, shape[1], shape[2], shape[3], to))
+        return out
+
     # -- pose path (scannertools_caffe) -------------------------------------------------------
     def cpm2_input(self, frames, scale, out=None):
         """CPM2Input (scannertools_caffe_cpp/cpm2_input_kernel_gpu.cpp:104-140): (n,h,w,3) uint8 RGB frames
@@ -692,6 +711,34 @@ def unpack_r(flat, h, w):
     """Inverse of :func:`pack_r`."""
     n = h * w
     return torch.cat([flat[:4 * n].view(h, w, 4), flat[4 * n:].view(h, w, 1)], dim=2).contiguous()
+
+
+def probe_jpeg(stream):
+    """st_jpeg_probe (host only): {'h', 'w', 'channels', 'h_samp', 'v_samp', 'restart_interval'} of a baseline JPEG stream;
+    StError with the library's message for a stream that is refused or malformed."""
+    info = _native.JpegInfo()
+    data = bytes(stream)
+    st = _native.lib().st_jpeg_probe(data, len(data), ctypes.byref(info))
+    if st != 0:
+        raise StError(st, info.message.decode())
+    return {k: getattr(info, k) for k in ("h", "w", "channels", "h_samp", "v_samp", "restart_interval")}
+
+
+def jpeg_coefficients(stream):
+    """st_jpeg_coefficients (host only): (int16 coefficients in the layout the header documents, (channels, 64) uint16
+    quantisation tables in natural order) of a baseline JPEG stream."""
+    data = bytes(stream)
+    info = probe_jpeg(data)
+    H, V = info["h_samp"], info["v_samp"]
+    mcux, mcuy = -(-info["w"] // (8 * H)), -(-info["h"] // (8 * V))
+    blocks = mcux * mcuy * (H * V + 2) if info["channels"] == 3 else mcux * mcuy
+    coef = np.empty(blocks * 64, np.int16)
+    quant = np.empty((info["channels"], 64), np.uint16)
+    ji = _native.JpegInfo()
+    st = _native.lib().st_jpeg_coefficients(data, len(data), coef.ctypes.data, coef.size, quant.ctypes.data, ctypes.byref(ji))
+    if st != 0:
+        raise StError(st, ji.message.decode())
+    return coef, quant
 
 
 def cpm2_geometry(h, w, scale):

@@ -1,0 +1,109 @@
+// ImageDecoder op for Scanner on MI355X.
+//
+// Drop-in for the reference's kernels
+//   ImageDecoderKernelCPU  /root/reference/scannertools/scannertools_cpp/imgproc/image_decoder_kernel_cpu.cpp:10-58
+//   ImageDecoderKernelGPU  /root/reference/scannertools/scannertools_cpp/imgproc/image_decoder_kernel_gpu.cpp
+// Same op declaration (input("img") -> frame_output("frame"); the GPU file adds protobuf_name("ImageDecoderArgs")), same
+// elements: `img` is the bytes of one encoded image, `frame` the decoded U8 frame in R, G, B order (cv::imdecode(
+// IMREAD_UNCHANGED) + COLOR_BGR2RGB, :23-29) or with one channel.  The per-image cv::imdecode calls of the reference's
+// 32-thread pool become ONE st_jpeg_decode_batch() call per execute(): Huffman decoding on host threads, everything dense in
+// HIP kernels, bit-exact to libjpeg's defaults (include/scannertools_hip.h).
+//
+// JPEG only, as the reference's GPU kernel (:78-88 is fatal on PNG and ANY).  ImageDecoderArgs { image_type: PNG = 0 | JPEG = 1
+// | ANY = 2 }: JPEG and a message without the field (the reference's CPU kernel takes no arguments at all) are accepted; the
+// field present with PNG or ANY fails validate().  (proto3 does not write a field that holds its default, so a PNG request
+// serialised by protoc is an empty message and cannot be told from "no arguments": it is accepted, and a PNG stream then
+// fails in execute() as any stream that is not a JPEG does.)
+//
+// The frame shape of an execute() is that of its first element.  Where the reference is undefined this fails instead: an
+// element of another shape (the reference's CPU kernel copies it into a frame of the first one's size, :46-50), and an element
+// that is not a baseline JPEG this library decodes ("Failed to decode image" there) are fatal with the row and the cause.
+// Registered twice like the other classes: DeviceType::GPU reads host bytes and produces device frames, the staged
+// DeviceType::CPU form decodes into a device buffer and copies host frames out.
+#include "scanner/api/kernel.h"
+#include "scanner/api/op.h"
+#include "scanner/util/hip.h"
+#include "scanner/util/memory.h"
+#include "proto_lite.h"
+#include "scannertools_hip.h"
+#include "kernel_core.h"
+
+namespace scanner {
+namespace {
+// false: not a message; *image_type: -1 when the field is absent
+bool parse_image_decoder_args(const std::vector<u8>& args, int* image_type) {
+  std::vector<proto_lite::Field> fields;
+  *image_type = -1;
+  if (!proto_lite::parse(args.data(), args.size(), &fields)) return false;
+  for (auto& f : fields)
+    if (f.number == 1 && f.wire == 0) *image_type = (int)f.value;
+  return true;
+}
+}  // namespace
+
+template <bool STAGED>
+class ImageDecoderKernelHIPImpl : public BatchedKernel {
+ public:
+  ImageDecoderKernelHIPImpl(const KernelConfig& config) : BatchedKernel(config), core_(config, STAGED), stage_(core_.gpu) {
+    int image_type = -1;
+    if (!parse_image_decoder_args(config.args, &image_type)) RESULT_ERROR(&core_.valid, "ImageDecoder: could not parse ImageDecoderArgs");
+    else if (image_type == 0 || image_type == 2)
+      RESULT_ERROR(&core_.valid, "ImageDecoder: image_type %s is not supported (JPEG only)", image_type == 0 ? "PNG" : "ANY");
+    else if (image_type != -1 && image_type != 1) RESULT_ERROR(&core_.valid, "ImageDecoder: invalid image_type %d", image_type);
+    else core_.open("ImageDecoderKernelHIP");
+  }
+  void validate(Result* result) override { core_.validate(result); }
+
+  void execute(const BatchedElements& input_columns, BatchedElements& output_columns) override {
+    auto& img_col = input_columns[0];
+    const i32 n = (i32)num_rows(img_col);
+    if (n == 0) return;
+    // the shape of the batch is that of its first element; every element is probed before anything is launched
+    st_jpeg_info first = {};
+    for (i32 i = 0; i < n; ++i) {
+      st_jpeg_info info;
+      const int st = st_jpeg_probe(img_col[i].buffer, img_col[i].size, &info);
+      LOG_IF(FATAL, st != ST_OK) << "ImageDecoder: row " << i << " of the batch: " << info.message;
+      if (i == 0) first = info;
+      LOG_IF(FATAL, info.h != first.h || info.w != first.w || info.channels != first.channels)
+          << "ImageDecoder: row " << i << " of the batch changes shape inside a batch (" << info.w << "x" << info.h << "x" << info.channels
+          << " after " << first.w << "x" << first.h << "x" << first.channels << ")";
+    }
+    FrameInfo info(first.h, first.w, first.channels, FrameType::U8);
+    std::vector<Frame*> output_frames = new_frames(core_.device, info, n);
+    bufs_.resize(n);
+    sizes_.resize(n);
+    for (i32 i = 0; i < n; ++i) { bufs_[i] = img_col[i].buffer; sizes_[i] = img_col[i].size; }
+    const size_t out_bytes = info.size(), out_stride = DeviceStage::align(out_bytes);
+    u8* dev = nullptr;
+    if (STAGED) {
+      dev = stage_.reserve(out_stride * n);
+      strided_ptrs(dst_, n, dev, out_stride);
+    } else {
+      output_ptrs(dst_, output_frames);
+    }
+    st_ctx* ctx = core_.ctx;
+    const int st = st_jpeg_decode_batch(ctx, bufs_.data(), sizes_.data(), n, first.h, first.w, first.channels, dst_.data());
+    LOG_IF(FATAL, st != ST_OK) << "ImageDecoder: " << st_ctx_last_error(ctx);
+    core_.sync();
+    if (STAGED) stage_.download_frames(output_frames, dev, out_stride, out_bytes);
+    for (i32 i = 0; i < n; ++i) insert_frame(output_columns[0], output_frames[i]);
+  }
+
+ private:
+  KernelCore core_;
+  DeviceStage stage_;   // staged: the decoded frames
+  std::vector<const uint8_t*> bufs_;
+  std::vector<size_t> sizes_;
+  std::vector<uint8_t*> dst_;
+};
+
+using ImageDecoderKernelHIP = ImageDecoderKernelHIPImpl<false>;
+using ImageDecoderKernelHIPStaged = ImageDecoderKernelHIPImpl<true>;
+
+REGISTER_OP(ImageDecoder).input("img").frame_output("frame").protobuf_name("ImageDecoderArgs");
+
+REGISTER_KERNEL(ImageDecoder, ImageDecoderKernelHIPStaged).device(DeviceType::CPU).batch().num_devices(1);
+
+REGISTER_KERNEL(ImageDecoder, ImageDecoderKernelHIP).device(DeviceType::GPU).batch().num_devices(1);
+}  // namespace scanner

@@ -1,0 +1,136 @@
+"""ImageDecoder on the MI355X: 1080p 4:2:0 baseline JPEG streams at quality 75 and 90, batches of 1, 8 and 32.
+Prints one JSON line.
+
+Needs Pillow to make the streams (seeded synthetic frames) and as the yardstick: Pillow's full decode (libjpeg-turbo at its
+defaults, what cv::imdecode calls) on a thread pool stands in for the reference's cv::imdecode pool.  Per quality:
+  (a) kernel time of the two kernels per frame from the library's events (st_ctx_timing_*, ST_K_JPEG brackets both launches
+      of a sub-batch) and the share of 8 TB/s it is in the as-built byte model (coefficients in, planes out and in again,
+      frames out); per-kernel durations come from a trace run, see below;
+  (b) the host stage alone (st_jpeg_coefficients: markers + Huffman decoding) in frames/s on 1, 4 and 16 threads;
+  (c) st_jpeg_decode_batch end to end (streams in host memory -> frames in device memory, synchronised) in frames/s at
+      ST_JPEG_THREADS = 1, 4 and 16, beside Pillow's full decode of the same streams on as many threads.
+The first frame of every quality is compared with Pillow byte for byte before anything is timed.
+
+    python scripts/bench_image_decoder.py [--rounds 5]
+    rocprofv3 --kernel-trace --stats -d DIR -- python scripts/bench_image_decoder.py --trace
+
+--trace makes three calls per quality and batch and times nothing: the kernel statistics of the trace then hold k_jpeg_idct
+and k_jpeg_color over known work.
+"""
+import argparse
+import ctypes
+import io
+import json
+import os
+import statistics
+import sys
+import time
+from concurrent.futures import ThreadPoolExecutor
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np
+
+H, W = 1080, 1920
+BATCHES = (1, 8, 32)
+THREADS = (1, 4, 16)
+DISTINCT = 8
+# as-built byte model per frame (two launches): 4:2:0 has 1.5 samples per pixel on the block-padded planes (1088 rows)
+BLOCKS = (W // 16) * ((H + 15) // 16) * 6
+MODEL_BYTES = BLOCKS * 128 + 2 * BLOCKS * 64 + H * W * 3
+
+
+def make_streams(Image, quality):
+    out = []
+    for i in range(DISTINCT):
+        rng = np.random.default_rng(100 + i)
+        y, x = np.mgrid[0:H, 0:W].astype(np.float32)
+        ph = rng.uniform(0, 6.28, 6)
+        img = np.stack([127 + 100 * np.sin(x / 37 + ph[0]) * np.cos(y / 23 + ph[1]), 127 + 100 * np.sin((x + y) / 51 + ph[2]) * np.cos(y / 9 + ph[3]),
+                        127 + 100 * np.cos(x / 13 + ph[4]) * np.sin((x - y) / 29 + ph[5])], axis=-1)
+        img = np.clip(img + rng.normal(0, 12, img.shape), 0, 255).astype(np.uint8)   # sensor-like noise: a few hundred KB at q75
+        buf = io.BytesIO()
+        Image.fromarray(img).save(buf, "JPEG", quality=quality, subsampling="4:2:0")
+        out.append(buf.getvalue())
+    return out
+
+
+def rate(fn, frames, rounds):
+    fn()
+    times = []
+    for _ in range(rounds):
+        t0 = time.perf_counter()
+        fn()
+        times.append(time.perf_counter() - t0)
+    return frames / statistics.median(times)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--trace", action="store_true")
+    args = ap.parse_args()
+    try:
+        from PIL import Image
+    except ImportError:
+        sys.exit("bench_image_decoder.py needs Pillow to make its 1080p streams and as its yardstick")
+    import torch
+    from scannertools_amd import _native
+    from scannertools_amd.hip import HipContext
+    L = _native.lib()
+    ctx = HipContext(0)
+    result = {"bench": "image_decoder", "h": H, "w": W, "sampling": "4:2:0", "model_bytes_per_frame": MODEL_BYTES, "qualities": {}}
+    for quality in (75, 90):
+        streams = make_streams(Image, quality)
+        got = ctx.decode_jpeg(streams[:1]).cpu().numpy()[0]
+        assert np.array_equal(got, np.asarray(Image.open(io.BytesIO(streams[0])))), "decode differs from Pillow"
+        q = {"stream_bytes": int(statistics.mean(len(s) for s in streams))}
+        outs = {n: torch.empty((n, H, W, 3), dtype=torch.uint8, device=ctx.device) for n in BATCHES}
+
+        def gpu_call(n):
+            ctx.decode_jpeg([streams[i % DISTINCT] for i in range(n)], out=outs[n])
+            ctx.sync()
+
+        if args.trace:
+            os.environ["ST_JPEG_THREADS"] = "16"
+            for n in BATCHES:
+                for _ in range(3):
+                    gpu_call(n)
+            continue
+        # (b) the host stage alone
+        coefs = [np.empty(BLOCKS * 64, np.int16) for _ in range(32)]
+
+        def host_stage(i):
+            s = streams[i % DISTINCT]
+            assert L.st_jpeg_coefficients(s, len(s), coefs[i].ctypes.data, coefs[i].size, None, None) == 0
+
+        def pillow(i):
+            Image.open(io.BytesIO(streams[i % DISTINCT])).load()
+
+        q["host_stage_fps"], q["pillow_fps"], q["decode_batch_fps"], q["kernel_ms_per_frame"] = {}, {}, {}, {}
+        for t in THREADS:
+            with ThreadPoolExecutor(t) as pool:
+                q["host_stage_fps"][t] = round(rate(lambda: list(pool.map(host_stage, range(32))), 32, args.rounds), 1)
+                q["pillow_fps"][t] = round(rate(lambda: list(pool.map(pillow, range(32))), 32, args.rounds), 1)
+            # (c) end to end, (a) kernel time from the library's events
+            os.environ["ST_JPEG_THREADS"] = str(t)
+            for n in BATCHES:
+                q["decode_batch_fps"]["threads%d_batch%d" % (t, n)] = round(rate(lambda: gpu_call(n), n, args.rounds), 1)
+        os.environ["ST_JPEG_THREADS"] = "16"
+        ctx.timing_enable([_native.K_JPEG])
+        for n in BATCHES:
+            gpu_call(n)
+            ctx.timing_reset()
+            for _ in range(args.rounds):
+                gpu_call(n)
+            launches, ms = ctx.timing_read(_native.K_JPEG)
+            per_frame = ms / (args.rounds * n)
+            q["kernel_ms_per_frame"]["batch%d" % n] = round(per_frame, 4)
+            q["kernel_share_of_8TBps_batch%d" % n] = round(MODEL_BYTES / (per_frame * 1e-3) / 8e12, 3)
+        ctx.timing_enable([])
+        result["qualities"]["q%d" % quality] = q
+    ctx.close()
+    print(json.dumps(result))
+
+
+if __name__ == "__main__":
+    main()
