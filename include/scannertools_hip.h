@@ -100,7 +100,8 @@ enum st_kernel_id {
   ST_K_CPM2_NMS = 15,
   ST_K_FRAME_STATS = 16, /* moments + finishing launches of the frame-statistics ops */
   ST_K_JPEG = 17,        /* inverse DCT + upsample / colour launches of the ImageDecoder op */
-  ST_K_COUNT = 18
+  ST_K_NET_INPUT = 18,   /* the FacenetInput and CaffeInput launches */
+  ST_K_COUNT = 19
 };
 int st_ctx_timing_enable(st_ctx* ctx, unsigned kernel_mask);
 int st_ctx_timing_reset(st_ctx* ctx);
@@ -499,6 +500,45 @@ int st_cpm2_resize_merge_maps(st_ctx* ctx, const float* const* src_dev, const in
  * cpm2_output_kernel_cpu.cpp:481-499 reads. */
 int st_cpm2_nms(st_ctx* ctx, const float* const* maps_dev, int n, int h, int w, int parts, int max_peaks, float threshold,
                 float* const* joints_dev);
+
+/* ---- Network inputs (scannertools_caffe): FacenetInput and CaffeInput ----------------------------------
+ * Geometry of the Facenet network input for a frame of (h, w) at `scale`, as FacenetInputKernelCPU::new_frame_info derives
+ * it (scannertools_caffe_cpp/facenet_input_kernel_cpu.cpp:21-29): floor(float(size) * scale) in float32, rounded up to a
+ * multiple of 8.  Host-only (no context).  ST_ERR_INVALID for scale <= 0 or a size below one pixel. */
+int st_facenet_geometry(int h, int w, float scale, int* net_h, int* net_w);
+
+/* FacenetInput: replaces the per-frame body of FacenetInputKernelCPU::execute (facenet_input_kernel_cpu.cpp:81-117:
+ * cv::resize INTER_LINEAR to (net_w, net_h), convertTo(CV_32FC3), subtract the mean_colors Scalar, split, three
+ * transposes, three plane copies, a row-wise memcpy) for a whole batch in one launch.  frames: n device pointers to
+ * (h, w, 3) uint8 RGB frames; mean: mean_colors[0..2], subtracted from channels R, G, B in float32; out: n device pointers
+ * to dense float32 frames of FrameInfo(3, net_w, net_h, F32) (:75): element [c][x][y] = float(resized[y][x][c]) - mean[c],
+ * every plane transposed, channels in frame order.  The resize is the Resize op's INTER_LINEAR (cv::resize for 8-bit
+ * data: 11-bit fixed point, the exact 2 x 2 mean at a precise 2:1 ratio, a copy at equal size); parity is with this CPU
+ * kernel, not with facenet_input_kernel_gpu.cpp, whose cv::cuda::resize interpolates in float. */
+int st_facenet_input_batch(st_ctx* ctx, const uint8_t* const* frames_dev, int n, int h, int w, float scale,
+                           const float* mean, float* const* out_dev);
+
+/* One axis of CaffeInput's box filter (caffe_input_transformer_base.h:51-70, kernel_box :10-13), n_in source samples ->
+ * n_out outputs, every operation an IEEE float32 operation: scale = float(n_out) / float(n_in), ks = 0.5f / scale and per
+ * output x: src = (float(x) + 0.5f) / scale, begin[x] = int(src - ks + 0.5f); tap k of [0, int(2.0f * ks + 1.0f)) is a
+ * member when fabsf((float(k + begin) - src) * scale) <= 0.5f.  first[x]: the first member's k (-1: none), count[x]: the
+ * number of members; member k reads source index min(begin + k, n_in - 1) with weight 1.0f / float(count).  Host only (no
+ * context, no GPU); the arrays hold n_out entries each and are always filled.  ST_ERR_UNSUPPORTED when some window is
+ * empty (the reference divides 0 by 0 there: non-integer enlargements) or its members are not contiguous;
+ * ST_ERR_INVALID for sizes outside 1 .. 2^24 or a null array. */
+int st_caffe_input_axis(int n_in, int n_out, int* begin, int* first, int* count);
+
+/* CaffeInput: replaces CaffeInputKernel::transform_halide (caffe_input_kernel.cpp:75-138; the pipeline is
+ * caffe_input_transformer_base.h:43-105) for a whole batch in one launch.  frames: n device pointers to (h, w, 3) uint8
+ * RGB frames; out: n device pointers to dense planar (3, net_h, net_w) float32 frames, the FrameInfo(3, net_h, net_w,
+ * F32) of :186.  Horizontal pass first: per source row, channel and output column the sum over the window's members of
+ * weight * float(pixel), accumulated in member order, multiply and add rounded separately; the vertical pass is the same
+ * sum over those rows; then clamp to [0, 255].  Output plane c = (clamped value of input channel 2 - c) - mean_bgr[c]
+ * (mean_colors in B, G, R order, :129-130), divided by 255.0f when `normalize`.  The window tables come from
+ * st_caffe_input_axis, computed on the host once per geometry and kept in the context.  A geometry that function refuses
+ * is ST_ERR_UNSUPPORTED here, before anything is launched or written (known deviation: the reference produces NaN). */
+int st_caffe_input_batch(st_ctx* ctx, const uint8_t* const* frames_dev, int n, int h, int w, int net_h, int net_w,
+                         const float* mean_bgr, int normalize, float* const* out_dev);
 
 /* ---- ImageDecoder: baseline JPEG ------------------------------------------------------------
  * Replaces the reference's ImageDecoder kernels (scannertools_cpp/imgproc/image_decoder_kernel_cpu.cpp: cv::imdecode(

@@ -56,8 +56,8 @@ COLOR_CODES = {"COLOR_BGR2RGB": 4, "COLOR_RGB2BGR": 4, "COLOR_BGR2GRAY": 6, "COL
                "COLOR_GRAY2BGR565": 20, "COLOR_BGR5652GRAY": 21, "COLOR_BGR2BGR555": 22, "COLOR_RGB2BGR555": 23,
                "COLOR_BGR5552BGR": 24, "COLOR_BGR5552RGB": 25, "COLOR_BGRA2BGR555": 26, "COLOR_RGBA2BGR555": 27,
                "COLOR_BGR5552BGRA": 28, "COLOR_BGR5552RGBA": 29, "COLOR_GRAY2BGR555": 30, "COLOR_BGR5552GRAY": 31}
-K_HIST, K_GRAY, K_PYR, K_POLYEXP, K_UPDATE_MATRICES, K_BLUR_UPDATE, K_FLOW_HIST, K_DRAW_FLOW, K_BLUR_OP, K_RESIZE, K_CVT_COLOR, K_CPM2_INPUT, K_CPM2_LIMBS, K_CONV, K_CPM2_RESIZE, K_CPM2_NMS, K_FRAME_STATS, K_JPEG, K_COUNT = range(19)
-KERNEL_NAMES = ["hist", "gray", "pyr", "polyexp", "update_matrices", "blur_update", "flow_hist", "draw_flow", "blur_op", "resize", "cvt_color", "cpm2_input", "cpm2_limbs", "conv", "cpm2_resize", "cpm2_nms", "frame_stats", "jpeg"]
+K_HIST, K_GRAY, K_PYR, K_POLYEXP, K_UPDATE_MATRICES, K_BLUR_UPDATE, K_FLOW_HIST, K_DRAW_FLOW, K_BLUR_OP, K_RESIZE, K_CVT_COLOR, K_CPM2_INPUT, K_CPM2_LIMBS, K_CONV, K_CPM2_RESIZE, K_CPM2_NMS, K_FRAME_STATS, K_JPEG, K_NET_INPUT, K_COUNT = range(20)
+KERNEL_NAMES = ["hist", "gray", "pyr", "polyexp", "update_matrices", "blur_update", "flow_hist", "draw_flow", "blur_op", "resize", "cvt_color", "cpm2_input", "cpm2_limbs", "conv", "cpm2_resize", "cpm2_nms", "frame_stats", "jpeg", "net_input"]
 assert len(KERNEL_NAMES) == K_COUNT
 
 
@@ -164,6 +164,10 @@ SIGNATURES = {
     "st_cpm2_resize_merge_maps": (_i, [_vp, _c.POINTER(_vp), _c.POINTER(_i), _c.POINTER(_i), _c.POINTER(_c.c_float), _c.POINTER(_c.c_float), _i, _i,
                                        _i, _c.POINTER(_i), _i, _i, _i, _c.POINTER(_vp)]),
     "st_cpm2_nms": (_i, [_vp, _c.POINTER(_vp), _i, _i, _i, _i, _i, _c.c_float, _c.POINTER(_vp)]),
+    "st_facenet_geometry": (_i, [_i, _i, _c.c_float, _c.POINTER(_i), _c.POINTER(_i)]),
+    "st_facenet_input_batch": (_i, [_vp, _c.POINTER(_vp), _i, _i, _i, _c.c_float, _c.POINTER(_c.c_float), _c.POINTER(_vp)]),
+    "st_caffe_input_axis": (_i, [_i, _i, _c.POINTER(_i), _c.POINTER(_i), _c.POINTER(_i)]),
+    "st_caffe_input_batch": (_i, [_vp, _c.POINTER(_vp), _i, _i, _i, _i, _i, _c.POINTER(_c.c_float), _i, _c.POINTER(_vp)]),
     "st_jpeg_probe": (_i, [_vp, _sz, _c.POINTER(JpegInfo)]),
     "st_jpeg_coefficients": (_i, [_vp, _sz, _vp, _sz, _vp, _c.POINTER(JpegInfo)]),
     "st_jpeg_decode_batch": (_i, [_vp, _c.POINTER(_vp), _c.POINTER(_sz), _i, _i, _i, _i, _c.POINTER(_vp)]),
@@ -184,7 +188,7 @@ def source_hash():
     st_build_info() of a library built from THIS tree reports."""
     import hashlib
     srcs = ["st_context.hip", "st_hist.hip", "st_farneback.hip", "st_flowvis.hip", "st_imgproc.hip", "st_pose.hip", "st_conv.hip",
-            "st_conv_tile_bf16x3.hip", "st_conv_tile_f32.hip", "st_framestats.hip", "st_jpeg.hip", "st_jpeg_parse.cpp", "st_internal.h",
+            "st_conv_tile_bf16x3.hip", "st_conv_tile_f32.hip", "st_framestats.hip", "st_jpeg.hip", "st_netinput.hip", "st_jpeg_parse.cpp", "st_internal.h",
             "st_conv_tile.h", "st_jpeg_parse.h",
             os.path.join("..", "..", "include", "scannertools_hip.h"), "Makefile"]
     hsh = hashlib.sha256()

@@ -1,5 +1,6 @@
 """Tiny proto3 wire-format writer for the ops' argument messages
-(/root/reference/scannertools/scannertools_cpp/imgproc/scannertools_imgproc.proto); the C++ side
+(/root/reference/scannertools/scannertools_cpp/imgproc/scannertools_imgproc.proto and
+/root/reference/scannertools_caffe/scannertools_caffe_cpp/scannertools_caffe.proto); the C++ side
 reads them with scanner_kernels/proto_lite.h.  Default-valued fields are omitted, as proto3 does."""
 import struct
 
@@ -122,3 +123,36 @@ def parse_image_decoder_args(buf):
         if number == 1 and wt == 0:
             out["image_type"] = names.get(value, value)
     return out
+
+
+def repeated_float(number, values, packed=True):
+    """A `repeated float` field: packed (one length-delimited field, what proto3 writes) or unpacked (one fixed32 field per
+    value, zeros included).  No values: nothing."""
+    values = [float(v) for v in values]
+    if not values:
+        return b""
+    if packed:
+        return message(number, struct.pack("<%df" % len(values), *values))
+    return b"".join(_varint(number << 3 | 5) + struct.pack("<f", v) for v in values)
+
+
+def net_descriptor(input_width=0, input_height=0, mean_colors=(), normalize=False, packed=True):
+    """A serialised NetDescriptor (scannertools_caffe.proto:5-26) with the fields the network-input ops read: input_width = 5,
+    input_height = 6, mean_colors = 7, normalize = 11."""
+    return (encode([(5, "int32", input_width), (6, "int32", input_height)]) + repeated_float(7, mean_colors, packed) +
+            encode([(11, "bool", normalize)]))
+
+
+def facenet_args(scale, mean_colors, templates_path="", threshold=0.0, packed=True):
+    """A serialised FacenetArgs (scannertools_caffe.proto:38-43): caffe_args = 1 (CaffeArgs{net_descriptor = 1}),
+    templates_path = 2, scale = 3, threshold = 4."""
+    nd = net_descriptor(mean_colors=mean_colors, packed=packed)
+    caffe_args = message(1, nd) if nd else b""
+    return ((message(1, caffe_args) if caffe_args else b"") +
+            encode([(2, "string", templates_path), (3, "float", scale), (4, "float", threshold)]))
+
+
+def caffe_input_args(input_width, input_height, mean_colors, normalize=False, batch_size=0, packed=True):
+    """A serialised CaffeInputArgs (scannertools_caffe.proto:28-31): net_descriptor = 1, batch_size = 2."""
+    nd = net_descriptor(input_width, input_height, mean_colors, normalize, packed)
+    return (message(1, nd) if nd else b"") + encode([(2, "int32", batch_size)])

@@ -53,8 +53,10 @@ struct st_ctx {
   std::string last_error;
   int num_cus = 256;
   struct st_jpeg_state* jpeg = nullptr;   // page-locked slots of st_jpeg_decode_batch (st_jpeg.hip), made at its first call
+  struct st_netin_state* netin = nullptr; // per-geometry tables of the FacenetInput / CaffeInput entry points (st_netinput.hip)
 };
 void st_jpeg_release(st_ctx* ctx);   // frees ctx->jpeg (st_ctx_destroy)
+void st_netin_release(st_ctx* ctx);  // frees ctx->netin (st_ctx_destroy)
 
 int st_set_error(st_ctx* ctx, int status, const char* fmt, ...);
 
@@ -132,14 +134,15 @@ inline int st_rs_linear_mode(int h, int w, int out_h, int out_w, const st_rs_sca
 }
 
 #ifdef __HIPCC__
+// (coordinates and taps are __host__ __device__: st_netinput.hip tabulates them on the host with the same code)
 // saturate_cast<short>(float): cvRound = round half to even, then saturation
-__device__ __forceinline__ int rs_coef(float v) {
+__host__ __device__ __forceinline__ int rs_coef(float v) {
   const float r = rintf(v);
   return r < -32768.f ? -32768 : (r > 32767.f ? 32767 : (int)r);
 }
 
 // INTER_LINEAR's source coordinate of destination index d: the first tap's index and the fraction towards the second
-__device__ __forceinline__ float rs_linear_coord(int d, double scale, int* s) {
+__host__ __device__ __forceinline__ float rs_linear_coord(int d, double scale, int* s) {
   const float f = (float)((d + 0.5) * scale - 0.5);
   *s = (int)floorf(f);
   return f - *s;
@@ -148,7 +151,7 @@ __device__ __forceinline__ float rs_linear_coord(int d, double scale, int* s) {
 // Horizontal taps of one destination column: the column is clamped into the row (a single tap * 2048 at the right edge),
 // 11-bit weights.  sx: the first tap's column; two: a second tap exists at sx + 1.
 struct RsTapX { int sx, a0, a1; bool two; };
-__device__ __forceinline__ RsTapX rs_linear_tap_x(int sx, float fx, int sw) {
+__host__ __device__ __forceinline__ RsTapX rs_linear_tap_x(int sx, float fx, int sw) {
   RsTapX t;
   if (sx < 0) { fx = 0; sx = 0; }
   if (sx >= sw - 1) { fx = 0; sx = sw - 1; }
@@ -159,7 +162,7 @@ __device__ __forceinline__ RsTapX rs_linear_tap_x(int sx, float fx, int sw) {
 }
 // Vertical taps of one destination row: both rows clamped into the image
 struct RsTapY { int y0, y1, b0, b1; };
-__device__ __forceinline__ RsTapY rs_linear_tap_y(int sy, float fy, int sh) {
+__host__ __device__ __forceinline__ RsTapY rs_linear_tap_y(int sy, float fy, int sh) {
   RsTapY t;
   t.b0 = rs_coef((1.f - fy) * 2048); t.b1 = rs_coef(fy * 2048);
   t.y0 = sy < 0 ? 0 : (sy > sh - 1 ? sh - 1 : sy);

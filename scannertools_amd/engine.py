@@ -891,6 +891,22 @@ class _Ops:
         from . import _proto
         return _CppOpNode(self.sc, "CPM2Input", frame, device, batch, None, _proto.encode([(2, "float", float(scale))]))
 
+    def FacenetInput(self, frame, scale, mean_colors, templates_path="", threshold=0.0, device=None, batch=None, packed=True):
+        """sc.ops.FacenetInput(frame=..., args FacenetArgs{caffe_args{net_descriptor{mean_colors}}, scale}) -> the column
+        facenet_input (facenet_input_kernel_cpu.cpp:138-141): (3, net_w, net_h) float32 frames.  ``packed``: how mean_colors
+        goes on the wire (proto3 packs; the kernel reads both)."""
+        from . import _proto
+        return _CppOpNode(self.sc, "FacenetInput", frame, device, batch, None,
+                          _proto.facenet_args(scale, mean_colors, templates_path, threshold, packed))
+
+    def CaffeInput(self, frame, input_width, input_height, mean_colors, normalize=False, device=None, batch=None, packed=True):
+        """sc.ops.CaffeInput(frame=..., args CaffeInputArgs{net_descriptor{input_width, input_height, mean_colors, normalize}})
+        -> the column caffe_frame (caffe_input_kernel_cpu.cpp): (3, input_height, input_width) float32 frames, planes B, G, R;
+        input_width -1: the frame's own size.  mean_colors in B, G, R order."""
+        from . import _proto
+        return _CppOpNode(self.sc, "CaffeInput", frame, device, batch, None,
+                          _proto.caffe_input_args(input_width, input_height, mean_colors, normalize, packed=packed))
+
     def CPM2(self, cpm2_input, weights=None, seed=0, batch=8, max_peaks=64, nms_threshold=0.05, device=None, prototxt=None):
         """sc.ops.CPM2(cpm2_input=...) (cpm2_kernel.cpp:46-52): returns the columns (cpm2_resized_map, cpm2_joints).
         `weights`: path of the model's caffemodel -> the registered C++ kernel class (CPM2KernelHIP, the drop-in; args

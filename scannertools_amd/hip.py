@@ -479,6 +479,61 @@ class HipContext:
         self._check(self._L.st_cpm2_input_batch(self._h, tf, n, h, w, float(scale), to))
         return out
 
+    # -- network inputs (scannertools_caffe) ----------------------------------------------------
+    def _net_input_frames(self, frames):
+        fr = list(frames) if isinstance(frames, (list, tuple)) else list(frames.unbind(0))
+        if fr:
+            h, w, _ = fr[0].shape
+            for f in fr:
+                _require_cuda(f, torch.uint8, "frame", self.device)
+                if tuple(f.shape) != (h, w, 3):
+                    raise ValueError("all frames must be (h,w,3) with equal shape")
+        return fr
+
+    def facenet_input(self, frames, scale, mean_colors, out=None):
+        """FacenetInput (scannertools_caffe_cpp/facenet_input_kernel_cpu.cpp:81-117): (n,h,w,3) uint8 RGB frames (a tensor or a
+        list of (h,w,3) tensors) -> (n,3,net_w,net_h) float32: INTER_LINEAR resize to `facenet_geometry(h, w, scale)`, minus
+        ``mean_colors[c]`` per channel (frame order R, G, B), every plane transposed."""
+        self._bind()
+        mean = [float(v) for v in mean_colors]
+        if len(mean) != 3:
+            raise ValueError("mean_colors must hold 3 values, got %d" % len(mean))
+        fr = self._net_input_frames(frames)
+        n = len(fr)
+        if n == 0:
+            return torch.zeros((0, 3, 0, 0), dtype=torch.float32, device=self.device)
+        h, w, _ = fr[0].shape
+        nh, nw = facenet_geometry(h, w, scale)
+        out = (torch.empty((n, 3, nw, nh), dtype=torch.float32, device=self.device) if out is None
+               else _check_out(out, (n, 3, nw, nh), torch.float32, self.device))
+        tf = (ctypes.c_void_p * n)(*[f.data_ptr() for f in fr])
+        to = (ctypes.c_void_p * n)(*[out[i].data_ptr() for i in range(n)])
+        self._check(self._L.st_facenet_input_batch(self._h, tf, n, h, w, float(scale), (ctypes.c_float * 3)(*mean), to))
+        return out
+
+    def caffe_input(self, frames, input_width, input_height, mean_colors, normalize=False, out=None):
+        """CaffeInput (scannertools_caffe_cpp/caffe_input_kernel.cpp:75-138): (n,h,w,3) uint8 RGB frames (a tensor or a list of
+        (h,w,3) tensors) -> (n,3,input_height,input_width) float32, planes B, G, R: the reference's box filter, clamped to
+        0..255, minus ``mean_colors`` (B, G, R order), divided by 255 when ``normalize``.  ``input_width`` -1: the frame's
+        own size.  A geometry with an empty filter window (non-integer enlargements) raises StError (unsupported) and
+        nothing is written."""
+        self._bind()
+        mean = [float(v) for v in mean_colors]
+        if len(mean) != 3:
+            raise ValueError("mean_colors must hold 3 values, got %d" % len(mean))
+        fr = self._net_input_frames(frames)
+        n = len(fr)
+        if n == 0:
+            return torch.zeros((0, 3, 0, 0), dtype=torch.float32, device=self.device)
+        h, w, _ = fr[0].shape
+        nw, nh = (w, h) if int(input_width) == -1 else (int(input_width), int(input_height))
+        out = (torch.empty((n, 3, nh, nw), dtype=torch.float32, device=self.device) if out is None
+               else _check_out(out, (n, 3, nh, nw), torch.float32, self.device))
+        tf = (ctypes.c_void_p * n)(*[f.data_ptr() for f in fr])
+        to = (ctypes.c_void_p * n)(*[out[i].data_ptr() for i in range(n)])
+        self._check(self._L.st_caffe_input_batch(self._h, tf, n, h, w, nh, nw, (ctypes.c_float * 3)(*mean), int(bool(normalize)), to))
+        return out
+
     def cpm2_limb_scores(self, heatmaps, peaks, inter_threshold=0.05, min_above=9):
         """Candidate-pair scores of CPM2Output (cpm2_output_kernel_cpu.cpp:424-487): heatmaps
         (n,57,H,W) float32, peaks (n,18,max_peaks+1,3) float32 -> (n,19,max_peaks,max_peaks) float32."""
@@ -748,6 +803,27 @@ def cpm2_geometry(h, w, scale):
     if st != 0:
         raise StError(st, "st_cpm2_geometry(%d, %d, %r)" % (h, w, scale))
     return tuple(x.value for x in v)
+
+
+def facenet_geometry(h, w, scale):
+    """(net_h, net_w) of the Facenet network input for an (h, w) frame at ``scale`` (st_facenet_geometry)."""
+    nh, nw = ctypes.c_int(), ctypes.c_int()
+    st = _native.lib().st_facenet_geometry(int(h), int(w), float(scale), ctypes.byref(nh), ctypes.byref(nw))
+    if st != 0:
+        raise StError(st, "st_facenet_geometry(%d, %d, %r)" % (h, w, scale))
+    return nh.value, nw.value
+
+
+def caffe_input_axis(n_in, n_out):
+    """(status, begin, first, count) of one axis of CaffeInput's box filter (st_caffe_input_axis, host only): int32 arrays
+    of n_out entries; status is ST_ERR_UNSUPPORTED when some window is empty (count 0)."""
+    begin, first, count = (np.empty(int(n_out), np.int32) for _ in range(3))
+    ip = ctypes.POINTER(ctypes.c_int)
+    st = _native.lib().st_caffe_input_axis(int(n_in), int(n_out), begin.ctypes.data_as(ip), first.ctypes.data_as(ip),
+                                           count.ctypes.data_as(ip))
+    if st not in (_native.ST_OK, _native.ST_ERR_UNSUPPORTED):
+        raise StError(st, "st_caffe_input_axis(%d, %d)" % (n_in, n_out))
+    return st, begin, first, count
 
 
 def cpm2_scale_for_height(h, target_h):

@@ -1,5 +1,6 @@
 // Minimal proto3 wire-format reader for the argument messages of the imgproc ops
-// (/root/reference/scannertools/scannertools_cpp/imgproc/scannertools_imgproc.proto).  With a real
+// (/root/reference/scannertools/scannertools_cpp/imgproc/scannertools_imgproc.proto) and of the caffe ops
+// (/root/reference/scannertools_caffe/scannertools_caffe_cpp/scannertools_caffe.proto).  With a real
 // Scanner build the generated scannertools_imgproc.pb.h classes can be used instead; this reader
 // only keeps the op library free of a protoc step.  Unknown fields are skipped.
 #pragma once
@@ -59,6 +60,36 @@ inline float as_float(const Field& f) {
   float r;
   memcpy(&r, &v, 4);
   return r;
+}
+
+// A nested message: the fields of the LAST occurrence of length-delimited field `number` (an absent field is an empty
+// message).  Returns false when that payload is malformed.
+inline bool nested(const std::vector<Field>& fields, uint32_t number, std::vector<Field>* out) {
+  const Field* last = nullptr;
+  for (auto& f : fields)
+    if (f.number == number && f.wire == 2) last = &f;
+  out->clear();
+  return !last || parse((const uint8_t*)last->bytes.data(), last->bytes.size(), out);
+}
+
+// `repeated float` field `number`, in wire order: proto3 writes it packed (one length-delimited field of 4-byte values),
+// proto2 and some writers unpacked (one fixed32 field per value); a reader has to accept both, also mixed.  Returns false
+// when a packed payload is not a whole number of floats.
+inline bool repeated_floats(const std::vector<Field>& fields, uint32_t number, std::vector<float>* out) {
+  for (auto& f : fields) {
+    if (f.number != number) continue;
+    if (f.wire == 5) {
+      out->push_back(as_float(f));
+    } else if (f.wire == 2) {
+      if (f.bytes.size() % 4) return false;
+      for (size_t i = 0; i < f.bytes.size(); i += 4) {
+        float v;
+        memcpy(&v, f.bytes.data() + i, 4);
+        out->push_back(v);
+      }
+    }
+  }
+  return true;
 }
 
 }  // namespace proto_lite
