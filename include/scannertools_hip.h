@@ -540,6 +540,55 @@ int st_caffe_input_axis(int n_in, int n_out, int* begin, int* first, int* count)
 int st_caffe_input_batch(st_ctx* ctx, const uint8_t* const* frames_dev, int n, int h, int w, int net_h, int net_w,
                          const float* mean_bgr, int normalize, float* const* out_dev);
 
+/* ---- Generic Caffe networks (scannertools_caffe: the Caffe and Facenet ops) ---------------------------
+ * The layers of a Caffe forward pass (scannertools_caffe_cpp/caffe_kernel.cpp:382) beyond the stride-1 "same" convolutions
+ * above.  Layer rules restated from Caffe's public sources ([EXT], unpinned).  Activations are NHWC
+ * float32; a call reads c channels from channel x_offset on (x_stride floats per pixel) and writes c channels from y_offset
+ * on.  No other channel is read or written: the zero pad channels of a buffer stay zero and never take part.  No result
+ * depends on the batch size n: every output element is accumulated in an order fixed by the layer.
+ *
+ * InnerProduct: y[m][j] = sum_k x[m][k] * W[j][k] (+ bias[j]) (+ ReLU), m < n, j < nout, on v_mfma_f32_32x32x2_f32.  k must be
+ * a multiple of 8 (the NHWC-padded length of the bottom blob; W holds zero columns for pad channels).  wp_dev: W rearranged
+ * ONCE by st_inner_product_pack_weights from the row-major [nout][k] float32 tensor into a 16-byte aligned buffer of
+ * st_inner_product_packed_bytes(k, nout) bytes.  The weights are streamed once per 32 rows of x; the sum over k is cut into
+ * chunks of 512 whose partial sums are added in ascending order.  bias_dev may be null.  Row m of y starts at y_dev + m *
+ * y_stride; columns >= nout are not written. */
+long long st_inner_product_packed_bytes(int k, int nout);
+int st_inner_product_pack_weights(st_ctx* ctx, const float* w_dev, int k, int nout, void* out_dev);
+int st_inner_product_f32(st_ctx* ctx, const float* x_dev, int n, int k, int x_stride, const void* wp_dev, const float* bias_dev,
+                         int nout, int relu, float* y_dev, int y_stride);
+/* Output sizes of one axis, host only: Convolution floor((size + 2 pad - k) / stride) + 1; Pooling ceil((size + 2 pad - k) /
+ * stride) + 1, less one when pad > 0 and the last window would start in the padding.  0 for arguments Caffe refuses. */
+int st_conv_out_size(int size, int k, int stride, int pad);
+int st_pool_out_size(int size, int k, int stride, int pad);
+/* Convolution of any square kernel, stride, pad and group (+ bias, may be null) (+ ReLU): the correctness path for the
+ * geometries st_conv2d_nhwc_f32 does not take.  w_dev: [cout][k][k][cin / group]; each output is one fmaf chain over (ky, kx,
+ * channel). */
+int st_conv2d_general_nhwc_f32(st_ctx* ctx, const float* x_dev, int n, int h, int w, int cin, int x_stride, int x_offset,
+                               const float* w_dev, const float* bias_dev, int k, int stride, int pad, int group, int cout,
+                               int relu, float* y_dev, int y_stride, int y_offset);
+/* Pooling: window [o * stride - pad, min(o * stride - pad + k, size + pad)) per axis, clipped to the map; ST_POOL_MAX over the
+ * clipped window, ST_POOL_AVE its sum divided by the UNCLIPPED window's size.  global: one window, the whole map (k, stride,
+ * pad ignored). */
+enum { ST_POOL_MAX = 0, ST_POOL_AVE = 1 };
+int st_pool_nhwc_f32(st_ctx* ctx, const float* x_dev, int n, int h, int w, int c, int x_stride, int x_offset, int method, int k,
+                     int stride, int pad, int global, float* y_dev, int y_stride, int y_offset);
+/* LRN across channels: x * (k + alpha / local_size * sum x^2)^-beta over channels c - (local_size - 1) / 2 .. c + (local_size
+ * - 1) / 2 clipped to [0, c); local_size odd.  pixels = n * h * w. */
+int st_lrn_nhwc_f32(st_ctx* ctx, const float* x_dev, long long pixels, int c, int x_stride, int x_offset, int local_size,
+                    float alpha, float beta, float k, float* y_dev, int y_stride, int y_offset);
+/* Softmax over the c channels of every pixel, the maximum subtracted first. */
+int st_softmax_nhwc_f32(st_ctx* ctx, const float* x_dev, long long pixels, int c, int x_stride, int x_offset, float* y_dev,
+                        int y_stride, int y_offset);
+/* A channel slice copied between two NHWC buffers (Concat where the producers cannot write their slices themselves), with
+ * max(x, 0) on the way when `relu` (a ReLU that could not be fused into its producer; x and y may be the same slice). */
+int st_copy_channels_nhwc_f32(st_ctx* ctx, const float* x_dev, long long pixels, int c, int x_stride, int x_offset, int relu,
+                              float* y_dev, int y_stride, int y_offset);
+/* NHWC (n, h, w, x_stride) -> n dense planar (c, h, w) frames, the blob as Caffe lays it out (out_dev: host array of n device
+ * pointers). */
+int st_nhwc_to_planar_f32(st_ctx* ctx, const float* x_dev, int n, int h, int w, int c, int x_stride, int x_offset,
+                          float* const* out_dev);
+
 /* ---- ImageDecoder: baseline JPEG ------------------------------------------------------------
  * Replaces the reference's ImageDecoder kernels (scannertools_cpp/imgproc/image_decoder_kernel_cpu.cpp: cv::imdecode(
  * IMREAD_UNCHANGED) + BGR->RGB on a thread pool; image_decoder_kernel_gpu.cpp: cv::cudacodec, JPEG only).  Entropy decoding

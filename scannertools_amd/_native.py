@@ -14,6 +14,7 @@ CSRC = os.path.join(_HERE, "csrc")
 
 ST_OK, ST_ERR_INVALID, ST_ERR_HIP, ST_ERR_OOM, ST_ERR_UNSUPPORTED = range(5)
 FM_LUMA, FM_LAPLACIAN = 1, 2   # st_frame_moment_mask
+POOL_MAX, POOL_AVE = 0, 1      # st_pool_nhwc_f32's method
 # st_frame_stat_kind: the six frame statistics (float32 for the *CPP kinds, float64 for the Python ops' values)
 FS_KINDS = {"BrightnessCPP": 0, "ContrastCPP": 1, "SharpnessCPP": 2, "Brightness": 3, "Contrast": 4, "Sharpness": 5}
 BBOX_SIDE = 200   # ST_BBOX_SIDE: the SharpnessBBox ops resize every box to BBOX_SIDE x BBOX_SIDE
@@ -168,6 +169,17 @@ SIGNATURES = {
     "st_facenet_input_batch": (_i, [_vp, _c.POINTER(_vp), _i, _i, _i, _c.c_float, _c.POINTER(_c.c_float), _c.POINTER(_vp)]),
     "st_caffe_input_axis": (_i, [_i, _i, _c.POINTER(_i), _c.POINTER(_i), _c.POINTER(_i)]),
     "st_caffe_input_batch": (_i, [_vp, _c.POINTER(_vp), _i, _i, _i, _i, _i, _c.POINTER(_c.c_float), _i, _c.POINTER(_vp)]),
+    "st_inner_product_packed_bytes": (ctypes.c_longlong, [_i, _i]),
+    "st_inner_product_pack_weights": (_i, [_vp, _vp, _i, _i, _vp]),
+    "st_inner_product_f32": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _i, _i, _vp, _i]),
+    "st_conv_out_size": (_i, [_i, _i, _i, _i]),
+    "st_pool_out_size": (_i, [_i, _i, _i, _i]),
+    "st_conv2d_general_nhwc_f32": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _i, _i]),
+    "st_pool_nhwc_f32": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _i, _i]),
+    "st_lrn_nhwc_f32": (_i, [_vp, _vp, _c.c_longlong, _i, _i, _i, _i, _c.c_float, _c.c_float, _c.c_float, _vp, _i, _i]),
+    "st_softmax_nhwc_f32": (_i, [_vp, _vp, _c.c_longlong, _i, _i, _i, _vp, _i, _i]),
+    "st_copy_channels_nhwc_f32": (_i, [_vp, _vp, _c.c_longlong, _i, _i, _i, _i, _vp, _i, _i]),
+    "st_nhwc_to_planar_f32": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _c.POINTER(_vp)]),
     "st_jpeg_probe": (_i, [_vp, _sz, _c.POINTER(JpegInfo)]),
     "st_jpeg_coefficients": (_i, [_vp, _sz, _vp, _sz, _vp, _c.POINTER(JpegInfo)]),
     "st_jpeg_decode_batch": (_i, [_vp, _c.POINTER(_vp), _c.POINTER(_sz), _i, _i, _i, _i, _c.POINTER(_vp)]),
@@ -188,7 +200,7 @@ def source_hash():
     st_build_info() of a library built from THIS tree reports."""
     import hashlib
     srcs = ["st_context.hip", "st_hist.hip", "st_farneback.hip", "st_flowvis.hip", "st_imgproc.hip", "st_pose.hip", "st_conv.hip",
-            "st_conv_tile_bf16x3.hip", "st_conv_tile_f32.hip", "st_framestats.hip", "st_jpeg.hip", "st_netinput.hip", "st_jpeg_parse.cpp", "st_internal.h",
+            "st_conv_tile_bf16x3.hip", "st_conv_tile_f32.hip", "st_framestats.hip", "st_jpeg.hip", "st_netinput.hip", "st_nn.hip", "st_jpeg_parse.cpp", "st_internal.h",
             "st_conv_tile.h", "st_jpeg_parse.h",
             os.path.join("..", "..", "include", "scannertools_hip.h"), "Makefile"]
     hsh = hashlib.sha256()

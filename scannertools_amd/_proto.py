@@ -136,19 +136,28 @@ def repeated_float(number, values, packed=True):
     return b"".join(_varint(number << 3 | 5) + struct.pack("<f", v) for v in values)
 
 
-def net_descriptor(input_width=0, input_height=0, mean_colors=(), normalize=False, packed=True):
-    """A serialised NetDescriptor (scannertools_caffe.proto:5-26) with the fields the network-input ops read: input_width = 5,
-    input_height = 6, mean_colors = 7, normalize = 11."""
-    return (encode([(5, "int32", input_width), (6, "int32", input_height)]) + repeated_float(7, mean_colors, packed) +
-            encode([(11, "bool", normalize)]))
+def net_descriptor(input_width=0, input_height=0, mean_colors=(), normalize=False, packed=True, model_path="", model_weights_path="",
+                   input_layer_names=(), output_layer_names=(), preserve_aspect_ratio=False, transpose=False, pad_mod=0):
+    """A serialised NetDescriptor (scannertools_caffe.proto:5-26): model_path = 1, model_weights_path = 2, input_layer_names = 3,
+    output_layer_names = 4 (what the Caffe and Facenet ops read), input_width = 5, input_height = 6, mean_colors = 7,
+    normalize = 11 (what the network-input ops read), preserve_aspect_ratio = 12, transpose = 13, pad_mod = 14."""
+    names = b"".join(message(3, str(n).encode()) for n in input_layer_names) + b"".join(message(4, str(n).encode()) for n in output_layer_names)
+    return (encode([(1, "string", str(model_path)), (2, "string", str(model_weights_path))]) + names +
+            encode([(5, "int32", input_width), (6, "int32", input_height)]) + repeated_float(7, mean_colors, packed) +
+            encode([(11, "bool", normalize), (12, "bool", preserve_aspect_ratio), (13, "bool", transpose), (14, "int32", pad_mod)]))
 
 
-def facenet_args(scale, mean_colors, templates_path="", threshold=0.0, packed=True):
-    """A serialised FacenetArgs (scannertools_caffe.proto:38-43): caffe_args = 1 (CaffeArgs{net_descriptor = 1}),
-    templates_path = 2, scale = 3, threshold = 4."""
-    nd = net_descriptor(mean_colors=mean_colors, packed=packed)
-    caffe_args = message(1, nd) if nd else b""
-    return ((message(1, caffe_args) if caffe_args else b"") +
+def caffe_args(batch_size=0, **descriptor):
+    """A serialised CaffeArgs (scannertools_caffe.proto:33-36): net_descriptor = 1 (net_descriptor()'s keywords), batch_size = 2."""
+    nd = net_descriptor(**descriptor)
+    return (message(1, nd) if nd else b"") + encode([(2, "int32", batch_size)])
+
+
+def facenet_args(scale, mean_colors, templates_path="", threshold=0.0, packed=True, batch_size=0, **descriptor):
+    """A serialised FacenetArgs (scannertools_caffe.proto:38-43): caffe_args = 1 (CaffeArgs{net_descriptor = 1, batch_size = 2}; the
+    descriptor takes net_descriptor()'s keywords), templates_path = 2, scale = 3, threshold = 4."""
+    ca = caffe_args(batch_size, mean_colors=mean_colors, packed=packed, **descriptor)
+    return ((message(1, ca) if ca else b"") +
             encode([(2, "string", templates_path), (3, "float", scale), (4, "float", threshold)]))
 
 

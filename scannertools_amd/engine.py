@@ -907,6 +907,29 @@ class _Ops:
         return _CppOpNode(self.sc, "CaffeInput", frame, device, batch, None,
                           _proto.caffe_input_args(input_width, input_height, mean_colors, normalize, packed=packed))
 
+    def Caffe(self, caffe_frame, model_path, model_weights_path, input_layer_names, output_layer_names, batch_size=0, device=None, batch=None,
+              input_width=0, input_height=0, preserve_aspect_ratio=False, transpose=False, pad_mod=0):
+        """sc.ops.Caffe(caffe_frame=..., args CaffeArgs{net_descriptor{model_path, model_weights_path, input_layer_names,
+        output_layer_names, ...}, batch_size}) -> the column caffe_output (caffe_kernel_cpu.cpp:5-8): per frame the output blob's
+        item as a (C, H or 1, W or 1) float32 frame.  caffe_frame: planar (C, H, W) float32 frames (CaffeInput's column).  The
+        frames of a call are run batch_size at a time (0: all at once); no frame's result depends on it."""
+        from . import _proto
+        args = _proto.caffe_args(batch_size, model_path=model_path, model_weights_path=model_weights_path, input_layer_names=input_layer_names,
+                                 output_layer_names=output_layer_names, input_width=input_width, input_height=input_height,
+                                 preserve_aspect_ratio=preserve_aspect_ratio, transpose=transpose, pad_mod=pad_mod)
+        return _CppOpNode(self.sc, "Caffe", caffe_frame, device, batch, None, args)
+
+    def Facenet(self, facenet_input, model_path, model_weights_path, input_layer_names, output_layer_names, scale=1.0, mean_colors=(),
+                templates_path="", threshold=0.0, batch_size=0, device=None, batch=None):
+        """sc.ops.Facenet(facenet_input=..., args FacenetArgs{caffe_args{net_descriptor{...}, batch_size}, scale, ...}) -> the
+        column facenet_output (facenet_kernel.cpp:37-40).  facenet_input: FacenetInput's (3, net_w, net_h) float32 frames; the
+        network runs on those W x H planes as they are."""
+        from . import _proto
+        args = _proto.facenet_args(scale, mean_colors, templates_path, threshold, batch_size=batch_size, model_path=model_path,
+                                   model_weights_path=model_weights_path, input_layer_names=input_layer_names,
+                                   output_layer_names=output_layer_names)
+        return _CppOpNode(self.sc, "Facenet", facenet_input, device, batch, None, args)
+
     def CPM2(self, cpm2_input, weights=None, seed=0, batch=8, max_peaks=64, nms_threshold=0.05, device=None, prototxt=None):
         """sc.ops.CPM2(cpm2_input=...) (cpm2_kernel.cpp:46-52): returns the columns (cpm2_resized_map, cpm2_joints).
         `weights`: path of the model's caffemodel -> the registered C++ kernel class (CPM2KernelHIP, the drop-in; args

@@ -620,6 +620,103 @@ class HipContext:
         return out
 
     # -- OpticalFlow ------------------------------------------------------------------------
+    # -- layers of a generic Caffe network (st_nn.hip); activations are NHWC float32 (n, h, w, channel stride) ----------
+    @staticmethod
+    def _vp(t):
+        return ctypes.c_void_p(t.data_ptr()) if t is not None else None
+
+    def _nhwc(self, x, name="x"):
+        _require_cuda(x, torch.float32, name, self.device)
+        if x.dim() != 4:
+            raise ValueError("%s must be (n, h, w, channels)" % name)
+        return x.shape
+
+    def _nhwc_out(self, out, n, oh, ow, c, y_offset):
+        if out is None:
+            return torch.zeros((n, oh, ow, (c + y_offset + 15) // 16 * 16), dtype=torch.float32, device=self.device)
+        _require_cuda(out, torch.float32, "out", self.device)
+        if out.dim() != 4 or tuple(out.shape[:3]) != (n, oh, ow):
+            raise ValueError("out must be (%d, %d, %d, channels), got %s" % (n, oh, ow, tuple(out.shape)))
+        return out
+
+    def inner_product_pack(self, w):
+        """The InnerProduct weights (nout, k) float32, k a multiple of 8, in the kernel's operand order (a uint8 tensor)."""
+        _require_cuda(w, torch.float32, "w", self.device)
+        nout, k = w.shape
+        nb = self._L.st_inner_product_packed_bytes(k, nout)
+        if nb <= 0:
+            raise ValueError("inner_product: k must be a positive multiple of 8, got (%d, %d)" % (nout, k))
+        packed = torch.empty((nb,), dtype=torch.uint8, device=self.device)
+        self._bind()
+        self._check(self._L.st_inner_product_pack_weights(self._h, self._vp(w), k, nout, self._vp(packed)))
+        return packed
+
+    def inner_product(self, x, packed, nout, bias=None, relu=False, out=None):
+        """y = x (n, k) . W^T (+ bias) (+ ReLU) with W packed by inner_product_pack; out: (n, >= nout), columns past nout untouched."""
+        _require_cuda(x, torch.float32, "x", self.device)
+        n, k = x.shape
+        if out is None:
+            out = torch.zeros((n, nout), dtype=torch.float32, device=self.device)
+        _require_cuda(out, torch.float32, "out", self.device)
+        self._bind()
+        self._check(self._L.st_inner_product_f32(self._h, self._vp(x), n, k, k, self._vp(packed), self._vp(bias), nout, int(relu),
+                                                 self._vp(out), out.shape[1]))
+        return out
+
+    def conv2d_general(self, x, cin, w, bias, stride=1, pad=0, group=1, relu=False, x_offset=0, out=None, y_offset=0):
+        """Convolution of any geometry; w: (cout, k, k, cin / group)."""
+        n, h, wd, xs = self._nhwc(x)
+        _require_cuda(w, torch.float32, "w", self.device)
+        cout, k = w.shape[0], w.shape[1]
+        oh, ow = self._L.st_conv_out_size(h, k, stride, pad), self._L.st_conv_out_size(wd, k, stride, pad)
+        out = self._nhwc_out(out, n, oh, ow, cout, y_offset)
+        self._bind()
+        self._check(self._L.st_conv2d_general_nhwc_f32(self._h, self._vp(x), n, h, wd, cin, xs, x_offset, self._vp(w), self._vp(bias), k, stride, pad,
+                                                       group, cout, int(relu), self._vp(out), out.shape[3], y_offset))
+        return out
+
+    def pool(self, x, c, method, kernel_size=0, stride=1, pad=0, global_pooling=False, x_offset=0, out=None, y_offset=0):
+        """Caffe's Pooling: method _native.POOL_MAX / POOL_AVE."""
+        n, h, wd, xs = self._nhwc(x)
+        oh = 1 if global_pooling else self._L.st_pool_out_size(h, kernel_size, stride, pad)
+        ow = 1 if global_pooling else self._L.st_pool_out_size(wd, kernel_size, stride, pad)
+        out = self._nhwc_out(out, n, oh, ow, c, y_offset)
+        self._bind()
+        self._check(self._L.st_pool_nhwc_f32(self._h, self._vp(x), n, h, wd, c, xs, x_offset, method, kernel_size, stride, pad, int(global_pooling),
+                                             self._vp(out), out.shape[3], y_offset))
+        return out
+
+    def lrn(self, x, c, local_size=5, alpha=1.0, beta=0.75, k=1.0, x_offset=0, out=None, y_offset=0):
+        n, h, wd, xs = self._nhwc(x)
+        out = self._nhwc_out(out, n, h, wd, c, y_offset)
+        self._bind()
+        self._check(self._L.st_lrn_nhwc_f32(self._h, self._vp(x), n * h * wd, c, xs, x_offset, local_size, alpha, beta, k, self._vp(out), out.shape[3],
+                                            y_offset))
+        return out
+
+    def softmax(self, x, c, x_offset=0, out=None, y_offset=0):
+        n, h, wd, xs = self._nhwc(x)
+        out = self._nhwc_out(out, n, h, wd, c, y_offset)
+        self._bind()
+        self._check(self._L.st_softmax_nhwc_f32(self._h, self._vp(x), n * h * wd, c, xs, x_offset, self._vp(out), out.shape[3], y_offset))
+        return out
+
+    def copy_channels(self, x, c, x_offset, out, y_offset, relu=False):
+        n, h, wd, xs = self._nhwc(x)
+        out = self._nhwc_out(out, n, h, wd, c, y_offset)
+        self._bind()
+        self._check(self._L.st_copy_channels_nhwc_f32(self._h, self._vp(x), n * h * wd, c, xs, x_offset, int(relu), self._vp(out), out.shape[3], y_offset))
+        return out
+
+    def nhwc_to_planar(self, x, c, x_offset=0):
+        """(n, h, w, stride) -> (n, c, h, w), every frame through its own pointer as the Caffe op writes its output frames."""
+        n, h, wd, xs = self._nhwc(x)
+        out = torch.empty((n, c, h, wd), dtype=torch.float32, device=self.device)
+        ptrs = (ctypes.c_void_p * n)(*[out[i].data_ptr() for i in range(n)])
+        self._bind()
+        self._check(self._L.st_nhwc_to_planar_f32(self._h, self._vp(x), n, h, wd, c, xs, x_offset, ptrs))
+        return out
+
     def optical_flow(self, frames, pairs=None, params=None, out=None):
         """Farneback flow for a batch of frame pairs.
 
