@@ -97,7 +97,7 @@ enum st_kernel_id {
   ST_K_CPM2_LIMBS = 12,
   ST_K_CONV = 13,       /* convolution / pooling launches of the pose network */
   ST_K_CPM2_RESIZE = 14,
-  ST_K_CPM2_NMS = 15,
+  ST_K_CPM2_NMS = 15,      /* the library's non-maximum suppressions: CPM2's peak search and the FacenetOutput launches (decode, sort + greedy NMS, pack) */
   ST_K_FRAME_STATS = 16, /* moments + finishing launches of the frame-statistics ops */
   ST_K_JPEG = 17,        /* inverse DCT + upsample / colour launches of the ImageDecoder op */
   ST_K_NET_INPUT = 18,   /* the FacenetInput and CaffeInput launches */
@@ -539,6 +539,48 @@ int st_caffe_input_axis(int n_in, int n_out, int* begin, int* first, int* count)
  * is ST_ERR_UNSUPPORTED here, before anything is launched or written (known deviation: the reference produces NaN). */
 int st_caffe_input_batch(st_ctx* ctx, const uint8_t* const* frames_dev, int n, int h, int w, int net_h, int net_w,
                          const float* mean_bgr, int normalize, float* const* out_dev);
+
+/* ---- FacenetOutput (scannertools_caffe): detector maps to NMS-filtered face boxes ------------------------
+ * Replaces the per-frame body of FacenetOutputKernel::execute (scannertools_caffe_cpp/facenet_output_kernel_cpu.cpp:72-163)
+ * for a whole batch.  maps_dev: n device pointers (4-byte aligned) to the Facenet op's float32 maps of 125 * G values,
+ * G = grid_w * grid_h, grid = ceil(net / 8) of st_facenet_geometry(h, w, scale): 25 * G confidences conf[t][xi][yi], then
+ * 100 * G adjustments adj[k][t][xi][yi] (k = dcx, dcy, dcw, dch).  templates: the 25 x 4 floats of the templates file.
+ * Candidates are numbered t over the valid templates ({4..11, 18..24}; {4..11} when scale > 1), then xi, then yi.  Per
+ * candidate, every operation an IEEE float32 operation rounded on its own unless said otherwise:
+ *   e = float32(exp(float64(-c))); score = float32(1.0 / (1.0 + float64(e))); dropped when float64(score) < float64(threshold);
+ *   x = float(8 xi - 1), y = float(8 yi - 1); tw = (T[t][2] - T[t][0]) + 1, th = (T[t][3] - T[t][1]) + 1;
+ *   x += tw * dcx; y += th * dcy; bw = tw * float32(exp(float64(dcw))); bh = th * float32(exp(float64(dch)));
+ *   each of x, y, bw, bh: (v / float(net_dim)) * float(frame_dim); dropped on bw < 0, bh < 0 or a NaN among the four;
+ *   x1 = (x - bw / 2) / w, y1 = (y - bh / 2) / h, x2 = (x + bw / 2) / w, y2 = (y + bh / 2) / h.  Nothing is clamped.
+ * The survivors of a frame then go through the greedy suppression of st_bbox_nms_f32 with `overlap` and `offset`.
+ * counts_host[i]: the boxes frame i keeps.  The rows [x1, y1, x2, y2, score] of all frames, frame after frame, each frame's
+ * in kept order (descending score), stay in a buffer of the context until its next st_facenet_output_batch call;
+ * st_facenet_output_fetch copies them.  One device-to-host copy here (the counts), one in the fetch, whatever n is; the
+ * call returns with the stream synchronised.  n = 0 is a successful no-op.  ST_ERR_INVALID: n < 0, a null argument or
+ * row, a geometry st_facenet_geometry refuses, a threshold, overlap or offset that is not finite.  Exponentials are
+ * evaluated in float64 on the device and rounded: the correctly rounded float32 value except where the float64 result lies
+ * within its own error of a rounding boundary (known deviation from the reference's expf: DESIGN.md section 4.15). */
+int st_facenet_output_batch(st_ctx* ctx, const float* const* maps_dev, int n, int h, int w, float scale, const float* templates,
+                            float threshold, float overlap, float offset, int32_t* counts_host);
+/* The rows of the context's last st_facenet_output_batch call: rows_host receives 5 floats per kept box; capacity_rows
+ * must be at least the sum of that call's counts (ST_ERR_INVALID otherwise, nothing copied). */
+int st_facenet_output_fetch(st_ctx* ctx, float* rows_host, int64_t capacity_rows);
+
+/* Greedy non-maximum suppression (Scanner's best_nms, [EXT] restated: DESIGN.md section 4.15) of n independent sets of
+ * boxes.  rows_dev: device float32 rows [x1, y1, x2, y2, score], set after set; counts_host[i]: the rows of set i.
+ * Boxes are visited by descending score (as unsigned bit patterns, so a NaN score goes first), equal scores by ascending
+ * row index.  A visited box that is still valid is kept; it then invalidates every still-valid box i, itself included,
+ * unless ov(i) < overlap, with
+ *   ov(i) = max(0, (min(x2c, x2i) - max(x1c, x1i)) + o) * max(0, (min(y2c, y2i) - max(y1c, y1i)) + o)
+ *           / (((x2i - x1i) + o) * ((y2i - y1i) + o))
+ * in float32, min(a, b) = b < a ? b : a and max(a, b) = a < b ? b : a (std::min / std::max: a NaN in b is ignored, in a
+ * kept), 0 / 0 = NaN is not below any overlap.  kept_dev: device int32, one slot per input row; the first
+ * kept_counts_host[i] slots of set i's range receive the kept boxes' row indices within the set, in kept order.  One
+ * workgroup per set sorts in LDS up to 6144 boxes and in global scratch beyond; the result does not depend on the path.
+ * The call returns with the stream synchronised (one device-to-host copy).  ST_ERR_INVALID: n < 0, a null argument, a
+ * negative count, an overlap or offset that is not finite; ST_ERR_UNSUPPORTED: more than 2^31 - 1 rows in all. */
+int st_bbox_nms_f32(st_ctx* ctx, const float* rows_dev, const int32_t* counts_host, int n, float overlap, float offset,
+                    int32_t* kept_dev, int32_t* kept_counts_host);
 
 /* ---- Generic Caffe networks (scannertools_caffe: the Caffe and Facenet ops) ---------------------------
  * The layers of a Caffe forward pass (scannertools_caffe_cpp/caffe_kernel.cpp:382) beyond the stride-1 "same" convolutions

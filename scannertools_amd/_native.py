@@ -167,6 +167,10 @@ SIGNATURES = {
     "st_cpm2_nms": (_i, [_vp, _c.POINTER(_vp), _i, _i, _i, _i, _i, _c.c_float, _c.POINTER(_vp)]),
     "st_facenet_geometry": (_i, [_i, _i, _c.c_float, _c.POINTER(_i), _c.POINTER(_i)]),
     "st_facenet_input_batch": (_i, [_vp, _c.POINTER(_vp), _i, _i, _i, _c.c_float, _c.POINTER(_c.c_float), _c.POINTER(_vp)]),
+    "st_facenet_output_batch": (_i, [_vp, _c.POINTER(_vp), _i, _i, _i, _c.c_float, _c.POINTER(_c.c_float), _c.c_float, _c.c_float, _c.c_float,
+                                     _c.POINTER(_c.c_int32)]),
+    "st_facenet_output_fetch": (_i, [_vp, _vp, _c.c_int64]),
+    "st_bbox_nms_f32": (_i, [_vp, _vp, _c.POINTER(_c.c_int32), _i, _c.c_float, _c.c_float, _vp, _c.POINTER(_c.c_int32)]),
     "st_caffe_input_axis": (_i, [_i, _i, _c.POINTER(_i), _c.POINTER(_i), _c.POINTER(_i)]),
     "st_caffe_input_batch": (_i, [_vp, _c.POINTER(_vp), _i, _i, _i, _i, _i, _c.POINTER(_c.c_float), _i, _c.POINTER(_vp)]),
     "st_inner_product_packed_bytes": (ctypes.c_longlong, [_i, _i]),
@@ -200,7 +204,7 @@ def source_hash():
     st_build_info() of a library built from THIS tree reports."""
     import hashlib
     srcs = ["st_context.hip", "st_hist.hip", "st_farneback.hip", "st_flowvis.hip", "st_imgproc.hip", "st_pose.hip", "st_conv.hip",
-            "st_conv_tile_bf16x3.hip", "st_conv_tile_f32.hip", "st_framestats.hip", "st_jpeg.hip", "st_netinput.hip", "st_nn.hip", "st_jpeg_parse.cpp", "st_internal.h",
+            "st_conv_tile_bf16x3.hip", "st_conv_tile_f32.hip", "st_framestats.hip", "st_jpeg.hip", "st_netinput.hip", "st_nn.hip", "st_detect.hip", "st_jpeg_parse.cpp", "st_internal.h",
             "st_conv_tile.h", "st_jpeg_parse.h",
             os.path.join("..", "..", "include", "scannertools_hip.h"), "Makefile"]
     hsh = hashlib.sha256()

@@ -54,9 +54,11 @@ struct st_ctx {
   int num_cus = 256;
   struct st_jpeg_state* jpeg = nullptr;   // page-locked slots of st_jpeg_decode_batch (st_jpeg.hip), made at its first call
   struct st_netin_state* netin = nullptr; // per-geometry tables of the FacenetInput / CaffeInput entry points (st_netinput.hip)
+  struct st_detect_state* detect = nullptr; // the kept rows of the last st_facenet_output_batch call (st_detect.hip)
 };
 void st_jpeg_release(st_ctx* ctx);   // frees ctx->jpeg (st_ctx_destroy)
 void st_netin_release(st_ctx* ctx);  // frees ctx->netin (st_ctx_destroy)
+void st_detect_release(st_ctx* ctx); // frees ctx->detect (st_ctx_destroy)
 
 int st_set_error(st_ctx* ctx, int status, const char* fmt, ...);
 

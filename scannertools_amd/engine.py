@@ -510,7 +510,7 @@ class _PoseNetColumn(_Node):
 
 
 class _CppMultiOpNode(_Node):
-    """A C++ op with several input columns (frames and/or bytes), no stencil: CPM2Output."""
+    """A C++ op with several input columns (frames and/or bytes), no stencil: CPM2Output, FacenetOutput."""
 
     def __init__(self, client, name, parents, device, batch, args):
         self.client, self.name, self.parents = client, name, parents
@@ -929,6 +929,17 @@ class _Ops:
                                    model_weights_path=model_weights_path, input_layer_names=input_layer_names,
                                    output_layer_names=output_layer_names)
         return _CppOpNode(self.sc, "Facenet", facenet_input, device, batch, None, args)
+
+    def FacenetOutput(self, facenet_output, original_frame_info, scale, threshold, templates_path, mean_colors=(), device=None, batch=None):
+        """sc.ops.FacenetOutput(facenet_output=..., original_frame_info=..., args FacenetArgs{templates_path, scale, threshold})
+        -> the column bboxes (facenet_output_kernel_cpu.cpp:186-190): per frame the NMS-filtered face boxes, normalised
+        coordinates and score, descending score; rows read with scannertools_amd.types.scored_bboxes.  facenet_output: the
+        Facenet op's (125, grid_w, grid_h) float32 maps; original_frame_info: sc.ops.InfoFromFrame of the decoded frames."""
+        from . import _proto
+        node = _CppMultiOpNode(self.sc, "FacenetOutput", [facenet_output, original_frame_info], device, batch,
+                               _proto.facenet_args(scale, mean_colors, templates_path, threshold))
+        node.reader = _types.scored_bboxes
+        return node
 
     def CPM2(self, cpm2_input, weights=None, seed=0, batch=8, max_peaks=64, nms_threshold=0.05, device=None, prototxt=None):
         """sc.ops.CPM2(cpm2_input=...) (cpm2_kernel.cpp:46-52): returns the columns (cpm2_resized_map, cpm2_joints).

@@ -534,6 +534,56 @@ class HipContext:
         self._check(self._L.st_caffe_input_batch(self._h, tf, n, h, w, nh, nw, (ctypes.c_float * 3)(*mean), int(bool(normalize)), to))
         return out
 
+    # -- FacenetOutput (scannertools_caffe) -----------------------------------------------------
+    def facenet_output(self, maps, h, w, scale, templates, threshold, overlap=0.1, offset=0.0):
+        """FacenetOutput (scannertools_caffe_cpp/facenet_output_kernel_cpu.cpp:72-163; st_facenet_output_batch): the Facenet
+        op's maps of frames of (h, w) at ``scale`` -> per frame a float32 numpy array (kept, 5) of rows
+        [x1, y1, x2, y2, score], normalised coordinates, descending score.  maps: a CUDA float32 tensor (n, 125, grid_w,
+        grid_h) or a list of contiguous tensors of 125 * grid_w * grid_h values each; templates: the 25 x 4 floats of the
+        templates file; overlap / offset: best_nms's threshold and the formula's pixel offset (the op passes 0.1 and 0)."""
+        self._bind()
+        fr = list(maps) if isinstance(maps, (list, tuple)) else list(maps.unbind(0))
+        tpl = np.ascontiguousarray(np.asarray(templates, dtype=np.float32).reshape(-1))
+        if tpl.size != 100:
+            raise ValueError("templates must hold 25 x 4 values, got %d" % tpl.size)
+        nh, nw = facenet_geometry(h, w, scale)
+        cells = 125 * ((nw + 7) // 8) * ((nh + 7) // 8)
+        for f in fr:
+            _require_cuda(f, torch.float32, "map", self.device)
+            if f.numel() != cells:
+                raise ValueError("a map of a %dx%d frame at scale %g holds 125 x %d x %d values, got %d"
+                                 % (w, h, scale, (nw + 7) // 8, (nh + 7) // 8, f.numel()))
+        n = len(fr)
+        counts = (ctypes.c_int32 * max(n, 1))()
+        tm = (ctypes.c_void_p * max(n, 1))(*[f.data_ptr() for f in fr])
+        self._check(self._L.st_facenet_output_batch(self._h, tm, n, int(h), int(w), float(scale), tpl.ctypes.data_as(ctypes.POINTER(ctypes.c_float)),
+                                                    float(threshold), float(overlap), float(offset), counts))
+        counts = [int(c) for c in counts[:n]]
+        rows = np.empty((sum(counts), 5), np.float32)
+        self._check(self._L.st_facenet_output_fetch(self._h, rows.ctypes.data_as(ctypes.c_void_p), rows.shape[0]))
+        return np.split(rows, np.cumsum(counts)[:-1]) if n else []
+
+    def bbox_nms(self, rows, counts=None, overlap=0.1, offset=0.0):
+        """Greedy non-maximum suppression (st_bbox_nms_f32) of sets of boxes.  rows: CUDA float32
+        (total, 5) [x1, y1, x2, y2, score], set after set; counts: the rows of each set (None: one set).  Returns per set
+        the int32 numpy array of the kept boxes' row indices within the set, in kept order (descending score, equal scores
+        by ascending index)."""
+        self._bind()
+        _require_cuda(rows, torch.float32, "rows", self.device)
+        if rows.dim() != 2 or rows.shape[1] != 5:
+            raise ValueError("rows must be (total, 5)")
+        counts = [int(rows.shape[0])] if counts is None else [int(c) for c in counts]
+        if any(c < 0 for c in counts) or sum(counts) != rows.shape[0]:
+            raise ValueError("counts %s do not add up to the %d rows" % (counts, rows.shape[0]))
+        n = len(counts)
+        kept = torch.empty((max(int(rows.shape[0]), 1),), dtype=torch.int32, device=self.device)
+        kc = (ctypes.c_int32 * max(n, 1))()
+        self._check(self._L.st_bbox_nms_f32(self._h, ctypes.c_void_p(rows.data_ptr()), (ctypes.c_int32 * max(n, 1))(*counts), n, float(overlap),
+                                            float(offset), ctypes.c_void_p(kept.data_ptr()), kc))
+        kept = kept.cpu().numpy()
+        first = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+        return [kept[first[i]:first[i] + kc[i]].copy() for i in range(n)]
+
     def cpm2_limb_scores(self, heatmaps, peaks, inter_threshold=0.05, min_above=9):
         """Candidate-pair scores of CPM2Output (cpm2_output_kernel_cpu.cpp:424-487): heatmaps
         (n,57,H,W) float32, peaks (n,18,max_peaks+1,3) float32 -> (n,19,max_peaks,max_peaks) float32."""

@@ -147,6 +147,42 @@ def bboxes(buf, protobufs=None):
     return out
 
 
+# ---- FacenetOutput elements: boxes with a score --------------------------------------------------------------------------
+BBOX_SCORE_FIELD = 5   # BoundingBox.score, stated from knowledge of scanner/types.proto like BBOX_FIELDS, not checked against it
+
+
+def write_scored_bboxes(rows):
+    """One ``bboxes`` element of the FacenetOutput op from rows [x1, y1, x2, y2, score] (any (m, 5) array-like): write_bboxes'
+    format with the score as float field 5; like a coordinate, a score that is 0 is left out."""
+    from . import _proto
+    rows = np.asarray(rows, dtype=np.float32).reshape(-1, 5)
+    return write_bboxes([bbox_message(r[:4], _proto.encode([(BBOX_SCORE_FIELD, "float", float(r[4]))])) for r in rows])
+
+
+def scored_bboxes(buf, protobufs=None):
+    """Reader of a FacenetOutput ``bboxes`` element: float32 (m, 5) rows [x1, y1, x2, y2, score], absent fields 0, in the
+    element's order (descending score).  ValueError as for ``bboxes``, and on a score field that is not a float."""
+    import struct
+    if buf is None:
+        return None
+    buf = bytes(buf)
+    boxes = bboxes(buf)                      # every structural check, and the coordinates
+    from . import _proto
+    out = np.zeros((len(boxes), 5), np.float32)
+    off = 8
+    for i, b in enumerate(boxes):
+        (ln,) = struct.unpack_from("<Q", buf, off)
+        off += 8
+        out[i, :4] = b
+        for number, wt, v in _proto.fields(buf[off:off + ln]):
+            if number == BBOX_SCORE_FIELD:
+                if wt != 5:
+                    raise ValueError("box %d: score field is not a float" % i)
+                out[i, 4] = np.frombuffer(struct.pack("<I", v), np.float32)[0]
+        off += ln
+    return out
+
+
 def truncate_bboxes(boxes, h, w, where=""):
     """(int)coordinate per box as the reference truncates it (toward zero; imgproc.cpp:205-208, old/imgproc.py:47-50):
     int32 (m, 4) rows x1, y1, x2, y2.  ValueError, naming the box, for a coordinate that is not finite or does not fit an
