@@ -15,23 +15,14 @@ import os
 
 import numpy as np
 
-from . import _proto
+from . import caffe_files
 
 
 def write_caffemodel(path, weights, types=None):
-    """Writes {layer name: [blob, ...]} (float32 arrays of the blobs' Caffe shapes) as a serialised NetParameter:
-    NetParameter{name = 1, layer = 100 {name = 1, type = 2, blobs = 7 {shape = 7 {dim = 1}, data = 5}}} ([EXT] caffe.proto).
-    types: {layer name: type string}, "Convolution" where absent.  pose_net.read_caffemodel reads it back."""
-    def blob(arr):
-        arr = np.ascontiguousarray(arr, dtype="<f4")
-        return _proto.message(7, _proto.message(1, b"".join(_proto._varint(d) for d in arr.shape))) + _proto.message(5, arr.tobytes())
-
-    with open(path, "wb") as fh:
-        fh.write(_proto.message(1, b"net"))
-        for name, blobs in weights.items():
-            typ = (types or {}).get(name, "Convolution")
-            fh.write(_proto.message(100, _proto.message(1, name.encode()) + _proto.message(2, typ.encode()) +
-                                    b"".join(_proto.message(7, blob(b)) for b in blobs)))
+    """Writes {layer name: [blob, ...]} (float32 arrays of the blobs' Caffe shapes) as a serialised NetParameter
+    (caffe_files.write_caffemodel).  types: {layer name: type string}, "Convolution" where absent.
+    caffe_files.read_caffemodel reads it back."""
+    caffe_files.write_caffemodel(path, [(name, (types or {}).get(name, "Convolution"), blobs) for name, blobs in weights.items()])
 
 
 def _text(fields, indent):

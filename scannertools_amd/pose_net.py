@@ -22,7 +22,8 @@ import ctypes
 
 import numpy as np
 
-from . import _native
+from . import _native, caffe_files
+from .caffe_files import parse_prototxt, read_caffemodel  # noqa: F401  (the names this module has always had)
 
 # (name, cin, cout, kernel, relu); "pool" = 2x2 max pooling
 TRUNK = [("conv1_1", 3, 64, 3, 1), ("conv1_2", 64, 64, 3, 1), "pool",
@@ -81,52 +82,15 @@ def caffe_layer_names():
 
 
 # ---- prototxt (the network DESCRIPTION the reference hands Caffe next to the weights: cpm2_kernel.cpp:8-52 through
-# CaffeArgs.net_descriptor.model_path; OpenPose reads <model_directory>/pose/coco/pose_deploy_linevec.prototxt) -------------
-def parse_prototxt(text):
-    """Protobuf text format -> nested {field: [values]} (every field a list: repeated fields are the rule in a NetParameter)."""
-    import re
-    tok = re.findall(r'#[^\n]*|"(?:[^"\\]|\\.)*"|\'(?:[^\'\\]|\\.)*\'|[{}:]|[^\s{}:#"\']+', text)
-    tok = [t for t in tok if not t.startswith("#")]
-    pos = 0
-
-    def message(closing):
-        nonlocal pos
-        out = {}
-        while pos < len(tok):
-            t = tok[pos]
-            if t == "}":
-                if not closing:
-                    raise ValueError("prototxt: unbalanced '}'")
-                pos += 1
-                return out
-            name = t
-            pos += 1
-            if pos < len(tok) and tok[pos] == ":":
-                pos += 1
-            if pos >= len(tok):
-                raise ValueError("prototxt: field %r has no value" % name)
-            if tok[pos] == "{":
-                pos += 1
-                val = message(True)
-            else:
-                val = tok[pos]
-                pos += 1
-                if val[0] in "\"'":
-                    val = val[1:-1]
-            out.setdefault(name, []).append(val)
-        if closing:
-            raise ValueError("prototxt: missing '}'")
-        return out
-
-    return message(False)
-
-
-def layers_from_prototxt(path):
+# CaffeArgs.net_descriptor.model_path; OpenPose reads <model_directory>/pose/coco/pose_deploy_linevec.prototxt); the text
+# format itself is caffe_files.parse_prototxt's ----------------------------------------------------------------------------
+def layers_from_prototxt(path, net=None):
     """The convolutions a deploy prototxt describes, in file order, with the input channel count of each inferred by
     walking the blobs (input_dim / input_shape, Convolution, Pooling, ReLU, Concat; the fork's trailing `resize` / `nms`
     layers and anything after them are ignored): [(name, cin, cout, kernel, relu, bottom blob, top blob)], plus the names
-    of the pooling layers' bottoms (where the trunk pools)."""
-    net = parse_prototxt(open(path).read())
+    of the pooling layers' bottoms (where the trunk pools).  net: the file's tree when the caller has parsed it already."""
+    if net is None:
+        net = parse_prototxt(open(path).read())
     chans = {}
     if "input" in net:
         dims = [int(d) for d in net.get("input_dim", [])]
@@ -179,13 +143,13 @@ def names_from_prototxt(path):
     the blob two convolutions read; a stage = the two chains behind that blob, told apart by their output counts (38 = L1,
     19 = L2); next stage input = the Concat of (L1, L2, features), in that order (the order the weights are packed for).
     Raises ValueError naming the first difference."""
-    convs, pools = layers_from_prototxt(path)
+    net = parse_prototxt(open(path).read())
+    convs, pools = layers_from_prototxt(path, net)
     arch = all_layers()
     if len(convs) != len(arch):
         raise ValueError("prototxt %s describes %d convolutions, the kernels implement %d" % (path, len(convs), len(arch)))
     if len(pools) != 3:
         raise ValueError("prototxt %s has %d pooling layers, the kernels implement 3" % (path, len(pools)))
-    net = parse_prototxt(open(path).read())
     readers, pool_of, concats, alias = {}, {}, [], {}
     layers = net.get("layer", []) + net.get("layers", [])
     def io(layer, key):
@@ -332,88 +296,24 @@ def write_prototxt(path, names=None, interleaved=False):
         fh.write("\n".join(out) + "\n")
 
 
-def read_caffemodel(path):
-    """Weights of a Caffe model file: {layer name: [blob, ...]} with every blob a float32 array of its stored
-    shape.  Reads the NetParameter wire format directly (caffe.proto, [EXT]: NetParameter.layer = 100 and the V1
-    `layers` = 2; LayerParameter.name = 1, .blobs = 7 (V1: name = 4, blobs = 6); BlobProto.data = 5 packed float,
-    .shape = 7 {dim = 1}, legacy num/channels/height/width = 1..4)."""
-    from . import _proto
-    with open(path, "rb") as fh:
-        buf = fh.read()
-    out = {}
-
-    def blob(mv):
-        data, dims, legacy = None, [], {}
-        for num, wt, v in _proto.fields(mv):
-            if num == 5 and wt == 2:
-                data = np.frombuffer(v, dtype="<f4")
-            elif num == 5 and wt == 5:   # unpacked repeated float
-                data = np.append(data if data is not None else np.zeros(0, "<f4"), np.frombuffer(v.to_bytes(4, "little"), "<f4"))
-            elif num == 7 and wt == 2:
-                for n2, w2, v2 in _proto.fields(v):
-                    if n2 == 1 and w2 == 2:   # packed int64 dims
-                        dims += _varints(v2)
-                    elif n2 == 1 and w2 == 0:
-                        dims.append(v2)
-            elif num in (1, 2, 3, 4) and wt == 0:
-                legacy[num] = v
-        if data is None:
-            data = np.zeros(0, "<f4")
-        if not dims and legacy:
-            dims = [legacy.get(k, 1) for k in (1, 2, 3, 4)]
-        return np.array(data, dtype=np.float32).reshape(dims) if dims and int(np.prod(dims)) == data.size else np.array(data, dtype=np.float32)
-
-    def _varints(mv):
-        vals, v, shift = [], 0, 0
-        for b in bytes(mv):
-            v |= (b & 0x7F) << shift
-            shift += 7
-            if not b & 0x80:
-                vals.append(v)
-                v, shift = 0, 0
-        return vals
-
-    for num, wt, v in _proto.fields(buf):
-        if wt != 2 or num not in (100, 2):
-            continue
-        name_field, blob_field = (1, 7) if num == 100 else (4, 6)
-        name, blobs = None, []
-        for n2, w2, v2 in _proto.fields(v):
-            if n2 == name_field and w2 == 2:
-                name = bytes(v2).decode()
-            elif n2 == blob_field and w2 == 2:
-                blobs.append(blob(v2))
-        if name is not None and blobs:
-            out[name] = blobs
-    return out
-
-
 def write_caffemodel(path, weights, names=None, order=None, extra_layers=()):
     """Writes {architecture layer name: (weight (cout, cin, k, k), bias)} (PoseNet.weights) as a caffemodel file with the
-    published layer names: NetParameter{name, layer{name, type, blobs{shape, data}}}.  Used by tests and the benchmark
-    to hand the kernel classes a model file when only random weights exist.  names: other layer names (all_layers() order);
-    order: a permutation of range(92), the order the layers are written in (readers find layers by NAME, a trained file
-    also holds its layers in whatever order the training graph had); extra_layers: names of blob-less layers (ReLU,
-    Pooling, Concat ...) interleaved as a real file has them."""
-    from . import _proto
+    published layer names (caffe_files.write_caffemodel).  Used by tests and the benchmark to hand the kernel classes a model
+    file when only random weights exist.  names: other layer names (all_layers() order); order: a permutation of range(92),
+    the order the layers are written in (readers find layers by NAME, a trained file also holds its layers in whatever
+    order the training graph had); extra_layers: names of blob-less layers (ReLU, Pooling, Concat ...) interleaved as a
+    real file has them."""
+    entries = list(zip(all_layers(), names or caffe_layer_names()))
+    extra = list(extra_layers)
 
-    def blob(arr):
-        arr = np.ascontiguousarray(arr, dtype="<f4")
-        return _proto.message(7, _proto.message(1, b"".join(_proto._varint(d) for d in arr.shape))) + _proto.message(5, arr.tobytes())
-
-    with open(path, "wb") as fh:
-        fh.write(_proto.message(1, b"pose"))
-        entries = list(zip(all_layers(), names or caffe_layer_names()))
-        extra = list(extra_layers)
+    def layers():
         for i in (order if order is not None else range(len(entries))):
             (name, *_), cname = entries[i]
-            wt, b = weights[name]
-            wt = wt.numpy() if hasattr(wt, "numpy") else wt
-            b = b.numpy() if hasattr(b, "numpy") else b
-            fh.write(_proto.message(100, _proto.message(1, cname.encode()) + _proto.message(2, b"Convolution") +
-                                    _proto.message(7, blob(wt)) + _proto.message(7, blob(b))))
+            yield cname, "Convolution", [b.numpy() if hasattr(b, "numpy") else b for b in weights[name]]
             if extra:
-                fh.write(_proto.message(100, _proto.message(1, extra.pop(0).encode()) + _proto.message(2, b"ReLU")))
+                yield extra.pop(0), "ReLU", []
+
+    caffe_files.write_caffemodel(path, layers(), name="pose")
 
 
 def check_caffemodel(path):

@@ -16,36 +16,16 @@
 #include "scanner/api/op.h"
 #include "scanner/util/hip.h"
 #include "scanner/util/memory.h"
-#include "proto_lite.h"
+#include "caffe_args.h"
 #include "scannertools_hip.h"
 #include "kernel_core.h"
 
 namespace scanner {
-namespace {
-struct CaffeInputArgsLite {
-  i32 input_width = 0, input_height = 0;
-  std::vector<f32> mean_colors;
-  bool normalize = false;
-};
-// CaffeInputArgs.net_descriptor (1) . {input_width 5, input_height 6, mean_colors 7, normalize 11}
-bool parse_caffe_input_args(const std::vector<u8>& args, CaffeInputArgsLite* out) {
-  std::vector<proto_lite::Field> fields, net;
-  if (!proto_lite::parse(args.data(), args.size(), &fields) || !proto_lite::nested(fields, 1, &net)) return false;
-  for (auto& f : net) {
-    if (f.wire != 0) continue;
-    if (f.number == 5) out->input_width = (i32)f.value;   // a negative int32 travels as a 64-bit varint
-    if (f.number == 6) out->input_height = (i32)f.value;
-    if (f.number == 11) out->normalize = f.value != 0;
-  }
-  return proto_lite::repeated_floats(net, 7, &out->mean_colors);
-}
-}  // namespace
-
 template <bool STAGED>
 class CaffeInputKernelHIPImpl : public BatchedKernel, public VideoKernel {
  public:
   CaffeInputKernelHIPImpl(const KernelConfig& config) : BatchedKernel(config), core_(config, STAGED), stage_(core_.gpu) {
-    if (!parse_caffe_input_args(config.args, &args_)) {
+    if (!parse_caffe_args(config.args.data(), config.args.size(), &args_)) {   // CaffeInputArgs has CaffeArgs' fields
       RESULT_ERROR(&core_.valid, "Could not parse CaffeInputArgs");
     } else if (args_.mean_colors.size() != 3) {
       RESULT_ERROR(&core_.valid, "CaffeInput: net_descriptor.mean_colors must hold 3 values, got %d", (int)args_.mean_colors.size());
@@ -110,7 +90,7 @@ class CaffeInputKernelHIPImpl : public BatchedKernel, public VideoKernel {
  private:
   KernelCore core_;
   DeviceStage stage_;
-  CaffeInputArgsLite args_;
+  CaffeArgsLite args_;
   int net_input_width_ = 0, net_input_height_ = 0;
   std::vector<const uint8_t*> src_;
   std::vector<float*> dst_;

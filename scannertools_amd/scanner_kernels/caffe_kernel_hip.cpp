@@ -16,12 +16,12 @@ extern "C" __attribute__((visibility("default"))) int scannertools_caffe_plan_ne
   int steps = -1;
   try {
     namespace cn = scanner::caffe_net;
-    std::map<std::string, cn::Weights> weights;
+    scanner::caffe_files::Blobs weights;
     std::vector<cn::Layer> layers;
     cn::Plan plan;
     if (!prototxt || !output_blob) {
       msg = "null argument";
-    } else if ((!caffemodel || cn::read_caffemodel(caffemodel, &weights, &msg)) && cn::parse_layers(prototxt, &layers, &msg)) {
+    } else if ((!caffemodel || scanner::caffe_files::read_caffemodel(caffemodel, &weights, &msg)) && cn::parse_layers(prototxt, &layers, &msg)) {
       std::string input;
       for (auto& l : layers)
         if (input.empty() && l.kind == cn::kInput && l.num_output != -1 && !l.tops.empty()) input = l.tops[0];

@@ -7,10 +7,10 @@
 // Same arguments: CaffeArgs{net_descriptor = 1, batch_size = 2}; of NetDescriptor (scannertools_caffe.proto:5-26) model_path (1),
 // model_weights_path (2), input_layer_names (3), output_layer_names (4), input_width / input_height (5 / 6),
 // preserve_aspect_ratio (12), transpose (13), pad_mod (14) are used; uses_python (15) is refused.  Facenet takes FacenetArgs and
-// unwraps caffe_args (1).  The reference hands both files to Caffe; here the forward pass is caffe_net.h (a plan over the C-ABI
-// layer calls).  Input frames are planar (C, H, W) float32 (CaffeInput's and FacenetInput's output), taken batch_size at a time
-// (caffe_kernel.cpp:355-361; 0: the whole call); the output is one FrameInfo(shape[1], shape[2] or 1, shape[3] or 1, F32) frame
-// per input frame, the output blob's item as Caffe lays it out (:397-400).
+// unwraps caffe_args (1); both are read by caffe_args.h.  The reference hands both files to Caffe; here the forward pass is
+// caffe_net.h (a plan over the C-ABI layer calls).  Input frames are planar (C, H, W) float32 (CaffeInput's and FacenetInput's
+// output), taken batch_size at a time (caffe_kernel.cpp:355-361; 0: the whole call); the output is one FrameInfo(shape[1],
+// shape[2] or 1, shape[3] or 1, F32) frame per input frame, the output blob's item as Caffe lays it out (:397-400).
 // The input blob's size follows CaffeKernel::new_frame_info() (:284-333) with two readings of proto3's defaults: input_width 0
 // and pad_mod 0 mean "not set", as -1 does (the reference compares with -1 only and would then size the blob 0 x 0 or divide by
 // zero).  The frames are copied into the blob as they are (:372-376), so the blob must hold exactly a frame's values: anything
@@ -21,60 +21,21 @@
 #include "scanner/api/op.h"
 #include "scanner/util/hip.h"
 #include "scanner/util/memory.h"
+#include "caffe_args.h"
 #include "caffe_net.h"
-#include "proto_lite.h"
 #include "scannertools_hip.h"
 #include "kernel_core.h"
 
 namespace scanner {
-
-struct CaffeArgsLite {
-  std::string model_path, model_weights_path;
-  std::vector<std::string> input_layer_names, output_layer_names;
-  i32 input_width = 0, input_height = 0, pad_mod = 0, batch_size = 0;
-  bool preserve_aspect_ratio = false, transpose = false, uses_python = false;
-};
-
-// CaffeArgs{net_descriptor (1){...}, batch_size (2)}
-inline bool parse_caffe_args(const uint8_t* data, size_t size, CaffeArgsLite* out) {
-  std::vector<proto_lite::Field> fields, net;
-  if (!proto_lite::parse(data, size, &fields) || !proto_lite::nested(fields, 1, &net)) return false;
-  for (auto& f : fields)
-    if (f.number == 2 && f.wire == 0) out->batch_size = (i32)f.value;
-  for (auto& f : net) {
-    if (f.wire == 2) {
-      if (f.number == 1) out->model_path = f.bytes;
-      if (f.number == 2) out->model_weights_path = f.bytes;
-      if (f.number == 3) out->input_layer_names.push_back(f.bytes);
-      if (f.number == 4) out->output_layer_names.push_back(f.bytes);
-    } else if (f.wire == 0) {
-      if (f.number == 5) out->input_width = (i32)f.value;   // a negative int32 travels as a 64-bit varint
-      if (f.number == 6) out->input_height = (i32)f.value;
-      if (f.number == 12) out->preserve_aspect_ratio = f.value != 0;
-      if (f.number == 13) out->transpose = f.value != 0;
-      if (f.number == 14) out->pad_mod = (i32)f.value;
-      if (f.number == 15) out->uses_python = f.value != 0;
-    }
-  }
-  return true;
-}
-
-// FacenetArgs{caffe_args (1)} -> the CaffeArgs inside (facenet_kernel.cpp:21-31)
-inline bool parse_facenet_args(const uint8_t* data, size_t size, CaffeArgsLite* out) {
-  std::vector<proto_lite::Field> fields;
-  if (!proto_lite::parse(data, size, &fields)) return false;
-  const proto_lite::Field* last = nullptr;
-  for (auto& f : fields)
-    if (f.number == 1 && f.wire == 2) last = &f;
-  return last ? parse_caffe_args((const uint8_t*)last->bytes.data(), last->bytes.size(), out) : parse_caffe_args(nullptr, 0, out);
-}
 
 template <bool STAGED, bool FACENET>
 class CaffeKernelHIPImpl : public BatchedKernel, public VideoKernel {
  public:
   CaffeKernelHIPImpl(const KernelConfig& config) : BatchedKernel(config), core_(config, STAGED), stage_(core_.gpu) {
     const char* op = FACENET ? "Facenet" : "Caffe";
-    const bool parsed = FACENET ? parse_facenet_args(config.args.data(), config.args.size(), &args_) : parse_caffe_args(config.args.data(), config.args.size(), &args_);
+    std::vector<proto_lite::Field> top;   // FacenetArgs' own scalars are FacenetInput's and FacenetOutput's
+    const bool parsed = FACENET ? parse_wrapped_caffe_args(config.args.data(), config.args.size(), &args_, &top)
+                                : parse_caffe_args(config.args.data(), config.args.size(), &args_);
     if (!parsed) {
       RESULT_ERROR(&core_.valid, "Could not parse %s", FACENET ? "FacenetArgs" : "CaffeArgs");
       return;

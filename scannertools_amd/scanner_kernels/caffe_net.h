@@ -25,64 +25,14 @@
 #include <vector>
 
 #include "caffe_files.h"
-#include "proto_lite.h"
+#include "net_weights.h"
 #include "scannertools_hip.h"
 
 namespace scanner {
 namespace caffe_net {
 
-// ---- protobuf text format as a tree --------------------------------------------------------------------------------------
-struct Msg {
-  std::vector<std::pair<std::string, std::string>> scalars;
-  std::vector<std::pair<std::string, Msg>> subs;
-  const std::string* get(const std::string& k) const {
-    for (auto& s : scalars)
-      if (s.first == k) return &s.second;
-    return nullptr;
-  }
-  std::vector<std::string> all(const std::string& k) const {
-    std::vector<std::string> v;
-    for (auto& s : scalars)
-      if (s.first == k) v.push_back(s.second);
-    return v;
-  }
-  const Msg* sub(const std::string& k) const {
-    for (auto& s : subs)
-      if (s.first == k) return &s.second;
-    return nullptr;
-  }
-  int geti(const std::string& k, int dflt) const { auto* s = get(k); return s ? atoi(s->c_str()) : dflt; }
-  float getf(const std::string& k, float dflt) const { auto* s = get(k); return s ? strtof(s->c_str(), nullptr) : dflt; }
-  bool getb(const std::string& k, bool dflt) const { auto* s = get(k); return s ? (*s == "true" || *s == "1") : dflt; }
-};
-
-inline bool parse_msg(const std::vector<std::string>& tok, size_t* i, bool closing, int depth, Msg* out, std::string* err) {
-  if (depth > 64) { *err = "prototxt nests deeper than 64 messages"; return false; }
-  while (*i < tok.size()) {
-    const std::string& t = tok[*i];
-    if (t == "}") {
-      if (!closing) { *err = "unbalanced '}' in the prototxt"; return false; }
-      ++*i;
-      return true;
-    }
-    if (t == "{" || t == ":") { *err = "unexpected '" + t + "' in the prototxt"; return false; }
-    size_t j = *i + 1;
-    if (j < tok.size() && tok[j] == ":") ++j;
-    if (j >= tok.size()) { *err = "field " + t + " has no value in the prototxt"; return false; }
-    if (tok[j] == "{") {
-      *i = j + 1;
-      out->subs.emplace_back(t, Msg());
-      if (!parse_msg(tok, i, true, depth + 1, &out->subs.back().second, err)) return false;
-    } else {
-      std::string v = tok[j];
-      if (!v.empty() && v[0] == '"') v = v.substr(1);
-      out->scalars.emplace_back(t, v);
-      *i = j + 1;
-    }
-  }
-  if (closing) { *err = "missing '}' in the prototxt"; return false; }
-  return true;
-}
+using caffe_files::Blobs;
+using caffe_files::Msg;
 
 // ---- layers --------------------------------------------------------------------------------------------------------------
 enum Kind { kInput, kConv, kReLU, kPool, kLRN, kConcat, kIP, kDropout, kSplit, kSoftmax };
@@ -131,44 +81,9 @@ inline std::string canon(const std::string& type) {
 }
 inline int pad16(int c) { return (c + 15) / 16 * 16; }
 
-struct Weights { std::vector<std::vector<float>> blobs; };
-
-// every layer of the file that carries blobs (any number of them), by name
-inline bool read_caffemodel(const std::string& path, std::map<std::string, Weights>* out, std::string* err) try {
-  std::string buf;
-  if (!caffe_files::read_file(path, &buf)) { *err = "cannot read the weights file " + path; return false; }
-  std::vector<proto_lite::Field> top;
-  if (!proto_lite::parse((const uint8_t*)buf.data(), buf.size(), &top)) { *err = path + " is not a serialized NetParameter"; return false; }
-  for (auto& f : top) {
-    if (f.wire != 2 || (f.number != 100 && f.number != 2)) continue;
-    const uint32_t name_field = f.number == 100 ? 1 : 4, blob_field = f.number == 100 ? 7 : 6;
-    std::vector<proto_lite::Field> lf;
-    if (!proto_lite::parse((const uint8_t*)f.bytes.data(), f.bytes.size(), &lf)) { *err = "malformed layer in " + path; return false; }
-    std::string name;
-    Weights w;
-    for (auto& g : lf) {
-      if (g.number == name_field && g.wire == 2) name = g.bytes;
-      else if (g.number == blob_field && g.wire == 2) {
-        w.blobs.emplace_back();
-        if (!caffe_files::blob_floats(g.bytes, &w.blobs.back())) { *err = "malformed blob in " + path; return false; }
-      }
-    }
-    if (!name.empty() && !w.blobs.empty()) (*out)[name] = std::move(w);
-  }
-  return true;
-} catch (const std::exception& e) {
-  *err = "cannot parse " + path + ": " + e.what();
-  out->clear();
-  return false;
-}
-
 inline bool parse_layers(const std::string& path, std::vector<Layer>* out, std::string* err) {
-  std::string text;
-  if (!caffe_files::read_file(path, &text)) { *err = "cannot read the model description " + path; return false; }
-  std::vector<std::string> tok;
   Msg net;
-  size_t i = 0;
-  if (!caffe_files::prototxt_tokens(text, &tok, err) || !parse_msg(tok, &i, false, 0, &net, err)) { *err += " (" + path + ")"; return false; }
+  if (!caffe_files::read_prototxt(path, &net, err)) return false;
   // the legacy header: input: "data" + input_dim x 4 or input_shape { dim ... }
   if (const std::string* in = net.get("input")) {
     Layer l;
@@ -262,7 +177,7 @@ inline bool parse_layers(const std::string& path, std::vector<Layer>* out, std::
 // The plan for an input of (c, h, w): c 0 takes the description's own channel count, h or w 0 its own size.  weights (may be
 // null): every Convolution / InnerProduct on the path must have blobs of the right element counts; strict_ip false leaves an
 // InnerProduct whose input length does not match its weights to the caller (validate() does not know the frame size yet).
-inline bool make_plan(const std::string& prototxt, const std::map<std::string, Weights>* weights, int c, int h, int w, const std::string& input_blob,
+inline bool make_plan(const std::string& prototxt, const Blobs* weights, int c, int h, int w, const std::string& input_blob,
                       const std::string& output_blob, bool strict_ip, Plan* plan, std::string* err) try {
   Plan& p = *plan;
   p = Plan();
@@ -368,7 +283,7 @@ inline bool make_plan(const std::string& prototxt, const std::map<std::string, W
     if (weights && (l.kind == kConv || l.kind == kIP)) {
       auto it = weights->find(l.name);
       if (it == weights->end()) return refuse("the weights file has no blobs for this layer");
-      const auto& bl = it->second.blobs;
+      const auto& bl = it->second;
       const size_t want = l.kind == kConv ? (size_t)l.num_output * (b0.c / l.group) * l.k * l.k : (size_t)l.num_output * b0.c * b0.h * b0.w;
       if (bl.size() < (l.bias ? 2u : 1u)) return refuse("the weights file holds " + std::to_string(bl.size()) + " blobs for this layer, " + (l.bias ? "2" : "1") + " are needed");
       if (l.bias && bl[1].size() != (size_t)l.num_output)
@@ -476,7 +391,7 @@ class Net {
     release();
     prototxt_ = prototxt; input_blob_ = input_blob; output_blob_ = output_blob;
     weights_.clear();
-    if (!read_caffemodel(caffemodel, &weights_, err)) return false;
+    if (!caffe_files::read_caffemodel(caffemodel, &weights_, err)) return false;
     Plan p;
     return make_plan(prototxt_, &weights_, 0, 0, 0, input_blob_, output_blob_, false, &p, err);
   }
@@ -560,28 +475,15 @@ class Net {
 
   void release() {
     free_buffers();
-    for (auto& kv : packed_) {
-      if (kv.second.w) (void)hipFree(kv.second.w);
-      if (kv.second.b) (void)hipFree(kv.second.b);
-      if (kv.second.wt) (void)hipFree(kv.second.wt);
-    }
     packed_.clear();
     planned_ = false;
   }
 
  private:
-  struct Packed {
-    float* w = nullptr;   // Convolution: [cout_pad][k][k][cin_pad] (MFMA) or [cout][k][k][cin / group]; InnerProduct: st_inner_product_pack_weights' order
-    float* b = nullptr;
-    void* wt = nullptr;   // MFMA convolutions: the spatial-tile kernel's operand order
-    int cout_pad = 0;
+  // w: Convolution: [cout_pad][k][k][cin_pad] (MFMA) or [cout][k][k][cin / group]; InnerProduct: st_inner_product_pack_weights' order
+  struct Packed : net_weights::DeviceWeights {
     long long key = -1;   // InnerProduct: the bottom geometry the weights were permuted for
   };
-
-  static bool to_device(const std::vector<float>& host, float** dev) {
-    return hipMalloc(dev, std::max<size_t>(host.size(), 4) * 4) == hipSuccess &&
-           (host.empty() || hipMemcpy(*dev, host.data(), host.size() * 4, hipMemcpyHostToDevice) == hipSuccess);
-  }
 
   bool upload(st_ctx* ctx, const Step& st, std::string* err) {
     const Layer& l = plan_.layers[st.layer];
@@ -590,29 +492,16 @@ class Net {
     Packed& k = packed_[l.name];
     const long long key = l.kind == kIP ? ((long long)xs.h << 40) | ((long long)xs.w << 20) | xcs : 0;
     if (k.w && k.key == key) return true;
-    if (k.w) (void)hipFree(k.w);
-    if (k.b) (void)hipFree(k.b);
-    if (k.wt) (void)hipFree(k.wt);
-    k = Packed();
+    k.release();
     k.key = key;
-    const auto& bl = weights_[l.name].blobs;
+    const auto& bl = weights_[l.name];
     const int co = l.num_output;
     auto oom = [&]() { *err = "out of device memory while uploading layer " + l.name; return false; };
     if (l.kind == kConv && st.mfma) {
-      const int cip = pad16(xs.c), cop = (co + 63) / 64 * 64, kk = l.k * l.k;
-      std::vector<float> wp((size_t)cop * kk * cip, 0.f), bp(cop, 0.f);
-      for (int o = 0; o < co; ++o) {
-        if (l.bias) bp[o] = bl[1][o];
-        for (int c = 0; c < xs.c; ++c)
-          for (int t = 0; t < kk; ++t) wp[((size_t)o * kk + t) * cip + c] = bl[0][((size_t)o * xs.c + c) * kk + t];
-      }
-      k.cout_pad = cop;
-      if (!to_device(wp, &k.w) || !to_device(bp, &k.b)) return oom();
-      const long long nb = st_conv_f32_tile_bytes(cop, l.k, l.k, cip);
-      if (nb > 0) {
-        if (hipMalloc(&k.wt, (size_t)nb) != hipSuccess) return oom();
-        if (st_conv_pack_weights_f32_tile(ctx, k.w, cop, l.k, l.k, cip, k.wt) != ST_OK) { *err = "layer " + l.name + ": " + st_ctx_last_error(ctx); return false; }
-      }
+      if (!net_weights::upload_mfma(bl[0].data(), l.bias ? bl[1].data() : nullptr, co, xs.c, l.k, pad16(xs.c), nullptr, &k)) return oom();
+      const int rc = net_weights::pack_tile(ctx, l.k, &k);
+      if (rc == ST_ERR_OOM) return oom();
+      if (rc != ST_OK) { *err = "layer " + l.name + ": " + st_ctx_last_error(ctx); return false; }
     } else if (l.kind == kConv) {
       const int cg = xs.c / l.group, kk = l.k * l.k;
       std::vector<float> wp((size_t)co * kk * cg), bp(co, 0.f);
@@ -621,7 +510,7 @@ class Net {
         for (int c = 0; c < cg; ++c)
           for (int t = 0; t < kk; ++t) wp[((size_t)o * kk + t) * cg + c] = bl[0][((size_t)o * cg + c) * kk + t];
       }
-      if (!to_device(wp, &k.w) || !to_device(bp, &k.b)) return oom();
+      if (!net_weights::to_device(wp, &k.w) || !net_weights::to_device(bp, &k.b)) return oom();
     } else {
       // the bottom is flattened C, H, W in the file and H, W, padded C in the buffer
       const size_t hw = (size_t)xs.h * xs.w, kp = hw * xcs;
@@ -633,7 +522,7 @@ class Net {
       }
       float* rowmajor = nullptr;
       const long long nb = st_inner_product_packed_bytes((int)kp, co);
-      bool ok = nb > 0 && to_device(wp, &rowmajor) && to_device(bp, &k.b) && hipMalloc(&k.w, (size_t)nb) == hipSuccess;
+      bool ok = nb > 0 && net_weights::to_device(wp, &rowmajor) && net_weights::to_device(bp, &k.b) && hipMalloc(&k.w, (size_t)nb) == hipSuccess;
       if (ok && (st_inner_product_pack_weights(ctx, rowmajor, (int)kp, co, k.w) != ST_OK || st_ctx_sync(ctx) != ST_OK)) {
         *err = "layer " + l.name + ": " + st_ctx_last_error(ctx);
         (void)hipFree(rowmajor);
@@ -675,7 +564,7 @@ class Net {
   }
 
   std::string prototxt_, input_blob_, output_blob_;
-  std::map<std::string, Weights> weights_;
+  Blobs weights_;
   Plan plan_;
   bool planned_ = false;
   std::map<std::string, Packed> packed_;

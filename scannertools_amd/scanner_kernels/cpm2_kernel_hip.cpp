@@ -18,8 +18,8 @@
 #include "scanner/api/op.h"
 #include "scanner/util/hip.h"
 #include "scanner/util/memory.h"
+#include "caffe_args.h"
 #include "pose_net.h"
-#include "proto_lite.h"
 #include "scannertools_hip.h"
 #include "kernel_core.h"
 
@@ -27,32 +27,20 @@ namespace scanner {
 namespace {
 constexpr int kMaxPeaks = 64;           // cpm2_output_kernel_cpu.cpp:760-761 (max_peaks_)
 constexpr float kNmsThreshold = 0.05f;  // the model's nms_param ([EXT] pose_deploy_linevec.prototxt)
-
-// CPM2Args.caffe_args.net_descriptor.model_weights_path (and .model_path, the deploy prototxt, when given)
-bool parse_weights_path(const std::vector<u8>& args, std::string* path, std::string* prototxt) {
-  std::vector<proto_lite::Field> top, caffe, net;
-  if (!proto_lite::parse(args.data(), args.size(), &top)) return false;
-  for (auto& f : top)
-    if (f.number == 1 && f.wire == 2 && !proto_lite::parse((const uint8_t*)f.bytes.data(), f.bytes.size(), &caffe)) return false;
-  for (auto& f : caffe)
-    if (f.number == 1 && f.wire == 2 && !proto_lite::parse((const uint8_t*)f.bytes.data(), f.bytes.size(), &net)) return false;
-  for (auto& f : net) {
-    if (f.number == 2 && f.wire == 2) *path = f.bytes;
-    if (f.number == 1 && f.wire == 2) *prototxt = f.bytes;
-  }
-  return true;
-}
 }  // namespace
 
 template <bool STAGED>
 class CPM2KernelHIPImpl : public BatchedKernel, public VideoKernel {
  public:
   CPM2KernelHIPImpl(const KernelConfig& config) : BatchedKernel(config), core_(config, STAGED), stage_(core_.gpu) {
-    std::string path, prototxt;
-    if (!parse_weights_path(config.args, &path, &prototxt)) {
+    // CPM2Args.caffe_args.net_descriptor.model_weights_path (and .model_path, the deploy prototxt, when given)
+    CaffeArgsLite args;
+    std::vector<proto_lite::Field> top;   // CPM2Args.scale is CPM2Input's and CPM2Output's
+    if (!parse_wrapped_caffe_args(config.args.data(), config.args.size(), &args, &top)) {
       RESULT_ERROR(&core_.valid, "Could not parse CPM2Args");
       return;
     }
+    const std::string &path = args.model_weights_path, &prototxt = args.model_path;
     if (path.empty()) {
       RESULT_ERROR(&core_.valid, "CPM2: CPM2Args.caffe_args.net_descriptor.model_weights_path is empty");
       return;
@@ -135,11 +123,9 @@ class CPM2KernelHIPImpl : public BatchedKernel, public VideoKernel {
 // or -1 with the reason in `err`.
 extern "C" __attribute__((visibility("default"))) int scannertools_caffe_check_model(const char* caffemodel, char* err, size_t err_len) {
   std::string msg;
-  int matched = 0;
-  const bool ok = caffemodel && scanner::pose::check_caffemodel(caffemodel, &matched, &msg);
-  if (!caffemodel) msg = "null path";
+  const bool ok = caffemodel ? scanner::pose::check_caffemodel(caffemodel, std::string(), &msg) : (msg = "null path", false);
   if (err && err_len) { strncpy(err, msg.c_str(), err_len - 1); err[err_len - 1] = 0; }
-  return ok ? matched : -1;
+  return ok ? (int)scanner::pose::all_layers().size() : -1;
 }
 
 // Deploy-description check without a GPU: 92 when the prototxt describes the network the kernels implement and, if
@@ -148,36 +134,12 @@ extern "C" __attribute__((visibility("default"))) int scannertools_caffe_check_m
 extern "C" __attribute__((visibility("default"))) int scannertools_caffe_check_prototxt(const char* prototxt, const char* caffemodel, char* err,
                                                                                         size_t err_len) {
   std::string msg;
-  int matched = -1;
-  try {
-    std::vector<std::string> names;
-    if (!prototxt) {
-      msg = "null path";
-    } else if (scanner::pose::prototxt_layer_names(prototxt, &names, &msg)) {
-      matched = (int)names.size();
-      if (caffemodel) {
-        std::map<std::string, scanner::pose::Blobs> blobs;
-        const auto arch = scanner::pose::all_layers();
-        if (!scanner::pose::read_caffemodel(caffemodel, &blobs, &msg)) {
-          matched = -1;
-        } else {
-          for (size_t i = 0; i < arch.size() && matched >= 0; ++i) {
-            auto it = blobs.find(names[i]);
-            if (it == blobs.end() || it->second.w.size() != (size_t)arch[i].cout * arch[i].cin * arch[i].k * arch[i].k ||
-                it->second.b.size() != (size_t)arch[i].cout) {
-              msg = "caffemodel has no weights of the right size for prototxt layer " + names[i];
-              matched = -1;
-            }
-          }
-        }
-      }
-    }
-  } catch (const std::exception& e) {
-    msg = e.what();
-    matched = -1;
-  }
+  std::vector<std::string> names;
+  const bool ok = !prototxt ? (msg = "null path", false)
+                  : caffemodel ? scanner::pose::check_caffemodel(caffemodel, prototxt, &msg)
+                               : scanner::pose::prototxt_layer_names(prototxt, &names, &msg);
   if (err && err_len) { strncpy(err, msg.c_str(), err_len - 1); err[err_len - 1] = 0; }
-  return matched;
+  return ok ? (int)scanner::pose::all_layers().size() : -1;
 }
 
 namespace scanner {

@@ -16,30 +16,23 @@
 #include "scanner/api/op.h"
 #include "scanner/util/hip.h"
 #include "scanner/util/memory.h"
-#include "proto_lite.h"
+#include "caffe_args.h"
 #include "scannertools_hip.h"
 #include "kernel_core.h"
 
 namespace scanner {
-namespace {
-// FacenetArgs.scale (field 3) and FacenetArgs.caffe_args (1) . net_descriptor (1) . mean_colors (7)
-bool parse_facenet_args(const std::vector<u8>& args, f32* scale, std::vector<f32>* mean) {
-  std::vector<proto_lite::Field> fields, caffe_args, net;
-  *scale = 0.f;
-  if (!proto_lite::parse(args.data(), args.size(), &fields)) return false;
-  for (auto& f : fields)
-    if (f.number == 3 && f.wire == 5) *scale = proto_lite::as_float(f);
-  return proto_lite::nested(fields, 1, &caffe_args) && proto_lite::nested(caffe_args, 1, &net) &&
-         proto_lite::repeated_floats(net, 7, mean);
-}
-}  // namespace
-
 template <bool STAGED>
 class FacenetInputKernelHIPImpl : public BatchedKernel, public VideoKernel {
  public:
   FacenetInputKernelHIPImpl(const KernelConfig& config) : BatchedKernel(config), core_(config, STAGED), stage_(core_.gpu) {
-    std::vector<f32> mean;
-    if (!parse_facenet_args(config.args, &scale_, &mean)) {
+    // FacenetArgs.scale (field 3) and FacenetArgs.caffe_args (1) . net_descriptor (1) . mean_colors (7)
+    CaffeArgsLite args;
+    std::vector<proto_lite::Field> top;
+    const bool parsed = parse_wrapped_caffe_args(config.args.data(), config.args.size(), &args, &top);
+    for (auto& f : top)
+      if (f.number == 3 && f.wire == 5) scale_ = proto_lite::as_float(f);
+    const std::vector<f32>& mean = args.mean_colors;
+    if (!parsed) {
       RESULT_ERROR(&core_.valid, "Could not parse FacenetArgs");
     } else if (!(scale_ > 0.f)) {
       RESULT_ERROR(&core_.valid, "FacenetInput: scale must be positive, got %f", scale_);

@@ -85,7 +85,7 @@ class OpenPoseKernelHIPImpl : public BatchedKernel, public VideoKernel {
     std::string err;
     // the deploy description beside the weights (OpenPose's own file layout), when the directory holds it
     std::string proto = args_.model_directory + "/pose/coco/pose_deploy_linevec.prototxt", probe;
-    if (!pose::read_file(proto, &probe)) proto.clear();
+    if (!caffe_files::read_file(proto, &probe)) proto.clear();
     const std::string model = args_.model_directory + "/pose/coco/pose_iter_440000.caffemodel";
     if (!proto.empty()) {
       // The description was found by probing, not named by the caller (OpenPoseArgs has no field for it): a file this

@@ -23,10 +23,8 @@
 #include <string>
 #include <vector>
 
-#include <sys/stat.h>
-
 #include "caffe_files.h"
-#include "proto_lite.h"
+#include "net_weights.h"
 #include "scannertools_hip.h"
 
 namespace scanner {
@@ -67,56 +65,6 @@ inline std::vector<LayerSpec> branch_layers(int stage, int branch /*1 | 2*/) {
   return l;
 }
 
-// ---- caffemodel ------------------------------------------------------------------------------------------
-// NetParameter wire format ([EXT] caffe.proto): layer = 100 (LayerParameter: name = 1, blobs = 7) or the V1
-// `layers` = 2 (name = 4, blobs = 6); BlobProto: data = 5 (packed float).  Only the float payloads are needed:
-// the shapes are the architecture's.
-struct Blobs {
-  std::vector<float> w, b;
-};
-
-using caffe_files::read_file;
-using caffe_files::blob_floats;
-
-inline bool read_caffemodel_impl(const std::string& path, std::map<std::string, Blobs>* out, std::string* err) {
-  std::string buf;
-  if (!read_file(path, &buf)) { *err = "cannot read " + path; return false; }
-  std::vector<proto_lite::Field> top;
-  if (!proto_lite::parse((const uint8_t*)buf.data(), buf.size(), &top)) { *err = path + " is not a serialized NetParameter"; return false; }
-  for (auto& f : top) {
-    if (f.wire != 2 || (f.number != 100 && f.number != 2)) continue;
-    const uint32_t name_field = f.number == 100 ? 1 : 4, blob_field = f.number == 100 ? 7 : 6;
-    std::vector<proto_lite::Field> lf;
-    if (!proto_lite::parse((const uint8_t*)f.bytes.data(), f.bytes.size(), &lf)) { *err = "malformed layer in " + path; return false; }
-    std::string name;
-    std::vector<const std::string*> blobs;
-    for (auto& g : lf) {
-      if (g.number == name_field && g.wire == 2) name = g.bytes;
-      else if (g.number == blob_field && g.wire == 2) blobs.push_back(&g.bytes);
-    }
-    if (name.empty() || blobs.size() < 2) continue;
-    Blobs bl;
-    if (!blob_floats(*blobs[0], &bl.w) || !blob_floats(*blobs[1], &bl.b)) { *err = "malformed blob in layer " + name; return false; }
-    (*out)[name] = std::move(bl);
-  }
-  return true;
-}
-
-// The file is untrusted input and these readers sit behind extern "C" entry points and kernel constructors: nothing
-// may leave them as an exception (std::bad_alloc / std::length_error on a hostile length field would otherwise
-// cross the C ABI and end the host process instead of becoming a validate() error).
-inline bool read_caffemodel(const std::string& path, std::map<std::string, Blobs>* out, std::string* err) {
-  try {
-    return read_caffemodel_impl(path, out, err);
-  } catch (const std::exception& e) {
-    *err = "cannot parse " + path + ": " + e.what();
-  } catch (...) {
-    *err = "cannot parse " + path;
-  }
-  out->clear();
-  return false;
-}
-
 inline std::vector<LayerSpec> all_layers() {
   std::vector<LayerSpec> all = trunk_layers();
   for (int st = 1; st <= 6; ++st)
@@ -127,9 +75,9 @@ inline std::vector<LayerSpec> all_layers() {
 
 // ---- prototxt ----------------------------------------------------------------------------------------------
 // The deploy description the reference hands Caffe next to the weights (CaffeArgs.net_descriptor.model_path; OpenPose reads
-// <model_directory>/pose/coco/pose_deploy_linevec.prototxt).  Protobuf text format, read far enough to list the
-// convolutions: layer { name: ".." type: "Convolution" convolution_param { num_output: N kernel_size: K } }.  The kernels
-// implement ONE architecture; what the file is used for is (i) refusing a description of another network and (ii) the
+// <model_directory>/pose/coco/pose_deploy_linevec.prototxt).  Protobuf text format (caffe_files.h: read_prototxt), of
+// which the convolutions are used: layer { name: ".." type: "Convolution" convolution_param { num_output: N kernel_size: K } }.
+// The kernels implement ONE architecture; what the file is used for is (i) refusing a description of another network and (ii) the
 // layer NAMES the weights are looked up by (scannertools_amd/pose_net.py: names_from_prototxt does the same check with
 // the channel counts walked through the blobs).
 struct ProtoLayer {
@@ -142,51 +90,24 @@ struct ProtoLayer {
   bool concat() const { return type == "Concat" || type == "CONCAT"; }
 };
 
-// Every layer of the description in file order (name, type, blobs, convolution parameters) and the net-level `input:`.
-inline bool prototxt_layers_impl(const std::string& text, std::vector<ProtoLayer>* out, std::string* net_input, std::string* err) {
-  std::vector<std::string> tok;
-  if (!caffe_files::prototxt_tokens(text, &tok, err)) return false;
-  // walk the nesting: path of open message fields; remember the fields of the current top-level layer
-  std::vector<std::string> path;
-  ProtoLayer cur;
-  for (size_t i = 0; i < tok.size(); ++i) {
-    const std::string& t = tok[i];
-    if (t == "}") {
-      if (path.empty()) { *err = "unbalanced '}' in the prototxt"; return false; }
-      const bool layer_end = path.size() == 1 && (path[0] == "layer" || path[0] == "layers");
-      path.pop_back();
-      if (layer_end) {
-        out->push_back(cur);
-        cur = ProtoLayer();
-      }
-      continue;
+// Every layer of the description in file order (name, type, blobs, convolution parameters).
+inline std::vector<ProtoLayer> prototxt_layers(const caffe_files::Msg& net) {
+  std::vector<ProtoLayer> out;
+  for (auto& s : net.subs) {
+    if (s.first != "layer" && s.first != "layers") continue;
+    const caffe_files::Msg& m = s.second;
+    ProtoLayer l;
+    if (auto* v = m.get("name")) l.name = *v;
+    if (auto* v = m.get("type")) l.type = *v;
+    l.bottoms = m.all("bottom");
+    l.tops = m.all("top");
+    if (const caffe_files::Msg* p = m.sub("convolution_param")) {
+      l.cout = p->geti("num_output", 0);
+      l.k = p->geti("kernel_size", p->geti("kernel_h", 1));
     }
-    if (t == "{" || t == ":") { *err = "unexpected '" + t + "' in the prototxt"; return false; }
-    // a field name
-    size_t j = i + 1;
-    if (j < tok.size() && tok[j] == ":") ++j;
-    if (j >= tok.size()) { *err = "field " + t + " has no value in the prototxt"; return false; }
-    if (tok[j] == "{") {
-      path.push_back(t);
-      i = j;
-      continue;
-    }
-    std::string v = tok[j];
-    if (!v.empty() && v[0] == '"') v = v.substr(1);
-    const bool in_layer = !path.empty() && (path[0] == "layer" || path[0] == "layers");
-    if (path.empty() && t == "input" && net_input->empty()) *net_input = v;
-    if (in_layer && path.size() == 1 && t == "name") cur.name = v;
-    if (in_layer && path.size() == 1 && t == "type") cur.type = v;
-    if (in_layer && path.size() == 1 && t == "bottom") cur.bottoms.push_back(v);
-    if (in_layer && path.size() == 1 && t == "top") cur.tops.push_back(v);
-    if (in_layer && path.size() == 2 && path[1] == "convolution_param") {
-      if (t == "num_output") cur.cout = atoi(v.c_str());
-      if (t == "kernel_size" || t == "kernel_h") cur.k = atoi(v.c_str());
-    }
-    i = j;
+    out.push_back(l);
   }
-  if (!path.empty()) { *err = "missing '}' in the prototxt"; return false; }
-  return true;
+  return out;
 }
 
 // Names of the 92 convolutions of `path` in all_layers() order; false (with the first difference in *err) if the file is
@@ -197,11 +118,10 @@ inline bool prototxt_layers_impl(const std::string& text, std::vector<ProtoLayer
 // chains behind that blob, told apart by their output counts (38 = L1, 19 = L2); the next stage reads the Concat of
 // (L1, L2, features) in that order -- the order load() packs the weights for.
 inline bool prototxt_layer_names(const std::string& path, std::vector<std::string>* names, std::string* err) try {
-  std::string text;
-  if (!read_file(path, &text)) { *err = "cannot read " + path; return false; }
-  std::vector<ProtoLayer> layers;
-  std::string cur;
-  if (!prototxt_layers_impl(text, &layers, &cur, err)) { *err += " (" + path + ")"; return false; }
+  caffe_files::Msg net;
+  if (!caffe_files::read_prototxt(path, &net, err)) return false;
+  const std::vector<ProtoLayer> layers = prototxt_layers(net);
+  std::string cur = net.get("input") ? *net.get("input") : std::string();   // the net-level `input:`, else an Input layer's top
   const std::vector<LayerSpec> arch = all_layers();
   size_t nconv = 0;
   for (auto& l : layers) nconv += l.conv();
@@ -319,24 +239,34 @@ inline bool prototxt_layer_names(const std::string& path, std::vector<std::strin
   return false;
 }
 
-// Does the file hold weights of the right sizes for every layer of the architecture?  (No GPU involved: what
-// CPM2's validate() reports for a wrong or damaged model file, and a check a deployment can run up front.)
-inline bool check_caffemodel(const std::string& path, int* matched, std::string* err) try {
-  std::map<std::string, Blobs> blobs;
-  if (matched) *matched = 0;
-  if (!read_caffemodel(path, &blobs, err)) return false;
+// Do the blobs of a caffemodel have the architecture's element counts for every layer of all_layers()?  names: the layers'
+// names in the file, in all_layers() order (prototxt_layer_names); empty: the architecture's own.  path: for the messages.
+inline bool match_weights(const std::vector<std::string>& names, const caffe_files::Blobs& blobs, const std::string& path, std::string* err) {
+  size_t li = 0;
   for (auto& l : all_layers()) {
-    auto it = blobs.find(l.name);
-    if (it == blobs.end()) { *err = "caffemodel " + path + " has no weights for layer " + l.name; return false; }
-    if (it->second.w.size() != (size_t)l.cout * l.cin * l.k * l.k || it->second.b.size() != (size_t)l.cout) {
-      *err = "layer " + l.name + ": the file's blob sizes do not match the architecture";
+    const std::string& fname = names.empty() ? l.name : names[li];
+    ++li;
+    auto it = blobs.find(fname);
+    if (it == blobs.end() || it->second.size() < 2) { *err = "caffemodel " + path + " has no weights for layer " + fname; return false; }
+    if (it->second[0].size() != (size_t)l.cout * l.cin * l.k * l.k || it->second[1].size() != (size_t)l.cout) {
+      *err = names.empty() ? "layer " + l.name + ": the file's blob sizes do not match the architecture"
+                           : "caffemodel " + path + " has no weights of the right size for prototxt layer " + fname;
       return false;
     }
-    if (matched) ++*matched;
   }
   return true;
+}
+
+// Does the file hold weights of the right sizes for every layer of the architecture -- under the names of `prototxt`, when one
+// is given, which then has to describe the architecture?  (No GPU involved: what CPM2's validate() reports for a wrong or
+// damaged model file, and a check a deployment can run up front.)
+inline bool check_caffemodel(const std::string& caffemodel, const std::string& prototxt, std::string* err) try {
+  std::vector<std::string> names;
+  caffe_files::Blobs blobs;
+  return (prototxt.empty() || prototxt_layer_names(prototxt, &names, err)) && caffe_files::read_caffemodel(caffemodel, &blobs, err) &&
+         match_weights(names, blobs, caffemodel, err);
 } catch (const std::exception& e) {
-  *err = "cannot check " + path + ": " + e.what();
+  *err = "cannot check " + caffemodel + ": " + e.what();
   return false;
 }
 
@@ -368,35 +298,18 @@ class Net {
     release();  // a second load (or one after a failure part-way through) starts from nothing: no allocation is overwritten
     std::vector<std::string> file_names;
     if (!prototxt.empty() && !prototxt_layer_names(prototxt, &file_names, err)) return false;
-    std::map<std::string, Blobs> blobs;
-    if (!read_caffemodel(caffemodel, &blobs, err)) return false;
+    caffe_files::Blobs blobs;
+    if (!caffe_files::read_caffemodel(caffemodel, &blobs, err) || !match_weights(file_names, blobs, caffemodel, err)) return false;
+    // stage-input channel order of the prototxt is (L1 38, L2 19, features 128); the buffer holds the features first
+    int cat_chan[kCat];
+    for (int c = 0; c < kCat; ++c) cat_chan[c] = c < kPaf + kHeat ? kFeat + c : c - (kPaf + kHeat);
     size_t li = 0;
     for (auto& l : all_layers()) {
-      const std::string& fname = file_names.empty() ? l.name : file_names[li];
+      const auto& bl = blobs[file_names.empty() ? l.name : file_names[li]];
       ++li;
-      auto it = blobs.find(fname);
-      if (it == blobs.end()) { *err = "caffemodel " + caffemodel + " has no weights for layer " + fname; return false; }
-      const Blobs& bl = it->second;
-      if (bl.w.size() != (size_t)l.cout * l.cin * l.k * l.k || bl.b.size() != (size_t)l.cout) {
-        *err = "layer " + l.name + ": the file's blob sizes do not match the architecture";
-        return false;
-      }
-      const int cip = l.cin == kCat ? kCatPad : (l.cin + 15) / 16 * 16, cop = (l.cout + 63) / 64 * 64;
-      std::vector<float> wp((size_t)cop * l.k * l.k * cip, 0.f), bp(cop, 0.f);
-      for (int o = 0; o < l.cout; ++o) {
-        bp[o] = bl.b[o];
-        for (int c = 0; c < l.cin; ++c) {
-          // stage-input channel order of the prototxt is (L1 38, L2 19, features 128); the buffer holds the features first
-          const int cb = l.cin == kCat ? (c < kPaf + kHeat ? kFeat + c : c - (kPaf + kHeat)) : c;
-          for (int kk = 0; kk < l.k * l.k; ++kk)
-            wp[((size_t)o * l.k * l.k + kk) * cip + cb] = bl.w[((size_t)o * l.cin + c) * l.k * l.k + kk];
-        }
-      }
       Packed& p = packed_[l.name];  // registered first, so that release() frees whatever part of it was allocated
-      p.cin_pad = cip; p.cout_pad = cop;
-      if (hipMalloc(&p.w, wp.size() * 4) != hipSuccess || hipMalloc(&p.b, bp.size() * 4) != hipSuccess ||
-          hipMemcpy(p.w, wp.data(), wp.size() * 4, hipMemcpyHostToDevice) != hipSuccess ||
-          hipMemcpy(p.b, bp.data(), bp.size() * 4, hipMemcpyHostToDevice) != hipSuccess) {
+      const bool cat = l.cin == kCat;
+      if (!net_weights::upload_mfma(bl[0].data(), bl[1].data(), l.cout, l.cin, l.k, cat ? kCatPad : (l.cin + 15) / 16 * 16, cat ? cat_chan : nullptr, &p)) {
         *err = "out of device memory while uploading layer " + l.name;
         return false;
       }
@@ -479,46 +392,18 @@ class Net {
   }
 
  private:
-  struct Packed {
-    float* w = nullptr;
-    float* b = nullptr;
-    void* w3 = nullptr;  // the same weights as bf16 triples (bf16x3 arithmetic only; packed on first use)
-    void* wt = nullptr;  // float32 weights in the spatial-tile kernel's operand order (float32 arithmetic, eligible layers; on first use)
-    bool wt_tried = false;
-    int cin_pad = 0, cout_pad = 0, k = 0;
+  struct Packed : net_weights::DeviceWeights {
+    bool wt_tried = false;   // the spatial-tile form is packed on first use, where the kernel takes the layer's geometry
   };
 
   // the layer's weights in the form(s) the selected arithmetic reads, packed on first use
   int prepare_weights(st_ctx* ctx, Packed& p, const LayerSpec& l) {
     if (!bf16x3_) {
-      if (!p.wt_tried) {
-        p.wt_tried = true;
-        const long long nb = st_conv_f32_tile_bytes(p.cout_pad, l.k, l.k, p.cin_pad);
-        if (nb > 0) {
-          void* wt = nullptr;
-          if (hipMalloc(&wt, (size_t)nb) != hipSuccess) return ST_ERR_HIP;
-          const int st = st_conv_pack_weights_f32_tile(ctx, p.w, p.cout_pad, l.k, l.k, p.cin_pad, wt);
-          if (st != ST_OK) {
-            (void)hipFree(wt);
-            return st;
-          }
-          p.wt = wt;
-        }
-      }
-      return ST_OK;
+      if (p.wt_tried) return ST_OK;
+      p.wt_tried = true;
+      return net_weights::pack_tile(ctx, l.k, &p);
     }
-    if (!p.w3) {
-      void* w3 = nullptr;
-      const size_t w3_bytes = (size_t)st_conv_bf16x3_packed_bytes(p.cout_pad, l.k, l.k, p.cin_pad);
-      if (hipMalloc(&w3, w3_bytes) != hipSuccess) return ST_ERR_HIP;
-      const int st = st_conv_pack_weights_bf16x3_n(ctx, p.w, p.cout_pad, l.k, l.k, p.cin_pad, w3, w3_bytes);
-      if (st != ST_OK) {  // an unpacked buffer must never be mistaken for packed weights by the next call
-        (void)hipFree(w3);
-        return st;
-      }
-      p.w3 = w3;
-    }
-    return ST_OK;
+    return p.w3 ? ST_OK : net_weights::pack_bf16x3(ctx, l.k, &p);
   }
 
   // one convolution layer in the selected arithmetic
@@ -576,12 +461,6 @@ class Net {
   }
   void release() {
     free_buffers();
-    for (auto& kv : packed_) {
-      if (kv.second.w) (void)hipFree(kv.second.w);
-      if (kv.second.b) (void)hipFree(kv.second.b);
-      if (kv.second.w3) (void)hipFree(kv.second.w3);
-      if (kv.second.wt) (void)hipFree(kv.second.wt);
-    }
     packed_.clear();
   }
 

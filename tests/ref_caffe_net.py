@@ -1,12 +1,12 @@
 """The independent definition of a Caffe forward pass for the Caffe / Facenet op tests: the deploy prototxt is parsed with
-pose_net.parse_prototxt, the weights read with pose_net.read_caffemodel, and every layer evaluated with torch ON THE CPU IN
+caffe_files.parse_prototxt, the weights read with caffe_files.read_caffemodel, and every layer evaluated with torch ON THE CPU IN
 FLOAT64 by the rules of DESIGN.md section 4.14 ([EXT] Caffe's public sources).  It shares nothing with the C++ planner
 (scanner_kernels/caffe_net.h).  Also the two fixture networks of the tests."""
 import numpy as np
 import torch
 import torch.nn.functional as F
 
-from scannertools_amd import caffe_net, pose_net
+from scannertools_amd import caffe_files, caffe_net
 
 
 def _p(layer, key):
@@ -20,8 +20,8 @@ def _i(msg, key, default):
 def forward(prototxt, caffemodel, x, input_blob="data"):
     """x: (n, C, H, W) array.  Returns {blob name: float64 tensor} after the whole description ran in file order (an in-place layer
     overwrites its blob, as in Caffe)."""
-    net = pose_net.parse_prototxt(open(prototxt).read())
-    weights = pose_net.read_caffemodel(caffemodel)
+    net = caffe_files.parse_prototxt(open(prototxt).read())
+    weights = caffe_files.read_caffemodel(caffemodel)
     blobs = {input_blob: torch.as_tensor(np.asarray(x), dtype=torch.float64)}
     for layer in net.get("layer", []) + net.get("layers", []):
         typ = str(layer["type"][0]).replace("_", "").lower()
