@@ -114,6 +114,7 @@ ST_EXPORT int st_ctx_create(int device_id, st_ctx** out_ctx) {
   if (const char* e = getenv("ST_ITER_ROLES")) c->roles_mode = atoi(e);
   if (const char* e = getenv("ST_ROLES_NCW")) c->roles_ncw = atoi(e);
   if (const char* e = getenv("ST_PYR_ROLES")) c->pyr_roles = atoi(e);
+  if (const char* e = getenv("ST_PYR_ROLES_RGB")) c->pyr_roles_rgb = atoi(e) != 0;
   if (const char* e = getenv("ST_CONV_TILE")) c->conv_tile = atoi(e);
   if (const char* e = getenv("ST_CONCURRENT")) c->concurrency_mode = atoi(e);
   hipDeviceProp_t prop;

@@ -2,7 +2,7 @@
 //
 // Replaces the arithmetic of OpticalFlowKernelCPU::execute
 // (/root/reference/scannertools/scannertools_cpp/imgproc/optical_flow_kernel_cpu.cpp:36-41):
-//   cv::cvtColor(BGR2GRAY) x2  ->  k_gray4 / k_gray
+//   cv::cvtColor(BGR2GRAY) x2  ->  k_gray4 / k_gray (calls above 16 pairs: inside k_pyr_roles<false, true>)
 //   cv::FarnebackOpticalFlow::calc:
 //     convertTo(F32) + GaussianBlur + resize        ->  k_pyr_fused      (all four levels in one pass over
 //                                                       the gray frame; k_pyr0 / k_pyr_dec / k_pyr per
@@ -25,6 +25,8 @@
 //         the flow is smooth); see the note above update_matrices_px
 //   M     f32 planar (5,lh,lw): [G11, G12, G22, h1, h2] -- unfused path only (ping-pong per iteration)
 //   flow  f32 (lh,lw,2) interleaved (u,v): the op's output format
+#include <hip/hip_ext.h>
+
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -633,6 +635,7 @@ __global__ __launch_bounds__(256) void k_pyr_dec(PyrDecArgs a) {
 struct PyrFusedArgs {
   const uint8_t* gray;          // n x (h*w), or
   const uint8_t* const* frames; // RGB instance: device table of n (h,w,3) frames, converted on the fly
+  uint8_t* gray_out;            // k_pyr_roles<false, true>: n x (h*w), the gray plane written as a by-product
   int cb, cg, cr, rnd, shift;   // luma table of the RGB instance (see launch_gray)
   float* img0; float* img1; float* img2; float* img3;  // n x (h>>k)*(w>>k)
   int h, w, rows_per_seg;       // rows_per_seg: source rows per segment, multiple of 8
@@ -881,7 +884,34 @@ __global__ __launch_bounds__(256) void k_pyr_fused(PyrFusedArgs a) {
 // in one wave), three waves share a SIMD, and each role keeps only its own rings in registers.  Arithmetic and
 // association are those of k_pyr_fused (and of k_pyr0 / k_pyr_dec): bit-identical images.
 // ---------------------------------------------------------------------------------------------
-template <int ROLE, bool L0 = true>
+// RGB (with L0 = false, calls above 16 pairs): the source is the RGB frame itself and the gray plane k_polyexp_u8 reads is a
+// by-product -- the separate luma pass (k_gray4: 1.6 GB read, 0.53 GB written per 257 frames of 1080p) is not run.  A staged
+// dword is the 12 source bytes of its four pixels, one non-temporal 12-byte load kept raw while the batch in LDS is consumed
+// and converted with k_gray4's integer expression when it is stashed; the same dword goes to the gray plane for the pixels the
+// workgroup owns (rows [Y0, Y1), columns of its strip inside the frame: every gray byte is stored exactly once).  Dwords that
+// touch a frame border are converted at once through pf_load4_rgb's reflecting branch.
+typedef unsigned pf_u3nt __attribute__((ext_vector_type(3), aligned(4)));
+__device__ __forceinline__ pf_u3nt pf_fetch_rgb(const uint8_t* __restrict__ row, int col0, int w, const PyrFusedArgs& a) {
+  if (col0 >= 0 && col0 + 3 < w) return __builtin_nontemporal_load(reinterpret_cast<const pf_u3nt*>(row + 3 * col0));
+  pf_u3nt v = {0u, 0u, 0u};
+  if (col0 >= w + 8 || col0 < -8) return v;  // never read
+  // (pf_load4_rgb's reflecting branch, its four pixels' loads issued together)
+#pragma unroll
+  for (int k = 0; k < 4; ++k) v.x |= pf_gray1(row + 3 * d_reflect101(col0 + k, w), a) << (8 * k);
+  return v;
+}
+// inside: the dword was fetched raw (the same test as pf_fetch_rgb's); else v.x already holds the four gray bytes
+__device__ __forceinline__ unsigned pf_gray_of(pf_u3nt v, bool inside, const PyrFusedArgs& a) {
+  if (!inside) return v.x;
+  const unsigned w0 = v.x, w1 = v.y, w2 = v.z;
+  const int g0 = (int)((w0 & 0xff) * a.cb + ((w0 >> 8) & 0xff) * a.cg + ((w0 >> 16) & 0xff) * a.cr + a.rnd) >> a.shift;
+  const int g1 = (int)((w0 >> 24) * a.cb + (w1 & 0xff) * a.cg + ((w1 >> 8) & 0xff) * a.cr + a.rnd) >> a.shift;
+  const int g2 = (int)(((w1 >> 16) & 0xff) * a.cb + (w1 >> 24) * a.cg + (w2 & 0xff) * a.cr + a.rnd) >> a.shift;
+  const int g3 = (int)(((w2 >> 8) & 0xff) * a.cb + ((w2 >> 16) & 0xff) * a.cg + (w2 >> 24) * a.cr + a.rnd) >> a.shift;
+  return (unsigned)g0 | ((unsigned)g1 << 8) | ((unsigned)g2 << 16) | ((unsigned)g3 << 24);
+}
+
+template <int ROLE, bool L0 = true, bool RGB = false>
 __device__ __forceinline__ void pyr_role_run(const PyrFusedArgs& a, unsigned (*srow)[PF_RB][PF_ROWDW]) {
   const int t = threadIdx.x & 255, lane = t & 63, wv = t >> 6;
   const int h = a.h, w = a.w;
@@ -889,7 +919,8 @@ __device__ __forceinline__ void pyr_role_run(const PyrFusedArgs& a, unsigned (*s
   const int X0 = blockIdx.x * SW;
   const int Y0 = blockIdx.y * a.rows_per_seg, Y1 = min(h, Y0 + a.rows_per_seg);
   const size_t np = (size_t)h * w;
-  const uint8_t* __restrict__ g = a.gray + (size_t)blockIdx.z * np;
+  const uint8_t* __restrict__ g = RGB ? st_gl(a.frames[blockIdx.z]) : a.gray + (size_t)blockIdx.z * np;
+  const int gw = RGB ? 3 * w : w;  // bytes per source row
   float* __restrict__ o0 = a.img0 + (size_t)blockIdx.z * np;
   float* __restrict__ o1 = a.img1 + (size_t)blockIdx.z * (np >> 2);
   float* __restrict__ o2 = a.img2 + (size_t)blockIdx.z * (np >> 4);
@@ -900,26 +931,43 @@ __device__ __forceinline__ void pyr_role_run(const PyrFusedArgs& a, unsigned (*s
   const int hq = t & 3, hrow = (t >> 2) & 7;
   const int hcol = hq < 2 ? X0 - 8 + 4 * hq : X0 + SW + 4 * (hq - 2);
   const int hidx = hq < 2 ? hq : 2 + (SW >> 2) + (hq - 2);
+  // RGB: the thread's own dword / its halo dword lies inside the frame and is fetched raw (pf_fetch_rgb)
+  const bool in_t = X0 + 4 * t + 3 < w, in_h = hcol >= 0 && hcol + 3 < w;
+  uint8_t* __restrict__ gout = RGB ? a.gray_out + (size_t)blockIdx.z * np : nullptr;
 
   // staging: role r fetches rows r, r + 3, r + 6 (< 8) of a batch, dword column t; role 0's threads 0..31 the halo
   unsigned pre[3], preh = 0u;
+  pf_u3nt raw[3] = {{0u, 0u, 0u}, {0u, 0u, 0u}, {0u, 0u, 0u}}, rawh = {0u, 0u, 0u};
   auto fetch = [&](int ybase) {
 #pragma unroll
     for (int j = 0; j < 3; ++j) {
       const int r = ROLE + 3 * j;
-      if (r < PF_RB) pre[j] = pf_load4(g + (size_t)d_reflect101(ybase + r, h) * w, X0 + 4 * t, w);
+      if (r < PF_RB) {
+        if (RGB) { if (4 * t < SW) raw[j] = pf_fetch_rgb(g + (size_t)d_reflect101(ybase + r, h) * gw, X0 + 4 * t, w, a); }
+        else pre[j] = pf_load4(g + (size_t)d_reflect101(ybase + r, h) * gw, X0 + 4 * t, w);
+      }
     }
-    if (ROLE == 0 && t < 32) preh = pf_load4(g + (size_t)d_reflect101(ybase + hrow, h) * w, hcol, w);
+    if (ROLE == 0 && t < 32) {
+      if (RGB) rawh = pf_fetch_rgb(g + (size_t)d_reflect101(ybase + hrow, h) * gw, hcol, w, a);
+      else preh = pf_load4(g + (size_t)d_reflect101(ybase + hrow, h) * gw, hcol, w);
+    }
   };
-  auto stash = [&](int buf) {
+  // ybase: first row of the batch being stashed.  own: it is one of the segment's own batches (the first and the last batch of
+  // a segment are context rows another segment owns, or reflected rows)
+  auto stash = [&](int buf, int ybase) {
+    const bool own = RGB && ybase >= Y0 && ybase < Y1;  // uniform
     if (4 * t < SW) {
 #pragma unroll
       for (int j = 0; j < 3; ++j) {
         const int r = ROLE + 3 * j;
-        if (r < PF_RB) srow[buf][r][2 + t] = pre[j];
+        if (r < PF_RB) {
+          const unsigned v = RGB ? pf_gray_of(raw[j], in_t, a) : pre[j];
+          srow[buf][r][2 + t] = v;
+          if (RGB && own && live) *reinterpret_cast<unsigned*>(gout + (size_t)(ybase + r) * w + X0 + 4 * t) = v;
+        }
       }
     }
-    if (ROLE == 0 && t < 32) srow[buf][hrow][hidx] = preh;
+    if (ROLE == 0 && t < 32) srow[buf][hrow][hidx] = RGB ? pf_gray_of(rawh, in_h, a) : preh;
   };
 
   float hm[4], hc[4], r1A[2][4], r1B[2][4];  // role 0
@@ -938,7 +986,7 @@ __device__ __forceinline__ void pyr_role_run(const PyrFusedArgs& a, unsigned (*s
 
   const int nb = (Y1 - Y0) / PF_RB + 2;
   fetch(Y0 - PF_RB);
-  stash(0);
+  stash(0, Y0 - PF_RB);
   __syncthreads();
   for (int b = 0; b < nb; ++b) {
     const int ybase = Y0 - PF_RB + b * PF_RB;
@@ -1042,18 +1090,19 @@ __device__ __forceinline__ void pyr_role_run(const PyrFusedArgs& a, unsigned (*s
         }
       }
     }
-    if (b + 1 < nb) stash(buf ^ 1);
+    if (b + 1 < nb) stash(buf ^ 1, ybase + PF_RB);
     __syncthreads();
   }
 }
 
-template <bool L0>
+template <bool L0, bool RGB = false>
 __global__ __launch_bounds__(768) void k_pyr_roles(PyrFusedArgs a) {
+  static_assert(!(L0 && RGB), "the RGB-source instance leaves level 0 to k_polyexp_u8");
   __shared__ unsigned srow[2][PF_RB][PF_ROWDW];
   const int role = threadIdx.x >> 8;  // wave-uniform; every role passes the same barriers
-  if (role == 0) pyr_role_run<0, L0>(a, srow);
-  else if (role == 1) pyr_role_run<1>(a, srow);
-  else pyr_role_run<2>(a, srow);
+  if (role == 0) pyr_role_run<0, L0, RGB>(a, srow);
+  else if (role == 1) pyr_role_run<1, true, RGB>(a, srow);
+  else pyr_role_run<2, true, RGB>(a, srow);
 }
 
 typedef float f2u __attribute__((ext_vector_type(2), aligned(4)));
@@ -2133,7 +2182,7 @@ __global__ __launch_bounds__(B2_T, 2) void k_flow_iter3(IterArgs a) {
   const int x = (int)bx * B2_OUT - B2_HALO + tid;
   const int xc = d_clamp(x, 0, w - 1);
   const int y0 = by * a.rows_per_seg;
-  const int y1 = min(h, y0 + a.rows_per_seg);
+  const int y1 = by + 1 == gridDim.y ? h : min(h, y0 + a.rows_per_seg);   // the last segment takes the remainder (launch_flow_iter)
   const bool writer = tid >= B2_HALO && tid < B2_T - B2_HALO && x < w;
   const int vpos = f3_pos(tid);
   // paired flow stores (even widths): writer k = tid - HALO stores pixels (2 j, 2 j + 1) of rows 4 hh .. 4 hh + 3 of a group,
@@ -3012,11 +3061,13 @@ bool pyr_fused_ok(int h, int w, const st_fb_params& p) {
 // gray != null: from the gray images; else from the RGB frames of the device table `frames` (4-byte
 // aligned), the luma conversion folded into the loads
 // skip0 (role-split instance only): level 0 is not produced -- the expansion reads the gray frame (launch_polyexp's gray)
+// gray_out (role-split instance with skip0 only): the source is `frames` and the gray frames are WRITTEN to `gray` on the way
 int launch_pyr_fused(st_ctx* ctx, const uint8_t* gray, const uint8_t* const* frames, int n, int h, int w,
-                     const st_fb_params& p, float* const imgs[4], bool skip0 = false) {
+                     const st_fb_params& p, float* const imgs[4], bool skip0 = false, bool gray_out = false) {
   PyrFusedArgs a;
   memset(&a, 0, sizeof(a));
   a.gray = gray; a.frames = frames;
+  if (gray_out) a.gray_out = const_cast<uint8_t*>(gray);
   if (p.gray_bits == 14) { a.cb = 1868; a.cg = 9617; a.cr = 4899; } else { a.cb = 3735; a.cg = 19235; a.cr = 9798; }
   a.shift = p.gray_bits; a.rnd = 1 << (p.gray_bits - 1);
   a.img0 = imgs[0]; a.img1 = imgs[1]; a.img2 = imgs[2]; a.img3 = imgs[3];
@@ -3052,7 +3103,9 @@ int launch_pyr_fused(st_ctx* ctx, const uint8_t* gray, const uint8_t* const* fra
   const int roles_env = ctx->pyr_roles;
   const bool roles = gray && roles_env != 0;
   if (skip0 && !roles) return st_set_error(ctx, ST_ERR_INVALID, "pyr: level 0 can only be left out of the role-split kernel");
-  if (roles && skip0) hipLaunchKernelGGL(k_pyr_roles<false>, dim3(strips, (h + rows - 1) / rows, n), dim3(768), 0, ctx->stream, a);
+  if (gray_out && !(skip0 && frames)) return st_set_error(ctx, ST_ERR_INVALID, "pyr: the RGB-source role-split kernel leaves level 0 out");
+  if (gray_out) hipLaunchKernelGGL((k_pyr_roles<false, true>), dim3(strips, (h + rows - 1) / rows, n), dim3(768), 0, ctx->stream, a);
+  else if (roles && skip0) hipLaunchKernelGGL(k_pyr_roles<false>, dim3(strips, (h + rows - 1) / rows, n), dim3(768), 0, ctx->stream, a);
   else if (roles) hipLaunchKernelGGL(k_pyr_roles<true>, dim3(strips, (h + rows - 1) / rows, n), dim3(768), 0, ctx->stream, a);
   else if (gray) hipLaunchKernelGGL(k_pyr_fused<false>, dim3(strips, (h + rows - 1) / rows, n), dim3(256), 0, ctx->stream, a);
   else hipLaunchKernelGGL(k_pyr_fused<true>, dim3(strips, (h + rows - 1) / rows, n), dim3(256), 0, ctx->stream, a);
@@ -3157,14 +3210,17 @@ int launch_flow_iter(st_ctx* ctx, IterArgs a, int n_pairs) {
   // the choice, like the segment height below, changes the schedule and not one bit of the result:
   // a pair's flow does not depend on how many pairs share the call.  ST_ITER_TILE=0 / 1 (read at
   // st_ctx_create) force the marching / the tile kernel (A/B runs, parity tests of each kernel).
+  // Timing events travel with the dispatch itself (st_time_dispatch, as the Histogram launch): the figure is the kernel's own
+  // duration, and a timed step carries no marker packets before and after each of its iteration launches.
+  hipEvent_t e0, e1;
   constexpr long long kTilePx = 600000;
   const bool tile = ctx->tile_mode == 1 || (ctx->tile_mode != 0 && (long long)n_pairs * a.h * a.w <= kTilePx);
   if (tile && (a.h + FT_T - 1) / FT_T <= 65535) {
     dim3 grid((a.w + FT_T - 1) / FT_T, (a.h + FT_T - 1) / FT_T, n_pairs);
-    st_timed t(ctx, ST_K_BLUR_UPDATE);
-    if (a.coarse) hipLaunchKernelGGL((k_flow_iter_tile<FLOW_COARSE>), grid, dim3(FT_NT), 0, ctx->stream, a);
-    else if (a.flow_in) hipLaunchKernelGGL((k_flow_iter_tile<FLOW_FIELD>), grid, dim3(FT_NT), 0, ctx->stream, a);
-    else hipLaunchKernelGGL((k_flow_iter_tile<FLOW_ZERO>), grid, dim3(FT_NT), 0, ctx->stream, a);
+    ST_TRY(st_time_dispatch(ctx, ST_K_BLUR_UPDATE, &e0, &e1));
+    if (a.coarse) hipExtLaunchKernelGGL((k_flow_iter_tile<FLOW_COARSE>), grid, dim3(FT_NT), 0, ctx->stream, e0, e1, 0, a);
+    else if (a.flow_in) hipExtLaunchKernelGGL((k_flow_iter_tile<FLOW_FIELD>), grid, dim3(FT_NT), 0, ctx->stream, e0, e1, 0, a);
+    else hipExtLaunchKernelGGL((k_flow_iter_tile<FLOW_ZERO>), grid, dim3(FT_NT), 0, ctx->stream, e0, e1, 0, a);
     ST_HIP(ctx, hipGetLastError());
     return ST_OK;
   }
@@ -3230,36 +3286,50 @@ int launch_flow_iter(st_ctx* ctx, IterArgs a, int n_pairs) {
       a.out_w = best_out;
       const int rstrips = (a.w + best_out - 1) / best_out;
       dim3 grid(rstrips, (a.h + best_rows - 1) / best_rows, n_pairs);
-      st_timed t(ctx, ST_K_BLUR_UPDATE);
+      ST_TRY(st_time_dispatch(ctx, ST_K_BLUR_UPDATE, &e0, &e1));
       const int mode = a.coarse ? (a.h == 2 * a.ch ? FLOW_COARSE2 : FLOW_COARSE) : (a.flow_in ? FLOW_FIELD : FLOW_ZERO);
       // One maker set, two rows of gathers in flight per maker wave.  Measured and not kept:
       // two maker sets of the 4-column-wave instance (16 waves: 6.8 against 5.2 ms per 256-pair level-0 launch), four rows
       // in flight (163 registers; 8 pairs per call 1.37 against 1.23 ms).
       if (best_ncw == 5) {
         const dim3 blk(FrGeom<5>::THREADS);
-        if (mode == FLOW_COARSE2) hipLaunchKernelGGL((k_flow_iter_roles<5, FLOW_COARSE2>), grid, blk, 0, ctx->stream, a);
-        else if (mode == FLOW_COARSE) hipLaunchKernelGGL((k_flow_iter_roles<5, FLOW_COARSE>), grid, blk, 0, ctx->stream, a);
-        else if (mode == FLOW_FIELD) hipLaunchKernelGGL((k_flow_iter_roles<5, FLOW_FIELD>), grid, blk, 0, ctx->stream, a);
-        else hipLaunchKernelGGL((k_flow_iter_roles<5, FLOW_ZERO>), grid, blk, 0, ctx->stream, a);
+        if (mode == FLOW_COARSE2) hipExtLaunchKernelGGL((k_flow_iter_roles<5, FLOW_COARSE2>), grid, blk, 0, ctx->stream, e0, e1, 0, a);
+        else if (mode == FLOW_COARSE) hipExtLaunchKernelGGL((k_flow_iter_roles<5, FLOW_COARSE>), grid, blk, 0, ctx->stream, e0, e1, 0, a);
+        else if (mode == FLOW_FIELD) hipExtLaunchKernelGGL((k_flow_iter_roles<5, FLOW_FIELD>), grid, blk, 0, ctx->stream, e0, e1, 0, a);
+        else hipExtLaunchKernelGGL((k_flow_iter_roles<5, FLOW_ZERO>), grid, blk, 0, ctx->stream, e0, e1, 0, a);
       } else {
         const dim3 blk(FrGeom<4>::THREADS);
-        if (mode == FLOW_COARSE2) hipLaunchKernelGGL((k_flow_iter_roles<4, FLOW_COARSE2>), grid, blk, 0, ctx->stream, a);
-        else if (mode == FLOW_COARSE) hipLaunchKernelGGL((k_flow_iter_roles<4, FLOW_COARSE>), grid, blk, 0, ctx->stream, a);
-        else if (mode == FLOW_FIELD) hipLaunchKernelGGL((k_flow_iter_roles<4, FLOW_FIELD>), grid, blk, 0, ctx->stream, a);
-        else hipLaunchKernelGGL((k_flow_iter_roles<4, FLOW_ZERO>), grid, blk, 0, ctx->stream, a);
+        if (mode == FLOW_COARSE2) hipExtLaunchKernelGGL((k_flow_iter_roles<4, FLOW_COARSE2>), grid, blk, 0, ctx->stream, e0, e1, 0, a);
+        else if (mode == FLOW_COARSE) hipExtLaunchKernelGGL((k_flow_iter_roles<4, FLOW_COARSE>), grid, blk, 0, ctx->stream, e0, e1, 0, a);
+        else if (mode == FLOW_FIELD) hipExtLaunchKernelGGL((k_flow_iter_roles<4, FLOW_FIELD>), grid, blk, 0, ctx->stream, e0, e1, 0, a);
+        else hipExtLaunchKernelGGL((k_flow_iter_roles<4, FLOW_ZERO>), grid, blk, 0, ctx->stream, e0, e1, 0, a);
       }
       ST_HIP(ctx, hipGetLastError());
       return ST_OK;
     }
   }
+  // The last segment of k_flow_iter3's grid ends at the frame's last row, so the segments need not be equal: for each segment
+  // count also the height rounded DOWN to whole periods, the last segment taking the remainder.  A round then costs its tallest
+  // segment: 135 rows in 256 pairs x 1 strip are 64 + 71 (one round of 71 + 15) instead of 96 + 39 (96 + 15).  Segment starts
+  // stay multiples of 32, the anchor rows, so this is again a change of schedule only.
+  int nseg3 = (a.h + rows - 1) / rows;
+  for (int segs = 1; segs <= periods; ++segs) {
+    const int r = periods / segs * F3_ANCHOR;
+    if (r < F3_ANCHOR) break;
+    const int last = a.h - (segs - 1) * r;
+    const long long wgs = (long long)strips * n_pairs * segs;
+    const long long rounds = (wgs + resident - 1) / resident;
+    const double cost = (double)rounds * ((r > last ? r : last) + 15);
+    if (cost < best * 0.999) { best = cost; rows = r; nseg3 = segs; }
+  }
   a.rows_per_seg = rows;
-  dim3 grid(strips, (a.h + rows - 1) / rows, n_pairs);
-  st_timed t(ctx, ST_K_BLUR_UPDATE);
+  dim3 grid(strips, nseg3, n_pairs);
+  ST_TRY(st_time_dispatch(ctx, ST_K_BLUR_UPDATE, &e0, &e1));
   const int mode = a.coarse ? (a.h == 2 * a.ch ? FLOW_COARSE2 : FLOW_COARSE) : (a.flow_in ? FLOW_FIELD : FLOW_ZERO);
-  if (mode == FLOW_COARSE2) hipLaunchKernelGGL((k_flow_iter3<FLOW_COARSE2>), grid, dim3(B2_T), 0, ctx->stream, a);
-  else if (mode == FLOW_COARSE) hipLaunchKernelGGL((k_flow_iter3<FLOW_COARSE>), grid, dim3(B2_T), 0, ctx->stream, a);
-  else if (mode == FLOW_FIELD) hipLaunchKernelGGL((k_flow_iter3<FLOW_FIELD>), grid, dim3(B2_T), 0, ctx->stream, a);
-  else hipLaunchKernelGGL((k_flow_iter3<FLOW_ZERO>), grid, dim3(B2_T), 0, ctx->stream, a);
+  if (mode == FLOW_COARSE2) hipExtLaunchKernelGGL((k_flow_iter3<FLOW_COARSE2>), grid, dim3(B2_T), 0, ctx->stream, e0, e1, 0, a);
+  else if (mode == FLOW_COARSE) hipExtLaunchKernelGGL((k_flow_iter3<FLOW_COARSE>), grid, dim3(B2_T), 0, ctx->stream, e0, e1, 0, a);
+  else if (mode == FLOW_FIELD) hipExtLaunchKernelGGL((k_flow_iter3<FLOW_FIELD>), grid, dim3(B2_T), 0, ctx->stream, e0, e1, 0, a);
+  else hipExtLaunchKernelGGL((k_flow_iter3<FLOW_ZERO>), grid, dim3(B2_T), 0, ctx->stream, e0, e1, 0, a);
   ST_HIP(ctx, hipGetLastError());
   return ST_OK;
 }
@@ -3356,20 +3426,25 @@ int farneback_pass(st_ctx* ctx, const uint8_t* const* frames, int nf, const int3
   // ST_PYR_FOLD_GRAY=1: the luma conversion rides on the loads of the one-pass pyramid (no gray pass, no
   // gray image in memory).  Bit-identical, but measured SLOWER (32.5 vs 31.6 ms per 256-pair step: 12
   // bytes per lane at a 12-byte lane stride, three loads per row instead of one, on a kernel that is
-  // already VALU-bound), so the separate k_gray4 pass stays the default.
+  // already VALU-bound), so it stays a switch.  (Large calls fold the conversion into the ROLE-SPLIT pyramid instead, which has
+  // a separate stager, ALU headroom and a gray plane for the expansion: roles_rgb below.)
   const bool pyr_rgb = pyr1 && aligned4 && ctx->fold_gray;
-  if (!pyr_rgb) {
-    ST_TRY(launch_gray(ctx, d_frames, nf, h, w, p.gray_bits, gray, aligned4, small_tables ? &ta : nullptr));
-  } else if (small_tables) {
-    hipLaunchKernelGGL(k_set_tables, dim3(1), dim3(64), 0, ctx->stream, ta);
-    ST_HIP(ctx, hipGetLastError());
-  }
   // Level 0 straight from the gray frames (ST_POLY_U8, read at st_ctx_create): the role-split pyramid leaves level 0 out and the
   // level-0 expansion evaluates the 3 x 3 blur itself -- large calls only (the single multi-level launch keeps its float source)
   const bool single = pyr1 && levels >= 1 && levels <= 3 && npairs <= 16;
   const bool poly_u8 = pyr1 && !pyr_rgb && !single && ctx->poly_u8 && ctx->pyr_roles != 0 && geom[0].ksize == 3 && geom[0].sigma <= 0 &&
                        geom[0].lh == h && geom[0].lw == w && w >= 8;
-  if (pyr1) ST_TRY(launch_pyr_fused(ctx, pyr_rgb ? nullptr : gray, d_frames, nf, h, w, p, imgs, poly_u8));
+  // ... and on that path the role-split pyramid reads the RGB frames itself and leaves the gray frames behind for the level-0
+  // expansion: no luma pass (k_pyr_roles<false, true>; 4-byte aligned frames).  ST_PYR_ROLES_RGB=0 (read at st_ctx_create)
+  // restores the separate pass; bit-identical either way.
+  const bool roles_rgb = poly_u8 && aligned4 && ctx->pyr_roles_rgb;
+  if (!pyr_rgb && !roles_rgb) {
+    ST_TRY(launch_gray(ctx, d_frames, nf, h, w, p.gray_bits, gray, aligned4, small_tables ? &ta : nullptr));
+  } else if (small_tables) {
+    hipLaunchKernelGGL(k_set_tables, dim3(1), dim3(64), 0, ctx->stream, ta);
+    ST_HIP(ctx, hipGetLastError());
+  }
+  if (pyr1) ST_TRY(launch_pyr_fused(ctx, pyr_rgb ? nullptr : gray, d_frames, nf, h, w, p, imgs, poly_u8, roles_rgb));
   // Small batches: the expansions of all levels in ONE launch (level 0 first, the coarse levels fill its tail).  Measured
   // against the former arrangement -- level 0 on a second, low-priority stream beside the coarse levels' iterations --
   // at 1 / 2 / 4 / 8 pairs of 1080p per call: 292 / 444 / 731 / 1193 us per step against 308 / 458 / 744 / 1197: the

@@ -34,6 +34,7 @@ struct st_ctx {
   // role-split kernels (scheduling switches like tile_mode, read when the context is created; results do not depend on them):
   // ST_ITER_ROLES / ST_PYR_ROLES: -1 by launch size (default), 0 never, 1 always; ST_ROLES_NCW: 0 = by cost, 4 or 5 column waves
   int roles_mode = -1, roles_ncw = 0, pyr_roles = -1;
+  bool pyr_roles_rgb = true;  // ST_PYR_ROLES_RGB=0: large calls run the separate luma pass (k_gray4) ahead of the role-split pyramid instead of its RGB-source instance
   int conv_tile = -1;   // ST_CONV_TILE: 0 = bf16x3 convolutions always on the per-tap kernel (st_conv.hip)
   // Concurrent kernel instances (Scanner's pipeline_instances_per_node: K contexts of one process on one GPU, each call followed
   // by st_ctx_sync).  flow_busy: an OpticalFlow call of this context has been enqueued and not yet synchronised; flow_enter_ns:
