@@ -2955,10 +2955,32 @@ int rows_per_segment(st_ctx* ctx, int h, int strips, int batch, int halo) {
 }
 
 // Segment height of the polynomial expansion (a scheduling choice: the vertical pass is a direct 11-tap sum, so a
-// pixel's value does not depend on where its segment starts).  Large launches take whole-height segments; a launch
-// of a few frames is latency-bound (a workgroup marches its rows one barrier per 4 rows), so it is cut into many
-// short segments even though each re-reads 2N rows of context.
-int polyexp_rows(st_ctx* ctx, int h, int strips, int n, int poly_n) {
+// pixel's value does not depend on where its segment starts).  A workgroup marches its rows one barrier per 4 rows and
+// a new segment only re-reads 2N rows of a 1 or 4 B/px source against 20 B/px written, so segments are cheap and short
+// ones are what every launch wants: a launch of a few frames is latency-bound and needs the workgroups, and a launch of
+// many frames ends on a nearly empty chip for as long as its last workgroups march (257 frames of 1080p in whole-height
+// segments: 2056 workgroups of 1080 rows on 256 CUs that hold 5 each -- one frame more than 256 cost the level-0 launch
+// 261 us, twenty times its share).
+//
+// Two steps.  (1) The floor on parallelism, the former rule: at least num_cus * 8 workgroups where the height allows.
+// (2) Among that cut and every finer one down to 12 rows, the cheapest by the model the segment sweep supports
+// (profiles/polyexp_segments_sweep.txt: 257 frames of 1080p, levels 0 and 1, 1 to 90 segments), in rows marched per CU:
+//     cost = strips * n * (h + segments * c) / num_cus  +  kPolyexpTail * (rows + c)
+// the launch's work spread evenly over the CUs (a CU's rate does not depend on how many workgroups it holds: the kernel
+// is bound by its vector ALU) plus a tail in which the chip drains, proportional to one segment's march.  c is a
+// workgroup's fixed cost in rows: 1.5 for the gray-source instance (its 3-row blur window is set up per segment), not
+// resolved from 0 for the float-source one, whose launches therefore take the 12-row minimum.  A rounds model
+// (ceil(workgroups / resident) rounds of rows + c, as launch_flow_iter's) fits the sweep five times worse: the
+// workgroups of a partly filled round run faster, so whole rounds buy nothing here and the residency does not enter.
+// A finer cut never has fewer workgroups, so step 2 cannot take a small launch's parallelism away; ties keep the taller segment.
+constexpr double kPolyexpSegCostU8 = 1.5, kPolyexpSegCostF32 = 0.0, kPolyexpTail = 0.85;
+
+double polyexp_plan_cost(int h, long long per, int num_cus, int rows, double c) {
+  const long long nseg = (h + rows - 1) / rows;
+  return (double)per * (h + nseg * c) / num_cus + kPolyexpTail * ((rows < h ? rows : h) + c);
+}
+
+int polyexp_rows(st_ctx* ctx, int h, int strips, int n, bool gray_source) {
   const int min_rows = 12;  // measured at 1-8 pairs of 1080p: 12 rows +4 % over the former 44, nothing below
   const long long target = (long long)ctx->num_cus * 8, per = (long long)strips * n;
   long long segs = (target + per - 1) / per;
@@ -2967,6 +2989,12 @@ int polyexp_rows(st_ctx* ctx, int h, int strips, int n, int poly_n) {
   rows = (rows + PE_RB - 1) / PE_RB * PE_RB;
   if (rows < min_rows) rows = min_rows;
   if (rows > h) rows = h;
+  const double c = gray_source ? kPolyexpSegCostU8 : kPolyexpSegCostF32;
+  double best = polyexp_plan_cost(h, per, ctx->num_cus, rows, c);
+  for (int r = (rows - 1) / PE_RB * PE_RB; r >= min_rows && (h + r - 1) / r <= 65535; r -= PE_RB) {   // (grid.y)
+    const double cost = polyexp_plan_cost(h, per, ctx->num_cus, r, c);
+    if (cost < best) { best = cost; rows = r; }
+  }
   return rows;
 }
 
@@ -3126,7 +3154,7 @@ int launch_polyexp(st_ctx* ctx, const float* img, int n, int h, int w, int poly_
   a.img = img; a.gray = gray; a.R = R; a.h = h; a.w = w;
   poly_prepare(poly_n, poly_sigma, &a.c);
   const int strips = (w + PE_OUT - 1) / PE_OUT;
-  a.rows_per_seg = polyexp_rows(ctx, h, strips, n, poly_n);
+  a.rows_per_seg = polyexp_rows(ctx, h, strips, n, gray != nullptr);
   dim3 grid(strips, (h + a.rows_per_seg - 1) / a.rows_per_seg, n);
   st_timed t(ctx, ST_K_POLYEXP);
   if (gray && w < 8) return st_set_error(ctx, ST_ERR_INVALID, "polyexp: the gray-source instance needs rows of at least 8 pixels");
@@ -3154,7 +3182,7 @@ int launch_polyexp_ml(st_ctx* ctx, float* const* imgs, const LevelGeom* geom, fl
     if (!polyexp_frame_fits(g.lh, g.lw)) return st_set_error(ctx, ST_ERR_UNSUPPORTED, "polyexp: frames above 64 M pixels are not supported");
     l.img = imgs[ks[i]]; l.R = R[ks[i]]; l.h = g.lh; l.w = g.lw;
     l.strips = (g.lw + PE_OUT - 1) / PE_OUT;
-    l.rows_per_seg = polyexp_rows(ctx, g.lh, l.strips, n, poly_n);
+    l.rows_per_seg = polyexp_rows(ctx, g.lh, l.strips, n, false);
     l.block0 = blocks;
     blocks += l.strips * ((g.lh + l.rows_per_seg - 1) / l.rows_per_seg);
   }
