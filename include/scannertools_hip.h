@@ -99,7 +99,7 @@ enum st_kernel_id {
   ST_K_CPM2_RESIZE = 14,
   ST_K_CPM2_NMS = 15,      /* the library's non-maximum suppressions: CPM2's peak search and the FacenetOutput launches (decode, sort + greedy NMS, pack) */
   ST_K_FRAME_STATS = 16, /* moments + finishing launches of the frame-statistics ops */
-  ST_K_JPEG = 17,        /* inverse DCT + upsample / colour launches of the ImageDecoder op */
+  ST_K_JPEG = 17,        /* inverse DCT + upsample / colour launches of the ImageDecoder op; the ImageEncoder op's four launches */
   ST_K_NET_INPUT = 18,   /* the FacenetInput and CaffeInput launches */
   ST_K_COUNT = 19
 };
@@ -671,6 +671,44 @@ int st_jpeg_coefficients(const uint8_t* buf, size_t size, int16_t* coef, size_t 
  * sub-batches already enqueued are (a call of at most ST_JPEG_THREADS streams is one sub-batch: nothing is written). */
 int st_jpeg_decode_batch(st_ctx* ctx, const uint8_t* const* bufs_host, const size_t* sizes, int n, int h, int w, int channels,
                          uint8_t* const* out_dev);
+
+/* ---- ImageEncoder: baseline JPEG ------------------------------------------------------------
+ * The counterpart of the ImageDecoder block (Scanner's stdlib ImageEncoder wraps cv::imencode on the host; it is not part of
+ * the reference tree).  Resident (h, w, 3) uint8 frames in R, G, B order become baseline JPEG streams; colour conversion,
+ * chroma downsampling, forward DCT, quantisation AND the Huffman coding run in HIP kernels, so only the compressed streams
+ * cross to the host.  A stream is, byte for byte, what libjpeg(-turbo) writes for the same picture at the same quality and
+ * sampling with JDCT_ISLOW, the standard (Annex K) Huffman tables and one restart interval per MCU row (Pillow:
+ * save(quality=q, subsampling=s, restart_marker_rows=1)): SOI, JFIF APP0, DQT luma, DQT chroma, SOF0, four DHT, DRI (= MCUs
+ * per row), SOS, the scan with RST0..7 cycling between MCU rows, EOI.  Three YCbCr components, one interleaved scan, luma
+ * sampling h_samp x v_samp = 1x1 (4:4:4), 2x1 (4:2:2) or 2x2 (4:2:0), chroma 1x1.  DESIGN.md section 4.16 restates the
+ * arithmetic.  Not written: grayscale or 4-channel frames, optimised Huffman tables, progressive streams, EXIF / ICC.
+ *
+ * Host only (no context, no GPU), re-entrant: */
+/* The quantisation tables of `quality` (1..100) in natural (row-major) order: the Annex K tables scaled as libjpeg's
+ * jpeg_set_quality with force_baseline does.  ST_ERR_INVALID: quality out of range, a null pointer. */
+int st_jpeg_quant_tables(int quality, uint16_t luma[64], uint16_t chroma[64]);
+/* The stream's bytes from SOI up to and including SOS (629 for every stream this encoder writes) into buf[0, cap); *size (may
+ * be null) receives their number whenever the other arguments are valid.  ST_ERR_INVALID: quality outside 1..100, h or w
+ * outside 1..65535, buf null or cap too small; ST_ERR_UNSUPPORTED: another sampling. */
+int st_jpeg_encode_header(int h, int w, int quality, int h_samp, int v_samp, uint8_t* buf, size_t cap, size_t* size);
+/* An upper bound of a stream's bytes whatever the picture and quality: the header, 416 bytes per coded 8 x 8 block (padding
+ * blocks included: 1660 bits of codes at most, every byte stuffed), the RST markers and EOI.  -1 for arguments
+ * st_jpeg_encode_header refuses. */
+long long st_jpeg_encode_bound(int h, int w, int h_samp, int v_samp);
+/* frames_dev: host array of n device pointers to dense (h, w, 3) uint8 frames, any alignment.  Enqueues the encoder's four
+ * launches on the context's stream and returns without waiting (it waits only where its buffers have to grow, or for the upload
+ * of new tables when h, w, quality or sampling differ from the last call's); the streams stay in a buffer of the context until its next
+ * st_jpeg_encode_batch call, st_jpeg_encode_fetch copies them.  Refused before anything is launched, the message naming the
+ * cause: ST_ERR_INVALID for n < 0, quality outside 1..100, h or w outside 1..65535, a null table or frame pointer;
+ * ST_ERR_UNSUPPORTED for a sampling other than 1x1, 2x1, 2x2 and for more than 2^31 - 1 MCU rows in all.  n = 0 is a successful
+ * no-op.  Device memory of a call: 128 bytes of coefficients and 2 x 416 bytes of stream space per coded block. */
+int st_jpeg_encode_batch(st_ctx* ctx, const uint8_t* const* frames_dev, int n, int h, int w, int quality, int h_samp, int v_samp);
+/* The streams of the context's last st_jpeg_encode_batch call.  sizes[i] receives stream i's bytes; bufs_host: n host buffers of
+ * `capacity` bytes each, or null to learn the sizes alone.  One wait for the kernels, with the copy of the stream offsets;
+ * then all streams come in ONE device-to-host copy of exactly their bytes and are handed out on the host.  ST_ERR_INVALID: no
+ * call to fetch from, sizes null, a null buffer, a stream longer than capacity (sizes is filled in all the same, nothing is
+ * copied). */
+int st_jpeg_encode_fetch(st_ctx* ctx, uint8_t* const* bufs_host, size_t* sizes, size_t capacity);
 
 #ifdef __cplusplus
 }

@@ -125,6 +125,23 @@ def parse_image_decoder_args(buf):
     return out
 
 
+def image_encoder_args(quality=0, subsampling=""):
+    """A serialised ImageEncoderArgs (scannertools_imgproc_amd.proto): quality = 1, subsampling = 2.  The defaults (0, "") are
+    not written, as proto3 does; the op then takes quality 95 and "4:2:0"."""
+    return encode([(1, "int32", int(quality)), (2, "string", subsampling or "")])
+
+
+def parse_image_encoder_args(buf):
+    """{'quality': int, 'subsampling': str} of a serialised ImageEncoderArgs; an absent field is left out."""
+    out = {}
+    for number, wt, value in fields(buf):
+        if number == 1 and wt == 0:
+            out["quality"] = value - (1 << 64) if value >> 63 else value
+        elif number == 2 and wt == 2:
+            out["subsampling"] = bytes(value).decode()
+    return out
+
+
 def repeated_float(number, values, packed=True):
     """A `repeated float` field: packed (one length-delimited field, what proto3 writes) or unpacked (one fixed32 field per
     value, zeros included).  No values: nothing."""

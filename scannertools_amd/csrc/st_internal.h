@@ -56,8 +56,10 @@ struct st_ctx {
   struct st_jpeg_state* jpeg = nullptr;   // page-locked slots of st_jpeg_decode_batch (st_jpeg.hip), made at its first call
   struct st_netin_state* netin = nullptr; // per-geometry tables of the FacenetInput / CaffeInput entry points (st_netinput.hip)
   struct st_detect_state* detect = nullptr; // the kept rows of the last st_facenet_output_batch call (st_detect.hip)
+  struct st_jpeg_enc_state* jpeg_enc = nullptr; // tables and the packed streams of the last st_jpeg_encode_batch call (st_jpeg_enc.hip)
 };
 void st_jpeg_release(st_ctx* ctx);   // frees ctx->jpeg (st_ctx_destroy)
+void st_jpeg_enc_release(st_ctx* ctx); // frees ctx->jpeg_enc (st_ctx_destroy)
 void st_netin_release(st_ctx* ctx);  // frees ctx->netin (st_ctx_destroy)
 void st_detect_release(st_ctx* ctx); // frees ctx->detect (st_ctx_destroy)
 

@@ -1,0 +1,591 @@
+// ImageEncoder op, baseline JPEG: st_jpeg_encode_batch / st_jpeg_encode_fetch and their kernels.
+//
+// Resident (h, w, 3) uint8 frames become the streams libjpeg(-turbo) writes for them at the same quality and sampling with
+// one restart interval per MCU row (include/scannertools_hip.h), byte for byte.  Everything runs on the GPU;
+// only the finished streams cross to the host.  Four launches per call, no waiting between workgroups:
+//   k_jpeg_fdct     one thread per 8 x 8 block: jccolor's RGB -> YCbCr, jcsample's h2v1 / h2v2 box filter with its
+//                   alternating bias, the edge replication, jfdctint's forward DCT and the quantisation, all in registers;
+//                   int16 coefficients in zigzag order, blocks in MCU order (padding blocks included), to the workspace
+//   k_jpeg_entropy  one wave per restart interval, 64 blocks at a time: each lane measures its block's code length, a wave
+//                   prefix sum places the blocks, the lanes OR their codes into a bit buffer in LDS (words on block
+//                   boundaries are shared, hence ds_or), a second prefix sum over the 0xFF bytes places the stuffed zeros; the
+//                   bytes go to the interval's slot, its length to a table.  A slot has the proven worst-case size
+//                   (st_jpeg_enc_host.h: 416 bytes per block), so no interval depends on another's length.
+//   k_jpeg_layout   one workgroup: every interval's offset in its stream (header, lengths, + 2 per RST marker), every
+//                   stream's size, and the exclusive scan of the sizes = each stream's offset in the packed buffer
+//   k_jpeg_pack     one workgroup per interval: copies the header (the frame's first interval), the interval's bytes and the
+//                   marker that follows them (RSTn, or EOI after the last) to their place
+// The header (SOI .. SOS) and the Huffman code tables are built on the host once per (h, w, quality, sampling) and uploaded.
+#include <climits>
+#include <cstring>
+#include <vector>
+
+#include "st_internal.h"
+#include "st_jpeg_enc_host.h"
+
+struct st_jpeg_enc_state {
+  // device: the header bytes at 0, the Huffman code words at kParamsHuff; what they were built for
+  uint8_t* params = nullptr;
+  int key[5] = {0, 0, 0, 0, 0};
+  std::vector<uint8_t> params_host;
+  // the streams of the last st_jpeg_encode_batch call, packed one after the other, and their n + 1 offsets
+  uint8_t* blob = nullptr;
+  size_t blob_cap = 0;
+  unsigned long long* offs = nullptr;
+  size_t offs_cap = 0;
+  int n = -1;   // streams of the last call; -1: none to fetch
+  // st_jpeg_encode_fetch: page-locked staging for the one copy of the packed streams
+  uint8_t* pin = nullptr;
+  size_t pin_cap = 0;
+  std::vector<unsigned long long> offs_host;
+};
+
+void st_jpeg_enc_release(st_ctx* ctx) {
+  st_jpeg_enc_state* s = ctx->jpeg_enc;
+  if (!s) return;
+  if (s->params) (void)hipFree(s->params);
+  if (s->blob) (void)hipFree(s->blob);
+  if (s->offs) (void)hipFree(s->offs);
+  if (s->pin) (void)hipHostFree(s->pin);
+  delete s;
+  ctx->jpeg_enc = nullptr;
+}
+
+namespace {
+
+typedef unsigned long long u64;
+
+constexpr size_t kParamsHuff = 640;   // the header's 629 bytes, padded
+constexpr size_t kParamsBytes = kParamsHuff + sizeof(uint32_t) * kJpegEncHuffWords;
+
+// ---- colour, downsampling, forward DCT, quantisation ---------------------------------------------------------------------
+struct EncTransformK {
+  const uint8_t* const* frames;
+  int16_t* coef;          // 64 per block; blocks of an interval in MCU order, intervals frame after frame
+  long long total;        // blocks in all
+  int h, w, mcols, mrows;
+  int nbx, nby;           // real luma blocks per row / column
+  int ch;                 // chroma rows
+  unsigned short div[2][64];   // 8 * the quantisation tables (luma, chroma), natural order
+};
+
+// jccolor.c in 16 fractional bits
+__device__ __forceinline__ int ycc_y(int r, int g, int b) { return (19595 * r + 38470 * g + 7471 * b + 32768) >> 16; }
+__device__ __forceinline__ int ycc_c(int r, int g, int b, int c) {
+  return c == 0 ? (-11059 * r - 21709 * g + 32768 * b + (128 << 16) + 32767) >> 16
+                : (32768 * r - 27439 * g - 5329 * b + (128 << 16) + 32767) >> 16;
+}
+
+// One pass of jfdctint's 8-point forward DCT (CONST_BITS 13, PASS1_BITS 2) over d[0 .. 7 * S] in place.  FIRST: outputs 0 and 4
+// are << 2 and the others descaled by 11 bits; otherwise outputs 0 and 4 are descaled by 2 bits and the others by 15.
+template <bool FIRST, int S>
+__device__ __forceinline__ void fdct_pass(int* d) {
+  const int t0 = d[0] + d[7 * S], t7 = d[0] - d[7 * S], t1 = d[S] + d[6 * S], t6 = d[S] - d[6 * S];
+  const int t2 = d[2 * S] + d[5 * S], t5 = d[2 * S] - d[5 * S], t3 = d[3 * S] + d[4 * S], t4 = d[3 * S] - d[4 * S];
+  const int t10 = t0 + t3, t13 = t0 - t3, t11 = t1 + t2, t12 = t1 - t2;
+  constexpr int N = FIRST ? 11 : 15, R = 1 << (N - 1);
+  if (FIRST) {
+    d[0] = (t10 + t11) << 2;
+    d[4 * S] = (t10 - t11) << 2;
+  } else {
+    d[0] = (t10 + t11 + 2) >> 2;
+    d[4 * S] = (t10 - t11 + 2) >> 2;
+  }
+  int z1 = (t12 + t13) * 4433;
+  d[2 * S] = (z1 + t13 * 6270 + R) >> N;
+  d[6 * S] = (z1 - t12 * 15137 + R) >> N;
+  z1 = t4 + t7;
+  int z2 = t5 + t6, z3 = t4 + t6, z4 = t5 + t7;
+  const int z5 = (z3 + z4) * 9633;
+  const int a4 = t4 * 2446, a5 = t5 * 16819, a6 = t6 * 25172, a7 = t7 * 12299;
+  z1 *= -7373; z2 *= -20995;
+  z3 = z3 * -16069 + z5; z4 = z4 * -3196 + z5;
+  d[7 * S] = (a4 + z1 + z3 + R) >> N;
+  d[5 * S] = (a5 + z2 + z4 + R) >> N;
+  d[3 * S] = (a6 + z2 + z3 + R) >> N;
+  d[S] = (a7 + z1 + z4 + R) >> N;
+}
+
+__device__ constexpr unsigned char kZigzag[64] = {ST_JPEG_ENC_ZIGZAG};
+
+// Threads of an interval are numbered block-in-MCU first (all MCUs' first luma block, then their second, ...), so a wave works
+// on one component and on neighbouring pixels; the block is stored at its place in MCU order.
+template <int HS, int VS>
+__global__ __launch_bounds__(256) void k_jpeg_fdct(EncTransformK a) {
+  constexpr int NL = HS * VS, BPM = NL + 2;
+  const int nblk = a.mcols * BPM;
+  for (long long g = (long long)blockIdx.x * 256 + threadIdx.x; g < a.total; g += (long long)gridDim.x * 256) {
+    const long long iv = g / nblk;
+    const int t = (int)(g - iv * nblk);
+    const int f = (int)(iv / a.mrows), my = (int)(iv - (long long)f * a.mrows);
+    const int k = t / a.mcols, mx = t - k * a.mcols;
+    const uint8_t* __restrict__ F = st_gl(a.frames[f]);
+    const size_t pitch = (size_t)a.w * 3;
+    int v[64];
+    bool pad = false;
+    if (k < NL) {
+      int bx = mx * HS + k % HS, by = my * VS + k / HS;
+      // A padding block repeats the quantised DC of the block before it in MCU order and has no AC terms: in a dummy block row
+      // that is the last block of the row above in the same MCU, to the right of the picture the row's last real block.
+      if (by >= a.nby) {
+        pad = true;
+        by = a.nby - 1;
+        bx = mx * HS + HS - 1;
+      }
+      if (bx >= a.nbx) {
+        pad = true;
+        bx = a.nbx - 1;
+      }
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const int y = by * 8 + j < a.h ? by * 8 + j : a.h - 1;
+        const uint8_t* __restrict__ R = F + (size_t)y * pitch;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+          const int x = bx * 8 + i < a.w ? bx * 8 + i : a.w - 1;
+          v[j * 8 + i] = ycc_y(R[3 * x], R[3 * x + 1], R[3 * x + 2]) - 128;
+        }
+      }
+    } else {
+      const int c = k - NL;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        // the downsampled component's last row is replicated downwards; below the picture the input's last row is
+        const int cy = my * 8 + j < a.ch ? my * 8 + j : a.ch - 1;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+          const int cx = mx * 8 + i;
+          int acc = 0;
+#pragma unroll
+          for (int dy = 0; dy < VS; ++dy) {
+            const int y = cy * VS + dy < a.h ? cy * VS + dy : a.h - 1;
+            const uint8_t* __restrict__ R = F + (size_t)y * pitch;
+#pragma unroll
+            for (int dx = 0; dx < HS; ++dx) {
+              const int x = cx * HS + dx < a.w ? cx * HS + dx : a.w - 1;
+              acc += ycc_c(R[3 * x], R[3 * x + 1], R[3 * x + 2], c);
+            }
+          }
+          if (HS == 2 && VS == 1) acc = (acc + (cx & 1)) >> 1;
+          if (HS == 2 && VS == 2) acc = (acc + 1 + (cx & 1)) >> 2;
+          v[j * 8 + i] = acc - 128;
+        }
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < 8; ++j) fdct_pass<true, 1>(v + 8 * j);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) fdct_pass<false, 8>(v + i);
+    const int tq = k < NL ? 0 : 1;
+    int q[64];
+#pragma unroll
+    for (int i = 0; i < 64; ++i) {
+      const unsigned d = a.div[tq][i];
+      const int x = v[i];
+      unsigned m = ((unsigned)(x < 0 ? -x : x) + (d >> 1)) / d;
+      if (i > 0 && m > 1023u) m = 1023u;   // ten magnitude bits: no 8-bit picture gets there (st_jpeg_enc_host.h)
+      q[i] = x < 0 ? -(int)m : (int)m;
+      if (i > 0 && pad) q[i] = 0;
+    }
+    uint4* __restrict__ out = reinterpret_cast<uint4*>(a.coef + ((size_t)iv * nblk + (size_t)mx * BPM + k) * 64);
+#pragma unroll
+    for (int s = 0; s < 8; ++s) {
+      unsigned wd[4];
+#pragma unroll
+      for (int p = 0; p < 4; ++p)
+        wd[p] = ((unsigned)q[kZigzag[8 * s + 2 * p]] & 0xffffu) | ((unsigned)q[kZigzag[8 * s + 2 * p + 1]] << 16);
+      out[s] = make_uint4(wd[0], wd[1], wd[2], wd[3]);
+    }
+  }
+}
+
+// ---- entropy coding -------------------------------------------------------------------------------------------------------
+constexpr int kChunk = 64;                                                     // blocks per pass of the wave, one per lane
+constexpr int kRawBits = kChunk * kJpegEncBlockBits + 7 + 7;                   // carried-in bits in front, padding behind
+constexpr int kRawWords = (kRawBits + 31) / 32 + 1;
+constexpr int kOutBytes = ((kRawBits + 7) / 8) * 2;                            // every byte stuffed
+constexpr int kCoefPitch = 33;                                                 // dwords per lane: 32 of coefficients + 1 against bank conflicts
+
+struct EncEntropyK {
+  const int16_t* coef;
+  const uint32_t* huff;
+  uint8_t* slots;
+  unsigned* ilen;
+  size_t slot_bytes;
+  int nblk, bpm, nluma;
+};
+
+// nb bits (the low ones of val) at bit p of the stream; bit 0 of the stream is the top bit of raw[0]
+__device__ __forceinline__ void put_bits(uint32_t* raw, int p, uint32_t val, int nb) {
+  const int wd = p >> 5, sh = 32 - (p & 31) - nb;
+  if (sh >= 0) {
+    atomicOr(&raw[wd], val << sh);
+  } else {
+    atomicOr(&raw[wd], val >> -sh);
+    atomicOr(&raw[wd + 1], val << (32 + sh));
+  }
+}
+
+// A value's magnitude category and its bits (negative values as ones' complement)
+__device__ __forceinline__ void magnitude(int v, int most, int* nb, uint32_t* bits) {
+  const int t = v < 0 ? -v : v;
+  int n = 32 - __clz(t);   // 0 for 0
+  n = n > most ? most : n;
+  *nb = n;
+  *bits = (uint32_t)(v < 0 ? v - 1 : v) & ((1u << n) - 1u);
+}
+
+// jchuff's encode_one_block: the code length of the block; EMIT: also written at bit `pos`
+template <bool EMIT>
+__device__ __forceinline__ int code_block(const uint32_t* mine, const uint32_t* dc_tab, const uint32_t* ac_tab, int diff, uint32_t* raw, int pos) {
+  int len = 0, nb;
+  uint32_t mb;
+  magnitude(diff, 11, &nb, &mb);
+  {
+    const uint32_t hc = dc_tab[nb];
+    const int cl = (int)(hc >> 16);
+    if (EMIT) put_bits(raw, pos, ((hc & 0xffffu) << nb) | mb, cl + nb);
+    len += cl + nb;
+  }
+  int run = 0;
+  for (int k = 1; k < 64; ++k) {
+    const uint32_t wd = mine[k >> 1];
+    const int v = (int)(short)((k & 1) ? (wd >> 16) : (wd & 0xffffu));
+    if (v == 0) {
+      ++run;
+      continue;
+    }
+    while (run >= 16) {
+      const uint32_t hc = ac_tab[0xF0];
+      if (EMIT) put_bits(raw, pos + len, hc & 0xffffu, (int)(hc >> 16));
+      len += (int)(hc >> 16);
+      run -= 16;
+    }
+    magnitude(v, 10, &nb, &mb);
+    const uint32_t hc = ac_tab[(run << 4) | nb];
+    const int cl = (int)(hc >> 16);
+    if (EMIT) put_bits(raw, pos + len, ((hc & 0xffffu) << nb) | mb, cl + nb);
+    len += cl + nb;
+    run = 0;
+  }
+  if (run > 0) {
+    const uint32_t hc = ac_tab[0];
+    if (EMIT) put_bits(raw, pos + len, hc & 0xffffu, (int)(hc >> 16));
+    len += (int)(hc >> 16);
+  }
+  return len;
+}
+
+__device__ __forceinline__ int wave_inclusive_scan(int v, int lane) {
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const int t = __shfl_up(v, d);
+    if (lane >= d) v += t;
+  }
+  return v;
+}
+
+__device__ __forceinline__ unsigned raw_byte(const uint32_t* raw, int j) { return (raw[j >> 2] >> (24 - 8 * (j & 3))) & 0xffu; }
+
+// One wave per restart interval.
+__global__ __launch_bounds__(64) void k_jpeg_entropy(EncEntropyK a) {
+  __shared__ uint32_t s_huff[kJpegEncHuffWords];
+  __shared__ uint32_t s_coef[kChunk * kCoefPitch];
+  __shared__ uint32_t s_raw[kRawWords];
+  __shared__ uint8_t s_out[kOutBytes];
+  const int lane = threadIdx.x;
+  const size_t iv = blockIdx.x;
+  for (int i = lane; i < kJpegEncHuffWords; i += 64) s_huff[i] = a.huff[i];
+  const int16_t* __restrict__ C = a.coef + iv * (size_t)a.nblk * 64;
+  uint8_t* __restrict__ slot = a.slots + iv * a.slot_bytes;
+  uint32_t* mine = s_coef + lane * kCoefPitch;
+  size_t out_pos = 0;
+  int carry_bits = 0;        // bits of the last, unfinished byte of the previous chunk
+  uint32_t carry_val = 0;
+  for (int b0 = 0; b0 < a.nblk; b0 += kChunk) {
+    const int b = b0 + lane;
+    const bool live = b < a.nblk;
+    for (int i = lane; i < kRawWords; i += 64) s_raw[i] = 0;
+    int diff = 0;
+    const uint32_t *dc_tab = s_huff, *ac_tab = s_huff + 32;
+    if (live) {
+      const uint4* __restrict__ src = reinterpret_cast<const uint4*>(C + (size_t)b * 64);
+#pragma unroll
+      for (int s = 0; s < 8; ++s) {
+        const uint4 t = src[s];
+        mine[4 * s] = t.x; mine[4 * s + 1] = t.y; mine[4 * s + 2] = t.z; mine[4 * s + 3] = t.w;
+      }
+      // the DC difference to the previous block of the same component; 0 predicts the interval's first
+      const int k = b % a.bpm, m = b / a.bpm;
+      int prev;
+      if (k < a.nluma) {
+        prev = k > 0 ? b - 1 : (m > 0 ? b - a.bpm + a.nluma - 1 : -1);
+      } else {
+        prev = m > 0 ? b - a.bpm : -1;
+        dc_tab = s_huff + 16;
+        ac_tab = s_huff + 288;
+      }
+      diff = (int)C[(size_t)b * 64] - (prev >= 0 ? (int)C[(size_t)prev * 64] : 0);
+    }
+    __syncthreads();
+    const int len = live ? code_block<false>(mine, dc_tab, ac_tab, diff, nullptr, 0) : 0;
+    const int incl = wave_inclusive_scan(len, lane);
+    int total = carry_bits + __shfl(incl, 63);
+    if (lane == 0 && carry_bits) atomicOr(&s_raw[0], carry_val << (32 - carry_bits));
+    if (live) (void)code_block<true>(mine, dc_tab, ac_tab, diff, s_raw, carry_bits + incl - len);
+    if (b0 + kChunk >= a.nblk && (total & 7)) {   // the interval's last byte is filled with 1-bits
+      const int fill = 8 - (total & 7);
+      if (lane == 0) put_bits(s_raw, total, (1u << fill) - 1u, fill);
+      total += fill;
+    }
+    __syncthreads();
+    // byte stuffing: each lane takes a run of the chunk's whole bytes
+    const int nbytes = total >> 3;
+    const int per = (nbytes + 63) / 64;
+    const int s0 = lane * per < nbytes ? lane * per : nbytes, s1 = s0 + per < nbytes ? s0 + per : nbytes;
+    int ff = 0;
+    for (int j = s0; j < s1; ++j) ff += raw_byte(s_raw, j) == 0xffu;
+    const int ffi = wave_inclusive_scan(ff, lane);
+    const int stuffed = nbytes + __shfl(ffi, 63);
+    int o = s0 + ffi - ff;
+    for (int j = s0; j < s1; ++j) {
+      const unsigned v = raw_byte(s_raw, j);
+      s_out[o++] = (uint8_t)v;
+      if (v == 0xffu) s_out[o++] = 0;
+    }
+    carry_bits = total & 7;
+    carry_val = carry_bits ? raw_byte(s_raw, nbytes) >> (8 - carry_bits) : 0u;
+    __syncthreads();
+    for (int j = lane; j < stuffed; j += 64)
+      if (out_pos + j < a.slot_bytes) slot[out_pos + j] = s_out[j];   // always: the slot holds the worst case
+    out_pos += stuffed;
+    __syncthreads();
+  }
+  if (lane == 0) a.ilen[iv] = (unsigned)out_pos;
+}
+
+// ---- layout and packing -----------------------------------------------------------------------------------------------------
+struct EncLayoutK {
+  const unsigned* ilen;
+  u64* ioff;    // per interval: its offset in its stream
+  u64* offs;    // n + 1: each stream's offset in the packed buffer, then the total
+  int n, mrows;
+};
+
+__global__ __launch_bounds__(1024) void k_jpeg_layout(EncLayoutK a) {
+  __shared__ u64 part[1024];
+  const int tid = threadIdx.x;
+  const long long per = ((long long)a.n + 1023) / 1024;
+  const long long f0 = tid * per < a.n ? tid * per : a.n, f1 = f0 + per < a.n ? f0 + per : a.n;
+  u64 sum = 0;
+  for (long long f = f0; f < f1; ++f) {
+    u64 o = kJpegEncHeaderBytes;
+    for (int r = 0; r < a.mrows; ++r) {
+      const size_t iv = (size_t)f * a.mrows + r;
+      a.ioff[iv] = o;
+      o += (u64)a.ilen[iv] + 2;   // the interval, then RSTn or (after the last) EOI
+    }
+    a.offs[f] = o;   // the stream's size for now
+    sum += o;
+  }
+  part[tid] = sum;
+  __syncthreads();
+  if (tid == 0) {
+    u64 run = 0;
+    for (int i = 0; i < 1024; ++i) {
+      const u64 p = part[i];
+      part[i] = run;
+      run += p;
+    }
+    a.offs[a.n] = run;
+  }
+  __syncthreads();
+  u64 run = part[tid];
+  for (long long f = f0; f < f1; ++f) {
+    const u64 size = a.offs[f];
+    a.offs[f] = run;
+    run += size;
+  }
+}
+
+struct EncPackK {
+  const uint8_t* slots;
+  const unsigned* ilen;
+  const u64* ioff;
+  const u64* offs;
+  const uint8_t* header;
+  uint8_t* blob;
+  size_t slot_bytes;
+  int mrows;
+};
+
+__global__ __launch_bounds__(256) void k_jpeg_pack(EncPackK a) {
+  const size_t iv = blockIdx.x;
+  const size_t f = iv / (size_t)a.mrows;
+  const int r = (int)(iv - f * (size_t)a.mrows);
+  uint8_t* __restrict__ dst = a.blob + a.offs[f];
+  if (r == 0)
+    for (int j = threadIdx.x; j < (int)kJpegEncHeaderBytes; j += 256) dst[j] = a.header[j];
+  const uint8_t* __restrict__ src = a.slots + iv * a.slot_bytes;
+  const unsigned len = a.ilen[iv];
+  uint8_t* __restrict__ d = dst + a.ioff[iv];
+  for (unsigned j = threadIdx.x; j < len; j += 256) d[j] = src[j];
+  if (threadIdx.x == 0) {
+    d[len] = 0xFF;
+    d[len + 1] = (uint8_t)(r == a.mrows - 1 ? 0xD9 : 0xD0 + (r & 7));
+  }
+}
+
+template <class T>
+int grow(st_ctx* ctx, T** p, size_t* cap, size_t want, const char* what) {
+  if (want <= *cap) return ST_OK;
+  if (*p) ST_HIP(ctx, hipFree(*p));   // waits for the device
+  *p = nullptr;
+  *cap = 0;
+  const size_t bytes = (want + want / 4) * sizeof(T);
+  const hipError_t e = hipMalloc((void**)p, bytes);
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    *p = nullptr;
+    return st_set_error(ctx, ST_ERR_OOM, "jpeg_encode: hipMalloc(%zu) for %s failed: %s", bytes, what, hipGetErrorString(e));
+  }
+  *cap = want + want / 4;
+  return ST_OK;
+}
+
+}  // namespace
+
+ST_EXPORT int st_jpeg_encode_batch(st_ctx* ctx, const uint8_t* const* frames_dev, int n, int h, int w, int quality, int h_samp, int v_samp) {
+  ST_TRY(st_enter(ctx));
+  if (!ctx->jpeg_enc) ctx->jpeg_enc = new st_jpeg_enc_state();
+  st_jpeg_enc_state* s = ctx->jpeg_enc;
+  s->n = -1;   // a call that fails leaves nothing to fetch
+  if (n < 0) return st_set_error(ctx, ST_ERR_INVALID, "jpeg_encode: n = %d is negative", n);
+  char msg[160];
+  const int chk = st_jpeg_enc_check(h, w, quality, h_samp, v_samp, msg, sizeof msg);
+  if (chk != ST_OK) return st_set_error(ctx, chk, "jpeg_encode: %s", msg);
+  if (n == 0) {
+    s->n = 0;
+    return ST_OK;
+  }
+  if (!frames_dev) return st_set_error(ctx, ST_ERR_INVALID, "jpeg_encode: null frame table");
+  for (int i = 0; i < n; ++i)
+    if (!frames_dev[i]) return st_set_error(ctx, ST_ERR_INVALID, "jpeg_encode: frame %d is a null pointer", i);
+  StJpegEncGeom g;
+  st_jpeg_enc_geom(h, w, h_samp, v_samp, &g);
+  const long long intervals = (long long)n * g.mrows;
+  if (intervals > INT_MAX) return st_set_error(ctx, ST_ERR_UNSUPPORTED, "jpeg_encode: %lld restart intervals in one call (at most 2^31 - 1)", intervals);
+  const int nblk = g.mcols * g.bpm;
+  const size_t slot_bytes = st_jpeg_enc_slot_bytes(g);
+  const size_t bound = (size_t)st_jpeg_encode_bound(h, w, h_samp, v_samp);
+
+  // header and code tables, when the call differs from the last one
+  const int key[5] = {h, w, quality, h_samp, v_samp};
+  if (!s->params) {
+    ST_HIP(ctx, hipMalloc((void**)&s->params, kParamsBytes));
+    memset(s->key, 0, sizeof s->key);
+  }
+  if (memcmp(key, s->key, sizeof key) != 0) {
+    ST_HIP(ctx, hipStreamSynchronize(ctx->stream));   // an earlier upload may still read params_host
+    s->params_host.assign(kParamsBytes, 0);
+    size_t hb = 0;
+    (void)st_jpeg_encode_header(h, w, quality, h_samp, v_samp, s->params_host.data(), kParamsHuff, &hb);
+    st_jpeg_enc_huff(reinterpret_cast<uint32_t*>(s->params_host.data() + kParamsHuff));
+    memset(s->key, 0, sizeof s->key);
+    ST_HIP(ctx, hipMemcpyAsync(s->params, s->params_host.data(), kParamsBytes, hipMemcpyHostToDevice, ctx->stream));
+    memcpy(s->key, key, sizeof key);
+  }
+  ST_TRY(grow(ctx, &s->blob, &s->blob_cap, (size_t)n * bound, "the streams"));
+  ST_TRY(grow(ctx, &s->offs, &s->offs_cap, (size_t)n + 1, "the stream offsets"));
+
+  const size_t tb = sizeof(void*) * (size_t)n, cb = (size_t)intervals * (size_t)nblk * 128, sb = (size_t)intervals * slot_bytes;
+  const size_t lb = sizeof(unsigned) * (size_t)intervals, ob = sizeof(u64) * (size_t)intervals;
+  ST_TRY(st_ws_reserve(ctx, st_align_up(tb) + st_align_up(cb) + st_align_up(sb) + st_align_up(lb) + st_align_up(ob)));
+  const uint8_t** d_frames = (const uint8_t**)st_ws_alloc(ctx, tb);
+  int16_t* d_coef = (int16_t*)st_ws_alloc(ctx, cb);
+  uint8_t* d_slots = (uint8_t*)st_ws_alloc(ctx, sb);
+  unsigned* d_ilen = (unsigned*)st_ws_alloc(ctx, lb);
+  u64* d_ioff = (u64*)st_ws_alloc(ctx, ob);
+  if (!d_frames || !d_coef || !d_slots || !d_ilen || !d_ioff) return st_set_error(ctx, ST_ERR_OOM, "jpeg_encode: workspace exhausted");
+  ST_HIP(ctx, hipMemcpyAsync(d_frames, frames_dev, tb, hipMemcpyHostToDevice, ctx->stream));
+
+  EncTransformK t;
+  t.frames = d_frames; t.coef = d_coef; t.total = intervals * nblk;
+  t.h = h; t.w = w; t.mcols = g.mcols; t.mrows = g.mrows; t.nbx = g.nbx; t.nby = g.nby; t.ch = g.ch;
+  uint16_t q[2][64];
+  (void)st_jpeg_quant_tables(quality, q[0], q[1]);
+  for (int c = 0; c < 2; ++c)
+    for (int i = 0; i < 64; ++i) t.div[c][i] = (unsigned short)(q[c][i] * 8);
+  {
+    const long long wgs = (t.total + 255) / 256;
+    const dim3 grid((unsigned)(wgs < 0x7fffffffLL ? wgs : 0x7fffffffLL));
+    st_timed tm(ctx, ST_K_JPEG);
+    if (h_samp == 1) hipLaunchKernelGGL((k_jpeg_fdct<1, 1>), grid, dim3(256), 0, ctx->stream, t);
+    else if (v_samp == 1) hipLaunchKernelGGL((k_jpeg_fdct<2, 1>), grid, dim3(256), 0, ctx->stream, t);
+    else hipLaunchKernelGGL((k_jpeg_fdct<2, 2>), grid, dim3(256), 0, ctx->stream, t);
+    ST_HIP(ctx, hipGetLastError());
+  }
+  EncEntropyK e;
+  e.coef = d_coef; e.huff = reinterpret_cast<const uint32_t*>(s->params + kParamsHuff); e.slots = d_slots; e.ilen = d_ilen;
+  e.slot_bytes = slot_bytes; e.nblk = nblk; e.bpm = g.bpm; e.nluma = g.bpm - 2;
+  {
+    st_timed tm(ctx, ST_K_JPEG);
+    hipLaunchKernelGGL(k_jpeg_entropy, dim3((unsigned)intervals), dim3(64), 0, ctx->stream, e);
+    ST_HIP(ctx, hipGetLastError());
+  }
+  EncLayoutK l;
+  l.ilen = d_ilen; l.ioff = d_ioff; l.offs = s->offs; l.n = n; l.mrows = g.mrows;
+  {
+    st_timed tm(ctx, ST_K_JPEG);
+    hipLaunchKernelGGL(k_jpeg_layout, dim3(1), dim3(1024), 0, ctx->stream, l);
+    ST_HIP(ctx, hipGetLastError());
+  }
+  EncPackK p;
+  p.slots = d_slots; p.ilen = d_ilen; p.ioff = d_ioff; p.offs = s->offs; p.header = s->params; p.blob = s->blob;
+  p.slot_bytes = slot_bytes; p.mrows = g.mrows;
+  {
+    st_timed tm(ctx, ST_K_JPEG);
+    hipLaunchKernelGGL(k_jpeg_pack, dim3((unsigned)intervals), dim3(256), 0, ctx->stream, p);
+    ST_HIP(ctx, hipGetLastError());
+  }
+  s->n = n;
+  return ST_OK;
+}
+
+ST_EXPORT int st_jpeg_encode_fetch(st_ctx* ctx, uint8_t* const* bufs_host, size_t* sizes, size_t capacity) {
+  ST_TRY(st_enter(ctx));
+  st_jpeg_enc_state* s = ctx->jpeg_enc;
+  if (!s || s->n < 0) return st_set_error(ctx, ST_ERR_INVALID, "jpeg_encode_fetch: no st_jpeg_encode_batch call to fetch from");
+  if (s->n == 0) return ST_OK;
+  if (!sizes) return st_set_error(ctx, ST_ERR_INVALID, "jpeg_encode_fetch: null sizes");
+  const size_t n = (size_t)s->n;
+  s->offs_host.resize(n + 1);
+  ST_HIP(ctx, hipMemcpyAsync(s->offs_host.data(), s->offs, sizeof(u64) * (n + 1), hipMemcpyDeviceToHost, ctx->stream));
+  ST_HIP(ctx, hipStreamSynchronize(ctx->stream));   // the one wait for the kernels
+  size_t most = 0;
+  for (size_t i = 0; i < n; ++i) {
+    sizes[i] = (size_t)(s->offs_host[i + 1] - s->offs_host[i]);
+    most = sizes[i] > most ? sizes[i] : most;
+  }
+  if (!bufs_host) return ST_OK;   // the sizes alone
+  if (most > capacity) return st_set_error(ctx, ST_ERR_INVALID, "jpeg_encode_fetch: a stream has %zu bytes, the buffers hold %zu", most, capacity);
+  for (size_t i = 0; i < n; ++i)
+    if (!bufs_host[i]) return st_set_error(ctx, ST_ERR_INVALID, "jpeg_encode_fetch: buffer %zu is a null pointer", i);
+  const size_t total = (size_t)s->offs_host[n];
+  if (total > s->pin_cap) {
+    if (s->pin) ST_HIP(ctx, hipHostFree(s->pin));
+    s->pin = nullptr;
+    s->pin_cap = 0;
+    const size_t want = total + total / 4;
+    if (hipHostMalloc((void**)&s->pin, want, hipHostMallocDefault) != hipSuccess) {
+      (void)hipGetLastError();
+      s->pin = nullptr;
+      return st_set_error(ctx, ST_ERR_OOM, "jpeg_encode_fetch: cannot page-lock %zu bytes for the streams", want);
+    }
+    s->pin_cap = want;
+  }
+  ST_HIP(ctx, hipMemcpyAsync(s->pin, s->blob, total, hipMemcpyDeviceToHost, ctx->stream));   // every stream in one copy
+  ST_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  for (size_t i = 0; i < n; ++i) memcpy(bufs_host[i], s->pin + s->offs_host[i], sizes[i]);
+  return ST_OK;
+}

@@ -624,6 +624,28 @@ class _ImageDecoderNode(_CppMultiOpNode):
         return _CppMultiOpNode.rows(node, idx)
 
 
+class _ImageEncoderNode(_CppMultiOpNode):
+    """ImageEncoder: frames in, a bytes column out.  A requested row that is not an (h, w, 3) uint8 frame, or whose shape differs
+    from the first row's, is a ValueError naming the row, before any kernel instance exists (the kernel class can only abort)."""
+
+    def rows(self, idx):
+        import torch
+        if not idx:
+            return []
+        frames = self.parents[0].rows(idx)
+        first = None
+        for r, f in zip(idx, frames):
+            if isinstance(f, (bytes, bytearray)) or len(f.shape) != 3 or f.shape[2] != 3 or f.dtype not in (np.uint8, torch.uint8):
+                what = "%d bytes" % len(f) if isinstance(f, (bytes, bytearray)) else "%s %s" % (tuple(f.shape), f.dtype)
+                raise ValueError("%s: row %d is %s, not an (h, w, 3) uint8 frame" % (self.name, r, what))
+            first = tuple(f.shape) if first is None else first
+            if tuple(f.shape) != first:
+                raise ValueError("%s: row %d changes shape inside a batch: %s after %s" % (self.name, r, tuple(f.shape), first))
+        node = copy.copy(self)
+        node.parents = [_RowsNode(dict(zip(idx, frames)), self.length())]
+        return _CppMultiOpNode.rows(node, idx)
+
+
 class _PyOpNode(_Node):
     """A batched python op over one input column (ShotBoundaries: batch = whole stream)."""
 
@@ -881,6 +903,14 @@ class _Ops:
         if isinstance(args, dict):
             args = _proto.image_decoder_args(args.get("image_type"))
         return _ImageDecoderNode(self.sc, "ImageDecoder", [img], device, batch, args or b"")
+
+    def ImageEncoder(self, frame, quality=95, subsampling="4:2:0", device=None, batch=None):
+        """sc.ops.ImageEncoder(frame=..., quality=..., subsampling=..., device=..., batch=...): (h, w, 3) uint8 RGB frames ->
+        the column img, one baseline JPEG stream (bytes) per row -- what sc.ops.ImageDecoder(img=...) reads.  Args
+        ImageEncoderArgs{quality = 1, subsampling = 2} (scannertools_imgproc_amd.proto): quality 1..100, subsampling "4:4:4",
+        "4:2:2" or "4:2:0"; anything else fails validation.  The whole encoder, Huffman coding included, runs on the GPU."""
+        from . import _proto
+        return _ImageEncoderNode(self.sc, "ImageEncoder", [frame], device, batch, _proto.image_encoder_args(quality, subsampling))
 
     def InfoFromFrame(self, frame):
         """sc.ops.InfoFromFrame(frame=frame): the frame's FrameInfo as a bytes column."""

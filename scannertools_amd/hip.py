@@ -456,6 +456,34 @@ class HipContext:
         self._check(self._L.st_jpeg_decode_batch(self._h, bufs, sizes, n, shape[1], shape[2], shape[3], to))
         return out
 
+    def encode_jpeg(self, frames, quality=95, subsampling="4:2:0"):
+        """ImageEncoder op: (n, h, w, 3) uint8 CUDA frames (a tensor or a list of (h, w, 3) tensors of one shape), R, G, B
+        order -> a list of n baseline JPEG streams (bytes), byte for byte what libjpeg writes at this quality and sampling
+        with one restart interval per MCU row.  Colour conversion, downsampling, DCT, quantisation and Huffman coding run in
+        HIP kernels on the current stream; only the streams cross to the host, in one copy."""
+        self._bind()
+        hs, vs = jpeg_sampling(subsampling)
+        fr = list(frames) if isinstance(frames, (list, tuple)) else list(frames.unbind(0))
+        n = len(fr)
+        if n == 0:
+            return []
+        if fr[0].dim() != 3 or fr[0].shape[2] != 3:
+            raise ValueError("encode_jpeg takes (h, w, 3) frames, got %s" % (tuple(fr[0].shape),))
+        h, w, _ = fr[0].shape
+        for f in fr:
+            _require_cuda(f, torch.uint8, "frame", self.device)
+            if tuple(f.shape) != (h, w, 3):
+                raise ValueError("all frames must have the same (h,w,3) shape")
+        tf = (ctypes.c_void_p * n)(*[f.data_ptr() for f in fr])
+        self._check(self._L.st_jpeg_encode_batch(self._h, tf, n, h, w, int(quality), hs, vs))
+        sizes = (ctypes.c_size_t * n)()
+        self._check(self._L.st_jpeg_encode_fetch(self._h, None, sizes, 0))   # the sizes alone
+        most = max(sizes)
+        store = np.empty((n, most), np.uint8)
+        bufs = (ctypes.c_void_p * n)(*[store[i].ctypes.data for i in range(n)])
+        self._check(self._L.st_jpeg_encode_fetch(self._h, bufs, sizes, most))
+        return [store[i, :sizes[i]].tobytes() for i in range(n)]
+
     # -- pose path (scannertools_caffe) -------------------------------------------------------
     def cpm2_input(self, frames, scale, out=None):
         """CPM2Input (scannertools_caffe_cpp/cpm2_input_kernel_gpu.cpp:104-140): (n,h,w,3) uint8 RGB frames
@@ -941,6 +969,45 @@ def jpeg_coefficients(stream):
     if st != 0:
         raise StError(st, ji.message.decode())
     return coef, quant
+
+
+JPEG_SUBSAMPLINGS = {"4:4:4": (1, 1), "4:2:2": (2, 1), "4:2:0": (2, 2)}   # name -> luma sampling (h_samp, v_samp)
+
+
+def jpeg_sampling(subsampling):
+    """(h_samp, v_samp) of "4:4:4" / "4:2:2" / "4:2:0"; ValueError for anything else."""
+    if subsampling not in JPEG_SUBSAMPLINGS:
+        raise ValueError("subsampling %r is not supported (4:4:4, 4:2:2 or 4:2:0)" % (subsampling,))
+    return JPEG_SUBSAMPLINGS[subsampling]
+
+
+def jpeg_quant_tables(quality):
+    """st_jpeg_quant_tables (host only): the (luma, chroma) quantisation tables of ``quality``, (64,) uint16 each, natural order."""
+    luma, chroma = np.empty(64, np.uint16), np.empty(64, np.uint16)
+    st = _native.lib().st_jpeg_quant_tables(int(quality), luma.ctypes.data, chroma.ctypes.data)
+    if st != 0:
+        raise StError(st, "quality %d is outside 1..100" % int(quality))
+    return luma, chroma
+
+
+def jpeg_encode_header(h, w, quality=95, subsampling="4:2:0"):
+    """st_jpeg_encode_header (host only): the bytes SOI .. SOS of the stream encode_jpeg writes for such a frame."""
+    hs, vs = jpeg_sampling(subsampling)
+    buf = ctypes.create_string_buffer(1024)
+    size = ctypes.c_size_t()
+    st = _native.lib().st_jpeg_encode_header(int(h), int(w), int(quality), hs, vs, buf, 1024, ctypes.byref(size))
+    if st != 0:
+        raise StError(st, "st_jpeg_encode_header(h=%d, w=%d, quality=%d): quality outside 1..100 or size outside 1..65535" % (h, w, quality))
+    return buf.raw[:size.value]
+
+
+def jpeg_encode_bound(h, w, subsampling="4:2:0"):
+    """st_jpeg_encode_bound (host only): no stream of an (h, w, 3) frame at this sampling is longer, whatever its content."""
+    hs, vs = jpeg_sampling(subsampling)
+    v = _native.lib().st_jpeg_encode_bound(int(h), int(w), hs, vs)
+    if v < 0:
+        raise StError(1, "frame size %dx%d is outside 1..65535" % (w, h))
+    return v
 
 
 def cpm2_geometry(h, w, scale):

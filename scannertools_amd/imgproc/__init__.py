@@ -2,7 +2,7 @@
 (`_register_module(<pkg dir>, "scannertools_imgproc")`, /root/reference/scannertools/scannertools/
 imgproc/__init__.py:1-3).  Importing this module makes the ops Histogram, OpticalFlow,
 FlowHistogram, Blur, Resize, ConvertColor, Montage (a contact sheet: frame k resized into tile k of one canvas), ImageDecoder
-(baseline JPEG bytes -> frames) and the
+(baseline JPEG bytes -> frames), ImageEncoder (frames -> baseline JPEG bytes) and the
 legacy library's BrightnessCPP, ContrastCPP, SharpnessCPP and SharpnessBBoxCPP
 available: inside a Scanner deployment through
 ``scannertools_infra._register_module`` (Scanner then dlopens libscannertools_imgproc.so, whose

@@ -1,0 +1,124 @@
+// ImageEncoder op for Scanner on MI355X: the counterpart of ImageDecoder.
+//
+// Scanner's own stdlib has an ImageEncoder (a cv::imencode wrapper on the CPU); it is not part of the reference tree, so the
+// declaration here is this library's: frame_input("frame") -> output("img"), protobuf_name("ImageEncoderArgs"), `frame` a
+// U8 frame with 3 channels in R, G, B order, `img` the bytes of one baseline JPEG -- what ImageDecoder's `img` column reads.
+// ImageEncoderArgs { int32 quality = 1; string subsampling = 2; }: quality 0 or absent means 95, an empty subsampling means
+// "4:2:0".  Those are cv::imencode's defaults for JPEG (IMWRITE_JPEG_QUALITY 95, 4:2:0 sampling) as restated from OpenCV's
+// documentation; OpenCV is not available to check them against, so they are unpinned.
+//
+// One st_jpeg_encode_batch() call per execute(): colour conversion, downsampling, forward DCT, quantisation and Huffman coding
+// run in HIP kernels (include/scannertools_hip.h), the streams come back in one copy of exactly their bytes
+// (st_jpeg_encode_fetch).  A stream is byte for byte what libjpeg writes at the same settings with one restart interval per
+// MCU row.  Registered twice like the other classes: DeviceType::GPU reads device frames, the staged DeviceType::CPU form
+// uploads host frames first; both are batched.  No CPU fallback: without a GPU validate() fails.
+#include "scanner/api/kernel.h"
+#include "scanner/api/op.h"
+#include "scanner/util/hip.h"
+#include "scanner/util/memory.h"
+#include "proto_lite.h"
+#include "scannertools_hip.h"
+#include "kernel_core.h"
+
+namespace scanner {
+namespace {
+// false: not a message.  quality: 0 when the field is absent; subsampling: empty when absent
+bool parse_image_encoder_args(const std::vector<u8>& args, int* quality, std::string* subsampling) {
+  std::vector<proto_lite::Field> fields;
+  *quality = 0;
+  subsampling->clear();
+  if (!proto_lite::parse(args.data(), args.size(), &fields)) return false;
+  for (auto& f : fields) {
+    if (f.number == 1 && f.wire == 0) *quality = (int)(int64_t)f.value;
+    if (f.number == 2 && f.wire == 2) *subsampling = f.bytes;
+  }
+  return true;
+}
+}  // namespace
+
+template <bool STAGED>
+class ImageEncoderKernelHIPImpl : public BatchedKernel {
+ public:
+  ImageEncoderKernelHIPImpl(const KernelConfig& config) : BatchedKernel(config), core_(config, STAGED), stage_(core_.gpu) {
+    std::string sub;
+    if (!parse_image_encoder_args(config.args, &quality_, &sub)) {
+      RESULT_ERROR(&core_.valid, "ImageEncoder: could not parse ImageEncoderArgs");
+      return;
+    }
+    if (quality_ == 0) quality_ = 95;
+    if (quality_ < 1 || quality_ > 100) {
+      RESULT_ERROR(&core_.valid, "ImageEncoder: quality %d is outside 1..100", quality_);
+      return;
+    }
+    if (sub.empty() || sub == "4:2:0") { h_samp_ = 2; v_samp_ = 2; }
+    else if (sub == "4:2:2") { h_samp_ = 2; v_samp_ = 1; }
+    else if (sub == "4:4:4") { h_samp_ = 1; v_samp_ = 1; }
+    else {
+      RESULT_ERROR(&core_.valid, "ImageEncoder: subsampling \"%s\" is not supported (4:4:4, 4:2:2 or 4:2:0)", sub.c_str());
+      return;
+    }
+    core_.open("ImageEncoderKernelHIP");
+  }
+  void validate(Result* result) override { core_.validate(result); }
+
+  void execute(const BatchedElements& input_columns, BatchedElements& output_columns) override {
+    auto& frame_col = input_columns[0];
+    const i32 n = (i32)num_rows(frame_col);
+    if (n == 0) return;
+    const Frame* first = frame_col[0].as_const_frame();
+    const FrameInfo info = first->as_frame_info();
+    for (i32 i = 0; i < n; ++i) {
+      const Frame* frame = frame_col[i].as_const_frame();
+      LOG_IF(FATAL, frame->type != FrameType::U8 || frame->channels() != 3)
+          << "ImageEncoder: row " << i << " of the batch is not a U8 frame with 3 channels (" << frame->channels() << " channel(s))";
+    }
+    check_batch_shape(frame_col, info, "ImageEncoder");
+    const int h = info.height(), w = info.width();
+    const size_t frame_bytes = info.size();
+    if (STAGED) {
+      const size_t stride = DeviceStage::align(frame_bytes);
+      u8* dev = stage_.reserve(stride * n);
+      stage_.upload_frames(dev, stride, frame_col, frame_bytes);
+      strided_ptrs(src_, n, dev, stride);
+    } else {
+      input_ptrs(src_, frame_col);
+    }
+    st_ctx* ctx = core_.ctx;
+    ST_CHECK(ctx, st_jpeg_encode_batch(ctx, src_.data(), n, h, w, quality_, h_samp_, v_samp_));
+    sizes_.assign(n, 0);
+    ST_CHECK(ctx, st_jpeg_encode_fetch(ctx, nullptr, sizes_.data(), 0));   // the sizes alone
+    size_t total = 0, most = 0;
+    for (i32 i = 0; i < n; ++i) {
+      total += sizes_[i];
+      most = std::max(most, sizes_[i]);
+    }
+    // the fetch hands every stream a buffer of one capacity: rows of the longest stream's size
+    bytes_.resize(most * (size_t)n);
+    strided_ptrs(dst_, n, bytes_.data(), most);
+    ST_CHECK(ctx, st_jpeg_encode_fetch(ctx, dst_.data(), sizes_.data(), most));
+    for (i32 i = 0; i < n; ++i) {
+      u8* buffer = new_buffer(core_.device, sizes_[i]);
+      memcpy_buffer(buffer, core_.device, dst_[i], CPU_DEVICE, sizes_[i]);
+      insert_element(output_columns[0], buffer, sizes_[i]);
+    }
+  }
+
+ private:
+  KernelCore core_;
+  DeviceStage stage_;   // staged: the frames
+  int quality_ = 95, h_samp_ = 2, v_samp_ = 2;
+  std::vector<const uint8_t*> src_;
+  std::vector<uint8_t*> dst_;
+  std::vector<size_t> sizes_;
+  std::vector<u8> bytes_;
+};
+
+using ImageEncoderKernelHIP = ImageEncoderKernelHIPImpl<false>;
+using ImageEncoderKernelHIPStaged = ImageEncoderKernelHIPImpl<true>;
+
+REGISTER_OP(ImageEncoder).frame_input("frame").output("img").protobuf_name("ImageEncoderArgs");
+
+REGISTER_KERNEL(ImageEncoder, ImageEncoderKernelHIPStaged).device(DeviceType::CPU).batch().num_devices(1);
+
+REGISTER_KERNEL(ImageEncoder, ImageEncoderKernelHIP).device(DeviceType::GPU).batch().num_devices(1);
+}  // namespace scanner

@@ -1,0 +1,123 @@
+"""ImageEncoder on the MI355X: resident 1080p frames to baseline JPEG streams at quality 95, 4:2:0, batches of 32 and 256.
+Prints one JSON line.
+
+Needs Pillow as the yardstick: Pillow (libjpeg-turbo) encoding the same frames from host memory on a pool of 16 threads is
+the only baseline there is -- the op has no predecessor.  Per batch size, after a warm-up call, over --rounds repetitions:
+  (a) frames/s of the whole call, st_jpeg_encode_batch + st_jpeg_encode_fetch into host buffers (median, and the range);
+  (b) the four kernels' time per frame from the library's events (ST_K_JPEG brackets each launch);
+  (c) the bytes per frame that cross to the host (the streams), beside the 6.2 MB of a raw frame;
+  (d) Pillow's frames/s on 16 threads, host frames in, bytes out.
+The first stream is compared with Pillow's byte for byte before anything is timed.  The frames are synthetic (seeded smooth
+structure plus sensor-like noise), eight distinct ones repeated.
+
+    python scripts/bench_image_encoder.py [--rounds 7]
+    rocprofv3 --kernel-trace --stats --output-format csv -d DIR -- python scripts/bench_image_encoder.py --trace
+
+--trace makes three calls per batch size and times nothing: the kernel statistics of the trace then hold the four kernels'
+shares (k_jpeg_fdct, k_jpeg_entropy, k_jpeg_layout, k_jpeg_pack) over known work.
+"""
+import argparse
+import ctypes
+import io
+import json
+import os
+import statistics
+import sys
+import time
+from concurrent.futures import ThreadPoolExecutor
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np
+
+H, W = 1080, 1920
+QUALITY, SUBSAMPLING = 95, "4:2:0"
+BATCHES = (32, 256)
+DISTINCT = 8
+THREADS = 16
+
+
+def make_frames():
+    out = []
+    for i in range(DISTINCT):
+        rng = np.random.default_rng(100 + i)
+        y, x = np.mgrid[0:H, 0:W].astype(np.float32)
+        ph = rng.uniform(0, 6.28, 6)
+        img = np.stack([127 + 100 * np.sin(x / 37 + ph[0]) * np.cos(y / 23 + ph[1]), 127 + 100 * np.sin((x + y) / 51 + ph[2]) * np.cos(y / 9 + ph[3]),
+                        127 + 100 * np.cos(x / 13 + ph[4]) * np.sin((x - y) / 29 + ph[5])], axis=-1)
+        out.append(np.clip(img + rng.normal(0, 12, img.shape), 0, 255).astype(np.uint8))
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rounds", type=int, default=7)
+    ap.add_argument("--trace", action="store_true")
+    args = ap.parse_args()
+    try:
+        from PIL import Image
+    except ImportError:
+        sys.exit("bench_image_encoder.py needs Pillow as its yardstick")
+    import torch
+    from scannertools_amd import _native
+    from scannertools_amd.hip import HipContext, jpeg_encode_bound
+    L = _native.lib()
+    ctx = HipContext(0)
+    host = make_frames()
+    dev = [torch.from_numpy(f).cuda() for f in host]
+
+    def pillow(i):
+        buf = io.BytesIO()
+        Image.fromarray(host[i % DISTINCT]).save(buf, "JPEG", quality=QUALITY, subsampling=SUBSAMPLING, restart_marker_rows=1)
+        return buf.getvalue()
+
+    assert ctx.encode_jpeg([dev[0]], QUALITY, SUBSAMPLING)[0] == pillow(0), "the stream differs from Pillow's"
+    result = {"bench": "image_encoder", "h": H, "w": W, "quality": QUALITY, "sampling": SUBSAMPLING, "raw_frame_bytes": H * W * 3,
+              "bound_bytes": jpeg_encode_bound(H, W, SUBSAMPLING), "rounds": args.rounds, "batches": {}}
+    ctx._bind()
+    for n in BATCHES:
+        tab = (ctypes.c_void_p * n)(*[dev[i % DISTINCT].data_ptr() for i in range(n)])
+        sizes = (ctypes.c_size_t * n)()
+        store = np.empty((n, 1 << 22), np.uint8)   # no 1080p stream of these frames reaches 4 MiB; pages are touched only where written
+        bufs = (ctypes.c_void_p * n)(*[store[i].ctypes.data for i in range(n)])
+
+        def call():
+            ctx._check(L.st_jpeg_encode_batch(ctx._h, tab, n, H, W, QUALITY, 2, 2))
+            ctx._check(L.st_jpeg_encode_fetch(ctx._h, bufs, sizes, store.shape[1]))
+
+        if args.trace:
+            for _ in range(3):
+                call()
+            continue
+        call()   # warm-up: workspace, stream buffer and staging grow here
+        times = []
+        for _ in range(args.rounds):
+            t0 = time.perf_counter()
+            call()
+            times.append(time.perf_counter() - t0)
+        b = {"fps_median": round(n / statistics.median(times), 1), "fps_min": round(n / max(times), 1), "fps_max": round(n / min(times), 1),
+             "stream_bytes_per_frame": int(statistics.mean(sizes))}
+        ctx.timing_enable([_native.K_JPEG])
+        ctx.timing_reset()
+        for _ in range(args.rounds):
+            call()
+        launches, ms = ctx.timing_read(_native.K_JPEG)
+        ctx.timing_enable([])
+        b["kernel_ms_per_frame"] = round(ms / (args.rounds * n), 4)
+        b["kernel_launches_per_call"] = launches // args.rounds
+        with ThreadPoolExecutor(THREADS) as pool:
+            list(pool.map(pillow, range(n)))
+            times = []
+            for _ in range(max(3, args.rounds // 2)):
+                t0 = time.perf_counter()
+                list(pool.map(pillow, range(n)))
+                times.append(time.perf_counter() - t0)
+        b["pillow_%d_threads_fps_median" % THREADS] = round(n / statistics.median(times), 1)
+        b["pillow_fps_min"], b["pillow_fps_max"] = round(n / max(times), 1), round(n / min(times), 1)
+        result["batches"]["batch%d" % n] = b
+        del store
+    ctx.close()
+    print(json.dumps(result))
+
+
+if __name__ == "__main__":
+    main()
