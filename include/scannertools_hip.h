@@ -671,6 +671,35 @@ int st_jpeg_coefficients(const uint8_t* buf, size_t size, int16_t* coef, size_t 
  * sub-batches already enqueued are (a call of at most ST_JPEG_THREADS streams is one sub-batch: nothing is written). */
 int st_jpeg_decode_batch(st_ctx* ctx, const uint8_t* const* bufs_host, const size_t* sizes, int n, int h, int w, int channels,
                          uint8_t* const* out_dev);
+/* Host only, re-entrant: the restart intervals of a stream that has a DRI segment, for tests and tools.  An interval is an
+ * independently decodable piece of the scan: byte-aligned, DC predictors reset.  *count receives ceil(MCUs / restart_interval);
+ * table (may be null: the count alone) receives `count` (begin, end) pairs of byte offsets into buf: interval k's first
+ * entropy-coded byte, and the 0xFF of the marker that ends it (after any fill bytes; the end of the buffer where the stream
+ * stops without one).  cap: the number of pairs behind table; too few is ST_ERR_INVALID.  The scan is walked once for 0xFF
+ * bytes: FF00 and FFFF are data and fill, RSTn must be RST(k mod 8) after interval k, any other marker ends the scan, and
+ * what follows the last interval the frame needs is ignored.  ST_ERR_UNSUPPORTED: no DRI segment, or a stream of 4 GiB or
+ * more; ST_ERR_INVALID: fewer intervals than the frame needs, a marker out of sequence, and whatever st_jpeg_probe reports.
+ * info (may be null) receives the probe's fields and the message. */
+int st_jpeg_restart_intervals(const uint8_t* buf, size_t size, uint32_t* table, size_t cap, size_t* count, st_jpeg_info* info);
+/* Host only, re-entrant: st_jpeg_coefficients' contract and output layout, computed the way the device computes it: the
+ * intervals are scanned as st_jpeg_restart_intervals does and each one is decoded on its own by the bounded core the kernel
+ * of st_jpeg_decode_batch_gpu runs (st_jpeg_entropy.h).  The CPU twin of that kernel.  A corrupt interval is ST_ERR_INVALID,
+ * the message naming the interval and the cause; a stream without restart intervals is ST_ERR_UNSUPPORTED. */
+int st_jpeg_coefficients_by_interval(const uint8_t* buf, size_t size, int16_t* coef, size_t cap, uint16_t* quant, st_jpeg_info* info);
+/* st_jpeg_decode_batch with the entropy decoding on the device too, for streams that have restart intervals (every stream
+ * st_jpeg_encode_batch writes; Pillow's restart_marker_rows / restart_marker_blocks; libjpeg's -restart).  Same arguments,
+ * same frames byte for byte.  Every stream is probed first with the same refusals and messages; a stream without a DRI
+ * segment fails the call with ST_ERR_UNSUPPORTED naming it.  The intervals are then scanned on min(n, ST_JPEG_THREADS) host
+ * threads, and any scan error fails the call before anything is launched or written.  Per sub-batch ONE copy from page-locked
+ * memory carries the Huffman tables (per frame, as its scan selects them), the interval table, the entropy-coded bytes of
+ * every stream (16-byte aligned, padded by 16) and the frame headers; k_jpeg_entropy_dec (one lane per restart interval,
+ * each lane zeroing its blocks before it fills them) writes the coefficients into device memory where the inverse DCT reads
+ * them.  A sub-batch holds at most 2 GiB of coefficients (unless one frame has more).  After a sub-batch's entropy launch
+ * the call waits for its status word -- one host wait per sub-batch -- and launches the inverse DCT and colour kernels only
+ * when it is clean: a corrupt interval fails the call with ST_ERR_INVALID, the message naming the lowest (stream, interval)
+ * that failed and the cause; the frames of that sub-batch and of later ones are not written. */
+int st_jpeg_decode_batch_gpu(st_ctx* ctx, const uint8_t* const* bufs_host, const size_t* sizes, int n, int h, int w, int channels,
+                             uint8_t* const* out_dev);
 
 /* ---- ImageEncoder: baseline JPEG ------------------------------------------------------------
  * The counterpart of the ImageDecoder block (Scanner's stdlib ImageEncoder wraps cv::imencode on the host; it is not part of

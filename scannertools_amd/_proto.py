@@ -106,22 +106,36 @@ def message(number, payload):
 IMAGE_TYPES = {"PNG": 0, "JPEG": 1, "ANY": 2}   # ImageDecoderArgs.ImageType
 
 
-def image_decoder_args(image_type=None):
+ENTROPY_MODES = {"HOST": 0, "GPU": 1, "AUTO": 2}   # ImageDecoderArgs.Entropy
+
+
+def image_decoder_args(image_type=None, entropy=None):
     """A serialised ImageDecoderArgs.  None: the empty message (the op then decodes JPEG).  A named or numeric type is
-    written explicitly, PNG = 0 too (proto3 would omit it, and the kernel could not tell it from an absent field)."""
-    if image_type is None:
-        return b""
-    v = IMAGE_TYPES[image_type] if isinstance(image_type, str) else int(image_type)
-    return _varint(1 << 3 | 0) + _varint(v)
+    written explicitly, PNG = 0 too (proto3 would omit it, and the kernel could not tell it from an absent field).
+    entropy (field 2): None leaves the field out (HOST); "host" / "gpu" / "auto" in either case, or a number, is written."""
+    out = b""
+    if image_type is not None:
+        v = IMAGE_TYPES[image_type] if isinstance(image_type, str) else int(image_type)
+        out += _varint(1 << 3 | 0) + _varint(v)
+    if entropy is not None:
+        if isinstance(entropy, str) and entropy.upper() not in ENTROPY_MODES:
+            raise ValueError("entropy must be one of 'host', 'gpu', 'auto' or a number, got %r" % (entropy,))
+        v = ENTROPY_MODES[entropy.upper()] if isinstance(entropy, str) else int(entropy)
+        out += _varint(2 << 3 | 0) + _varint(v)
+    return out
 
 
 def parse_image_decoder_args(buf):
-    """{'image_type': name or number} of a serialised ImageDecoderArgs; {} when the field is absent."""
+    """{'image_type': name or number, 'entropy': name or number} of a serialised ImageDecoderArgs; a key is missing when its
+    field is absent."""
     names = {v: k for k, v in IMAGE_TYPES.items()}
+    modes = {v: k for k, v in ENTROPY_MODES.items()}
     out = {}
     for number, wt, value in fields(buf):
         if number == 1 and wt == 0:
             out["image_type"] = names.get(value, value)
+        if number == 2 and wt == 0:
+            out["entropy"] = modes.get(value, value)
     return out
 
 

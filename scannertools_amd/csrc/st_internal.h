@@ -59,6 +59,10 @@ struct st_ctx {
   struct st_jpeg_enc_state* jpeg_enc = nullptr; // tables and the packed streams of the last st_jpeg_encode_batch call (st_jpeg_enc.hip)
 };
 void st_jpeg_release(st_ctx* ctx);   // frees ctx->jpeg (st_ctx_destroy)
+struct StJpegEntArgs;
+// enqueues k_jpeg_entropy_dec (st_jpeg_entropy.hip) for one sub-batch of st_jpeg_decode_batch_gpu; max_groups: the most
+// groups of 64 restart intervals any of its frames has
+int st_jpeg_entropy_launch(st_ctx* ctx, const StJpegEntArgs& a, unsigned max_groups);
 void st_jpeg_enc_release(st_ctx* ctx); // frees ctx->jpeg_enc (st_ctx_destroy)
 void st_netin_release(st_ctx* ctx);  // frees ctx->netin (st_ctx_destroy)
 void st_detect_release(st_ctx* ctx); // frees ctx->detect (st_ctx_destroy)

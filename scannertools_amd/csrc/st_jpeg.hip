@@ -1,4 +1,6 @@
-// ImageDecoder op, baseline JPEG: st_jpeg_decode_batch and its two kernels.
+// ImageDecoder op, baseline JPEG: st_jpeg_decode_batch and its two kernels, and st_jpeg_decode_batch_gpu, the same call with the
+// entropy decoding on the device too (k_jpeg_entropy_dec, st_jpeg_entropy.hip) for streams with restart intervals; its part
+// of this file is at the end.
 //
 // Stage 1 (st_jpeg_parse.cpp, host threads) turns each stream into int16 coefficient blocks; this file uploads them and runs
 //   k_jpeg_idct   dequantisation + libjpeg's "islow" inverse DCT, one lane per block row, into block-tiled component planes
@@ -23,6 +25,7 @@
 #include <thread>
 
 #include "st_internal.h"
+#include "st_jpeg_entropy.h"
 #include "st_jpeg_parse.h"
 
 namespace {
@@ -277,6 +280,22 @@ int jpeg_threads(int n) {
   return std::max(1, std::min(std::min(t, 64), n));
 }
 
+// the header the two dense kernels read, from a parsed stream
+void jpeg_frame_hdr(const StJpegHeader& hd, uint8_t* out, int blk_off, JpegFrameHdr* fh) {
+  memset(fh, 0, sizeof *fh);
+  fh->out = out;
+  fh->blk_off = blk_off;
+  fh->nblk_y = (int)st_jpeg_comp_blocks(hd, 0);
+  fh->nblk_c = hd.ncomp == 3 ? (int)st_jpeg_comp_blocks(hd, 1) : 0;
+  fh->bw_y = hd.bw[0];
+  fh->bw_c = hd.ncomp == 3 ? hd.bw[1] : 0;
+  fh->mode = hd.mode;
+  fh->dw = (hd.w + hd.hs[0] - 1) / hd.hs[0];
+  fh->dh = (hd.h + hd.vs[0] - 1) / hd.vs[0];
+  fh->fancy = fh->dw > 2 ? 1 : 0;
+  for (int c = 0; c < hd.ncomp; ++c) memcpy(fh->quant[c], hd.quant[hd.tq[c]], 128);
+}
+
 constexpr size_t kSlotCoefBytes = (size_t)64 << 20;   // coefficients of one sub-batch, unless a single frame has more
 
 }  // namespace
@@ -286,6 +305,11 @@ struct st_jpeg_state {
   size_t cap[2] = {0, 0};
   hipEvent_t copied[2] = {nullptr, nullptr};   // the slot's last copy has left host memory
   bool busy[2] = {false, false};
+  // st_jpeg_decode_batch_gpu: its one upload slot (the call waits for every sub-batch, so the slot is free when it is
+  // refilled) and the page-locked word the status comes back in
+  uint8_t* gpin = nullptr;
+  size_t gcap = 0;
+  unsigned long long* gstatus = nullptr;
 };
 
 void st_jpeg_release(st_ctx* ctx) {
@@ -294,6 +318,8 @@ void st_jpeg_release(st_ctx* ctx) {
     if (ctx->jpeg->copied[s]) (void)hipEventDestroy(ctx->jpeg->copied[s]);
     if (ctx->jpeg->pin[s]) (void)hipHostFree(ctx->jpeg->pin[s]);
   }
+  if (ctx->jpeg->gpin) (void)hipHostFree(ctx->jpeg->gpin);
+  if (ctx->jpeg->gstatus) (void)hipHostFree(ctx->jpeg->gstatus);
   delete ctx->jpeg;
   ctx->jpeg = nullptr;
 }
@@ -390,18 +416,7 @@ ST_EXPORT int st_jpeg_decode_batch(st_ctx* ctx, const uint8_t* const* bufs_host,
         const StJpegHeader& hd = hds[i];
         uint8_t* slot = js->pin[k & 1];
         JpegFrameHdr* fh = reinterpret_cast<JpegFrameHdr*>(slot) + (i - sbs[k].first);
-        memset(fh, 0, sizeof *fh);
-        fh->out = out_dev[i];
-        fh->blk_off = blk_off[i];
-        fh->nblk_y = (int)st_jpeg_comp_blocks(hd, 0);
-        fh->nblk_c = hd.ncomp == 3 ? (int)st_jpeg_comp_blocks(hd, 1) : 0;
-        fh->bw_y = hd.bw[0];
-        fh->bw_c = hd.ncomp == 3 ? hd.bw[1] : 0;
-        fh->mode = hd.mode;
-        fh->dw = (hd.w + hd.hs[0] - 1) / hd.hs[0];
-        fh->dh = (hd.h + hd.vs[0] - 1) / hd.vs[0];
-        fh->fancy = fh->dw > 2 ? 1 : 0;
-        for (int c = 0; c < hd.ncomp; ++c) memcpy(fh->quant[c], hd.quant[hd.tq[c]], 128);
+        jpeg_frame_hdr(hd, out_dev[i], blk_off[i], fh);
         int16_t* coef = reinterpret_cast<int16_t*>(slot + (size_t)sbs[k].count * sizeof(JpegFrameHdr) + (size_t)blk_off[i] * 128);
         st = st_jpeg_decode_scan(bufs_host[i], sizes[i], hd, coef, msg, sizeof msg);
       }
@@ -474,4 +489,292 @@ ST_EXPORT int st_jpeg_decode_batch(st_ctx* ctx, const uint8_t* const* bufs_host,
   }
   for (std::thread& t : pool) t.join();
   return status;
+}
+
+// ---- entropy decoding on the device -----------------------------------------------------------------------------------------
+// The upload of a sub-batch of nf frames, one copy from the page-locked slot (every section 16-byte aligned):
+//   [status word, 16 B] [table sets: StJpegFrameTables, one per run of frames with equal tables] [nf x StJpegEntFrame]
+//   [interval tables: (begin, end) uint32 pairs relative to each frame's first entropy-coded byte]
+//   [each frame's entropy-coded bytes from scan_pos, 16-byte aligned, padded by >= 16 zero bytes] [pad to 256]
+//   [nf x JpegFrameHdr]
+// and in device memory the sub-batch's coefficients follow the headers directly, so k_jpeg_idct finds them where it finds the
+// uploaded ones of the host path (slot + nf * 512 + blk * 128).
+namespace {
+
+// Coefficients of one sub-batch, unless a single frame has more.  Device memory bounds it, not page-locked memory: the slot
+// holds stream bytes only.  2 GiB keeps a 256-frame 1080p call (1.6 GB of coefficients, 17 408 restart intervals) ONE launch
+// of one lane per interval; split further, each launch would have too few lanes to be worth it.
+constexpr size_t kGpuCoefBytes = (size_t)2 << 30;
+
+struct GpuStream {
+  JpegFrameHdr fh;        // out and blk_off set when the sub-batches are laid out
+  StJpegScanGeom geom;
+  size_t scan_pos = 0, nbytes = 0, nblocks = 0;
+  uint32_t nint = 0;
+  int owner = 0;          // the scanning thread whose table holds this stream's intervals, at iv_at
+  size_t iv_at = 0;
+  bool same_tabs = false; // the tables equal those of the stream before it
+  // its place in its sub-batch
+  int sb = 0, tabs = 0;
+  bool writes_tabs = false;
+  size_t iv_off = 0, bytes_off = 0;
+};
+
+struct GpuSubBatch {
+  int first = 0, count = 0, nsets = 0;
+  size_t blocks = 0, nint = 0;
+  unsigned max_groups = 0;
+  size_t tables_off = 0, frames_off = 0, hdr_off = 0, upload_bytes = 0;
+};
+
+inline size_t up16(size_t v) { return (v + 15) & ~(size_t)15; }
+
+void frame_tables(const StJpegHeader& hd, StJpegFrameTables* t) {
+  memset(t, 0, sizeof *t);
+  for (int c = 0; c < hd.ncomp; ++c) {
+    t->dc[c] = hd.dc[hd.td[c]];
+    t->ac[c] = hd.ac[hd.ta[c]];
+  }
+}
+
+template <class F>
+void run_threads(int T, F&& f) {
+  if (T <= 1) { f(0); return; }
+  std::vector<std::thread> pool;
+  pool.reserve((size_t)T);
+  for (int t = 0; t < T; ++t) pool.emplace_back(f, t);
+  for (std::thread& t : pool) t.join();
+}
+
+}  // namespace
+
+ST_EXPORT int st_jpeg_decode_batch_gpu(st_ctx* ctx, const uint8_t* const* bufs_host, const size_t* sizes, int n, int h, int w, int channels,
+                                       uint8_t* const* out_dev) {
+  ST_TRY(st_enter(ctx));
+  if (n < 0 || h <= 0 || w <= 0 || h > 65535 || w > 65535 || (channels != 1 && channels != 3))
+    return st_set_error(ctx, ST_ERR_INVALID, "jpeg: bad arguments (n=%d h=%d w=%d channels=%d)", n, h, w, channels);
+  if (n == 0) return ST_OK;
+  if (!bufs_host || !sizes || !out_dev) return st_set_error(ctx, ST_ERR_INVALID, "jpeg: null argument");
+  const int T = jpeg_threads(n);
+
+  // 1. every stream's markers and its restart intervals, on T threads over contiguous runs of streams.  The lowest stream
+  // that is refused wins; only when none is, the lowest stream whose scan is broken.  Nothing is launched or written before.
+  std::vector<GpuStream> gs((size_t)n);
+  std::vector<std::vector<uint32_t>> ivs((size_t)T);
+  struct Fail { int stream = INT_MAX, status = ST_OK; char msg[224]; };
+  Fail probe_fail, scan_fail;
+  std::mutex mu;
+  auto note = [&](Fail& f, int i, int status, const char* fmt, auto... args) {
+    std::lock_guard<std::mutex> lk(mu);
+    if (i >= f.stream) return;
+    f.stream = i;
+    f.status = status;
+    snprintf(f.msg, sizeof f.msg, fmt, args...);
+  };
+  try {
+    run_threads(T, [&](int t) {
+      const int lo = (int)((long long)n * t / T), hi = (int)((long long)n * (t + 1) / T);
+      std::vector<StJpegHeader> hdv(1);
+      std::vector<StJpegFrameTables> tv(2);
+      StJpegHeader& hd = hdv[0];
+      bool have_prev = false, scan_ok = true;
+      char msg[160];
+      for (int i = lo; i < hi; ++i) {
+        GpuStream& g = gs[(size_t)i];
+        if (!out_dev[i]) { note(probe_fail, i, ST_ERR_INVALID, "jpeg: stream %d has no output frame", i); return; }
+        const int st = st_jpeg_parse_header(bufs_host[i], sizes[i], &hd, msg, sizeof msg);
+        if (st != ST_OK) { note(probe_fail, i, st, "jpeg: stream %d: %s", i, msg); return; }
+        if (hd.h != h || hd.w != w || hd.ncomp != channels) {
+          note(probe_fail, i, ST_ERR_INVALID, "jpeg: stream %d is %dx%d with %d channel(s), the call decodes %dx%d with %d", i, hd.w, hd.h, hd.ncomp, w, h, channels);
+          return;
+        }
+        g.nint = (uint32_t)st_jpeg_interval_count(hd);
+        if (g.nint == 0) {
+          note(probe_fail, i, ST_ERR_UNSUPPORTED, "jpeg: stream %d: no restart intervals: the stream has no DRI segment, entropy decoding on the device needs one", i);
+          return;
+        }
+        if (!scan_ok) continue;   // a later stream of this run may still be refused, which comes first
+        jpeg_frame_hdr(hd, out_dev[i], 0, &g.fh);
+        g.geom = st_jpeg_scan_geom(hd);
+        g.scan_pos = hd.scan_pos;
+        g.nblocks = st_jpeg_blocks(hd);
+        frame_tables(hd, &tv[(size_t)(i & 1)]);
+        g.same_tabs = have_prev && memcmp(&tv[0], &tv[1], sizeof(StJpegFrameTables)) == 0;
+        have_prev = true;
+        std::vector<uint32_t>& iv = ivs[(size_t)t];
+        g.owner = t;
+        g.iv_at = iv.size();
+        iv.resize(iv.size() + 2 * (size_t)g.nint);
+        const int ss = st_jpeg_scan_intervals(bufs_host[i], sizes[i], hd, iv.data() + g.iv_at, msg, sizeof msg);
+        if (ss != ST_OK) {
+          note(scan_fail, i, ss, "jpeg: stream %d: %s", i, msg);
+          scan_ok = false;
+          continue;
+        }
+        g.nbytes = (size_t)iv[g.iv_at + 2 * (size_t)g.nint - 1] - g.scan_pos;
+      }
+    });
+  } catch (const std::exception&) {
+    return st_set_error(ctx, ST_ERR_OOM, "jpeg: out of host memory (or threads) for the interval tables");
+  }
+  if (probe_fail.stream != INT_MAX) return st_set_error(ctx, probe_fail.status, "%s", probe_fail.msg);
+  if (scan_fail.stream != INT_MAX) return st_set_error(ctx, scan_fail.status, "%s", scan_fail.msg);
+
+  // 2. sub-batches and the layout of each one's upload
+  std::vector<GpuSubBatch> sbs;
+  size_t upload_most = 0, dev_most = 0, plane_most = 0;
+  {
+    auto close = [&]() {
+      if (sbs.empty()) return;
+      GpuSubBatch& sb = sbs.back();
+      sb.tables_off = 16;
+      sb.frames_off = up16(sb.tables_off + (size_t)sb.nsets * sizeof(StJpegFrameTables));
+      size_t o = sb.frames_off + (size_t)sb.count * sizeof(StJpegEntFrame);
+      for (int i = sb.first; i < sb.first + sb.count; ++i) { gs[(size_t)i].iv_off = o; o += (size_t)gs[(size_t)i].nint * 8; }
+      o = up16(o);
+      for (int i = sb.first; i < sb.first + sb.count; ++i) { gs[(size_t)i].bytes_off = o; o += up16(gs[(size_t)i].nbytes + 16); }
+      sb.hdr_off = st_align_up(o);
+      sb.upload_bytes = sb.hdr_off + (size_t)sb.count * sizeof(JpegFrameHdr);
+      upload_most = std::max(upload_most, sb.upload_bytes);
+      dev_most = std::max(dev_most, sb.upload_bytes + sb.blocks * 128);
+      plane_most = std::max(plane_most, sb.blocks * 64);
+    };
+    for (int i = 0; i < n; ++i) {
+      GpuStream& g = gs[(size_t)i];
+      if (sbs.empty() || (sbs.back().blocks + g.nblocks) * 128 > kGpuCoefBytes) {
+        close();
+        sbs.push_back(GpuSubBatch());
+        sbs.back().first = i;
+      }
+      GpuSubBatch& sb = sbs.back();
+      g.sb = (int)sbs.size() - 1;
+      g.writes_tabs = sb.count == 0 || !g.same_tabs || gs[(size_t)i - 1].owner != g.owner;
+      if (g.writes_tabs) sb.nsets++;
+      g.tabs = sb.nsets - 1;
+      g.fh.blk_off = (int)sb.blocks;
+      sb.count++;
+      sb.blocks += g.nblocks;
+      sb.nint += g.nint;
+      sb.max_groups = std::max(sb.max_groups, (g.nint + (unsigned)kStJpegEntLanes - 1) / (unsigned)kStJpegEntLanes);
+    }
+    close();
+  }
+
+  if (!ctx->jpeg) {
+    ctx->jpeg = new (std::nothrow) st_jpeg_state();
+    if (!ctx->jpeg) return st_set_error(ctx, ST_ERR_OOM, "jpeg: out of host memory");
+  }
+  st_jpeg_state* js = ctx->jpeg;
+  if (!js->gstatus && hipHostMalloc((void**)&js->gstatus, 64, hipHostMallocDefault) != hipSuccess) {
+    (void)hipGetLastError();
+    js->gstatus = nullptr;
+    return st_set_error(ctx, ST_ERR_OOM, "jpeg: cannot page-lock the status word");
+  }
+  if (upload_most > js->gcap) {
+    if (js->gpin) ST_HIP(ctx, hipHostFree(js->gpin));
+    js->gpin = nullptr;
+    js->gcap = 0;
+    const size_t want = upload_most + upload_most / 8;
+    if (hipHostMalloc((void**)&js->gpin, want, hipHostMallocDefault) != hipSuccess) {
+      (void)hipGetLastError();
+      js->gpin = nullptr;
+      return st_set_error(ctx, ST_ERR_OOM, "jpeg: cannot page-lock %zu bytes for the streams", want);
+    }
+    js->gcap = want;
+  }
+  ST_TRY(st_ws_reserve(ctx, st_align_up(dev_most) + st_align_up(plane_most)));
+  uint8_t* d_up = (uint8_t*)st_ws_alloc(ctx, dev_most);
+  uint8_t* d_planes = (uint8_t*)st_ws_alloc(ctx, plane_most);
+  if (!d_up || !d_planes) return st_set_error(ctx, ST_ERR_OOM, "jpeg: workspace exhausted");
+
+  const unsigned align = [&] {
+    unsigned a = 0;
+    for (int i = 0; i < n; ++i) a |= (unsigned)(uintptr_t)out_dev[i];
+    return a;
+  }();
+  const int px = (w % 16 == 0 && (align & 15) == 0) ? 16 : ((w % 4 == 0 && (align & 3) == 0) ? 4 : 1);
+
+  for (const GpuSubBatch& sb : sbs) {
+    // 3. fill the slot on the threads (free: the previous sub-batch was waited for)
+    uint8_t* slot = js->gpin;
+    memset(slot, 0xFF, 16);   // the status word: clean
+    std::atomic<int> next{sb.first};
+    std::atomic<bool> bad{false};
+    run_threads(std::min(T, sb.count), [&](int) {
+      std::vector<StJpegHeader> hdv;
+      char msg[160];
+      for (;;) {
+        const int i = next.fetch_add(1);
+        if (i >= sb.first + sb.count) return;
+        const GpuStream& g = gs[(size_t)i];
+        const int j = i - sb.first;
+        StJpegEntFrame* ef = reinterpret_cast<StJpegEntFrame*>(slot + sb.frames_off) + j;
+        ef->geom = g.geom;
+        ef->nint = g.nint;
+        ef->tables = (uint32_t)g.tabs;
+        ef->intervals_off = g.iv_off;
+        ef->bytes_off = g.bytes_off;
+        ef->nbytes = (uint32_t)g.nbytes;
+        ef->blk_off = (uint32_t)g.fh.blk_off;
+        if (g.writes_tabs) {
+          if (hdv.empty()) hdv.resize(1);
+          if (st_jpeg_parse_header(bufs_host[i], sizes[i], &hdv[0], msg, sizeof msg) != ST_OK) { bad = true; return; }   // the caller changed the stream
+          frame_tables(hdv[0], reinterpret_cast<StJpegFrameTables*>(slot + sb.tables_off) + g.tabs);
+        }
+        const uint32_t* iv = ivs[(size_t)g.owner].data() + g.iv_at;
+        uint32_t* dv = reinterpret_cast<uint32_t*>(slot + g.iv_off);
+        for (size_t k = 0; k < 2 * (size_t)g.nint; ++k) dv[k] = iv[k] - (uint32_t)g.scan_pos;
+        memcpy(slot + g.bytes_off, bufs_host[i] + g.scan_pos, g.nbytes);
+        memset(slot + g.bytes_off + g.nbytes, 0, up16(g.nbytes + 16) - g.nbytes);
+        memcpy(slot + sb.hdr_off + (size_t)j * sizeof(JpegFrameHdr), &g.fh, sizeof(JpegFrameHdr));
+      }
+    });
+    if (bad) return st_set_error(ctx, ST_ERR_INVALID, "jpeg: a stream changed during the call");
+    // 4. one copy, the entropy launch, the ONE host wait of the sub-batch (its status word), then the dense kernels
+    unsigned long long word = kStJpegEntClean;
+    {
+      st_timed timed(ctx, ST_K_JPEG);
+      ST_HIP(ctx, hipMemcpyAsync(d_up, slot, sb.upload_bytes, hipMemcpyHostToDevice, ctx->stream));
+      StJpegEntArgs ea;
+      ea.upload = d_up;
+      ea.frames = reinterpret_cast<const StJpegEntFrame*>(d_up + sb.frames_off);
+      ea.tables = reinterpret_cast<const StJpegFrameTables*>(d_up + sb.tables_off);
+      ea.coef = reinterpret_cast<int16_t*>(d_up + sb.upload_bytes);
+      ea.status = reinterpret_cast<unsigned long long*>(d_up);
+      ea.nf = sb.count;
+      ea.first_stream = sb.first;
+      ST_TRY(st_jpeg_entropy_launch(ctx, ea, sb.max_groups));
+      ST_HIP(ctx, hipMemcpyAsync(js->gstatus, d_up, sizeof word, hipMemcpyDeviceToHost, ctx->stream));
+      ST_HIP(ctx, hipStreamSynchronize(ctx->stream));
+      word = *js->gstatus;
+      if (word == kStJpegEntClean) {
+        size_t most = 0;
+        for (int i = sb.first; i < sb.first + sb.count; ++i) most = std::max(most, gs[(size_t)i].nblocks);
+        long long bx = ((long long)h * w / px + 255) / 256;
+        if (bx > 8192) bx = 8192;
+        // the dense kernels take the frame from blockIdx.y: at most 65 535 frames per launch, the headers offset so that the
+        // coefficients stay where slot + nf * 512 points
+        for (int f0 = 0; f0 < sb.count; f0 += 65535) {
+          const int nfl = std::min(65535, sb.count - f0);
+          JpegArgsK a;
+          a.slot = d_up + sb.hdr_off + (size_t)f0 * sizeof(JpegFrameHdr);
+          a.planes = d_planes; a.nf = sb.count - f0; a.h = h; a.w = w; a.channels = channels;
+          hipLaunchKernelGGL(k_jpeg_idct, dim3((unsigned)((most + kIdctBlocks - 1) / kIdctBlocks), nfl), dim3(256), 0, ctx->stream, a);
+          const dim3 grid((unsigned)bx, nfl);
+          if (px == 16) hipLaunchKernelGGL(k_jpeg_color<16>, grid, dim3(256), 0, ctx->stream, a);
+          else if (px == 4) hipLaunchKernelGGL(k_jpeg_color<4>, grid, dim3(256), 0, ctx->stream, a);
+          else hipLaunchKernelGGL(k_jpeg_color<1>, grid, dim3(256), 0, ctx->stream, a);
+        }
+      }
+    }
+    ST_HIP(ctx, hipGetLastError());
+    if (word != kStJpegEntClean) {
+      const int stream = (int)(word >> 32);
+      const unsigned interval = (unsigned)((word >> 4) & 0xfffffffu);
+      const unsigned nint = stream >= 0 && stream < n ? gs[(size_t)stream].nint : 0u;
+      return st_set_error(ctx, ST_ERR_INVALID, "jpeg: stream %d: corrupt scan: restart interval %u of %u: %s", stream, interval, nint,
+                          st_jpeg_entropy_cause((int)(word & 15)));
+    }
+  }
+  return ST_OK;
 }

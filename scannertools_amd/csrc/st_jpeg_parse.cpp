@@ -7,8 +7,10 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
+#include <new>
 
 #include "scannertools_hip.h"
+#include "st_jpeg_entropy.h"
 
 #define ST_JPEG_EXPORT extern "C" __attribute__((visibility("default")))
 
@@ -317,6 +319,38 @@ int st_jpeg_decode_scan(const uint8_t* buf, size_t size, const StJpegHeader& hd,
   return ST_OK;
 }
 
+int st_jpeg_scan_intervals(const uint8_t* buf, size_t size, const StJpegHeader& hd, uint32_t* table, char* msg, size_t msg_len) {
+  if (msg && msg_len) msg[0] = 0;
+  const size_t need = st_jpeg_interval_count(hd);
+  if (need == 0) return fail(msg, msg_len, ST_ERR_UNSUPPORTED, "no restart intervals: the stream has no DRI segment");
+  if (size >= ((size_t)1 << 32)) return fail(msg, msg_len, ST_ERR_UNSUPPORTED, "no restart intervals: a stream of %zu bytes is too long (below 4 GiB only)", size);
+  size_t pos = hd.scan_pos, begin = hd.scan_pos, k = 0;
+  for (;;) {
+    const uint8_t* p = pos < size ? (const uint8_t*)memchr(buf + pos, 0xFF, size - pos) : nullptr;
+    size_t end = size;   // the end of the buffer ends the scan (a lone 0xFF as its last byte included)
+    int m = -1;
+    if (p && (size_t)(p - buf) + 1 < size) {
+      pos = (size_t)(p - buf);
+      m = p[1];
+      if (m == 0x00) { pos += 2; continue; }   // stuffed FF
+      if (m == 0xFF) { pos += 1; continue; }   // fill byte
+      end = pos;
+    }
+    const bool rst = m >= 0xD0 && m <= 0xD7;
+    if (rst && k + 1 < need && m != 0xD0 + (int)(k & 7))
+      return fail(msg, msg_len, ST_ERR_INVALID, "truncated or corrupt scan: no RST%d marker after restart interval %zu (RST%d at byte %zu)", (int)(k & 7), k,
+                  m - 0xD0, end);
+    table[2 * k] = (uint32_t)begin;
+    table[2 * k + 1] = (uint32_t)end;
+    ++k;
+    if (k == need) return ST_OK;   // what follows is ignored
+    if (!rst)
+      return fail(msg, msg_len, ST_ERR_INVALID, "truncated or corrupt scan: %zu of %zu restart intervals before %s", k, need,
+                  m < 0 ? "the end of the buffer" : "another marker");
+    pos = begin = end + 2;
+  }
+}
+
 namespace {
 void fill_info(const StJpegHeader& hd, st_jpeg_info* info) {
   info->h = hd.h;
@@ -348,6 +382,64 @@ ST_JPEG_EXPORT int st_jpeg_coefficients(const uint8_t* buf, size_t size, int16_t
   const size_t need = st_jpeg_blocks(hd) * 64;
   if (!coef || cap < need) return fail(info->message, sizeof info->message, ST_ERR_INVALID, "coef holds %zu values, the stream has %zu", coef ? cap : (size_t)0, need);
   st = st_jpeg_decode_scan(buf, size, hd, coef, info->message, sizeof info->message);
+  if (st != ST_OK) return st;
+  if (quant)
+    for (int c = 0; c < hd.ncomp; ++c) memcpy(quant + 64 * c, hd.quant[hd.tq[c]], 128);
+  return ST_OK;
+}
+
+ST_JPEG_EXPORT int st_jpeg_restart_intervals(const uint8_t* buf, size_t size, uint32_t* table, size_t cap, size_t* count, st_jpeg_info* info) {
+  st_jpeg_info local;
+  if (!info) info = &local;
+  memset(info, 0, sizeof *info);
+  if (count) *count = 0;
+  StJpegHeader hd;
+  const int st = st_jpeg_parse_header(buf, size, &hd, info->message, sizeof info->message);
+  if (st != ST_OK) return st;
+  fill_info(hd, info);
+  const size_t need = st_jpeg_interval_count(hd);
+  if (need == 0) return fail(info->message, sizeof info->message, ST_ERR_UNSUPPORTED, "no restart intervals: the stream has no DRI segment");
+  if (count) *count = need;
+  if (!table) return ST_OK;
+  if (cap < need) return fail(info->message, sizeof info->message, ST_ERR_INVALID, "table holds %zu pairs, the stream has %zu restart intervals", cap, need);
+  return st_jpeg_scan_intervals(buf, size, hd, table, info->message, sizeof info->message);
+}
+
+ST_JPEG_EXPORT int st_jpeg_coefficients_by_interval(const uint8_t* buf, size_t size, int16_t* coef, size_t cap, uint16_t* quant, st_jpeg_info* info) {
+  st_jpeg_info local;
+  if (!info) info = &local;
+  memset(info, 0, sizeof *info);
+  StJpegHeader hd;
+  int st = st_jpeg_parse_header(buf, size, &hd, info->message, sizeof info->message);
+  if (st != ST_OK) return st;
+  fill_info(hd, info);
+  const size_t need = st_jpeg_blocks(hd) * 64;
+  if (!coef || cap < need) return fail(info->message, sizeof info->message, ST_ERR_INVALID, "coef holds %zu values, the stream has %zu", coef ? cap : (size_t)0, need);
+  const size_t nint = st_jpeg_interval_count(hd);
+  if (nint == 0) return fail(info->message, sizeof info->message, ST_ERR_UNSUPPORTED, "no restart intervals: the stream has no DRI segment");
+  uint32_t* table = new (std::nothrow) uint32_t[2 * nint];
+  StJpegFrameTables* tabs = new (std::nothrow) StJpegFrameTables;
+  if (!table || !tabs) {
+    delete[] table;
+    delete tabs;
+    return fail(info->message, sizeof info->message, ST_ERR_OOM, "out of host memory for %zu restart intervals", nint);
+  }
+  st = st_jpeg_scan_intervals(buf, size, hd, table, info->message, sizeof info->message);
+  if (st == ST_OK) {
+    for (int c = 0; c < hd.ncomp; ++c) {
+      tabs->dc[c] = hd.dc[hd.td[c]];
+      tabs->ac[c] = hd.ac[hd.ta[c]];
+    }
+    const StJpegScanGeom g = st_jpeg_scan_geom(hd);
+    const StJpegZigzag zz = st_jpeg_zigzag();
+    for (size_t k = 0; k < nint && st == ST_OK; ++k) {
+      const int je = st_jpeg_decode_interval(buf, table[2 * k], table[2 * k + 1], (long long)k * hd.restart_interval, hd.restart_interval, g, tabs, zz.nat, coef);
+      if (je != ST_JE_OK)
+        st = fail(info->message, sizeof info->message, ST_ERR_INVALID, "corrupt scan: restart interval %zu of %zu: %s", k, nint, st_jpeg_entropy_cause(je));
+    }
+  }
+  delete[] table;
+  delete tabs;
   if (st != ST_OK) return st;
   if (quant)
     for (int c = 0; c < hd.ncomp; ++c) memcpy(quant + 64 * c, hd.quant[hd.tq[c]], 128);

@@ -44,4 +44,16 @@ int st_jpeg_parse_header(const uint8_t* buf, size_t size, StJpegHeader* hd, char
 // The scan of a parsed stream into st_jpeg_blocks(hd) * 64 coefficients (the layout of st_jpeg_coefficients).
 int st_jpeg_decode_scan(const uint8_t* buf, size_t size, const StJpegHeader& hd, int16_t* coef, char* msg, size_t msg_len);
 
+// Restart intervals of a parsed stream: ceil(MCUs / restart_interval), 0 for a stream without DRI.
+inline size_t st_jpeg_interval_count(const StJpegHeader& hd) {
+  if (hd.restart_interval <= 0) return 0;
+  const size_t mcus = (size_t)hd.mcux * hd.mcuy;
+  return (mcus + (size_t)hd.restart_interval - 1) / (size_t)hd.restart_interval;
+}
+// One walk over the entropy-coded segment from hd.scan_pos for 0xFF bytes: `table` receives st_jpeg_interval_count(hd)
+// (begin, end) pairs of offsets into buf, `end` on the 0xFF of the marker that ends the interval (or size).  Stops after the
+// last interval the frame needs.  ST_ERR_UNSUPPORTED: no DRI, or size >= 4 GiB; ST_ERR_INVALID: too few intervals, or an
+// RSTn out of sequence.
+int st_jpeg_scan_intervals(const uint8_t* buf, size_t size, const StJpegHeader& hd, uint32_t* table, char* msg, size_t msg_len);
+
 #endif  // ST_JPEG_PARSE_H_

@@ -599,7 +599,8 @@ class _SharpnessBBoxNode(_CppMultiOpNode):
 class _ImageDecoderNode(_CppMultiOpNode):
     """ImageDecoder (image_decoder_kernel_cpu.cpp / _gpu.cpp): a bytes column in, frames out.  Every requested row is probed
     on the host first (st_jpeg_probe): a row that is not a JPEG this library decodes, or whose shape differs from the first
-    row's, is a ValueError naming the row and the cause, before any kernel instance exists (the kernel class can only abort)."""
+    row's, or that has no restart intervals where the arguments say entropy = GPU, is a ValueError naming the row and the cause,
+    before any kernel instance exists (the kernel class can only abort)."""
 
     def rows(self, idx):
         if not idx:
@@ -607,6 +608,11 @@ class _ImageDecoderNode(_CppMultiOpNode):
         streams = self.parents[0].rows(idx)
         L = _native.lib()
         first = None
+        from . import _proto
+        try:
+            on_gpu = _proto.parse_image_decoder_args(self.args).get("entropy") == "GPU"
+        except Exception:
+            on_gpu = False   # not a message: the kernel's validate() reports it
         for r, data in zip(idx, streams):
             if not isinstance(data, (bytes, bytearray)):
                 raise ValueError("%s: row %d is %s, not the bytes of an encoded image" % (self.name, r, type(data).__name__))
@@ -619,6 +625,8 @@ class _ImageDecoderNode(_CppMultiOpNode):
             # the kernel takes the frame shape of an execute() from its first element: one stream, one shape
             if shape != first:
                 raise ValueError("%s: row %d changes shape inside a batch: %s after %s" % (self.name, r, shape, first))
+            if on_gpu and info.restart_interval <= 0:
+                raise ValueError("%s: row %d: no restart intervals: the stream has no DRI segment, entropy = GPU needs one" % (self.name, r))
         node = copy.copy(self)
         node.parents = [_RowsNode(dict(zip(idx, streams)), self.length())]
         return _CppMultiOpNode.rows(node, idx)
@@ -898,10 +906,11 @@ class _Ops:
         """sc.ops.ImageDecoder(img=..., device=..., batch=..., args={'image_type': 'JPEG'}): the bytes of one baseline JPEG per
         row (Client.ingest_rows) -> the decoded (h, w, 3) RGB or (h, w, 1) uint8 frame (image_decoder_kernel_cpu.cpp:57,
         ImageDecoderArgs of scannertools_imgproc.proto:41-49).  ``args``: None, a dict with image_type "JPEG" / "PNG" / "ANY"
-        (the last two fail validation: JPEG only), or serialised bytes."""
+        (the last two fail validation: JPEG only) and / or entropy "host" / "gpu" / "auto" (ImageDecoderArgs.entropy = 2:
+        where the Huffman decoder runs; "gpu" needs restart intervals in every row), or serialised bytes."""
         from . import _proto
         if isinstance(args, dict):
-            args = _proto.image_decoder_args(args.get("image_type"))
+            args = _proto.image_decoder_args(args.get("image_type"), args.get("entropy"))
         return _ImageDecoderNode(self.sc, "ImageDecoder", [img], device, batch, args or b"")
 
     def ImageEncoder(self, frame, quality=95, subsampling="4:2:0", device=None, batch=None):

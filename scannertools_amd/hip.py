@@ -437,11 +437,16 @@ class HipContext:
         self._check(self._L.st_cvt_color_u8_batch(self._h, tf, n, h, w, c, int(code), int(gray_bits), to))
         return out
 
-    def decode_jpeg(self, streams, out=None):
+    def decode_jpeg(self, streams, out=None, entropy="host"):
         """ImageDecoder op (image_decoder_kernel_cpu.cpp:16-29): a list of baseline JPEG streams (bytes) of one shape ->
         (n, h, w, c) uint8 CUDA tensor, c = 3 in R, G, B order or 1; bit-exact to libjpeg's defaults.  The shape is the first
         stream's; a stream of another shape, or one that is refused or malformed, raises StError naming it, and nothing is
-        written.  Entropy decoding runs on host threads (ST_JPEG_THREADS), the rest in HIP kernels on the current stream."""
+        written.  entropy="host" (the default): entropy decoding runs on host threads (ST_JPEG_THREADS), the rest in HIP
+        kernels on the current stream.  entropy="gpu": st_jpeg_decode_batch_gpu, the Huffman decoder is a HIP kernel too, one
+        lane per restart interval; every stream must have restart intervals (StError naming the one that has none).
+        entropy="auto": "gpu" when every stream's probe reports a restart interval, else "host".  Same frames either way."""
+        if entropy not in JPEG_ENTROPY_MODES:
+            raise ValueError("entropy must be one of %s, got %r" % (", ".join(repr(m) for m in JPEG_ENTROPY_MODES), entropy))
         self._bind()
         streams = [bytes(s) for s in streams]
         n = len(streams)
@@ -453,7 +458,10 @@ class HipContext:
         bufs = (ctypes.c_void_p * n)(*[ctypes.cast(ctypes.c_char_p(s), ctypes.c_void_p).value for s in streams])
         sizes = (ctypes.c_size_t * n)(*[len(s) for s in streams])
         to = (ctypes.c_void_p * n)(*[out[i].data_ptr() for i in range(n)])
-        self._check(self._L.st_jpeg_decode_batch(self._h, bufs, sizes, n, shape[1], shape[2], shape[3], to))
+        if entropy == "auto":
+            entropy = "gpu" if all(_jpeg_has_restarts(s) for s in streams) else "host"
+        call = self._L.st_jpeg_decode_batch_gpu if entropy == "gpu" else self._L.st_jpeg_decode_batch
+        self._check(call(self._h, bufs, sizes, n, shape[1], shape[2], shape[3], to))
         return out
 
     def encode_jpeg(self, frames, quality=95, subsampling="4:2:0"):
@@ -954,9 +962,35 @@ def probe_jpeg(stream):
     return {k: getattr(info, k) for k in ("h", "w", "channels", "h_samp", "v_samp", "restart_interval")}
 
 
-def jpeg_coefficients(stream):
+JPEG_ENTROPY_MODES = ("host", "gpu", "auto")   # decode_jpeg's entropy=; ImageDecoderArgs.entropy HOST = 0, GPU = 1, AUTO = 2
+
+
+def _jpeg_has_restarts(data):
+    """True when the stream's probe succeeds and reports restart_interval > 0 (a refused stream is left to the decoding call)."""
+    info = _native.JpegInfo()
+    return _native.lib().st_jpeg_probe(data, len(data), ctypes.byref(info)) == 0 and info.restart_interval > 0
+
+
+def jpeg_restart_intervals(stream):
+    """st_jpeg_restart_intervals (host only): the (n, 2) uint32 array of (begin, end) byte offsets of the stream's restart
+    intervals; StError for a stream without DRI (ST_ERR_UNSUPPORTED) or with a broken scan (ST_ERR_INVALID)."""
+    data = bytes(stream)
+    info = _native.JpegInfo()
+    count = ctypes.c_size_t(0)
+    st = _native.lib().st_jpeg_restart_intervals(data, len(data), None, 0, ctypes.byref(count), ctypes.byref(info))
+    if st != 0:
+        raise StError(st, info.message.decode())
+    table = np.empty((count.value, 2), np.uint32)
+    st = _native.lib().st_jpeg_restart_intervals(data, len(data), table.ctypes.data, count.value, ctypes.byref(count), ctypes.byref(info))
+    if st != 0:
+        raise StError(st, info.message.decode())
+    return table
+
+
+def jpeg_coefficients(stream, by_interval=False):
     """st_jpeg_coefficients (host only): (int16 coefficients in the layout the header documents, (channels, 64) uint16
-    quantisation tables in natural order) of a baseline JPEG stream."""
+    quantisation tables in natural order) of a baseline JPEG stream.  by_interval=True: st_jpeg_coefficients_by_interval, the
+    same result computed restart interval by restart interval with the core the device kernel runs."""
     data = bytes(stream)
     info = probe_jpeg(data)
     H, V = info["h_samp"], info["v_samp"]
@@ -965,7 +999,8 @@ def jpeg_coefficients(stream):
     coef = np.empty(blocks * 64, np.int16)
     quant = np.empty((info["channels"], 64), np.uint16)
     ji = _native.JpegInfo()
-    st = _native.lib().st_jpeg_coefficients(data, len(data), coef.ctypes.data, coef.size, quant.ctypes.data, ctypes.byref(ji))
+    fn = _native.lib().st_jpeg_coefficients_by_interval if by_interval else _native.lib().st_jpeg_coefficients
+    st = fn(data, len(data), coef.ctypes.data, coef.size, quant.ctypes.data, ctypes.byref(ji))
     if st != 0:
         raise StError(st, ji.message.decode())
     return coef, quant

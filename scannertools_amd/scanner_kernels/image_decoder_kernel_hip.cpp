@@ -15,6 +15,12 @@
 // serialised by protoc is an empty message and cannot be told from "no arguments": it is accepted, and a PNG stream then
 // fails in execute() as any stream that is not a JPEG does.)
 //
+// ImageDecoderArgs { ..., entropy = 2: HOST = 0 | GPU = 1 | AUTO = 2 } (this build's own field, scannertools_imgproc_amd.proto)
+// chooses where the Huffman decoder runs: HOST, and a message without the field, is st_jpeg_decode_batch() as above; GPU is
+// st_jpeg_decode_batch_gpu(), the Huffman decoder a HIP kernel with one lane per restart interval, and a row without restart
+// intervals is then fatal with the row and the cause; AUTO takes GPU for an execute() whose rows all have restart intervals
+// and HOST otherwise.  Any other value fails validate().  The frames are the same bytes either way.
+//
 // The frame shape of an execute() is that of its first element.  Where the reference is undefined this fails instead: an
 // element of another shape (the reference's CPU kernel copies it into a frame of the first one's size, :46-50), and an element
 // that is not a baseline JPEG this library decodes ("Failed to decode image" there) are fatal with the row and the cause.
@@ -30,13 +36,17 @@
 
 namespace scanner {
 namespace {
-// false: not a message; *image_type: -1 when the field is absent
-bool parse_image_decoder_args(const std::vector<u8>& args, int* image_type) {
+enum { ENTROPY_HOST = 0, ENTROPY_GPU = 1, ENTROPY_AUTO = 2 };
+// false: not a message; *image_type: -1 when the field is absent; *entropy: ENTROPY_HOST when the field is absent
+bool parse_image_decoder_args(const std::vector<u8>& args, int* image_type, long long* entropy) {
   std::vector<proto_lite::Field> fields;
   *image_type = -1;
+  *entropy = ENTROPY_HOST;
   if (!proto_lite::parse(args.data(), args.size(), &fields)) return false;
-  for (auto& f : fields)
+  for (auto& f : fields) {
     if (f.number == 1 && f.wire == 0) *image_type = (int)f.value;
+    if (f.number == 2 && f.wire == 0) *entropy = (long long)f.value;
+  }
   return true;
 }
 }  // namespace
@@ -46,11 +56,15 @@ class ImageDecoderKernelHIPImpl : public BatchedKernel {
  public:
   ImageDecoderKernelHIPImpl(const KernelConfig& config) : BatchedKernel(config), core_(config, STAGED), stage_(core_.gpu) {
     int image_type = -1;
-    if (!parse_image_decoder_args(config.args, &image_type)) RESULT_ERROR(&core_.valid, "ImageDecoder: could not parse ImageDecoderArgs");
+    long long entropy = ENTROPY_HOST;
+    if (!parse_image_decoder_args(config.args, &image_type, &entropy)) RESULT_ERROR(&core_.valid, "ImageDecoder: could not parse ImageDecoderArgs");
     else if (image_type == 0 || image_type == 2)
       RESULT_ERROR(&core_.valid, "ImageDecoder: image_type %s is not supported (JPEG only)", image_type == 0 ? "PNG" : "ANY");
     else if (image_type != -1 && image_type != 1) RESULT_ERROR(&core_.valid, "ImageDecoder: invalid image_type %d", image_type);
+    else if (entropy < ENTROPY_HOST || entropy > ENTROPY_AUTO)
+      RESULT_ERROR(&core_.valid, "ImageDecoder: invalid entropy %lld (HOST = 0, GPU = 1, AUTO = 2)", entropy);
     else core_.open("ImageDecoderKernelHIP");
+    entropy_ = (int)entropy;
   }
   void validate(Result* result) override { core_.validate(result); }
 
@@ -60,6 +74,7 @@ class ImageDecoderKernelHIPImpl : public BatchedKernel {
     if (n == 0) return;
     // the shape of the batch is that of its first element; every element is probed before anything is launched
     st_jpeg_info first = {};
+    bool restarts = true;   // every row has restart intervals
     for (i32 i = 0; i < n; ++i) {
       st_jpeg_info info;
       const int st = st_jpeg_probe(img_col[i].buffer, img_col[i].size, &info);
@@ -68,7 +83,11 @@ class ImageDecoderKernelHIPImpl : public BatchedKernel {
       LOG_IF(FATAL, info.h != first.h || info.w != first.w || info.channels != first.channels)
           << "ImageDecoder: row " << i << " of the batch changes shape inside a batch (" << info.w << "x" << info.h << "x" << info.channels
           << " after " << first.w << "x" << first.h << "x" << first.channels << ")";
+      LOG_IF(FATAL, entropy_ == ENTROPY_GPU && info.restart_interval <= 0)
+          << "ImageDecoder: row " << i << " of the batch: no restart intervals: the stream has no DRI segment, entropy = GPU needs one";
+      restarts = restarts && info.restart_interval > 0;
     }
+    const bool on_gpu = entropy_ == ENTROPY_GPU || (entropy_ == ENTROPY_AUTO && restarts);
     FrameInfo info(first.h, first.w, first.channels, FrameType::U8);
     std::vector<Frame*> output_frames = new_frames(core_.device, info, n);
     bufs_.resize(n);
@@ -83,7 +102,8 @@ class ImageDecoderKernelHIPImpl : public BatchedKernel {
       output_ptrs(dst_, output_frames);
     }
     st_ctx* ctx = core_.ctx;
-    const int st = st_jpeg_decode_batch(ctx, bufs_.data(), sizes_.data(), n, first.h, first.w, first.channels, dst_.data());
+    const int st = on_gpu ? st_jpeg_decode_batch_gpu(ctx, bufs_.data(), sizes_.data(), n, first.h, first.w, first.channels, dst_.data())
+                          : st_jpeg_decode_batch(ctx, bufs_.data(), sizes_.data(), n, first.h, first.w, first.channels, dst_.data());
     LOG_IF(FATAL, st != ST_OK) << "ImageDecoder: " << st_ctx_last_error(ctx);
     core_.sync();
     if (STAGED) stage_.download_frames(output_frames, dev, out_stride, out_bytes);
@@ -93,6 +113,7 @@ class ImageDecoderKernelHIPImpl : public BatchedKernel {
  private:
   KernelCore core_;
   DeviceStage stage_;   // staged: the decoded frames
+  int entropy_ = ENTROPY_HOST;
   std::vector<const uint8_t*> bufs_;
   std::vector<size_t> sizes_;
   std::vector<uint8_t*> dst_;

@@ -16,6 +16,16 @@ The first frame of every quality is compared with Pillow byte for byte before an
 
 --trace makes three calls per quality and batch and times nothing: the kernel statistics of the trace then hold k_jpeg_idct
 and k_jpeg_color over known work.
+
+    python scripts/bench_image_decoder.py --entropy gpu [--rounds 5]
+    rocprofv3 --kernel-trace --stats -d DIR -- python scripts/bench_image_decoder.py --entropy gpu --trace
+
+--entropy gpu measures st_jpeg_decode_batch_gpu (the Huffman decoder on the device, one lane per restart interval) over the
+same pictures re-encoded with one restart interval per MCU row (restart_marker_rows=1), at batches of 32 and 256: frames/s
+end to end (synchronised), kernel ms per frame from the library's events (one ST_K_JPEG bracket per sub-batch: the upload,
+the entropy launch, the wait for its status word and the two dense launches), and the bytes uploaded per frame.  Beside
+it, in the same run, st_jpeg_decode_batch of the same streams at ST_JPEG_THREADS=16: the baseline.  With --trace it makes
+three device-path calls per quality and batch, so that the trace's statistics give k_jpeg_entropy_dec's share.
 """
 import argparse
 import ctypes
@@ -64,15 +74,74 @@ def rate(fn, frames, rounds):
     return frames / statistics.median(times)
 
 
+GPU_BATCHES = (32, 256)
+
+
+def entropy_gpu(args, Image):
+    import torch
+    from scannertools_amd import _native
+    from scannertools_amd.hip import HipContext, jpeg_restart_intervals
+    os.environ["ST_JPEG_THREADS"] = "16"
+    ctx = HipContext(0)
+    result = {"bench": "image_decoder_entropy_gpu", "h": H, "w": W, "sampling": "4:2:0", "restart": "one interval per MCU row",
+              "host_threads": 16, "qualities": {}}
+    out = torch.empty((max(GPU_BATCHES), H, W, 3), dtype=torch.uint8, device=ctx.device)
+    for quality in (75, 90):
+        streams = []
+        for s in make_streams(Image, quality):
+            buf = io.BytesIO()
+            Image.open(io.BytesIO(s)).save(buf, "JPEG", quality=quality, subsampling="4:2:0", restart_marker_rows=1)
+            streams.append(buf.getvalue())
+        for entropy in ("gpu", "host"):
+            got = ctx.decode_jpeg(streams[:1], entropy=entropy).cpu().numpy()[0]
+            assert np.array_equal(got, np.asarray(Image.open(io.BytesIO(streams[0])))), "decode differs from Pillow (%s)" % entropy
+        tables = [jpeg_restart_intervals(s) for s in streams]
+        # what one frame adds to a sub-batch's upload: its entropy-coded bytes (padded), interval table, frame record and header
+        upload = statistics.mean(((int(t[-1, 1]) - int(t[0, 0]) + 16 + 15) & ~15) + 8 * len(t) + 96 + 512 for t in tables)
+        q = {"stream_bytes": int(statistics.mean(len(s) for s in streams)), "intervals_per_frame": len(tables[0]),
+             "upload_bytes_per_frame": int(upload), "coefficient_bytes_per_frame": BLOCKS * 128}
+
+        def call(n, entropy):
+            ctx.decode_jpeg([streams[i % DISTINCT] for i in range(n)], out=out[:n], entropy=entropy)
+            ctx.sync()
+
+        if args.trace:
+            for n in GPU_BATCHES:
+                for _ in range(3):
+                    call(n, "gpu")
+            continue
+        for entropy in ("gpu", "host"):
+            fps, kms = {}, {}
+            for n in GPU_BATCHES:
+                runs = [rate(lambda: call(n, entropy), n, args.rounds) for _ in range(3)]     # three medians: the run-to-run range
+                fps["batch%d" % n] = {"median": round(statistics.median(runs), 1), "min": round(min(runs), 1), "max": round(max(runs), 1)}
+            ctx.timing_enable([_native.K_JPEG])
+            for n in GPU_BATCHES:
+                call(n, entropy)
+                ctx.timing_reset()
+                for _ in range(args.rounds):
+                    call(n, entropy)
+                launches, ms = ctx.timing_read(_native.K_JPEG)
+                kms["batch%d" % n] = {"ms_per_frame": round(ms / (args.rounds * n), 4), "brackets_per_call": launches / args.rounds}
+            ctx.timing_enable([])
+            q[entropy + "_fps"], q[entropy + "_bracket"] = fps, kms
+        result["qualities"]["q%d" % quality] = q
+    ctx.close()
+    print(json.dumps(result))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--trace", action="store_true")
+    ap.add_argument("--entropy", choices=("host", "gpu"), default="host", help="gpu: measure st_jpeg_decode_batch_gpu beside the host path")
     args = ap.parse_args()
     try:
         from PIL import Image
     except ImportError:
         sys.exit("bench_image_decoder.py needs Pillow to make its 1080p streams and as its yardstick")
+    if args.entropy == "gpu":
+        return entropy_gpu(args, Image)
     import torch
     from scannertools_amd import _native
     from scannertools_amd.hip import HipContext
