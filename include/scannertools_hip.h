@@ -701,6 +701,41 @@ int st_jpeg_coefficients_by_interval(const uint8_t* buf, size_t size, int16_t* c
 int st_jpeg_decode_batch_gpu(st_ctx* ctx, const uint8_t* const* bufs_host, const size_t* sizes, int n, int h, int w, int channels,
                              uint8_t* const* out_dev);
 
+/* ---- Huffman decoding by subsequence: streams with or without restart intervals ----
+ * A SEGMENT is a byte range that is decoded from a known state: a restart interval, or the whole scan of a stream without a
+ * DRI segment.  A segment is cut into subsequences of subseq_bytes raw bytes; each is decoded on its own from a guessed state,
+ * then again from the exit state of the one before it, round after round, until a round changes no exit state: every
+ * subsequence has then verified that it entered where its predecessor left, and the chain is the sequential decoder's.  Only
+ * then are coefficients written.  max_rounds caps the rounds; a segment that has not converged by then is decoded by the
+ * interval decoder in one piece.  0 in either field, or a null pointer, means the library's default (128 bytes, 64 rounds);
+ * subseq_bytes must be a multiple of 8 in 8..4096, max_rounds must not be negative. */
+typedef struct st_jpeg_split_opts { int subseq_bytes; int max_rounds; } st_jpeg_split_opts;
+/* Host only, re-entrant: the segment table of any baseline stream this library decodes, in st_jpeg_restart_intervals' terms
+ * (count, cap, (begin, end) pairs, info).  With a DRI segment it is that function's table; without one it is ONE segment from
+ * the first entropy-coded byte to the first marker that is neither FF00 nor a fill byte (the end of the buffer where there is
+ * none).  Refusals and messages are st_jpeg_probe's. */
+int st_jpeg_scan_segments(const uint8_t* buf, size_t size, uint32_t* table, size_t cap, size_t* count, st_jpeg_info* info);
+/* Host only, re-entrant: st_jpeg_coefficients' contract and output layout, computed by the iteration above with the bounded
+ * core the kernels of st_jpeg_decode_batch_gpu_split run (st_jpeg_entropy.h): their CPU twin.  *rounds (may be null) receives
+ * the rounds that changed an exit state, the most over the segments, or max_rounds when a segment fell back to the interval
+ * decoder.  A corrupt segment is ST_ERR_INVALID, the message naming the segment and the cause. */
+int st_jpeg_coefficients_by_subsequence(const uint8_t* buf, size_t size, const st_jpeg_split_opts* opts, int16_t* coef, size_t cap,
+                                        uint16_t* quant, st_jpeg_info* info, int* rounds);
+/* st_jpeg_decode_batch with the entropy decoding on the device by subsequence: same arguments, same frames byte for byte, for
+ * every stream st_jpeg_decode_batch accepts, with or without restart intervals, mixed in one call.  The upload is
+ * st_jpeg_decode_batch_gpu's (one copy per sub-batch) with a prefix table of subsequence counts per frame.  Per sub-batch:
+ * round launches (one lane per subsequence, up to 16 rounds per launch inside a workgroup, a count of changed exit states per
+ * launch), a segmented scan of block counts and DC sums, a launch that zeroes the coefficients, the write launch, and the
+ * interval decoder for segments that did not converge within max_rounds launches; then the inverse DCT and colour kernels.
+ * The host waits once per group of round launches (three, then two at a time) and once for the status word: two waits for a
+ * sub-batch that converges within two launches.  A corrupt segment fails the call with ST_ERR_INVALID, the message naming the
+ * lowest (stream, segment) -- "restart interval k of n", or "the scan" -- and the cause; the frames of that sub-batch and
+ * of later ones are not written. */
+int st_jpeg_decode_batch_gpu_split(st_ctx* ctx, const uint8_t* const* bufs_host, const size_t* sizes, int n, int h, int w, int channels,
+                                   uint8_t* const* out_dev, const st_jpeg_split_opts* opts);
+/* The rounds st_jpeg_decode_batch_gpu_split's last call on this context took: round launches, the most over its sub-batches. */
+int st_jpeg_split_last_rounds(st_ctx* ctx);
+
 /* ---- ImageEncoder: baseline JPEG ------------------------------------------------------------
  * The counterpart of the ImageDecoder block (Scanner's stdlib ImageEncoder wraps cv::imencode on the host; it is not part of
  * the reference tree).  Resident (h, w, 3) uint8 frames in R, G, B order become baseline JPEG streams; colour conversion,

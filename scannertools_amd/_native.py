@@ -82,6 +82,11 @@ class JpegInfo(ctypes.Structure):
                 ("v_samp", ctypes.c_int), ("restart_interval", ctypes.c_int), ("message", ctypes.c_char * 160)]
 
 
+class JpegSplitOpts(ctypes.Structure):
+    """``st_jpeg_split_opts``: subsequence bytes and the cap on rounds of the decoding by subsequence; 0: the library's default."""
+    _fields_ = [("subseq_bytes", ctypes.c_int), ("max_rounds", ctypes.c_int)]
+
+
 class FbParams(ctypes.Structure):
     """``st_fb_params``: arguments of cv::FarnebackOpticalFlow::create as the reference passes
     them (scannertools_cpp/imgproc/optical_flow_kernel_cpu.cpp:15-16) + the gray table width."""
@@ -190,6 +195,10 @@ SIGNATURES = {
     "st_jpeg_restart_intervals": (_i, [_vp, _sz, _vp, _sz, _c.POINTER(_sz), _c.POINTER(JpegInfo)]),
     "st_jpeg_coefficients_by_interval": (_i, [_vp, _sz, _vp, _sz, _vp, _c.POINTER(JpegInfo)]),
     "st_jpeg_decode_batch_gpu": (_i, [_vp, _c.POINTER(_vp), _c.POINTER(_sz), _i, _i, _i, _i, _c.POINTER(_vp)]),
+    "st_jpeg_scan_segments": (_i, [_vp, _sz, _vp, _sz, _c.POINTER(_sz), _c.POINTER(JpegInfo)]),
+    "st_jpeg_coefficients_by_subsequence": (_i, [_vp, _sz, _c.POINTER(JpegSplitOpts), _vp, _sz, _vp, _c.POINTER(JpegInfo), _c.POINTER(_i)]),
+    "st_jpeg_decode_batch_gpu_split": (_i, [_vp, _c.POINTER(_vp), _c.POINTER(_sz), _i, _i, _i, _i, _c.POINTER(_vp), _c.POINTER(JpegSplitOpts)]),
+    "st_jpeg_split_last_rounds": (_i, [_vp]),
     "st_jpeg_quant_tables": (_i, [_i, _vp, _vp]),
     "st_jpeg_encode_header": (_i, [_i, _i, _i, _i, _i, _vp, _sz, _c.POINTER(_sz)]),
     "st_jpeg_encode_bound": (ctypes.c_longlong, [_i, _i, _i, _i]),
@@ -212,7 +221,7 @@ def source_hash():
     st_build_info() of a library built from THIS tree reports."""
     import hashlib
     srcs = ["st_context.hip", "st_hist.hip", "st_farneback.hip", "st_flowvis.hip", "st_imgproc.hip", "st_pose.hip", "st_conv.hip",
-            "st_conv_tile_bf16x3.hip", "st_conv_tile_f32.hip", "st_framestats.hip", "st_jpeg.hip", "st_netinput.hip", "st_nn.hip", "st_detect.hip", "st_jpeg_enc.hip", "st_jpeg_entropy.hip", "st_jpeg_parse.cpp", "st_jpeg_enc_host.cpp", "st_internal.h",
+            "st_conv_tile_bf16x3.hip", "st_conv_tile_f32.hip", "st_framestats.hip", "st_jpeg.hip", "st_netinput.hip", "st_nn.hip", "st_detect.hip", "st_jpeg_enc.hip", "st_jpeg_entropy.hip", "st_jpeg_subseq.hip", "st_jpeg_parse.cpp", "st_jpeg_enc_host.cpp", "st_internal.h",
             "st_conv_tile.h", "st_jpeg_parse.h", "st_jpeg_enc_host.h", "st_jpeg_entropy.h",
             os.path.join("..", "..", "include", "scannertools_hip.h"), "Makefile"]
     hsh = hashlib.sha256()

@@ -109,10 +109,14 @@ IMAGE_TYPES = {"PNG": 0, "JPEG": 1, "ANY": 2}   # ImageDecoderArgs.ImageType
 ENTROPY_MODES = {"HOST": 0, "GPU": 1, "AUTO": 2}   # ImageDecoderArgs.Entropy
 
 
-def image_decoder_args(image_type=None, entropy=None):
+ENTROPY_SPLITS = {"INTERVAL": 0, "SUBSEQUENCE": 1}   # ImageDecoderArgs.Split
+
+
+def image_decoder_args(image_type=None, entropy=None, split=None):
     """A serialised ImageDecoderArgs.  None: the empty message (the op then decodes JPEG).  A named or numeric type is
     written explicitly, PNG = 0 too (proto3 would omit it, and the kernel could not tell it from an absent field).
-    entropy (field 2): None leaves the field out (HOST); "host" / "gpu" / "auto" in either case, or a number, is written."""
+    entropy (field 2): None leaves the field out (HOST); "host" / "gpu" / "auto" in either case, or a number, is written.
+    split (field 3): None leaves the field out (INTERVAL); "interval" / "subsequence" in either case, or a number, is written."""
     out = b""
     if image_type is not None:
         v = IMAGE_TYPES[image_type] if isinstance(image_type, str) else int(image_type)
@@ -122,12 +126,17 @@ def image_decoder_args(image_type=None, entropy=None):
             raise ValueError("entropy must be one of 'host', 'gpu', 'auto' or a number, got %r" % (entropy,))
         v = ENTROPY_MODES[entropy.upper()] if isinstance(entropy, str) else int(entropy)
         out += _varint(2 << 3 | 0) + _varint(v)
+    if split is not None:
+        if isinstance(split, str) and split.upper() not in ENTROPY_SPLITS:
+            raise ValueError("split must be one of 'interval', 'subsequence' or a number, got %r" % (split,))
+        v = ENTROPY_SPLITS[split.upper()] if isinstance(split, str) else int(split)
+        out += _varint(3 << 3 | 0) + _varint(v)
     return out
 
 
 def parse_image_decoder_args(buf):
-    """{'image_type': name or number, 'entropy': name or number} of a serialised ImageDecoderArgs; a key is missing when its
-    field is absent."""
+    """{'image_type': name or number, 'entropy': name or number, 'split': name or number} of a serialised ImageDecoderArgs; a
+    key is missing when its field is absent."""
     names = {v: k for k, v in IMAGE_TYPES.items()}
     modes = {v: k for k, v in ENTROPY_MODES.items()}
     out = {}
@@ -136,6 +145,8 @@ def parse_image_decoder_args(buf):
             out["image_type"] = names.get(value, value)
         if number == 2 and wt == 0:
             out["entropy"] = modes.get(value, value)
+        if number == 3 and wt == 0:
+            out["split"] = {v: k for k, v in ENTROPY_SPLITS.items()}.get(value, value)
     return out
 
 

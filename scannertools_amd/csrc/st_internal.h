@@ -63,6 +63,13 @@ struct StJpegEntArgs;
 // enqueues k_jpeg_entropy_dec (st_jpeg_entropy.hip) for one sub-batch of st_jpeg_decode_batch_gpu; max_groups: the most
 // groups of 64 restart intervals any of its frames has
 int st_jpeg_entropy_launch(st_ctx* ctx, const StJpegEntArgs& a, unsigned max_groups);
+struct StJsqArgs;
+// st_jpeg_subseq.hip, for one sub-batch of st_jpeg_decode_batch_gpu_split.  max_groups: the most groups of 64 subsequences any of
+// its frames has; max_segments: the most segments.  A round launch (k_jsq_round) reads the exit states of array par ^ 1 and
+// writes array par, and adds the exits it changed to *changed (device memory); `first`: no state exists yet.  The finishing
+// launches: k_jsq_scan over array par, k_jsq_zero over coef_bytes of coefficients, k_jsq_write, k_jsq_fallback.
+int st_jsq_round_launch(st_ctx* ctx, const StJsqArgs& a, unsigned max_groups, bool first, int par, unsigned* changed);
+int st_jsq_finish_launch(st_ctx* ctx, const StJsqArgs& a, unsigned max_groups, unsigned max_segments, int par, size_t coef_bytes);
 void st_jpeg_enc_release(st_ctx* ctx); // frees ctx->jpeg_enc (st_ctx_destroy)
 void st_netin_release(st_ctx* ctx);  // frees ctx->netin (st_ctx_destroy)
 void st_detect_release(st_ctx* ctx); // frees ctx->detect (st_ctx_destroy)

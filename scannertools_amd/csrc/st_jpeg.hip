@@ -310,6 +310,7 @@ struct st_jpeg_state {
   uint8_t* gpin = nullptr;
   size_t gcap = 0;
   unsigned long long* gstatus = nullptr;
+  int split_rounds = 0;   // st_jpeg_split_last_rounds
 };
 
 void st_jpeg_release(st_ctx* ctx) {
@@ -518,6 +519,8 @@ struct GpuStream {
   int sb = 0, tabs = 0;
   bool writes_tabs = false;
   size_t iv_off = 0, bytes_off = 0;
+  // decoding by subsequence: its lanes, and where its prefix table of subsequence counts, its lanes and its segments start
+  size_t nlanes = 0, subpre_off = 0, lane_off = 0, seg_off = 0;
 };
 
 struct GpuSubBatch {
@@ -525,6 +528,9 @@ struct GpuSubBatch {
   size_t blocks = 0, nint = 0;
   unsigned max_groups = 0;
   size_t tables_off = 0, frames_off = 0, hdr_off = 0, upload_bytes = 0;
+  // decoding by subsequence: the StJsqFrame records in the upload, the lanes, and the per-lane state behind the coefficients
+  size_t sq_off = 0, lanes = 0, scratch_off = 0;
+  unsigned max_lane_groups = 0, max_segments = 0;
 };
 
 inline size_t up16(size_t v) { return (v + 15) & ~(size_t)15; }
@@ -548,9 +554,11 @@ void run_threads(int T, F&& f) {
 
 }  // namespace
 
-ST_EXPORT int st_jpeg_decode_batch_gpu(st_ctx* ctx, const uint8_t* const* bufs_host, const size_t* sizes, int n, int h, int w, int channels,
-                                       uint8_t* const* out_dev) {
-  ST_TRY(st_enter(ctx));
+namespace {
+// st_jpeg_decode_batch_gpu (split = false: one lane per restart interval) and st_jpeg_decode_batch_gpu_split (split = true: one
+// lane per subsequence of S bytes, at most R round launches) share everything but the entropy launches.
+int decode_batch_gpu(st_ctx* ctx, const uint8_t* const* bufs_host, const size_t* sizes, int n, int h, int w, int channels, uint8_t* const* out_dev,
+                     const bool split, const uint32_t S, const int R) {
   if (n < 0 || h <= 0 || w <= 0 || h > 65535 || w > 65535 || (channels != 1 && channels != 3))
     return st_set_error(ctx, ST_ERR_INVALID, "jpeg: bad arguments (n=%d h=%d w=%d channels=%d)", n, h, w, channels);
   if (n == 0) return ST_OK;
@@ -589,6 +597,7 @@ ST_EXPORT int st_jpeg_decode_batch_gpu(st_ctx* ctx, const uint8_t* const* bufs_h
           return;
         }
         g.nint = (uint32_t)st_jpeg_interval_count(hd);
+        if (g.nint == 0 && split) g.nint = 1;   // the whole scan is one segment
         if (g.nint == 0) {
           note(probe_fail, i, ST_ERR_UNSUPPORTED, "jpeg: stream %d: no restart intervals: the stream has no DRI segment, entropy decoding on the device needs one", i);
           return;
@@ -605,13 +614,16 @@ ST_EXPORT int st_jpeg_decode_batch_gpu(st_ctx* ctx, const uint8_t* const* bufs_h
         g.owner = t;
         g.iv_at = iv.size();
         iv.resize(iv.size() + 2 * (size_t)g.nint);
-        const int ss = st_jpeg_scan_intervals(bufs_host[i], sizes[i], hd, iv.data() + g.iv_at, msg, sizeof msg);
+        const int ss = split ? st_jpeg_segments(bufs_host[i], sizes[i], hd, iv.data() + g.iv_at, msg, sizeof msg)
+                             : st_jpeg_scan_intervals(bufs_host[i], sizes[i], hd, iv.data() + g.iv_at, msg, sizeof msg);
         if (ss != ST_OK) {
           note(scan_fail, i, ss, "jpeg: stream %d: %s", i, msg);
           scan_ok = false;
           continue;
         }
         g.nbytes = (size_t)iv[g.iv_at + 2 * (size_t)g.nint - 1] - g.scan_pos;
+        if (split)
+          for (size_t k = 0; k < g.nint; ++k) g.nlanes += st_jsq_count(iv[g.iv_at + 2 * k + 1] - iv[g.iv_at + 2 * k], S);
       }
     });
   } catch (const std::exception&) {
@@ -630,18 +642,25 @@ ST_EXPORT int st_jpeg_decode_batch_gpu(st_ctx* ctx, const uint8_t* const* bufs_h
       sb.tables_off = 16;
       sb.frames_off = up16(sb.tables_off + (size_t)sb.nsets * sizeof(StJpegFrameTables));
       size_t o = sb.frames_off + (size_t)sb.count * sizeof(StJpegEntFrame);
+      if (split) { sb.sq_off = o; o += (size_t)sb.count * sizeof(StJsqFrame); }
       for (int i = sb.first; i < sb.first + sb.count; ++i) { gs[(size_t)i].iv_off = o; o += (size_t)gs[(size_t)i].nint * 8; }
+      if (split)
+        for (int i = sb.first; i < sb.first + sb.count; ++i) { gs[(size_t)i].subpre_off = o; o += ((size_t)gs[(size_t)i].nint + 1) * 4; }
       o = up16(o);
       for (int i = sb.first; i < sb.first + sb.count; ++i) { gs[(size_t)i].bytes_off = o; o += up16(gs[(size_t)i].nbytes + 16); }
       sb.hdr_off = st_align_up(o);
       sb.upload_bytes = sb.hdr_off + (size_t)sb.count * sizeof(JpegFrameHdr);
       upload_most = std::max(upload_most, sb.upload_bytes);
-      dev_most = std::max(dev_most, sb.upload_bytes + sb.blocks * 128);
+      // behind the coefficients: per lane two exit states, the entered-from state and four counts; per segment a flag; four
+      // counters of changed exits
+      sb.scratch_off = up16(sb.upload_bytes + sb.blocks * 128);
+      dev_most = std::max(dev_most, split ? sb.scratch_off + sb.lanes * 40 + up16(sb.nint * 4) + 16 : sb.upload_bytes + sb.blocks * 128);
       plane_most = std::max(plane_most, sb.blocks * 64);
     };
     for (int i = 0; i < n; ++i) {
       GpuStream& g = gs[(size_t)i];
-      if (sbs.empty() || (sbs.back().blocks + g.nblocks) * 128 > kGpuCoefBytes) {
+      if (sbs.empty() || (sbs.back().blocks + g.nblocks) * 128 > kGpuCoefBytes || sbs.back().lanes + g.nlanes > ((size_t)1 << 31) ||
+          sbs.back().nint + g.nint > ((size_t)1 << 31)) {
         close();
         sbs.push_back(GpuSubBatch());
         sbs.back().first = i;
@@ -652,6 +671,11 @@ ST_EXPORT int st_jpeg_decode_batch_gpu(st_ctx* ctx, const uint8_t* const* bufs_h
       if (g.writes_tabs) sb.nsets++;
       g.tabs = sb.nsets - 1;
       g.fh.blk_off = (int)sb.blocks;
+      g.lane_off = sb.lanes;
+      g.seg_off = sb.nint;
+      sb.lanes += g.nlanes;
+      sb.max_lane_groups = std::max(sb.max_lane_groups, (unsigned)((g.nlanes + (size_t)kStJsqLanes - 1) / (size_t)kStJsqLanes));
+      sb.max_segments = std::max(sb.max_segments, g.nint);
       sb.count++;
       sb.blocks += g.nblocks;
       sb.nint += g.nint;
@@ -724,6 +748,18 @@ ST_EXPORT int st_jpeg_decode_batch_gpu(st_ctx* ctx, const uint8_t* const* bufs_h
         const uint32_t* iv = ivs[(size_t)g.owner].data() + g.iv_at;
         uint32_t* dv = reinterpret_cast<uint32_t*>(slot + g.iv_off);
         for (size_t k = 0; k < 2 * (size_t)g.nint; ++k) dv[k] = iv[k] - (uint32_t)g.scan_pos;
+        if (split) {
+          StJsqFrame* qf = reinterpret_cast<StJsqFrame*>(slot + sb.sq_off) + j;
+          memset(qf, 0, sizeof *qf);
+          qf->subpre_off = g.subpre_off;
+          qf->lane_off = (uint32_t)g.lane_off;
+          qf->seg_off = (uint32_t)g.seg_off;
+          qf->nlanes = (uint32_t)g.nlanes;
+          uint32_t* pre = reinterpret_cast<uint32_t*>(slot + g.subpre_off);
+          uint32_t sum = 0;
+          for (size_t k = 0; k < g.nint; ++k) { pre[k] = sum; sum += st_jsq_count(iv[2 * k + 1] - iv[2 * k], S); }
+          pre[g.nint] = sum;
+        }
         memcpy(slot + g.bytes_off, bufs_host[i] + g.scan_pos, g.nbytes);
         memset(slot + g.bytes_off + g.nbytes, 0, up16(g.nbytes + 16) - g.nbytes);
         memcpy(slot + sb.hdr_off + (size_t)j * sizeof(JpegFrameHdr), &g.fh, sizeof(JpegFrameHdr));
@@ -743,7 +779,37 @@ ST_EXPORT int st_jpeg_decode_batch_gpu(st_ctx* ctx, const uint8_t* const* bufs_h
       ea.status = reinterpret_cast<unsigned long long*>(d_up);
       ea.nf = sb.count;
       ea.first_stream = sb.first;
-      ST_TRY(st_jpeg_entropy_launch(ctx, ea, sb.max_groups));
+      if (!split) {
+        ST_TRY(st_jpeg_entropy_launch(ctx, ea, sb.max_groups));
+      } else {
+        StJsqArgs qa;
+        qa.ent = ea;
+        qa.sq = reinterpret_cast<const StJsqFrame*>(d_up + sb.sq_off);
+        uint8_t* scratch = d_up + sb.scratch_off;
+        qa.exits[0] = reinterpret_cast<uint64_t*>(scratch + sb.lanes * 16);
+        qa.exits[1] = reinterpret_cast<uint64_t*>(scratch + sb.lanes * 24);
+        qa.entered = reinterpret_cast<uint64_t*>(scratch + sb.lanes * 32);
+        qa.counts = reinterpret_cast<uint32_t*>(scratch);   // 16 bytes per lane, 16-byte aligned
+        qa.unconverged = reinterpret_cast<uint32_t*>(scratch + sb.lanes * 40);
+        qa.changed = reinterpret_cast<unsigned*>(scratch + sb.lanes * 40 + up16(sb.nint * 4));
+        qa.S = S;
+        // round launches in groups (three, then two at a time), one host wait per group for its counts of changed exits: a
+        // launch that changed none has verified the chain.  Launches behind it in its group change nothing either.
+        int launches = 0, rounds = R;
+        bool converged = false;
+        unsigned* back = reinterpret_cast<unsigned*>(js->gstatus + 1);
+        while (launches < R && !converged) {
+          const int group = std::min(launches == 0 ? 3 : 2, R - launches);
+          ST_HIP(ctx, hipMemsetAsync(qa.changed, 0, 16, ctx->stream));
+          for (int q = 0; q < group; ++q, ++launches) ST_TRY(st_jsq_round_launch(ctx, qa, sb.max_lane_groups, launches == 0, launches & 1, qa.changed + q));
+          ST_HIP(ctx, hipMemcpyAsync(back, qa.changed, 16, hipMemcpyDeviceToHost, ctx->stream));
+          ST_HIP(ctx, hipStreamSynchronize(ctx->stream));
+          for (int q = 0; q < group && !converged; ++q)
+            if (back[q] == 0) { converged = true; rounds = launches - group + q; }
+        }
+        js->split_rounds = std::max(js->split_rounds, rounds);
+        ST_TRY(st_jsq_finish_launch(ctx, qa, sb.max_lane_groups, sb.max_segments, (launches - 1) & 1, sb.blocks * 128));
+      }
       ST_HIP(ctx, hipMemcpyAsync(js->gstatus, d_up, sizeof word, hipMemcpyDeviceToHost, ctx->stream));
       ST_HIP(ctx, hipStreamSynchronize(ctx->stream));
       word = *js->gstatus;
@@ -772,9 +838,31 @@ ST_EXPORT int st_jpeg_decode_batch_gpu(st_ctx* ctx, const uint8_t* const* bufs_h
       const int stream = (int)(word >> 32);
       const unsigned interval = (unsigned)((word >> 4) & 0xfffffffu);
       const unsigned nint = stream >= 0 && stream < n ? gs[(size_t)stream].nint : 0u;
+      if (split && stream >= 0 && stream < n && gs[(size_t)stream].geom.restart_interval <= 0)
+        return st_set_error(ctx, ST_ERR_INVALID, "jpeg: stream %d: corrupt scan: the scan: %s", stream, st_jpeg_entropy_cause((int)(word & 15)));
       return st_set_error(ctx, ST_ERR_INVALID, "jpeg: stream %d: corrupt scan: restart interval %u of %u: %s", stream, interval, nint,
                           st_jpeg_entropy_cause((int)(word & 15)));
     }
   }
   return ST_OK;
 }
+}  // namespace
+
+ST_EXPORT int st_jpeg_decode_batch_gpu(st_ctx* ctx, const uint8_t* const* bufs_host, const size_t* sizes, int n, int h, int w, int channels,
+                                       uint8_t* const* out_dev) {
+  ST_TRY(st_enter(ctx));
+  return decode_batch_gpu(ctx, bufs_host, sizes, n, h, w, channels, out_dev, false, 0, 0);
+}
+
+ST_EXPORT int st_jpeg_decode_batch_gpu_split(st_ctx* ctx, const uint8_t* const* bufs_host, const size_t* sizes, int n, int h, int w, int channels,
+                                             uint8_t* const* out_dev, const st_jpeg_split_opts* opts) {
+  ST_TRY(st_enter(ctx));
+  const int S = opts && opts->subseq_bytes ? opts->subseq_bytes : kStJsqDefaultSubseqBytes;
+  const int R = opts && opts->max_rounds ? opts->max_rounds : kStJsqDefaultMaxRounds;
+  if (S < 8 || S > 4096 || S % 8 != 0 || R < 0)
+    return st_set_error(ctx, ST_ERR_INVALID, "jpeg: subseq_bytes %d / max_rounds %d: a multiple of 8 in 8..4096, and no negative cap", S, R);
+  if (ctx->jpeg) ctx->jpeg->split_rounds = 0;
+  return decode_batch_gpu(ctx, bufs_host, sizes, n, h, w, channels, out_dev, true, (uint32_t)S, R);
+}
+
+ST_EXPORT int st_jpeg_split_last_rounds(st_ctx* ctx) { return ctx && ctx->jpeg ? ctx->jpeg->split_rounds : 0; }

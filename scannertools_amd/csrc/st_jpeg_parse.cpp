@@ -4,6 +4,8 @@
 // status and a message, never a crash.  No state between calls.
 #include "st_jpeg_parse.h"
 
+#include <algorithm>
+#include <climits>
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
@@ -444,4 +446,148 @@ ST_JPEG_EXPORT int st_jpeg_coefficients_by_interval(const uint8_t* buf, size_t s
   if (quant)
     for (int c = 0; c < hd.ncomp; ++c) memcpy(quant + 64 * c, hd.quant[hd.tq[c]], 128);
   return ST_OK;
+}
+
+// ---- decoding by subsequence: the segment table and the CPU twin of st_jpeg_subseq.hip ------------------------
+int st_jpeg_segments(const uint8_t* buf, size_t size, const StJpegHeader& hd, uint32_t* table, char* msg, size_t msg_len) {
+  if (hd.restart_interval > 0) return st_jpeg_scan_intervals(buf, size, hd, table, msg, msg_len);
+  if (msg && msg_len) msg[0] = 0;
+  if (size >= ((size_t)1 << 32)) return fail(msg, msg_len, ST_ERR_UNSUPPORTED, "a stream of %zu bytes is too long (below 4 GiB only)", size);
+  size_t pos = hd.scan_pos, end = size;   // the end of the buffer ends the scan (a lone 0xFF as its last byte included)
+  while (pos < size) {
+    const uint8_t* p = (const uint8_t*)memchr(buf + pos, 0xFF, size - pos);
+    if (!p || (size_t)(p - buf) + 1 >= size) break;
+    pos = (size_t)(p - buf);
+    if (p[1] == 0x00) { pos += 2; continue; }   // stuffed FF
+    if (p[1] == 0xFF) { pos += 1; continue; }   // fill byte
+    end = pos;
+    break;
+  }
+  table[0] = (uint32_t)hd.scan_pos;
+  table[1] = (uint32_t)end;
+  return ST_OK;
+}
+
+ST_JPEG_EXPORT int st_jpeg_scan_segments(const uint8_t* buf, size_t size, uint32_t* table, size_t cap, size_t* count, st_jpeg_info* info) {
+  st_jpeg_info local;
+  if (!info) info = &local;
+  memset(info, 0, sizeof *info);
+  if (count) *count = 0;
+  StJpegHeader hd;
+  const int st = st_jpeg_parse_header(buf, size, &hd, info->message, sizeof info->message);
+  if (st != ST_OK) return st;
+  fill_info(hd, info);
+  const size_t need = st_jpeg_segment_count(hd);
+  if (count) *count = need;
+  if (!table) return ST_OK;
+  if (cap < need) return fail(info->message, sizeof info->message, ST_ERR_INVALID, "table holds %zu pairs, the stream has %zu segments", cap, need);
+  return st_jpeg_segments(buf, size, hd, table, info->message, sizeof info->message);
+}
+
+ST_JPEG_EXPORT int st_jpeg_coefficients_by_subsequence(const uint8_t* buf, size_t size, const st_jpeg_split_opts* opts, int16_t* coef, size_t cap,
+                                                       uint16_t* quant, st_jpeg_info* info, int* rounds) {
+  st_jpeg_info local;
+  if (!info) info = &local;
+  memset(info, 0, sizeof *info);
+  if (rounds) *rounds = 0;
+  const int S = opts && opts->subseq_bytes ? opts->subseq_bytes : kStJsqDefaultSubseqBytes;
+  const int R = opts && opts->max_rounds ? opts->max_rounds : kStJsqDefaultMaxRounds;
+  if (S < 8 || S > 4096 || S % 8 != 0 || R < 0)
+    return fail(info->message, sizeof info->message, ST_ERR_INVALID, "subseq_bytes %d / max_rounds %d: a multiple of 8 in 8..4096, and no negative cap", S, R);
+  StJpegHeader* hdp = new (std::nothrow) StJpegHeader;
+  StJpegFrameTables* tabs = new (std::nothrow) StJpegFrameTables;
+  uint32_t* table = nullptr;
+  uint64_t* words = nullptr;   // per lane: exit, next exit, entered-from
+  StJsqOut* outs = nullptr;
+  int st = ST_OK;
+  if (!hdp || !tabs) st = fail(info->message, sizeof info->message, ST_ERR_OOM, "out of host memory");
+  if (st == ST_OK) st = st_jpeg_parse_header(buf, size, hdp, info->message, sizeof info->message);
+  size_t need = 0, nseg = 0;
+  if (st == ST_OK) {
+    fill_info(*hdp, info);
+    need = st_jpeg_blocks(*hdp) * 64;
+    if (!coef || cap < need) st = fail(info->message, sizeof info->message, ST_ERR_INVALID, "coef holds %zu values, the stream has %zu", coef ? cap : (size_t)0, need);
+  }
+  if (st == ST_OK) {
+    nseg = st_jpeg_segment_count(*hdp);
+    table = new (std::nothrow) uint32_t[2 * nseg];
+    if (!table) st = fail(info->message, sizeof info->message, ST_ERR_OOM, "out of host memory for %zu segments", nseg);
+  }
+  if (st == ST_OK) st = st_jpeg_segments(buf, size, *hdp, table, info->message, sizeof info->message);
+  if (st == ST_OK) {
+    const StJpegHeader& hd = *hdp;
+    size_t most = 1;
+    for (size_t k = 0; k < nseg; ++k) most = std::max(most, (size_t)st_jsq_count(table[2 * k + 1] - table[2 * k], (uint32_t)S));
+    words = new (std::nothrow) uint64_t[3 * most];
+    outs = new (std::nothrow) StJsqOut[most];
+    if (!words || !outs) st = fail(info->message, sizeof info->message, ST_ERR_OOM, "out of host memory for %zu subsequences", most);
+    memset(tabs, 0, sizeof *tabs);
+    for (int c = 0; c < hd.ncomp; ++c) {
+      tabs->dc[c] = hd.dc[hd.td[c]];
+      tabs->ac[c] = hd.ac[hd.ta[c]];
+    }
+    const StJpegScanGeom g = st_jpeg_scan_geom(hd);
+    const StJpegZigzag zz = st_jpeg_zigzag();
+    const long long total = (long long)hd.mcux * hd.mcuy;
+    const uint32_t bpm = (uint32_t)st_jsq_mcu_blocks(g);
+    if (st == ST_OK) memset(coef, 0, need * sizeof(int16_t));   // the zeroing is a step of its own: two lanes may fill one block
+    int most_rounds = 0;
+    for (size_t k = 0; k < nseg && st == ST_OK; ++k) {
+      const uint32_t begin = table[2 * k], end = table[2 * k + 1];
+      const uint32_t nsub = st_jsq_count(end - begin, (uint32_t)S);
+      const long long mcu0 = hd.restart_interval > 0 ? (long long)k * hd.restart_interval : 0;
+      const long long nmcu = hd.restart_interval > 0 ? std::min<long long>(hd.restart_interval, total - mcu0) : total;
+      const uint32_t seg_blocks = (uint32_t)(std::max<long long>(nmcu, 0) * bpm);
+      uint64_t *E = words, *En = words + most, *U = words + 2 * most;
+      for (uint32_t i = 0; i < nsub; ++i) { E[i] = kStJsqInvalid; U[i] = kStJsqNever; }
+      auto sub_end = [&](uint32_t i) { return (uint32_t)std::min<uint64_t>((uint64_t)begin + ((uint64_t)i + 1) * (uint64_t)S, end); };
+      bool converged = false;
+      int seg_rounds = R;
+      for (int r = 1; r <= R && !converged; ++r) {
+        bool changed = r == 1;   // the first round gives every lane its first exit
+        for (uint32_t i = 0; i < nsub; ++i) {
+          const uint64_t enter = i == 0 ? st_jsq_pack(begin, 0, 0, 0) : E[i - 1];
+          En[i] = E[i];
+          if (enter == U[i]) continue;   // entered from the same state as before: same exit, same counts
+          const uint64_t from = enter == kStJsqInvalid ? st_jsq_guess(buf, begin, end, (uint32_t)((uint64_t)begin + (uint64_t)i * (uint64_t)S)) : enter;
+          st_jsq_run<false>(buf, end, sub_end(i), false, from, g, tabs, zz.nat, 0, 0, 0, nullptr, nullptr, &outs[i]);
+          U[i] = enter;
+          En[i] = outs[i].exit;
+          changed = changed || En[i] != E[i];
+        }
+        std::swap(E, En);
+        if (!changed) { converged = true; seg_rounds = r - 1; }
+        else if ((uint32_t)r >= nsub) { converged = true; seg_rounds = r; }   // lane r - 1 has entered from the true state
+      }
+      most_rounds = std::max(most_rounds, seg_rounds);
+      int je = ST_JE_OK;
+      if (!converged) {
+        je = st_jpeg_decode_interval(buf, begin, end, mcu0, (int)std::min<long long>(std::max<long long>(nmcu, 0), INT32_MAX), g, tabs, zz.nat, coef);
+      } else {
+        uint32_t before = 0, dc[3] = {0, 0, 0};
+        for (uint32_t i = 0; i < nsub && je == ST_JE_OK && before < seg_blocks; ++i) {
+          if (U[i] == kStJsqInvalid) break;   // the chain broke behind the segment's last block
+          StJsqOut o;
+          je = st_jsq_run<true>(buf, end, sub_end(i), i + 1 == nsub, U[i], g, tabs, zz.nat, mcu0, seg_blocks, before, dc, coef, &o);
+          before += o.blocks;
+          for (int c = 0; c < 3; ++c) dc[c] = o.dc[c];
+        }
+      }
+      if (je != ST_JE_OK) {
+        if (hd.restart_interval > 0)
+          st = fail(info->message, sizeof info->message, ST_ERR_INVALID, "corrupt scan: restart interval %zu of %zu: %s", k, nseg, st_jpeg_entropy_cause(je));
+        else
+          st = fail(info->message, sizeof info->message, ST_ERR_INVALID, "corrupt scan: the scan: %s", st_jpeg_entropy_cause(je));
+      }
+    }
+    if (rounds) *rounds = most_rounds;
+    if (st == ST_OK && quant)
+      for (int c = 0; c < hd.ncomp; ++c) memcpy(quant + 64 * c, hd.quant[hd.tq[c]], 128);
+  }
+  delete[] outs;
+  delete[] words;
+  delete[] table;
+  delete tabs;
+  delete hdp;
+  return st;
 }

@@ -56,4 +56,10 @@ inline size_t st_jpeg_interval_count(const StJpegHeader& hd) {
 // RSTn out of sequence.
 int st_jpeg_scan_intervals(const uint8_t* buf, size_t size, const StJpegHeader& hd, uint32_t* table, char* msg, size_t msg_len);
 
+// Segments of a parsed stream (byte ranges decoded from a known state): its restart intervals, or ONE for a stream without DRI.
+inline size_t st_jpeg_segment_count(const StJpegHeader& hd) { return hd.restart_interval > 0 ? st_jpeg_interval_count(hd) : 1; }
+// `table` receives st_jpeg_segment_count(hd) (begin, end) pairs: st_jpeg_scan_intervals' with DRI; without, the scan from
+// hd.scan_pos to the first marker that is neither FF00 nor a fill byte (or size).  ST_ERR_UNSUPPORTED: size >= 4 GiB.
+int st_jpeg_segments(const uint8_t* buf, size_t size, const StJpegHeader& hd, uint32_t* table, char* msg, size_t msg_len);
+
 #endif  // ST_JPEG_PARSE_H_

@@ -599,8 +599,8 @@ class _SharpnessBBoxNode(_CppMultiOpNode):
 class _ImageDecoderNode(_CppMultiOpNode):
     """ImageDecoder (image_decoder_kernel_cpu.cpp / _gpu.cpp): a bytes column in, frames out.  Every requested row is probed
     on the host first (st_jpeg_probe): a row that is not a JPEG this library decodes, or whose shape differs from the first
-    row's, or that has no restart intervals where the arguments say entropy = GPU, is a ValueError naming the row and the cause,
-    before any kernel instance exists (the kernel class can only abort)."""
+    row's, or that has no restart intervals where the arguments say entropy = GPU with split = INTERVAL (or no split), is a
+    ValueError naming the row and the cause, before any kernel instance exists (the kernel class can only abort)."""
 
     def rows(self, idx):
         if not idx:
@@ -610,7 +610,8 @@ class _ImageDecoderNode(_CppMultiOpNode):
         first = None
         from . import _proto
         try:
-            on_gpu = _proto.parse_image_decoder_args(self.args).get("entropy") == "GPU"
+            parsed = _proto.parse_image_decoder_args(self.args)
+            on_gpu = parsed.get("entropy") == "GPU" and parsed.get("split", "INTERVAL") == "INTERVAL"   # by subsequence needs none
         except Exception:
             on_gpu = False   # not a message: the kernel's validate() reports it
         for r, data in zip(idx, streams):
@@ -907,10 +908,12 @@ class _Ops:
         row (Client.ingest_rows) -> the decoded (h, w, 3) RGB or (h, w, 1) uint8 frame (image_decoder_kernel_cpu.cpp:57,
         ImageDecoderArgs of scannertools_imgproc.proto:41-49).  ``args``: None, a dict with image_type "JPEG" / "PNG" / "ANY"
         (the last two fail validation: JPEG only) and / or entropy "host" / "gpu" / "auto" (ImageDecoderArgs.entropy = 2:
-        where the Huffman decoder runs; "gpu" needs restart intervals in every row), or serialised bytes."""
+        where the Huffman decoder runs; "gpu" needs restart intervals in every row) and / or split "interval" / "subsequence"
+        (ImageDecoderArgs.split = 3: with entropy "gpu" or "auto", "subsequence" decodes on the device by subsequence and needs no
+        restart intervals), or serialised bytes."""
         from . import _proto
         if isinstance(args, dict):
-            args = _proto.image_decoder_args(args.get("image_type"), args.get("entropy"))
+            args = _proto.image_decoder_args(args.get("image_type"), args.get("entropy"), args.get("split"))
         return _ImageDecoderNode(self.sc, "ImageDecoder", [img], device, batch, args or b"")
 
     def ImageEncoder(self, frame, quality=95, subsampling="4:2:0", device=None, batch=None):

@@ -437,16 +437,23 @@ class HipContext:
         self._check(self._L.st_cvt_color_u8_batch(self._h, tf, n, h, w, c, int(code), int(gray_bits), to))
         return out
 
-    def decode_jpeg(self, streams, out=None, entropy="host"):
+    def decode_jpeg(self, streams, out=None, entropy="host", split="interval", subseq_bytes=None, max_rounds=None):
         """ImageDecoder op (image_decoder_kernel_cpu.cpp:16-29): a list of baseline JPEG streams (bytes) of one shape ->
         (n, h, w, c) uint8 CUDA tensor, c = 3 in R, G, B order or 1; bit-exact to libjpeg's defaults.  The shape is the first
         stream's; a stream of another shape, or one that is refused or malformed, raises StError naming it, and nothing is
         written.  entropy="host" (the default): entropy decoding runs on host threads (ST_JPEG_THREADS), the rest in HIP
         kernels on the current stream.  entropy="gpu": st_jpeg_decode_batch_gpu, the Huffman decoder is a HIP kernel too, one
         lane per restart interval; every stream must have restart intervals (StError naming the one that has none).
-        entropy="auto": "gpu" when every stream's probe reports a restart interval, else "host".  Same frames either way."""
+        entropy="auto": "gpu" when every stream's probe reports a restart interval, else "host".  Same frames either way.
+        split="subsequence" (with entropy "gpu" or "auto", which then mean the same): st_jpeg_decode_batch_gpu_split, one lane
+        per subsequence of ``subseq_bytes`` raw bytes, at most ``max_rounds`` round launches (None: the library's defaults);
+        streams need no restart intervals.  ``last_jpeg_rounds()`` then tells the round launches the call took."""
         if entropy not in JPEG_ENTROPY_MODES:
             raise ValueError("entropy must be one of %s, got %r" % (", ".join(repr(m) for m in JPEG_ENTROPY_MODES), entropy))
+        if split not in JPEG_ENTROPY_SPLITS:
+            raise ValueError("split must be one of %s, got %r" % (", ".join(repr(m) for m in JPEG_ENTROPY_SPLITS), split))
+        if split == "subsequence" and entropy == "host":
+            raise ValueError("split='subsequence' decodes on the device: entropy must be 'gpu' or 'auto', got 'host'")
         self._bind()
         streams = [bytes(s) for s in streams]
         n = len(streams)
@@ -458,11 +465,21 @@ class HipContext:
         bufs = (ctypes.c_void_p * n)(*[ctypes.cast(ctypes.c_char_p(s), ctypes.c_void_p).value for s in streams])
         sizes = (ctypes.c_size_t * n)(*[len(s) for s in streams])
         to = (ctypes.c_void_p * n)(*[out[i].data_ptr() for i in range(n)])
+        if split == "subsequence":
+            opts = _native.JpegSplitOpts(int(subseq_bytes or 0), int(max_rounds or 0))
+            self._check(self._L.st_jpeg_decode_batch_gpu_split(self._h, bufs, sizes, n, shape[1], shape[2], shape[3], to, ctypes.byref(opts)))
+            return out
         if entropy == "auto":
             entropy = "gpu" if all(_jpeg_has_restarts(s) for s in streams) else "host"
         call = self._L.st_jpeg_decode_batch_gpu if entropy == "gpu" else self._L.st_jpeg_decode_batch
         self._check(call(self._h, bufs, sizes, n, shape[1], shape[2], shape[3], to))
         return out
+
+    def last_jpeg_rounds(self):
+        """st_jpeg_split_last_rounds: the round launches the last decode_jpeg(split="subsequence") call took (the most over its
+        sub-batches; the cap where a segment fell back to the interval decoder)."""
+        self._bind()
+        return int(self._L.st_jpeg_split_last_rounds(self._h))
 
     def encode_jpeg(self, frames, quality=95, subsampling="4:2:0"):
         """ImageEncoder op: (n, h, w, 3) uint8 CUDA frames (a tensor or a list of (h, w, 3) tensors of one shape), R, G, B
@@ -963,6 +980,7 @@ def probe_jpeg(stream):
 
 
 JPEG_ENTROPY_MODES = ("host", "gpu", "auto")   # decode_jpeg's entropy=; ImageDecoderArgs.entropy HOST = 0, GPU = 1, AUTO = 2
+JPEG_ENTROPY_SPLITS = ("interval", "subsequence")   # decode_jpeg's split=; ImageDecoderArgs.split INTERVAL = 0, SUBSEQUENCE = 1
 
 
 def _jpeg_has_restarts(data):
@@ -987,10 +1005,12 @@ def jpeg_restart_intervals(stream):
     return table
 
 
-def jpeg_coefficients(stream, by_interval=False):
+def jpeg_coefficients(stream, by_interval=False, by_subsequence=False, subseq_bytes=None, max_rounds=None):
     """st_jpeg_coefficients (host only): (int16 coefficients in the layout the header documents, (channels, 64) uint16
     quantisation tables in natural order) of a baseline JPEG stream.  by_interval=True: st_jpeg_coefficients_by_interval, the
-    same result computed restart interval by restart interval with the core the device kernel runs."""
+    same result computed restart interval by restart interval with the core the device kernel runs.  by_subsequence=True:
+    st_jpeg_coefficients_by_subsequence, the same result by the iteration over subsequences of ``subseq_bytes`` bytes capped at
+    ``max_rounds`` rounds (None: the library's defaults); the return value is then (coefficients, tables, rounds)."""
     data = bytes(stream)
     info = probe_jpeg(data)
     H, V = info["h_samp"], info["v_samp"]
@@ -999,6 +1019,13 @@ def jpeg_coefficients(stream, by_interval=False):
     coef = np.empty(blocks * 64, np.int16)
     quant = np.empty((info["channels"], 64), np.uint16)
     ji = _native.JpegInfo()
+    if by_subsequence:
+        opts, rounds = _native.JpegSplitOpts(int(subseq_bytes or 0), int(max_rounds or 0)), ctypes.c_int(0)
+        st = _native.lib().st_jpeg_coefficients_by_subsequence(data, len(data), ctypes.byref(opts), coef.ctypes.data, coef.size, quant.ctypes.data,
+                                                               ctypes.byref(ji), ctypes.byref(rounds))
+        if st != 0:
+            raise StError(st, ji.message.decode())
+        return coef, quant, rounds.value
     fn = _native.lib().st_jpeg_coefficients_by_interval if by_interval else _native.lib().st_jpeg_coefficients
     st = fn(data, len(data), coef.ctypes.data, coef.size, quant.ctypes.data, ctypes.byref(ji))
     if st != 0:

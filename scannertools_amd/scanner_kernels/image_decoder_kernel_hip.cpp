@@ -21,6 +21,11 @@
 // intervals is then fatal with the row and the cause; AUTO takes GPU for an execute() whose rows all have restart intervals
 // and HOST otherwise.  Any other value fails validate().  The frames are the same bytes either way.
 //
+// ImageDecoderArgs { ..., split = 3: INTERVAL = 0 | SUBSEQUENCE = 1 } (this build's own field too) chooses how the device decoder
+// cuts the work.  INTERVAL, and a message without the field, is the above.  SUBSEQUENCE with entropy GPU or AUTO makes execute()
+// one st_jpeg_decode_batch_gpu_split() call: one lane per fixed-size piece of the entropy-coded bytes, and a row without restart
+// intervals is no error.  SUBSEQUENCE with entropy HOST (or absent) fails validate(), as any other value of split does.
+//
 // The frame shape of an execute() is that of its first element.  Where the reference is undefined this fails instead: an
 // element of another shape (the reference's CPU kernel copies it into a frame of the first one's size, :46-50), and an element
 // that is not a baseline JPEG this library decodes ("Failed to decode image" there) are fatal with the row and the cause.
@@ -37,15 +42,18 @@
 namespace scanner {
 namespace {
 enum { ENTROPY_HOST = 0, ENTROPY_GPU = 1, ENTROPY_AUTO = 2 };
-// false: not a message; *image_type: -1 when the field is absent; *entropy: ENTROPY_HOST when the field is absent
-bool parse_image_decoder_args(const std::vector<u8>& args, int* image_type, long long* entropy) {
+enum { SPLIT_INTERVAL = 0, SPLIT_SUBSEQUENCE = 1 };
+// false: not a message; *image_type: -1 when the field is absent; *entropy: ENTROPY_HOST, *split: SPLIT_INTERVAL when absent
+bool parse_image_decoder_args(const std::vector<u8>& args, int* image_type, long long* entropy, long long* split) {
   std::vector<proto_lite::Field> fields;
   *image_type = -1;
   *entropy = ENTROPY_HOST;
+  *split = SPLIT_INTERVAL;
   if (!proto_lite::parse(args.data(), args.size(), &fields)) return false;
   for (auto& f : fields) {
     if (f.number == 1 && f.wire == 0) *image_type = (int)f.value;
     if (f.number == 2 && f.wire == 0) *entropy = (long long)f.value;
+    if (f.number == 3 && f.wire == 0) *split = (long long)f.value;
   }
   return true;
 }
@@ -56,15 +64,20 @@ class ImageDecoderKernelHIPImpl : public BatchedKernel {
  public:
   ImageDecoderKernelHIPImpl(const KernelConfig& config) : BatchedKernel(config), core_(config, STAGED), stage_(core_.gpu) {
     int image_type = -1;
-    long long entropy = ENTROPY_HOST;
-    if (!parse_image_decoder_args(config.args, &image_type, &entropy)) RESULT_ERROR(&core_.valid, "ImageDecoder: could not parse ImageDecoderArgs");
+    long long entropy = ENTROPY_HOST, split = SPLIT_INTERVAL;
+    if (!parse_image_decoder_args(config.args, &image_type, &entropy, &split)) RESULT_ERROR(&core_.valid, "ImageDecoder: could not parse ImageDecoderArgs");
     else if (image_type == 0 || image_type == 2)
       RESULT_ERROR(&core_.valid, "ImageDecoder: image_type %s is not supported (JPEG only)", image_type == 0 ? "PNG" : "ANY");
     else if (image_type != -1 && image_type != 1) RESULT_ERROR(&core_.valid, "ImageDecoder: invalid image_type %d", image_type);
     else if (entropy < ENTROPY_HOST || entropy > ENTROPY_AUTO)
       RESULT_ERROR(&core_.valid, "ImageDecoder: invalid entropy %lld (HOST = 0, GPU = 1, AUTO = 2)", entropy);
+    else if (split < SPLIT_INTERVAL || split > SPLIT_SUBSEQUENCE)
+      RESULT_ERROR(&core_.valid, "ImageDecoder: invalid split %lld (INTERVAL = 0, SUBSEQUENCE = 1)", split);
+    else if (split == SPLIT_SUBSEQUENCE && entropy == ENTROPY_HOST)
+      RESULT_ERROR(&core_.valid, "ImageDecoder: split = SUBSEQUENCE decodes on the device: entropy must be GPU or AUTO, not HOST");
     else core_.open("ImageDecoderKernelHIP");
     entropy_ = (int)entropy;
+    by_subsequence_ = split == SPLIT_SUBSEQUENCE;
   }
   void validate(Result* result) override { core_.validate(result); }
 
@@ -83,7 +96,7 @@ class ImageDecoderKernelHIPImpl : public BatchedKernel {
       LOG_IF(FATAL, info.h != first.h || info.w != first.w || info.channels != first.channels)
           << "ImageDecoder: row " << i << " of the batch changes shape inside a batch (" << info.w << "x" << info.h << "x" << info.channels
           << " after " << first.w << "x" << first.h << "x" << first.channels << ")";
-      LOG_IF(FATAL, entropy_ == ENTROPY_GPU && info.restart_interval <= 0)
+      LOG_IF(FATAL, entropy_ == ENTROPY_GPU && !by_subsequence_ && info.restart_interval <= 0)
           << "ImageDecoder: row " << i << " of the batch: no restart intervals: the stream has no DRI segment, entropy = GPU needs one";
       restarts = restarts && info.restart_interval > 0;
     }
@@ -102,7 +115,8 @@ class ImageDecoderKernelHIPImpl : public BatchedKernel {
       output_ptrs(dst_, output_frames);
     }
     st_ctx* ctx = core_.ctx;
-    const int st = on_gpu ? st_jpeg_decode_batch_gpu(ctx, bufs_.data(), sizes_.data(), n, first.h, first.w, first.channels, dst_.data())
+    const int st = by_subsequence_ ? st_jpeg_decode_batch_gpu_split(ctx, bufs_.data(), sizes_.data(), n, first.h, first.w, first.channels, dst_.data(), nullptr)
+                   : on_gpu ? st_jpeg_decode_batch_gpu(ctx, bufs_.data(), sizes_.data(), n, first.h, first.w, first.channels, dst_.data())
                           : st_jpeg_decode_batch(ctx, bufs_.data(), sizes_.data(), n, first.h, first.w, first.channels, dst_.data());
     LOG_IF(FATAL, st != ST_OK) << "ImageDecoder: " << st_ctx_last_error(ctx);
     core_.sync();
@@ -114,6 +128,7 @@ class ImageDecoderKernelHIPImpl : public BatchedKernel {
   KernelCore core_;
   DeviceStage stage_;   // staged: the decoded frames
   int entropy_ = ENTROPY_HOST;
+  bool by_subsequence_ = false;
   std::vector<const uint8_t*> bufs_;
   std::vector<size_t> sizes_;
   std::vector<uint8_t*> dst_;

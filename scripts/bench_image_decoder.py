@@ -26,6 +26,16 @@ end to end (synchronised), kernel ms per frame from the library's events (one ST
 the entropy launch, the wait for its status word and the two dense launches), and the bytes uploaded per frame.  Beside
 it, in the same run, st_jpeg_decode_batch of the same streams at ST_JPEG_THREADS=16: the baseline.  With --trace it makes
 three device-path calls per quality and batch, so that the trace's statistics give k_jpeg_entropy_dec's share.
+
+    python scripts/bench_image_decoder.py --split subsequence [--rounds 3]
+    rocprofv3 --kernel-trace --stats -d DIR -- python scripts/bench_image_decoder.py --split subsequence --trace
+
+--split subsequence measures st_jpeg_decode_batch_gpu_split (one lane per subsequence of the entropy-coded bytes) in calls of 1,
+8, 32 and 256 frames, frames/s end to end (synchronised) as the median and range of three medians of --rounds calls: (a) on
+the streams as Pillow writes them by default (no DRI) beside st_jpeg_decode_batch at ST_JPEG_THREADS=16, (b) on the same pictures
+with one restart interval per MCU row beside st_jpeg_decode_batch_gpu (one lane per interval) and the host path.  It reports the
+round launches per call and the lanes per frame.  With --trace it makes three subsequence calls per quality, kind of stream and
+call size and times nothing.
 """
 import argparse
 import ctypes
@@ -130,16 +140,78 @@ def entropy_gpu(args, Image):
     print(json.dumps(result))
 
 
+SPLIT_BATCHES = (1, 8, 32, 256)
+
+
+def split_subsequence(args, Image):
+    import torch
+    from scannertools_amd.hip import HipContext
+    os.environ["ST_JPEG_THREADS"] = "16"
+    ctx = HipContext(0)
+    result = {"bench": "image_decoder_split_subsequence", "h": H, "w": W, "sampling": "4:2:0", "host_threads": 16, "subseq_bytes": args.subseq_bytes or 128,
+              "calls_per_median": args.rounds, "qualities": {}}
+    out = torch.empty((max(SPLIT_BATCHES), H, W, 3), dtype=torch.uint8, device=ctx.device)
+    for quality in (75, 90):
+        plain = make_streams(Image, quality)
+        rows = []
+        for s in plain:
+            buf = io.BytesIO()
+            Image.open(io.BytesIO(s)).save(buf, "JPEG", quality=quality, subsampling="4:2:0", restart_marker_rows=1)
+            rows.append(buf.getvalue())
+        q = {}
+        for kind, streams, paths in (("no_dri", plain, ("subsequence", "host")), ("restart_rows", rows, ("subsequence", "interval", "host"))):
+
+            def call(n, path):
+                batch = [streams[i % DISTINCT] for i in range(n)]
+                if path == "host":
+                    ctx.decode_jpeg(batch, out=out[:n])
+                elif path == "interval":
+                    ctx.decode_jpeg(batch, out=out[:n], entropy="gpu")
+                else:
+                    ctx.decode_jpeg(batch, out=out[:n], entropy="gpu", split="subsequence", subseq_bytes=args.subseq_bytes)
+                ctx.sync()
+
+            want = np.asarray(Image.open(io.BytesIO(streams[0])))
+            for path in paths:
+                call(1, path)
+                assert np.array_equal(out[0].cpu().numpy(), want), "decode differs from Pillow (%s, %s)" % (kind, path)
+            k = {"stream_bytes": int(statistics.mean(len(s) for s in streams)),
+                 "lanes_per_frame": int(statistics.mean(-(-(len(s) - s.index(b"\xff\xda")) // (args.subseq_bytes or 128)) for s in streams))}
+            if args.trace:
+                for n in SPLIT_BATCHES:
+                    for _ in range(3):
+                        call(n, "subsequence")
+                q[kind] = k
+                continue
+            for path in paths:
+                fps = {}
+                for n in SPLIT_BATCHES:
+                    runs = [rate(lambda: call(n, path), n, args.rounds) for _ in range(3)]     # three medians: the run-to-run range
+                    fps["batch%d" % n] = {"median": round(statistics.median(runs), 1), "min": round(min(runs), 1), "max": round(max(runs), 1)}
+                    if path == "subsequence":
+                        fps["batch%d" % n]["round_launches"] = ctx.last_jpeg_rounds()
+                k[path + "_fps"] = fps
+            q[kind] = k
+        result["qualities"]["q%d" % quality] = q
+    ctx.close()
+    print(json.dumps(result))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--trace", action="store_true")
     ap.add_argument("--entropy", choices=("host", "gpu"), default="host", help="gpu: measure st_jpeg_decode_batch_gpu beside the host path")
+    ap.add_argument("--split", choices=("interval", "subsequence"), default="interval",
+                    help="subsequence: measure st_jpeg_decode_batch_gpu_split beside the interval kernel and the host path")
+    ap.add_argument("--subseq-bytes", type=int, default=None, help="with --split subsequence: bytes per lane (default: the library's)")
     args = ap.parse_args()
     try:
         from PIL import Image
     except ImportError:
         sys.exit("bench_image_decoder.py needs Pillow to make its 1080p streams and as its yardstick")
+    if args.split == "subsequence":
+        return split_subsequence(args, Image)
     if args.entropy == "gpu":
         return entropy_gpu(args, Image)
     import torch
