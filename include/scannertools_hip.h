@@ -99,7 +99,7 @@ enum st_kernel_id {
   ST_K_CPM2_RESIZE = 14,
   ST_K_CPM2_NMS = 15,      /* the library's non-maximum suppressions: CPM2's peak search and the FacenetOutput launches (decode, sort + greedy NMS, pack) */
   ST_K_FRAME_STATS = 16, /* moments + finishing launches of the frame-statistics ops */
-  ST_K_JPEG = 17,        /* inverse DCT + upsample / colour launches of the ImageDecoder op; the ImageEncoder op's four launches */
+  ST_K_JPEG = 17,        /* inverse DCT + upsample / colour launches of the ImageDecoder op; the ImageEncoder op's launches (four, or five without restart markers) */
   ST_K_NET_INPUT = 18,   /* the FacenetInput and CaffeInput launches */
   ST_K_COUNT = 19
 };
@@ -773,6 +773,23 @@ int st_jpeg_encode_batch(st_ctx* ctx, const uint8_t* const* frames_dev, int n, i
  * call to fetch from, sizes null, a null buffer, a stream longer than capacity (sizes is filled in all the same, nothing is
  * copied). */
 int st_jpeg_encode_fetch(st_ctx* ctx, uint8_t* const* bufs_host, size_t* sizes, size_t capacity);
+/* Where the stream has restart markers.  ROW: one restart interval per MCU row, everything said above; what
+ * st_jpeg_encode_header and st_jpeg_encode_batch write.  NONE: no DRI segment and no RSTn markers, the stream libjpeg writes
+ * with restart_interval = 0, its default and that of cv::imencode, Pillow (save(quality=q, subsampling=s)) and cjpeg: the 623
+ * header bytes (the 629 without the DRI segment), ONE scan whose DC predictors carry over from MCU row to MCU row, whose last
+ * byte is padded with 1-bits and in which every 0xFF byte -- also one made of the bits of two MCU rows -- is followed by 0x00,
+ * then EOI.  Everything before the entropy coder is the same.  DESIGN.md section 4.16b. */
+enum { ST_JPEG_RESTART_ROW = 0, ST_JPEG_RESTART_NONE = 1 };
+/* st_jpeg_encode_header for either mode (ROW: the same bytes).  ST_ERR_INVALID also for any other `restart`. */
+int st_jpeg_encode_header_rst(int h, int w, int quality, int h_samp, int v_samp, int restart, uint8_t* buf, size_t cap, size_t* size);
+/* st_jpeg_encode_batch for either mode (ROW: the same launches, bytes and messages).  NONE enqueues five launches -- transform,
+ * entropy coding of each MCU row into its slot unpadded and unstuffed, a count of the 0xFF bytes each row owns once the rows are
+ * joined bit by bit, the layout, the pack that shifts, joins, stuffs and writes them -- and like ROW has no workgroup wait for
+ * another.  Any other `restart` is ST_ERR_INVALID, the message naming the value, before anything is launched or uploaded.
+ * st_jpeg_encode_fetch and st_jpeg_encode_bound serve both modes (the bound covers the shorter stream); the device memory per
+ * coded block is the same. */
+int st_jpeg_encode_batch_rst(st_ctx* ctx, const uint8_t* const* frames_dev, int n, int h, int w, int quality, int h_samp, int v_samp,
+                             int restart);
 
 #ifdef __cplusplus
 }

@@ -204,6 +204,8 @@ SIGNATURES = {
     "st_jpeg_encode_bound": (ctypes.c_longlong, [_i, _i, _i, _i]),
     "st_jpeg_encode_batch": (_i, [_vp, _c.POINTER(_vp), _i, _i, _i, _i, _i, _i]),
     "st_jpeg_encode_fetch": (_i, [_vp, _c.POINTER(_vp), _c.POINTER(_sz), _sz]),
+    "st_jpeg_encode_header_rst": (_i, [_i, _i, _i, _i, _i, _i, _vp, _sz, _c.POINTER(_sz)]),
+    "st_jpeg_encode_batch_rst": (_i, [_vp, _c.POINTER(_vp), _i, _i, _i, _i, _i, _i, _i]),
 }
 
 _LIB = None

@@ -150,20 +150,36 @@ def parse_image_decoder_args(buf):
     return out
 
 
-def image_encoder_args(quality=0, subsampling=""):
-    """A serialised ImageEncoderArgs (scannertools_imgproc_amd.proto): quality = 1, subsampling = 2.  The defaults (0, "") are
-    not written, as proto3 does; the op then takes quality 95 and "4:2:0"."""
-    return encode([(1, "int32", int(quality)), (2, "string", subsampling or "")])
+ENCODER_RESTARTS = {"MCU_ROW": 0, "NONE": 1}   # ImageEncoderArgs.Restart
+
+
+def image_encoder_args(quality=0, subsampling="", restart=0):
+    """A serialised ImageEncoderArgs (scannertools_imgproc_amd.proto): quality = 1, subsampling = 2, restart = 3 (a number, or
+    "mcu_row" / "none" in either case).  The defaults (0, "", MCU_ROW = 0) are not written, as proto3 does; the op then takes
+    quality 95, "4:2:0" and one restart interval per MCU row."""
+    if isinstance(restart, str):
+        if restart.upper() not in ENCODER_RESTARTS:
+            raise ValueError("restart must be one of 'mcu_row', 'none' or a number, got %r" % (restart,))
+        restart = ENCODER_RESTARTS[restart.upper()]
+    out = encode([(1, "int32", int(quality)), (2, "string", subsampling or "")])
+    if int(restart) != 0:
+        out += _varint(3 << 3 | 0) + _varint(int(restart) & ((1 << 64) - 1))
+    return out
 
 
 def parse_image_encoder_args(buf):
-    """{'quality': int, 'subsampling': str} of a serialised ImageEncoderArgs; an absent field is left out."""
+    """{'quality': int, 'subsampling': str, 'restart': name or number} of a serialised ImageEncoderArgs; an absent field is left
+    out."""
+    names = {v: k for k, v in ENCODER_RESTARTS.items()}
     out = {}
     for number, wt, value in fields(buf):
         if number == 1 and wt == 0:
             out["quality"] = value - (1 << 64) if value >> 63 else value
         elif number == 2 and wt == 2:
             out["subsampling"] = bytes(value).decode()
+        elif number == 3 and wt == 0:
+            value = value - (1 << 64) if value >> 63 else value
+            out["restart"] = names.get(value, value)
     return out
 
 

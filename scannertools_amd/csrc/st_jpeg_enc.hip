@@ -15,7 +15,19 @@
 //                   stream's size, and the exclusive scan of the sizes = each stream's offset in the packed buffer
 //   k_jpeg_pack     one workgroup per interval: copies the header (the frame's first interval), the interval's bytes and the
 //                   marker that follows them (RSTn, or EOI after the last) to their place
-// The header (SOI .. SOS) and the Huffman code tables are built on the host once per (h, w, quality, sampling) and uploaded.
+// The header (SOI .. SOS) and the Huffman code tables are built on the host once per (h, w, quality, sampling, restart mode)
+// and uploaded.
+//
+// st_jpeg_encode_batch_rst(..., ST_JPEG_RESTART_NONE) writes the stream without DRI and RSTn in five launches,
+// again with no waiting between workgroups:
+//   k_jpeg_fdct             as above
+//   k_jpeg_entropy<false>   one wave per MCU row: DC predecessors from the row above, no padding, no stuffing; the row's bits
+//                           and its length in bits
+//   k_jpeg_ff_count         one workgroup per MCU row: its bit offset in the frame's scan, the bytes it owns (those whose first
+//                           bit lies in it) and how many of them are 0xFF
+//   k_jpeg_layout<false>    as above over the rows' stuffed lengths, nothing between rows, EOI at the end
+//   k_jpeg_pack_bits        one workgroup per MCU row: header, the owned bytes shifted into place, completed from the next row
+//                           (or with 1-bits) and stuffed, EOI
 #include <climits>
 #include <cstring>
 #include <vector>
@@ -26,7 +38,7 @@
 struct st_jpeg_enc_state {
   // device: the header bytes at 0, the Huffman code words at kParamsHuff; what they were built for
   uint8_t* params = nullptr;
-  int key[5] = {0, 0, 0, 0, 0};
+  int key[6] = {0, 0, 0, 0, 0, 0};   // h, w, quality, sampling, restart mode
   std::vector<uint8_t> params_host;
   // the streams of the last st_jpeg_encode_batch call, packed one after the other, and their n + 1 offsets
   uint8_t* blob = nullptr;
@@ -213,6 +225,7 @@ struct EncEntropyK {
   unsigned* ilen;
   size_t slot_bytes;
   int nblk, bpm, nluma;
+  int mrows;   // RESTART false: MCU rows per frame
 };
 
 // nb bits (the low ones of val) at bit p of the stream; bit 0 of the stream is the top bit of raw[0]
@@ -287,7 +300,11 @@ __device__ __forceinline__ int wave_inclusive_scan(int v, int lane) {
 
 __device__ __forceinline__ unsigned raw_byte(const uint32_t* raw, int j) { return (raw[j >> 2] >> (24 - 8 * (j & 3))) & 0xffu; }
 
-// One wave per restart interval.
+// One wave per restart interval (RESTART) or, for a stream without restart markers, per MCU row: then the row's first blocks
+// take their DC predecessors from the last MCU of the row above in the same frame -- the coefficient buffer holds it, rows of a
+// frame one after the other, so no workgroup depends on another --, nothing is padded with 1-bits or stuffed, the bits go to the
+// slot with a zero-filled last byte, and ilen receives the row's length in BITS (at most 49 152 blocks x 1660 bits < 2^32).
+template <bool RESTART>
 __global__ __launch_bounds__(64) void k_jpeg_entropy(EncEntropyK a) {
   __shared__ uint32_t s_huff[kJpegEncHuffWords];
   __shared__ uint32_t s_coef[kChunk * kCoefPitch];
@@ -300,6 +317,8 @@ __global__ __launch_bounds__(64) void k_jpeg_entropy(EncEntropyK a) {
   uint8_t* __restrict__ slot = a.slots + iv * a.slot_bytes;
   uint32_t* mine = s_coef + lane * kCoefPitch;
   size_t out_pos = 0;
+  unsigned row_bits = 0;     // RESTART false: the row's code bits so far
+  const int floor_blk = !RESTART && iv % (size_t)a.mrows != 0 ? -a.bpm : 0;   // the first block index a predecessor may have
   int carry_bits = 0;        // bits of the last, unfinished byte of the previous chunk
   uint32_t carry_val = 0;
   for (int b0 = 0; b0 < a.nblk; b0 += kChunk) {
@@ -316,16 +335,17 @@ __global__ __launch_bounds__(64) void k_jpeg_entropy(EncEntropyK a) {
         mine[4 * s] = t.x; mine[4 * s + 1] = t.y; mine[4 * s + 2] = t.z; mine[4 * s + 3] = t.w;
       }
       // the DC difference to the previous block of the same component; 0 predicts the interval's first
-      const int k = b % a.bpm, m = b / a.bpm;
+      const int k = b % a.bpm;
       int prev;
       if (k < a.nluma) {
-        prev = k > 0 ? b - 1 : (m > 0 ? b - a.bpm + a.nluma - 1 : -1);
+        prev = k > 0 ? b - 1 : b - a.bpm + a.nluma - 1;
       } else {
-        prev = m > 0 ? b - a.bpm : -1;
+        prev = b - a.bpm;
         dc_tab = s_huff + 16;
         ac_tab = s_huff + 288;
       }
-      diff = (int)C[(size_t)b * 64] - (prev >= 0 ? (int)C[(size_t)prev * 64] : 0);
+      // a negative index is a block of the row above (its last MCU), read only where that row belongs to this frame
+      diff = (int)C[(size_t)b * 64] - (prev >= floor_blk ? (int)C[(ptrdiff_t)prev * 64] : 0);
     }
     __syncthreads();
     const int len = live ? code_block<false>(mine, dc_tab, ac_tab, diff, nullptr, 0) : 0;
@@ -333,6 +353,19 @@ __global__ __launch_bounds__(64) void k_jpeg_entropy(EncEntropyK a) {
     int total = carry_bits + __shfl(incl, 63);
     if (lane == 0 && carry_bits) atomicOr(&s_raw[0], carry_val << (32 - carry_bits));
     if (live) (void)code_block<true>(mine, dc_tab, ac_tab, diff, s_raw, carry_bits + incl - len);
+    if (!RESTART) {
+      // the chunk's whole bytes as they are; after the last chunk also the unfinished byte, its low bits zero
+      row_bits += (unsigned)(total - carry_bits);
+      __syncthreads();
+      const int nbytes = b0 + kChunk >= a.nblk ? (total + 7) >> 3 : total >> 3;
+      for (int j = lane; j < nbytes; j += 64)
+        if (out_pos + j < a.slot_bytes) slot[out_pos + j] = (uint8_t)raw_byte(s_raw, j);   // always: the slot holds the worst case
+      out_pos += nbytes;
+      carry_bits = total & 7;
+      carry_val = carry_bits ? raw_byte(s_raw, total >> 3) >> (8 - carry_bits) : 0u;
+      __syncthreads();
+      continue;
+    }
     if (b0 + kChunk >= a.nblk && (total & 7)) {   // the interval's last byte is filled with 1-bits
       const int fill = 8 - (total & 7);
       if (lane == 0) put_bits(s_raw, total, (1u << fill) - 1u, fill);
@@ -361,7 +394,7 @@ __global__ __launch_bounds__(64) void k_jpeg_entropy(EncEntropyK a) {
     out_pos += stuffed;
     __syncthreads();
   }
-  if (lane == 0) a.ilen[iv] = (unsigned)out_pos;
+  if (lane == 0) a.ilen[iv] = RESTART ? (unsigned)out_pos : row_bits;
 }
 
 // ---- layout and packing -----------------------------------------------------------------------------------------------------
@@ -372,6 +405,8 @@ struct EncLayoutK {
   int n, mrows;
 };
 
+// RESTART false: ilen holds the stuffed bytes each MCU row owns (k_jpeg_ff_count); nothing stands between them, EOI ends the stream
+template <bool RESTART>
 __global__ __launch_bounds__(1024) void k_jpeg_layout(EncLayoutK a) {
   __shared__ u64 part[1024];
   const int tid = threadIdx.x;
@@ -379,12 +414,13 @@ __global__ __launch_bounds__(1024) void k_jpeg_layout(EncLayoutK a) {
   const long long f0 = tid * per < a.n ? tid * per : a.n, f1 = f0 + per < a.n ? f0 + per : a.n;
   u64 sum = 0;
   for (long long f = f0; f < f1; ++f) {
-    u64 o = kJpegEncHeaderBytes;
+    u64 o = RESTART ? kJpegEncHeaderBytes : kJpegEncHeaderBytesNoRst;
     for (int r = 0; r < a.mrows; ++r) {
       const size_t iv = (size_t)f * a.mrows + r;
       a.ioff[iv] = o;
-      o += (u64)a.ilen[iv] + 2;   // the interval, then RSTn or (after the last) EOI
+      o += (u64)a.ilen[iv] + (RESTART ? 2 : 0);   // the interval, then RSTn or (after the last) EOI
     }
+    if (!RESTART) o += 2;
     a.offs[f] = o;   // the stream's size for now
     sum += o;
   }
@@ -436,6 +472,134 @@ __global__ __launch_bounds__(256) void k_jpeg_pack(EncPackK a) {
   }
 }
 
+// ---- streams without restart markers: the MCU rows joined bit by bit ---------------------------------------------------------
+// A frame's scan before stuffing is its rows' bits one after the other, padded with 1-bits to a whole byte.  Row r starts at
+// bit B(r) = the sum of the lengths above it and OWNS the bytes whose first bit lies in it: bytes ceil(B / 8) up to, not
+// including, ceil((B + L) / 8).  An owned byte is 8 bits of the row's slot from bit 8 * j + sh on (sh = -B mod 8: the row's
+// first sh bits completed the byte the row above owns); the last one may reach past the row's end and is completed with the
+// leading bits of the next row's slot, or with 1-bits in the frame's last row.  ONE next row is enough: a row has at least 14
+// bits (three blocks at least, each a DC code of 2 bits or more and an EOB of 2 (chroma) or 4 (luma)), the missing bits are
+// at most 7.  So every byte of the scan has exactly one owner, which computes it from memory the entropy launch finished
+// writing: no workgroup waits for another, nothing is ORed into shared bytes, nothing is read that this call did not write.
+struct EncMergeK {
+  const uint8_t* slots;   // per row: its bits, the last byte zero-filled (k_jpeg_entropy<false>)
+  const unsigned* bits;   // per row: its length in bits
+  u64* bitoff;            // per row: B, written by k_jpeg_ff_count and read by k_jpeg_pack_bits
+  unsigned* slen;         // per row: the bytes it owns, stuffed zeros included
+  const u64* ioff;
+  const u64* offs;
+  const uint8_t* header;
+  uint8_t* blob;
+  size_t slot_bytes, blob_bytes;
+  int mrows;
+};
+
+struct OwnedBytes {
+  const uint8_t* slot;
+  u64 bits;         // L
+  unsigned nvalid;  // bytes of the slot that were written: ceil(L / 8)
+  unsigned count;   // owned bytes
+  unsigned sh;
+  unsigned tail;    // what follows the row: the next row's first byte, or 0xFF after the frame's last
+};
+
+__device__ __forceinline__ OwnedBytes owned_bytes(const EncMergeK& a, size_t iv, int r, u64 B) {
+  OwnedBytes o;
+  o.slot = a.slots + iv * a.slot_bytes;
+  o.bits = a.bits[iv];
+  o.nvalid = (unsigned)((o.bits + 7) >> 3);
+  const u64 first = (B + 7) >> 3;
+  o.count = (unsigned)(((B + o.bits + 7) >> 3) - first);
+  o.sh = (unsigned)(first * 8 - B);
+  o.tail = r == a.mrows - 1 ? 0xffu : a.slots[(iv + 1) * a.slot_bytes];
+  return o;
+}
+
+__device__ __forceinline__ unsigned owned_byte(const OwnedBytes& o, unsigned j) {   // j < o.count, hence j < o.nvalid
+  unsigned v = o.slot[j];
+  if (o.sh) v = ((v << o.sh) | (j + 1 < o.nvalid ? (unsigned)o.slot[j + 1] >> (8 - o.sh) : 0u)) & 0xffu;
+  const u64 end = (u64)j * 8 + o.sh + 8;   // past the row's end by 1 .. 7 bits, which the slot holds as zeros
+  if (end > o.bits) v |= o.tail >> (8 - (unsigned)(end - o.bits));
+  return v;
+}
+
+__device__ __forceinline__ u64 block_sum(u64 v, u64* red) {   // 256 threads
+  red[threadIdx.x] = v;
+  __syncthreads();
+  for (int d = 128; d > 0; d >>= 1) {
+    if ((int)threadIdx.x < d) red[threadIdx.x] += red[threadIdx.x + d];
+    __syncthreads();
+  }
+  v = red[0];
+  __syncthreads();
+  return v;
+}
+
+// One workgroup per MCU row: its bit offset in the frame's scan (the lengths above it summed; at most 8192 rows) and the
+// number of bytes it owns, a zero after every 0xFF among them counted in.
+__global__ __launch_bounds__(256) void k_jpeg_ff_count(EncMergeK a) {
+  __shared__ u64 red[256];
+  const size_t iv = blockIdx.x;
+  const size_t f = iv / (size_t)a.mrows;
+  const int r = (int)(iv - f * (size_t)a.mrows);
+  u64 part = 0;
+  for (int i = threadIdx.x; i < r; i += 256) part += a.bits[f * (size_t)a.mrows + i];
+  const u64 B = block_sum(part, red);
+  const OwnedBytes o = owned_bytes(a, iv, r, B);
+  u64 ff = 0;
+  for (unsigned j = threadIdx.x; j < o.count; j += 256) ff += owned_byte(o, j) == 0xffu;
+  ff = block_sum(ff, red);
+  if (threadIdx.x == 0) {
+    a.bitoff[iv] = B;
+    a.slen[iv] = o.count + (unsigned)ff;
+  }
+}
+
+// One workgroup per MCU row: the header (the frame's first row), the row's owned bytes with their stuffed zeros -- computed
+// again, 256 at a time, a ballot and a prefix over the four waves placing them --, EOI after the frame's last row.
+__global__ __launch_bounds__(256) void k_jpeg_pack_bits(EncMergeK a) {
+  __shared__ unsigned s_w[4];
+  const size_t iv = blockIdx.x;
+  const size_t f = iv / (size_t)a.mrows;
+  const int r = (int)(iv - f * (size_t)a.mrows);
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const u64 at = a.offs[f];
+  const u64 room = at < a.blob_bytes ? a.blob_bytes - at : 0;   // every store below stays inside the blob
+  uint8_t* __restrict__ dst = a.blob + at;
+  if (r == 0)
+    for (int j = tid; j < (int)kJpegEncHeaderBytesNoRst; j += 256)
+      if ((u64)j < room) dst[j] = a.header[j];
+  const OwnedBytes o = owned_bytes(a, iv, r, a.bitoff[iv]);
+  const u64 base = a.ioff[iv];
+  unsigned ff_run = 0;
+  for (unsigned t0 = 0; t0 < o.count; t0 += 256) {
+    const unsigned j = t0 + tid;
+    const bool live = j < o.count;
+    const unsigned v = live ? owned_byte(o, j) : 0u;
+    const bool ff = v == 0xffu;
+    const u64 m = __ballot(ff);
+    if (lane == 0) s_w[wave] = (unsigned)__popcll(m);
+    __syncthreads();
+    unsigned before = (unsigned)__popcll(m & ((1ull << lane) - 1ull)), all = 0;
+    for (int k = 0; k < 4; ++k) {
+      before += k < wave ? s_w[k] : 0u;
+      all += s_w[k];
+    }
+    const u64 pos = base + j + ff_run + before;
+    if (live && pos < room) dst[pos] = (uint8_t)v;
+    if (ff && pos + 1 < room) dst[pos + 1] = 0;
+    ff_run += all;
+    __syncthreads();
+  }
+  if (r == a.mrows - 1 && tid == 0) {
+    const u64 pos = base + o.count + ff_run;
+    if (pos + 1 < room) {
+      dst[pos] = 0xFF;
+      dst[pos + 1] = 0xD9;
+    }
+  }
+}
+
 template <class T>
 int grow(st_ctx* ctx, T** p, size_t* cap, size_t want, const char* what) {
   if (want <= *cap) return ST_OK;
@@ -455,13 +619,16 @@ int grow(st_ctx* ctx, T** p, size_t* cap, size_t want, const char* what) {
 
 }  // namespace
 
-ST_EXPORT int st_jpeg_encode_batch(st_ctx* ctx, const uint8_t* const* frames_dev, int n, int h, int w, int quality, int h_samp, int v_samp) {
+ST_EXPORT int st_jpeg_encode_batch_rst(st_ctx* ctx, const uint8_t* const* frames_dev, int n, int h, int w, int quality, int h_samp, int v_samp,
+                                       int restart) {
   ST_TRY(st_enter(ctx));
   if (!ctx->jpeg_enc) ctx->jpeg_enc = new st_jpeg_enc_state();
   st_jpeg_enc_state* s = ctx->jpeg_enc;
   s->n = -1;   // a call that fails leaves nothing to fetch
-  if (n < 0) return st_set_error(ctx, ST_ERR_INVALID, "jpeg_encode: n = %d is negative", n);
   char msg[160];
+  if (st_jpeg_enc_check_restart(restart, msg, sizeof msg) != ST_OK) return st_set_error(ctx, ST_ERR_INVALID, "jpeg_encode: %s", msg);
+  const bool rst = restart == ST_JPEG_RESTART_ROW;
+  if (n < 0) return st_set_error(ctx, ST_ERR_INVALID, "jpeg_encode: n = %d is negative", n);
   const int chk = st_jpeg_enc_check(h, w, quality, h_samp, v_samp, msg, sizeof msg);
   if (chk != ST_OK) return st_set_error(ctx, chk, "jpeg_encode: %s", msg);
   if (n == 0) {
@@ -476,11 +643,12 @@ ST_EXPORT int st_jpeg_encode_batch(st_ctx* ctx, const uint8_t* const* frames_dev
   const long long intervals = (long long)n * g.mrows;
   if (intervals > INT_MAX) return st_set_error(ctx, ST_ERR_UNSUPPORTED, "jpeg_encode: %lld restart intervals in one call (at most 2^31 - 1)", intervals);
   const int nblk = g.mcols * g.bpm;
-  const size_t slot_bytes = st_jpeg_enc_slot_bytes(g);
+  // without markers a slot holds the row's bits as they are, half of what they could take stuffed
+  const size_t slot_bytes = rst ? st_jpeg_enc_slot_bytes(g) : st_jpeg_enc_raw_slot_bytes(g);
   const size_t bound = (size_t)st_jpeg_encode_bound(h, w, h_samp, v_samp);
 
   // header and code tables, when the call differs from the last one
-  const int key[5] = {h, w, quality, h_samp, v_samp};
+  const int key[6] = {h, w, quality, h_samp, v_samp, restart};
   if (!s->params) {
     ST_HIP(ctx, hipMalloc((void**)&s->params, kParamsBytes));
     memset(s->key, 0, sizeof s->key);
@@ -489,7 +657,7 @@ ST_EXPORT int st_jpeg_encode_batch(st_ctx* ctx, const uint8_t* const* frames_dev
     ST_HIP(ctx, hipStreamSynchronize(ctx->stream));   // an earlier upload may still read params_host
     s->params_host.assign(kParamsBytes, 0);
     size_t hb = 0;
-    (void)st_jpeg_encode_header(h, w, quality, h_samp, v_samp, s->params_host.data(), kParamsHuff, &hb);
+    (void)st_jpeg_encode_header_rst(h, w, quality, h_samp, v_samp, restart, s->params_host.data(), kParamsHuff, &hb);
     st_jpeg_enc_huff(reinterpret_cast<uint32_t*>(s->params_host.data() + kParamsHuff));
     memset(s->key, 0, sizeof s->key);
     ST_HIP(ctx, hipMemcpyAsync(s->params, s->params_host.data(), kParamsBytes, hipMemcpyHostToDevice, ctx->stream));
@@ -500,13 +668,17 @@ ST_EXPORT int st_jpeg_encode_batch(st_ctx* ctx, const uint8_t* const* frames_dev
 
   const size_t tb = sizeof(void*) * (size_t)n, cb = (size_t)intervals * (size_t)nblk * 128, sb = (size_t)intervals * slot_bytes;
   const size_t lb = sizeof(unsigned) * (size_t)intervals, ob = sizeof(u64) * (size_t)intervals;
-  ST_TRY(st_ws_reserve(ctx, st_align_up(tb) + st_align_up(cb) + st_align_up(sb) + st_align_up(lb) + st_align_up(ob)));
+  ST_TRY(st_ws_reserve(ctx, st_align_up(tb) + st_align_up(cb) + st_align_up(sb) + st_align_up(lb) + st_align_up(ob) +
+                                (rst ? 0 : st_align_up(lb) + st_align_up(ob))));
   const uint8_t** d_frames = (const uint8_t**)st_ws_alloc(ctx, tb);
   int16_t* d_coef = (int16_t*)st_ws_alloc(ctx, cb);
   uint8_t* d_slots = (uint8_t*)st_ws_alloc(ctx, sb);
   unsigned* d_ilen = (unsigned*)st_ws_alloc(ctx, lb);
   u64* d_ioff = (u64*)st_ws_alloc(ctx, ob);
-  if (!d_frames || !d_coef || !d_slots || !d_ilen || !d_ioff) return st_set_error(ctx, ST_ERR_OOM, "jpeg_encode: workspace exhausted");
+  unsigned* d_slen = rst ? d_ilen : (unsigned*)st_ws_alloc(ctx, lb);   // without markers: the rows' bits, and their stuffed bytes
+  u64* d_bitoff = rst ? d_ioff : (u64*)st_ws_alloc(ctx, ob);
+  if (!d_frames || !d_coef || !d_slots || !d_ilen || !d_ioff || !d_slen || !d_bitoff)
+    return st_set_error(ctx, ST_ERR_OOM, "jpeg_encode: workspace exhausted");
   ST_HIP(ctx, hipMemcpyAsync(d_frames, frames_dev, tb, hipMemcpyHostToDevice, ctx->stream));
 
   EncTransformK t;
@@ -527,18 +699,35 @@ ST_EXPORT int st_jpeg_encode_batch(st_ctx* ctx, const uint8_t* const* frames_dev
   }
   EncEntropyK e;
   e.coef = d_coef; e.huff = reinterpret_cast<const uint32_t*>(s->params + kParamsHuff); e.slots = d_slots; e.ilen = d_ilen;
-  e.slot_bytes = slot_bytes; e.nblk = nblk; e.bpm = g.bpm; e.nluma = g.bpm - 2;
+  e.slot_bytes = slot_bytes; e.nblk = nblk; e.bpm = g.bpm; e.nluma = g.bpm - 2; e.mrows = g.mrows;
   {
     st_timed tm(ctx, ST_K_JPEG);
-    hipLaunchKernelGGL(k_jpeg_entropy, dim3((unsigned)intervals), dim3(64), 0, ctx->stream, e);
+    if (rst) hipLaunchKernelGGL(k_jpeg_entropy<true>, dim3((unsigned)intervals), dim3(64), 0, ctx->stream, e);
+    else hipLaunchKernelGGL(k_jpeg_entropy<false>, dim3((unsigned)intervals), dim3(64), 0, ctx->stream, e);
+    ST_HIP(ctx, hipGetLastError());
+  }
+  EncMergeK m;
+  m.slots = d_slots; m.bits = d_ilen; m.bitoff = d_bitoff; m.slen = d_slen; m.ioff = d_ioff; m.offs = s->offs; m.header = s->params;
+  m.blob = s->blob; m.slot_bytes = slot_bytes; m.blob_bytes = (size_t)n * bound; m.mrows = g.mrows;
+  if (!rst) {
+    st_timed tm(ctx, ST_K_JPEG);
+    hipLaunchKernelGGL(k_jpeg_ff_count, dim3((unsigned)intervals), dim3(256), 0, ctx->stream, m);
     ST_HIP(ctx, hipGetLastError());
   }
   EncLayoutK l;
-  l.ilen = d_ilen; l.ioff = d_ioff; l.offs = s->offs; l.n = n; l.mrows = g.mrows;
+  l.ilen = d_slen; l.ioff = d_ioff; l.offs = s->offs; l.n = n; l.mrows = g.mrows;
   {
     st_timed tm(ctx, ST_K_JPEG);
-    hipLaunchKernelGGL(k_jpeg_layout, dim3(1), dim3(1024), 0, ctx->stream, l);
+    if (rst) hipLaunchKernelGGL(k_jpeg_layout<true>, dim3(1), dim3(1024), 0, ctx->stream, l);
+    else hipLaunchKernelGGL(k_jpeg_layout<false>, dim3(1), dim3(1024), 0, ctx->stream, l);
     ST_HIP(ctx, hipGetLastError());
+  }
+  if (!rst) {
+    st_timed tm(ctx, ST_K_JPEG);
+    hipLaunchKernelGGL(k_jpeg_pack_bits, dim3((unsigned)intervals), dim3(256), 0, ctx->stream, m);
+    ST_HIP(ctx, hipGetLastError());
+    s->n = n;
+    return ST_OK;
   }
   EncPackK p;
   p.slots = d_slots; p.ilen = d_ilen; p.ioff = d_ioff; p.offs = s->offs; p.header = s->params; p.blob = s->blob;
@@ -550,6 +739,10 @@ ST_EXPORT int st_jpeg_encode_batch(st_ctx* ctx, const uint8_t* const* frames_dev
   }
   s->n = n;
   return ST_OK;
+}
+
+ST_EXPORT int st_jpeg_encode_batch(st_ctx* ctx, const uint8_t* const* frames_dev, int n, int h, int w, int quality, int h_samp, int v_samp) {
+  return st_jpeg_encode_batch_rst(ctx, frames_dev, n, h, w, quality, h_samp, v_samp, ST_JPEG_RESTART_ROW);
 }
 
 ST_EXPORT int st_jpeg_encode_fetch(st_ctx* ctx, uint8_t* const* bufs_host, size_t* sizes, size_t capacity) {

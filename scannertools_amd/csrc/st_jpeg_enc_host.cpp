@@ -1,4 +1,4 @@
-// Host side of the ImageEncoder op (see st_jpeg_enc_host.h): st_jpeg_quant_tables, st_jpeg_encode_header,
+// Host side of the ImageEncoder op (see st_jpeg_enc_host.h): st_jpeg_quant_tables, st_jpeg_encode_header(_rst),
 // st_jpeg_encode_bound and what st_jpeg_enc.hip shares with them.  The tables are those of ITU-T T.81 Annex K; the scaling is
 // libjpeg's jpeg_set_quality with force_baseline; the marker order is libjpeg's.
 #include "st_jpeg_enc_host.h"
@@ -75,6 +75,15 @@ int st_jpeg_enc_check(int h, int w, int quality, int h_samp, int v_samp, char* m
   return ST_OK;
 }
 
+int st_jpeg_enc_check_restart(int restart, char* msg, size_t msg_len) {
+  msg[0] = 0;
+  if (restart != ST_JPEG_RESTART_ROW && restart != ST_JPEG_RESTART_NONE) {
+    snprintf(msg, msg_len, "restart %d is not supported (ST_JPEG_RESTART_ROW = 0 or ST_JPEG_RESTART_NONE = 1)", restart);
+    return ST_ERR_INVALID;
+  }
+  return ST_OK;
+}
+
 void st_jpeg_enc_geom(int h, int w, int hs, int vs, StJpegEncGeom* g) {
   g->h = h; g->w = w; g->hs = hs; g->vs = vs;
   g->mcols = (w + 8 * hs - 1) / (8 * hs);
@@ -109,12 +118,14 @@ ST_JPEG_EXPORT int st_jpeg_quant_tables(int quality, uint16_t* luma, uint16_t* c
   return ST_OK;
 }
 
-ST_JPEG_EXPORT int st_jpeg_encode_header(int h, int w, int quality, int h_samp, int v_samp, uint8_t* buf, size_t cap, size_t* size) {
+ST_JPEG_EXPORT int st_jpeg_encode_header_rst(int h, int w, int quality, int h_samp, int v_samp, int restart, uint8_t* buf, size_t cap, size_t* size) {
   char msg[160];
-  const int st = st_jpeg_enc_check(h, w, quality, h_samp, v_samp, msg, sizeof msg);
+  int st = st_jpeg_enc_check_restart(restart, msg, sizeof msg);
+  if (st == ST_OK) st = st_jpeg_enc_check(h, w, quality, h_samp, v_samp, msg, sizeof msg);
   if (st != ST_OK) return st;
-  if (size) *size = kJpegEncHeaderBytes;
-  if (!buf || cap < kJpegEncHeaderBytes) return ST_ERR_INVALID;
+  const size_t bytes = st_jpeg_enc_header_bytes(restart);
+  if (size) *size = bytes;
+  if (!buf || cap < bytes) return ST_ERR_INVALID;
   StJpegEncGeom g;
   st_jpeg_enc_geom(h, w, h_samp, v_samp, &g);
   uint16_t q[2][64];
@@ -139,11 +150,17 @@ ST_JPEG_EXPORT int st_jpeg_encode_header(int h, int w, int quality, int h_samp, 
     for (int i = 0; i < 16; ++i) put(s.bits[i]);
     for (int i = 0; i < s.nvals; ++i) put(s.vals[i]);
   }
-  put2(0xFFDD); put2(4); put2(g.mcols);   // one restart interval per MCU row
+  if (restart == ST_JPEG_RESTART_ROW) {
+    put2(0xFFDD); put2(4); put2(g.mcols);   // one restart interval per MCU row
+  }
   put2(0xFFDA); put2(12); put(3);
   put(1); put(0x00); put(2); put(0x11); put(3); put(0x11);
   put(0); put(63); put(0);
-  return ST_OK;   // p - buf == kJpegEncHeaderBytes: every segment above has a fixed length
+  return ST_OK;   // p - buf == st_jpeg_enc_header_bytes(restart): every segment above has a fixed length
+}
+
+ST_JPEG_EXPORT int st_jpeg_encode_header(int h, int w, int quality, int h_samp, int v_samp, uint8_t* buf, size_t cap, size_t* size) {
+  return st_jpeg_encode_header_rst(h, w, quality, h_samp, v_samp, ST_JPEG_RESTART_ROW, buf, cap, size);
 }
 
 ST_JPEG_EXPORT long long st_jpeg_encode_bound(int h, int w, int h_samp, int v_samp) {

@@ -916,13 +916,17 @@ class _Ops:
             args = _proto.image_decoder_args(args.get("image_type"), args.get("entropy"), args.get("split"))
         return _ImageDecoderNode(self.sc, "ImageDecoder", [img], device, batch, args or b"")
 
-    def ImageEncoder(self, frame, quality=95, subsampling="4:2:0", device=None, batch=None):
-        """sc.ops.ImageEncoder(frame=..., quality=..., subsampling=..., device=..., batch=...): (h, w, 3) uint8 RGB frames ->
-        the column img, one baseline JPEG stream (bytes) per row -- what sc.ops.ImageDecoder(img=...) reads.  Args
-        ImageEncoderArgs{quality = 1, subsampling = 2} (scannertools_imgproc_amd.proto): quality 1..100, subsampling "4:4:4",
-        "4:2:2" or "4:2:0"; anything else fails validation.  The whole encoder, Huffman coding included, runs on the GPU."""
+    def ImageEncoder(self, frame, quality=95, subsampling="4:2:0", restart="row", device=None, batch=None):
+        """sc.ops.ImageEncoder(frame=..., quality=..., subsampling=..., restart=..., device=..., batch=...): (h, w, 3) uint8 RGB
+        frames -> the column img, one baseline JPEG stream (bytes) per row -- what sc.ops.ImageDecoder(img=...) reads.  Args
+        ImageEncoderArgs{quality = 1, subsampling = 2, restart = 3} (scannertools_imgproc_amd.proto): quality 1..100,
+        subsampling "4:4:4", "4:2:2" or "4:2:0", restart "row" (one restart interval per MCU row; also "mcu_row") or "none" (no
+        restart markers: what cv::imencode and Pillow write by default), or the field's number; anything else fails validation.
+        The whole encoder, Huffman coding included, runs on the GPU."""
         from . import _proto
-        return _ImageEncoderNode(self.sc, "ImageEncoder", [frame], device, batch, _proto.image_encoder_args(quality, subsampling))
+        if isinstance(restart, str):
+            restart = {"row": 0, "mcu_row": 0, "none": 1}.get(restart.lower(), restart)
+        return _ImageEncoderNode(self.sc, "ImageEncoder", [frame], device, batch, _proto.image_encoder_args(quality, subsampling, restart))
 
     def InfoFromFrame(self, frame):
         """sc.ops.InfoFromFrame(frame=frame): the frame's FrameInfo as a bytes column."""

@@ -481,13 +481,15 @@ class HipContext:
         self._bind()
         return int(self._L.st_jpeg_split_last_rounds(self._h))
 
-    def encode_jpeg(self, frames, quality=95, subsampling="4:2:0"):
+    def encode_jpeg(self, frames, quality=95, subsampling="4:2:0", restart="row"):
         """ImageEncoder op: (n, h, w, 3) uint8 CUDA frames (a tensor or a list of (h, w, 3) tensors of one shape), R, G, B
         order -> a list of n baseline JPEG streams (bytes), byte for byte what libjpeg writes at this quality and sampling
-        with one restart interval per MCU row.  Colour conversion, downsampling, DCT, quantisation and Huffman coding run in
+        with one restart interval per MCU row (restart="row") or without restart markers (restart="none": libjpeg's, Pillow's
+        and cv::imencode's default).  Colour conversion, downsampling, DCT, quantisation and Huffman coding run in
         HIP kernels on the current stream; only the streams cross to the host, in one copy."""
-        self._bind()
         hs, vs = jpeg_sampling(subsampling)
+        rst = jpeg_restart(restart)
+        self._bind()
         fr = list(frames) if isinstance(frames, (list, tuple)) else list(frames.unbind(0))
         n = len(fr)
         if n == 0:
@@ -500,7 +502,7 @@ class HipContext:
             if tuple(f.shape) != (h, w, 3):
                 raise ValueError("all frames must have the same (h,w,3) shape")
         tf = (ctypes.c_void_p * n)(*[f.data_ptr() for f in fr])
-        self._check(self._L.st_jpeg_encode_batch(self._h, tf, n, h, w, int(quality), hs, vs))
+        self._check(self._L.st_jpeg_encode_batch_rst(self._h, tf, n, h, w, int(quality), hs, vs, rst))
         sizes = (ctypes.c_size_t * n)()
         self._check(self._L.st_jpeg_encode_fetch(self._h, None, sizes, 0))   # the sizes alone
         most = max(sizes)
@@ -1043,6 +1045,16 @@ def jpeg_sampling(subsampling):
     return JPEG_SUBSAMPLINGS[subsampling]
 
 
+JPEG_RESTARTS = {"row": 0, "none": 1}   # name -> ST_JPEG_RESTART_ROW / ST_JPEG_RESTART_NONE
+
+
+def jpeg_restart(restart):
+    """ST_JPEG_RESTART_* of "row" (one restart interval per MCU row) / "none" (no restart markers); ValueError for anything else."""
+    if not isinstance(restart, str) or restart not in JPEG_RESTARTS:
+        raise ValueError("restart %r is not supported ('row' or 'none')" % (restart,))
+    return JPEG_RESTARTS[restart]
+
+
 def jpeg_quant_tables(quality):
     """st_jpeg_quant_tables (host only): the (luma, chroma) quantisation tables of ``quality``, (64,) uint16 each, natural order."""
     luma, chroma = np.empty(64, np.uint16), np.empty(64, np.uint16)
@@ -1052,12 +1064,14 @@ def jpeg_quant_tables(quality):
     return luma, chroma
 
 
-def jpeg_encode_header(h, w, quality=95, subsampling="4:2:0"):
-    """st_jpeg_encode_header (host only): the bytes SOI .. SOS of the stream encode_jpeg writes for such a frame."""
+def jpeg_encode_header(h, w, quality=95, subsampling="4:2:0", restart="row"):
+    """st_jpeg_encode_header_rst (host only): the bytes SOI .. SOS of the stream encode_jpeg writes for such a frame: 629 with
+    restart="row", 623 (no DRI segment) with restart="none"."""
     hs, vs = jpeg_sampling(subsampling)
+    rst = jpeg_restart(restart)
     buf = ctypes.create_string_buffer(1024)
     size = ctypes.c_size_t()
-    st = _native.lib().st_jpeg_encode_header(int(h), int(w), int(quality), hs, vs, buf, 1024, ctypes.byref(size))
+    st = _native.lib().st_jpeg_encode_header_rst(int(h), int(w), int(quality), hs, vs, rst, buf, 1024, ctypes.byref(size))
     if st != 0:
         raise StError(st, "st_jpeg_encode_header(h=%d, w=%d, quality=%d): quality outside 1..100 or size outside 1..65535" % (h, w, quality))
     return buf.raw[:size.value]

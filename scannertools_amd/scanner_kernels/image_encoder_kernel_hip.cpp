@@ -3,14 +3,16 @@
 // Scanner's own stdlib has an ImageEncoder (a cv::imencode wrapper on the CPU); it is not part of the reference tree, so the
 // declaration here is this library's: frame_input("frame") -> output("img"), protobuf_name("ImageEncoderArgs"), `frame` a
 // U8 frame with 3 channels in R, G, B order, `img` the bytes of one baseline JPEG -- what ImageDecoder's `img` column reads.
-// ImageEncoderArgs { int32 quality = 1; string subsampling = 2; }: quality 0 or absent means 95, an empty subsampling means
-// "4:2:0".  Those are cv::imencode's defaults for JPEG (IMWRITE_JPEG_QUALITY 95, 4:2:0 sampling) as restated from OpenCV's
-// documentation; OpenCV is not available to check them against, so they are unpinned.
+// ImageEncoderArgs { int32 quality = 1; string subsampling = 2; Restart restart = 3; }: quality 0 or absent means 95, an empty
+// subsampling means "4:2:0".  Those are cv::imencode's defaults for JPEG (IMWRITE_JPEG_QUALITY 95, 4:2:0 sampling) as restated
+// from OpenCV's documentation; OpenCV is not available to check them against, so they are unpinned.  restart: MCU_ROW (0 or
+// absent) writes one restart interval per MCU row, NONE (1) no DRI segment and no RSTn markers -- the stream cv::imencode,
+// Pillow and cjpeg write by default; any other value fails validate().
 //
-// One st_jpeg_encode_batch() call per execute(): colour conversion, downsampling, forward DCT, quantisation and Huffman coding
+// One st_jpeg_encode_batch_rst() call per execute(): colour conversion, downsampling, forward DCT, quantisation and Huffman coding
 // run in HIP kernels (include/scannertools_hip.h), the streams come back in one copy of exactly their bytes
 // (st_jpeg_encode_fetch).  A stream is byte for byte what libjpeg writes at the same settings with one restart interval per
-// MCU row.  Registered twice like the other classes: DeviceType::GPU reads device frames, the staged DeviceType::CPU form
+// MCU row, or with restart = NONE with none at all.  Registered twice like the other classes: DeviceType::GPU reads device frames, the staged DeviceType::CPU form
 // uploads host frames first; both are batched.  No CPU fallback: without a GPU validate() fails.
 #include "scanner/api/kernel.h"
 #include "scanner/api/op.h"
@@ -22,15 +24,17 @@
 
 namespace scanner {
 namespace {
-// false: not a message.  quality: 0 when the field is absent; subsampling: empty when absent
-bool parse_image_encoder_args(const std::vector<u8>& args, int* quality, std::string* subsampling) {
+// false: not a message.  quality: 0 when the field is absent; subsampling: empty when absent; restart: 0 (MCU_ROW) when absent
+bool parse_image_encoder_args(const std::vector<u8>& args, int* quality, std::string* subsampling, long long* restart) {
   std::vector<proto_lite::Field> fields;
   *quality = 0;
+  *restart = 0;
   subsampling->clear();
   if (!proto_lite::parse(args.data(), args.size(), &fields)) return false;
   for (auto& f : fields) {
     if (f.number == 1 && f.wire == 0) *quality = (int)(int64_t)f.value;
     if (f.number == 2 && f.wire == 2) *subsampling = f.bytes;
+    if (f.number == 3 && f.wire == 0) *restart = (long long)(int64_t)f.value;
   }
   return true;
 }
@@ -41,7 +45,8 @@ class ImageEncoderKernelHIPImpl : public BatchedKernel {
  public:
   ImageEncoderKernelHIPImpl(const KernelConfig& config) : BatchedKernel(config), core_(config, STAGED), stage_(core_.gpu) {
     std::string sub;
-    if (!parse_image_encoder_args(config.args, &quality_, &sub)) {
+    long long restart = 0;
+    if (!parse_image_encoder_args(config.args, &quality_, &sub, &restart)) {
       RESULT_ERROR(&core_.valid, "ImageEncoder: could not parse ImageEncoderArgs");
       return;
     }
@@ -57,6 +62,11 @@ class ImageEncoderKernelHIPImpl : public BatchedKernel {
       RESULT_ERROR(&core_.valid, "ImageEncoder: subsampling \"%s\" is not supported (4:4:4, 4:2:2 or 4:2:0)", sub.c_str());
       return;
     }
+    if (restart != ST_JPEG_RESTART_ROW && restart != ST_JPEG_RESTART_NONE) {
+      RESULT_ERROR(&core_.valid, "ImageEncoder: restart %lld is not supported (MCU_ROW or NONE)", restart);
+      return;
+    }
+    restart_ = (int)restart;
     core_.open("ImageEncoderKernelHIP");
   }
   void validate(Result* result) override { core_.validate(result); }
@@ -84,7 +94,7 @@ class ImageEncoderKernelHIPImpl : public BatchedKernel {
       input_ptrs(src_, frame_col);
     }
     st_ctx* ctx = core_.ctx;
-    ST_CHECK(ctx, st_jpeg_encode_batch(ctx, src_.data(), n, h, w, quality_, h_samp_, v_samp_));
+    ST_CHECK(ctx, st_jpeg_encode_batch_rst(ctx, src_.data(), n, h, w, quality_, h_samp_, v_samp_, restart_));
     sizes_.assign(n, 0);
     ST_CHECK(ctx, st_jpeg_encode_fetch(ctx, nullptr, sizes_.data(), 0));   // the sizes alone
     size_t total = 0, most = 0;
@@ -106,7 +116,7 @@ class ImageEncoderKernelHIPImpl : public BatchedKernel {
  private:
   KernelCore core_;
   DeviceStage stage_;   // staged: the frames
-  int quality_ = 95, h_samp_ = 2, v_samp_ = 2;
+  int quality_ = 95, h_samp_ = 2, v_samp_ = 2, restart_ = ST_JPEG_RESTART_ROW;
   std::vector<const uint8_t*> src_;
   std::vector<uint8_t*> dst_;
   std::vector<size_t> sizes_;

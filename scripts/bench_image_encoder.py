@@ -10,11 +10,17 @@ the only baseline there is -- the op has no predecessor.  Per batch size, after 
 The first stream is compared with Pillow's byte for byte before anything is timed.  The frames are synthetic (seeded smooth
 structure plus sensor-like noise), eight distinct ones repeated.
 
-    python scripts/bench_image_encoder.py [--rounds 7]
-    rocprofv3 --kernel-trace --stats --output-format csv -d DIR -- python scripts/bench_image_encoder.py --trace
+    python scripts/bench_image_encoder.py [--rounds 7] [--restart row|none|both]
+    rocprofv3 --kernel-trace --stats --output-format csv -d DIR -- python scripts/bench_image_encoder.py --trace [--restart none]
 
 --trace makes three calls per batch size and times nothing: the kernel statistics of the trace then hold the four kernels'
 shares (k_jpeg_fdct, k_jpeg_entropy, k_jpeg_layout, k_jpeg_pack) over known work.
+
+--restart row (the default) measures streams with one restart interval per MCU row and prints what it always printed; none
+measures streams without restart markers (five launches: k_jpeg_fdct, k_jpeg_entropy<false>, k_jpeg_ff_count, k_jpeg_layout<false>,
+k_jpeg_pack_bits; Pillow then encodes without markers too); both measures the two in ONE run on the same frames, their timed
+calls alternating, so that the difference between them can be set against the spread between repeats of the run.  The figures
+of "none" go under "batches_norst".
 """
 import argparse
 import ctypes
@@ -52,6 +58,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--trace", action="store_true")
+    ap.add_argument("--restart", choices=("row", "none", "both"), default="row")
     args = ap.parse_args()
     try:
         from PIL import Image
@@ -65,14 +72,21 @@ def main():
     host = make_frames()
     dev = [torch.from_numpy(f).cuda() for f in host]
 
-    def pillow(i):
+    modes = ("row", "none") if args.restart == "both" else (args.restart,)
+
+    def pillow(i, mode="row"):
         buf = io.BytesIO()
-        Image.fromarray(host[i % DISTINCT]).save(buf, "JPEG", quality=QUALITY, subsampling=SUBSAMPLING, restart_marker_rows=1)
+        kw = {"restart_marker_rows": 1} if mode == "row" else {}
+        Image.fromarray(host[i % DISTINCT]).save(buf, "JPEG", quality=QUALITY, subsampling=SUBSAMPLING, **kw)
         return buf.getvalue()
 
-    assert ctx.encode_jpeg([dev[0]], QUALITY, SUBSAMPLING)[0] == pillow(0), "the stream differs from Pillow's"
+    for mode in modes:
+        assert ctx.encode_jpeg([dev[0]], QUALITY, SUBSAMPLING, restart=mode)[0] == pillow(0, mode), "the stream differs from Pillow's (restart=%s)" % mode
     result = {"bench": "image_encoder", "h": H, "w": W, "quality": QUALITY, "sampling": SUBSAMPLING, "raw_frame_bytes": H * W * 3,
-              "bound_bytes": jpeg_encode_bound(H, W, SUBSAMPLING), "rounds": args.rounds, "batches": {}}
+              "bound_bytes": jpeg_encode_bound(H, W, SUBSAMPLING), "rounds": args.rounds}
+    keys = {"row": "batches", "none": "batches_norst"}
+    for mode in modes:
+        result[keys[mode]] = {}
     ctx._bind()
     for n in BATCHES:
         tab = (ctypes.c_void_p * n)(*[dev[i % DISTINCT].data_ptr() for i in range(n)])
@@ -80,40 +94,49 @@ def main():
         store = np.empty((n, 1 << 22), np.uint8)   # no 1080p stream of these frames reaches 4 MiB; pages are touched only where written
         bufs = (ctypes.c_void_p * n)(*[store[i].ctypes.data for i in range(n)])
 
-        def call():
-            ctx._check(L.st_jpeg_encode_batch(ctx._h, tab, n, H, W, QUALITY, 2, 2))
+        def call(mode):
+            if mode == "row":
+                ctx._check(L.st_jpeg_encode_batch(ctx._h, tab, n, H, W, QUALITY, 2, 2))
+            else:
+                ctx._check(L.st_jpeg_encode_batch_rst(ctx._h, tab, n, H, W, QUALITY, 2, 2, 1))
             ctx._check(L.st_jpeg_encode_fetch(ctx._h, bufs, sizes, store.shape[1]))
 
         if args.trace:
-            for _ in range(3):
-                call()
+            for mode in modes:
+                for _ in range(3):
+                    call(mode)
             continue
-        call()   # warm-up: workspace, stream buffer and staging grow here
-        times = []
-        for _ in range(args.rounds):
-            t0 = time.perf_counter()
-            call()
-            times.append(time.perf_counter() - t0)
-        b = {"fps_median": round(n / statistics.median(times), 1), "fps_min": round(n / max(times), 1), "fps_max": round(n / min(times), 1),
-             "stream_bytes_per_frame": int(statistics.mean(sizes))}
-        ctx.timing_enable([_native.K_JPEG])
-        ctx.timing_reset()
-        for _ in range(args.rounds):
-            call()
-        launches, ms = ctx.timing_read(_native.K_JPEG)
-        ctx.timing_enable([])
-        b["kernel_ms_per_frame"] = round(ms / (args.rounds * n), 4)
-        b["kernel_launches_per_call"] = launches // args.rounds
-        with ThreadPoolExecutor(THREADS) as pool:
-            list(pool.map(pillow, range(n)))
-            times = []
-            for _ in range(max(3, args.rounds // 2)):
+        times, stream_bytes = {m: [] for m in modes}, {}
+        for mode in modes:
+            call(mode)   # warm-up: workspace, stream buffer and staging grow here
+            stream_bytes[mode] = int(statistics.mean(sizes))
+        for _ in range(args.rounds):   # the modes' timed calls alternate
+            for mode in modes:
                 t0 = time.perf_counter()
-                list(pool.map(pillow, range(n)))
-                times.append(time.perf_counter() - t0)
-        b["pillow_%d_threads_fps_median" % THREADS] = round(n / statistics.median(times), 1)
-        b["pillow_fps_min"], b["pillow_fps_max"] = round(n / max(times), 1), round(n / min(times), 1)
-        result["batches"]["batch%d" % n] = b
+                call(mode)
+                times[mode].append(time.perf_counter() - t0)
+        for mode in modes:
+            t = times[mode]
+            b = {"fps_median": round(n / statistics.median(t), 1), "fps_min": round(n / max(t), 1), "fps_max": round(n / min(t), 1),
+                 "stream_bytes_per_frame": stream_bytes[mode]}
+            ctx.timing_enable([_native.K_JPEG])
+            ctx.timing_reset()
+            for _ in range(args.rounds):
+                call(mode)
+            launches, ms = ctx.timing_read(_native.K_JPEG)
+            ctx.timing_enable([])
+            b["kernel_ms_per_frame"] = round(ms / (args.rounds * n), 4)
+            b["kernel_launches_per_call"] = launches // args.rounds
+            with ThreadPoolExecutor(THREADS) as pool:
+                list(pool.map(lambda i: pillow(i, mode), range(n)))
+                t = []
+                for _ in range(max(3, args.rounds // 2)):
+                    t0 = time.perf_counter()
+                    list(pool.map(lambda i: pillow(i, mode), range(n)))
+                    t.append(time.perf_counter() - t0)
+            b["pillow_%d_threads_fps_median" % THREADS] = round(n / statistics.median(t), 1)
+            b["pillow_fps_min"], b["pillow_fps_max"] = round(n / max(t), 1), round(n / min(t), 1)
+            result[keys[mode]]["batch%d" % n] = b
         del store
     ctx.close()
     print(json.dumps(result))
