@@ -3,7 +3,7 @@ save(quality=q, subsampling=s) and cjpeg write by default), in plain Python: wha
 It is tests/ref_jpeg_encode_np.scan with three changes: the DC predictors are kept across MCU rows, no MCU row is padded, and
 the padding with 1-bits and the FF -> FF 00 stuffing are applied once, over the whole scan.  The coefficients and their layout
 are those of ref_jpeg_encode_np.coefficients().  Checked against the streams Pillow wrote in tests/test_jpeg_encode_norst.py."""
-from ref_jpeg_encode_np import ZIGZAG, coefficients, huffman_tables   # noqa: F401  (coefficients: for the callers)
+from ref_jpeg_encode_np import ZIGZAG, BitString, coefficients, huffman_tables   # noqa: F401  (coefficients: for the callers)
 
 
 def row_bits(coef, h, w, hs, vs, header):
@@ -16,11 +16,8 @@ def row_bits(coef, h, w, hs, vs, header):
     pred = [0, 0, 0]   # only the picture's first MCU predicts from 0
     rows = []
     for my in range(mrows):
-        acc, nbits = 0, 0
-
-        def put(code, length):
-            nonlocal acc, nbits
-            acc, nbits = (acc << length) | code, nbits + length
+        bits = BitString()
+        put = bits.put
 
         def block(b, comp):
             b = [int(v) for v in b]
@@ -51,18 +48,20 @@ def row_bits(coef, h, w, hs, vs, header):
                 block(luma[my * vs + k // hs, mx * hs + k % hs], 0)
             block(chroma[0][my, mx], 1)
             block(chroma[1][my, mx], 2)
-        rows.append((acc, nbits))
+        rows.append(bits.value())
     return rows
 
 
 def scan_norst(coef, h, w, hs, vs, header):
     """(the entropy-coded scan and EOI, the MCU rows' bit offsets in the unstuffed scan followed by its length in bits) for
     coefficients in the layout of coefficients(): one scan, no restart interval, the tables of the header's DHT segments."""
-    acc, nbits, offsets = 0, 0, []
+    scan, nbits, offsets = BitString(), 0, []
     for value, length in row_bits(coef, h, w, hs, vs, header):
         offsets.append(nbits)
-        acc, nbits = (acc << length) | value, nbits + length
+        scan.put(value, length)
+        nbits += length
     offsets.append(nbits)
+    acc, nbits = scan.value()
     if nbits % 8:
         fill = 8 - nbits % 8
         acc, nbits = (acc << fill) | ((1 << fill) - 1), nbits + fill

@@ -123,6 +123,32 @@ def huffman_tables(header):
     return tables
 
 
+class BitString:
+    """Code bits appended first bit first.  The bits are kept in pieces of a few thousand and joined pairwise at the end, so that
+    a row of a million bits costs no more per code than a short one (one growing integer would be shifted whole at every code)."""
+    PIECE = 4096
+
+    def __init__(self):
+        self.parts, self.acc, self.n = [], 0, 0
+
+    def put(self, code, length):
+        self.acc, self.n = (self.acc << length) | code, self.n + length
+        if self.n >= self.PIECE:
+            self.parts.append((self.acc, self.n))
+            self.acc, self.n = 0, 0
+
+    def __len__(self):
+        return self.n + sum(n for _, n in self.parts)
+
+    def value(self):
+        """(the bits as an integer, the first bit the most significant; their number)"""
+        parts = self.parts + [(self.acc, self.n)]
+        while len(parts) > 1:
+            parts = [(parts[i][0] << parts[i + 1][1] | parts[i + 1][0], parts[i][1] + parts[i + 1][1]) if i + 1 < len(parts) else parts[i]
+                     for i in range(0, len(parts), 2)]
+        return parts[0]
+
+
 def scan(coef, h, w, hs, vs, header):
     """The entropy-coded scan and EOI for coefficients in the layout of coefficients(): one restart interval per MCU row
     (jchuff.c encode_mcu_huff with restart_interval = MCUs per row), the tables of the header's DHT segments."""
@@ -133,11 +159,8 @@ def scan(coef, h, w, hs, vs, header):
     chroma = [coef[(nl + c * mrows * mcols) * 64:(nl + (c + 1) * mrows * mcols) * 64].reshape(mrows, mcols, 64).astype(int) for c in range(2)]
     out = bytearray()
     for my in range(mrows):
-        acc, nbits, pred = 0, 0, [0, 0, 0]
-
-        def put(code, length):
-            nonlocal acc, nbits
-            acc, nbits = (acc << length) | code, nbits + length
+        bits, pred = BitString(), [0, 0, 0]
+        put = bits.put
 
         def block(b, comp):
             b = [int(v) for v in b]
@@ -168,8 +191,9 @@ def scan(coef, h, w, hs, vs, header):
                 block(luma[my * vs + k // hs, mx * hs + k % hs], 0)
             block(chroma[0][my, mx], 1)
             block(chroma[1][my, mx], 2)
-        if nbits % 8:
-            put((1 << (8 - nbits % 8)) - 1, 8 - nbits % 8)
+        if len(bits) % 8:
+            put((1 << (8 - len(bits) % 8)) - 1, 8 - len(bits) % 8)
+        acc, nbits = bits.value()
         data = acc.to_bytes(nbits // 8, "big")
         out += data.replace(b"\xff", b"\xff\x00")
         out += bytes([0xFF, 0xD0 + my % 8]) if my < mrows - 1 else b"\xff\xd9"

@@ -136,7 +136,9 @@ def test_store_width_does_not_change_a_byte(hip_ctx):
 
 
 def test_one_launch_past_a_grid_dimension(hip_ctx):
-    """65 537 streams in one call: one entropy launch whose grid strides over the frames, the dense kernels in two launches."""
+    """65 537 streams in one call: one entropy launch with the frames on grid.x, 65 537 workgroups wide (its stride over the
+    frames is NOT taken: the launch caps grid.x at 2^20 frames), the dense kernels, frames on grid.y, in two launches.  The stride
+    over a frame's groups of intervals (grid.y) is what tests/test_jpeg_large_gpu.py reaches."""
     n = 65537
     streams = [GOLD[t + "__jpg"].tobytes() for t in TINY]
     frames = np.stack([GOLD[t + "__img"] for t in TINY])

@@ -158,7 +158,10 @@ def test_store_width_does_not_change_a_byte(hip_ctx):
 
 
 def test_one_call_past_a_grid_dimension(hip_ctx):
-    """65 537 tiny streams without DRI in one call: the grids stride over the frames."""
+    """65 537 tiny streams without DRI in one call: more frames than one grid.y holds, so the dense kernels (frames on grid.y) run
+    in two launches, of 65 535 and 2 frames.  The subsequence kernels take frames on grid.x, here 65 537 workgroups wide: their
+    `f += gridDim.x` stride is NOT taken (lane_grid() caps grid.x at 2^20 frames), and no frame has more than one group of lanes.
+    The strides over groups and segments (grid.y) are what tests/test_jpeg_large_gpu.py reaches."""
     n = 65537
     streams = [GOLD[t + "__jpg"].tobytes() for t in TINY]
     frames = np.stack([GOLD[t + "__img"] for t in TINY])
