@@ -736,6 +736,31 @@ int st_jpeg_decode_batch_gpu_split(st_ctx* ctx, const uint8_t* const* bufs_host,
 /* The rounds st_jpeg_decode_batch_gpu_split's last call on this context took: round launches, the most over its sub-batches. */
 int st_jpeg_split_last_rounds(st_ctx* ctx);
 
+/* ---- ImageDecoder at a reduced scale: 1/2, 1/4, 1/8 ----
+ * libjpeg's scaled decoding (scale_num / scale_denom = 1 / d), bit-exact with libjpeg-turbo: what cv::imdecode returns for
+ * IMREAD_REDUCED_COLOR_2 / _4 / _8 (IMREAD_REDUCED_GRAYSCALE_* for a one-component stream) and Pillow after Image.draft().
+ * Every coefficient is still entropy-decoded; each component's blocks go through an inverse DCT of S = 1, 2, 4 or 8 samples
+ * a side instead of 8, and the frame written is (ceil(h / d), ceil(w / d), channels). */
+/* Host only: the size of an (h, w) frame decoded at 1 / scale_denom.  ST_ERR_INVALID: a denominator other than 1, 2, 4 or 8, a
+ * size outside 1..65 535, a null pointer. */
+int st_jpeg_scaled_size(int h, int w, int scale_denom, int* oh, int* ow);
+/* Host only, re-entrant: per component (entries behind `channels` are 0) the inverse DCT size S libjpeg's rule gives it at
+ * this scale -- from 8 / d, doubled while the component's remaining upsampling factor stays whole both ways: 4:2:0 chroma gets
+ * twice the luma's size and is never upsampled, 4:2:2 chroma the luma's and is still upsampled 2:1 horizontally -- and the
+ * extent dw x dh of its reduced plane in samples.  Refusals and messages are st_jpeg_probe's; a bad denominator or a null
+ * array is ST_ERR_INVALID.  info may be null. */
+int st_jpeg_scaled_geometry(const uint8_t* buf, size_t size, int scale_denom, int S[3], int dw[3], int dh[3], st_jpeg_info* info);
+/* Where st_jpeg_decode_batch_scaled decodes the Huffman codes: what st_jpeg_decode_batch, st_jpeg_decode_batch_gpu and
+ * st_jpeg_decode_batch_gpu_split do. */
+enum { ST_JPEG_ENTROPY_HOST = 0, ST_JPEG_ENTROPY_INTERVAL = 1, ST_JPEG_ENTROPY_SUBSEQUENCE = 2 };
+/* The call `entropy` names, writing the frames at 1 / scale_denom: h and w are the streams' own size, out_dev holds n device
+ * pointers to (ceil(h / d), ceil(w / d), channels) frames; opts is read for ST_JPEG_ENTROPY_SUBSEQUENCE only.  Refusals,
+ * messages, sub-batches, status words and the order of errors are those of the call it stands for, and with scale_denom = 1 it
+ * is that call.  A denominator other than 1, 2, 4 or 8, or an unknown `entropy`, is ST_ERR_INVALID naming the value before
+ * anything is launched or written. */
+int st_jpeg_decode_batch_scaled(st_ctx* ctx, const uint8_t* const* bufs_host, const size_t* sizes, int n, int h, int w, int channels,
+                                int scale_denom, int entropy, const st_jpeg_split_opts* opts, uint8_t* const* out_dev);
+
 /* ---- ImageEncoder: baseline JPEG ------------------------------------------------------------
  * The counterpart of the ImageDecoder block (Scanner's stdlib ImageEncoder wraps cv::imencode on the host; it is not part of
  * the reference tree).  Resident (h, w, 3) uint8 frames in R, G, B order become baseline JPEG streams; colour conversion,

@@ -199,6 +199,9 @@ SIGNATURES = {
     "st_jpeg_coefficients_by_subsequence": (_i, [_vp, _sz, _c.POINTER(JpegSplitOpts), _vp, _sz, _vp, _c.POINTER(JpegInfo), _c.POINTER(_i)]),
     "st_jpeg_decode_batch_gpu_split": (_i, [_vp, _c.POINTER(_vp), _c.POINTER(_sz), _i, _i, _i, _i, _c.POINTER(_vp), _c.POINTER(JpegSplitOpts)]),
     "st_jpeg_split_last_rounds": (_i, [_vp]),
+    "st_jpeg_scaled_size": (_i, [_i, _i, _i, _c.POINTER(_i), _c.POINTER(_i)]),
+    "st_jpeg_scaled_geometry": (_i, [_vp, _sz, _i, _c.POINTER(_i), _c.POINTER(_i), _c.POINTER(_i), _c.POINTER(JpegInfo)]),
+    "st_jpeg_decode_batch_scaled": (_i, [_vp, _c.POINTER(_vp), _c.POINTER(_sz), _i, _i, _i, _i, _i, _i, _c.POINTER(JpegSplitOpts), _c.POINTER(_vp)]),
     "st_jpeg_quant_tables": (_i, [_i, _vp, _vp]),
     "st_jpeg_encode_header": (_i, [_i, _i, _i, _i, _i, _vp, _sz, _c.POINTER(_sz)]),
     "st_jpeg_encode_bound": (ctypes.c_longlong, [_i, _i, _i, _i]),
@@ -223,8 +226,8 @@ def source_hash():
     st_build_info() of a library built from THIS tree reports."""
     import hashlib
     srcs = ["st_context.hip", "st_hist.hip", "st_farneback.hip", "st_flowvis.hip", "st_imgproc.hip", "st_pose.hip", "st_conv.hip",
-            "st_conv_tile_bf16x3.hip", "st_conv_tile_f32.hip", "st_framestats.hip", "st_jpeg.hip", "st_netinput.hip", "st_nn.hip", "st_detect.hip", "st_jpeg_enc.hip", "st_jpeg_entropy.hip", "st_jpeg_subseq.hip", "st_jpeg_parse.cpp", "st_jpeg_enc_host.cpp", "st_internal.h",
-            "st_conv_tile.h", "st_jpeg_parse.h", "st_jpeg_enc_host.h", "st_jpeg_entropy.h",
+            "st_conv_tile_bf16x3.hip", "st_conv_tile_f32.hip", "st_framestats.hip", "st_jpeg.hip", "st_netinput.hip", "st_nn.hip", "st_detect.hip", "st_jpeg_enc.hip", "st_jpeg_entropy.hip", "st_jpeg_subseq.hip", "st_jpeg_reduced.hip", "st_jpeg_parse.cpp", "st_jpeg_enc_host.cpp", "st_internal.h",
+            "st_conv_tile.h", "st_jpeg_parse.h", "st_jpeg_enc_host.h", "st_jpeg_entropy.h", "st_jpeg_dense.h",
             os.path.join("..", "..", "include", "scannertools_hip.h"), "Makefile"]
     hsh = hashlib.sha256()
     for f in srcs:

@@ -25,56 +25,11 @@
 #include <thread>
 
 #include "st_internal.h"
+#include "st_jpeg_dense.h"
 #include "st_jpeg_entropy.h"
 #include "st_jpeg_parse.h"
 
 namespace {
-
-struct alignas(16) JpegFrameHdr {
-  uint8_t* out;          // the frame's dense (h, w, channels) output
-  int blk_off;           // the frame's first block within the sub-batch
-  int nblk_y, nblk_c;    // blocks of the luma plane / of each chroma plane (0 for a one-component stream)
-  int bw_y, bw_c;        // blocks per row of them
-  int mode;              // ST_JPEG_*
-  int dw, dh;            // the chroma planes' real extent in samples
-  int fancy;             // 1: triangle filter; 0: replication (dw <= 2)
-  int pad0[5];
-  uint16_t quant[3][64];
-  uint8_t pad1[64];
-};
-static_assert(sizeof(JpegFrameHdr) == 512, "one header is 512 bytes");
-
-struct JpegArgsK {
-  const uint8_t* slot;   // headers, then coefficients
-  uint8_t* planes;
-  int nf, h, w, channels;
-};
-
-typedef short short8 __attribute__((ext_vector_type(8)));
-typedef unsigned short ushort8 __attribute__((ext_vector_type(8)));
-
-// One pass of jidctint's 8-point inverse DCT (CONST_BITS 13): out = DESCALE(..., n), arithmetic shifts.
-__device__ __forceinline__ void idct_pass(const int* i, int* o, int n) {
-  int z1 = (i[2] + i[6]) * 4433;
-  const int t2 = z1 - i[6] * 15137, t3 = z1 + i[2] * 6270;
-  const int t0 = (i[0] + i[4]) * 8192, t1 = (i[0] - i[4]) * 8192;
-  const int t10 = t0 + t3, t13 = t0 - t3, t11 = t1 + t2, t12 = t1 - t2;
-  int a = i[7], b = i[5], c = i[3], d = i[1];
-  z1 = a + d;
-  int z2 = b + c, z3 = a + c, z4 = b + d;
-  const int z5 = (z3 + z4) * 9633;
-  a *= 2446; b *= 16819; c *= 25172; d *= 12299;
-  z1 *= -7373; z2 *= -20995;
-  z3 = z3 * -16069 + z5; z4 = z4 * -3196 + z5;
-  a += z1 + z3; b += z2 + z4; c += z2 + z3; d += z1 + z4;
-  const int r = 1 << (n - 1);
-  o[0] = (t10 + d + r) >> n; o[7] = (t10 - d + r) >> n;
-  o[1] = (t11 + c + r) >> n; o[6] = (t11 - c + r) >> n;
-  o[2] = (t12 + b + r) >> n; o[5] = (t12 - b + r) >> n;
-  o[3] = (t13 + a + r) >> n; o[4] = (t13 - a + r) >> n;
-}
-
-__device__ __forceinline__ int clamp255(int v) { return v < 0 ? 0 : (v > 255 ? 255 : v); }
 
 // Lane = one row of one block: 16 B of coefficients in, 8 B of samples out; 32 blocks per workgroup, 8 per wave.  The two
 // transposes (rows -> columns for pass 1, back for pass 2) go through LDS, 72 dwords per block: lanes (block, c) of a
@@ -188,14 +143,6 @@ __device__ __forceinline__ void chroma16(const uint8_t* __restrict__ P, const Ch
   for (int p = 0; p < 16; ++p) o[p] = (3 * s[1 + (p >> 1)] + s[1 + (p >> 1) + ((p & 1) ? 1 : -1)] + ((p & 1) ? 7 : 8)) >> 4;
 }
 
-// jdcolor's YCbCr -> RGB in 16 fractional bits
-__device__ __forceinline__ void ycc_rgb(int Y, int Cb, int Cr, int* rgb) {
-  const int cb = Cb - 128, cr = Cr - 128;
-  rgb[0] = clamp255(Y + ((91881 * cr + 32768) >> 16));
-  rgb[1] = clamp255(Y + ((-22554 * cb - 46802 * cr + 32768) >> 16));
-  rgb[2] = clamp255(Y + ((116130 * cb + 32768) >> 16));
-}
-
 // PX pixels of one row per thread.  PX = 16: w % 16 == 0 and 16-byte aligned frames, whole 16-byte stores (three per thread, one
 // for a one-component frame); PX = 4: w % 4 == 0 and 4-byte aligned frames, dword stores; PX = 1: anything, byte stores.
 template <int PX>
@@ -280,8 +227,8 @@ int jpeg_threads(int n) {
   return std::max(1, std::min(std::min(t, 64), n));
 }
 
-// the header the two dense kernels read, from a parsed stream
-void jpeg_frame_hdr(const StJpegHeader& hd, uint8_t* out, int blk_off, JpegFrameHdr* fh) {
+// the header the two dense kernels read, from a parsed stream; d: the scale denominator (1: full size)
+void jpeg_frame_hdr(const StJpegHeader& hd, uint8_t* out, int blk_off, JpegFrameHdr* fh, int d) {
   memset(fh, 0, sizeof *fh);
   fh->out = out;
   fh->blk_off = blk_off;
@@ -293,7 +240,35 @@ void jpeg_frame_hdr(const StJpegHeader& hd, uint8_t* out, int blk_off, JpegFrame
   fh->dw = (hd.w + hd.hs[0] - 1) / hd.hs[0];
   fh->dh = (hd.h + hd.vs[0] - 1) / hd.vs[0];
   fh->fancy = fh->dw > 2 ? 1 : 0;
+  if (d > 1) {
+    // the reduced planes (st_jpeg_reduced.hip): what upsampling is left is h2v1, and libjpeg replicates at 1/8
+    int S[3], dw[3], dh[3];
+    st_jpeg_reduced_geom(hd, d, S, dw, dh);
+    fh->s_y = S[0];
+    fh->s_c = hd.ncomp == 3 ? S[1] : S[0];
+    fh->ups = hd.ncomp == 3 ? hd.hs[0] * (8 / d) / S[1] : 1;
+    fh->dw = hd.ncomp == 3 ? dw[1] : dw[0];
+    fh->dh = hd.ncomp == 3 ? dh[1] : dh[0];
+    fh->fancy = fh->ups == 2 && fh->dw > 2 && d < 8 ? 1 : 0;
+  }
   for (int c = 0; c < hd.ncomp; ++c) memcpy(fh->quant[c], hd.quant[hd.tq[c]], 128);
+}
+
+// the dense launches of nfl frames whose headers start at a.slot: the full-size pair, or the reduced ones
+void launch_dense(st_ctx* ctx, JpegArgsK a, int nfl, int d, int px, size_t most, size_t most1, size_t mostlds) {
+  if (d > 1) {
+    a.h = (a.h + d - 1) / d;
+    a.w = (a.w + d - 1) / d;
+    st_jpeg_reduced_launch(ctx, a, nfl, most1, mostlds, px);
+    return;
+  }
+  hipLaunchKernelGGL(k_jpeg_idct, dim3((unsigned)((most + kIdctBlocks - 1) / kIdctBlocks), nfl), dim3(256), 0, ctx->stream, a);
+  long long bx = ((long long)a.h * a.w / px + 255) / 256;
+  if (bx > 8192) bx = 8192;
+  const dim3 grid((unsigned)bx, nfl);
+  if (px == 16) hipLaunchKernelGGL(k_jpeg_color<16>, grid, dim3(256), 0, ctx->stream, a);
+  else if (px == 4) hipLaunchKernelGGL(k_jpeg_color<4>, grid, dim3(256), 0, ctx->stream, a);
+  else hipLaunchKernelGGL(k_jpeg_color<1>, grid, dim3(256), 0, ctx->stream, a);
 }
 
 constexpr size_t kSlotCoefBytes = (size_t)64 << 20;   // coefficients of one sub-batch, unless a single frame has more
@@ -325,9 +300,10 @@ void st_jpeg_release(st_ctx* ctx) {
   ctx->jpeg = nullptr;
 }
 
-ST_EXPORT int st_jpeg_decode_batch(st_ctx* ctx, const uint8_t* const* bufs_host, const size_t* sizes, int n, int h, int w, int channels,
-                                   uint8_t* const* out_dev) {
-  ST_TRY(st_enter(ctx));
+namespace {
+// st_jpeg_decode_batch, the frames written at 1/d
+int decode_batch_host(st_ctx* ctx, const uint8_t* const* bufs_host, const size_t* sizes, int n, int h, int w, int channels, uint8_t* const* out_dev,
+                      const int d) {
   if (n < 0 || h <= 0 || w <= 0 || h > 65535 || w > 65535 || (channels != 1 && channels != 3))
     return st_set_error(ctx, ST_ERR_INVALID, "jpeg: bad arguments (n=%d h=%d w=%d channels=%d)", n, h, w, channels);
   if (n == 0) return ST_OK;
@@ -417,7 +393,7 @@ ST_EXPORT int st_jpeg_decode_batch(st_ctx* ctx, const uint8_t* const* bufs_host,
         const StJpegHeader& hd = hds[i];
         uint8_t* slot = js->pin[k & 1];
         JpegFrameHdr* fh = reinterpret_cast<JpegFrameHdr*>(slot) + (i - sbs[k].first);
-        jpeg_frame_hdr(hd, out_dev[i], blk_off[i], fh);
+        jpeg_frame_hdr(hd, out_dev[i], blk_off[i], fh, d);
         int16_t* coef = reinterpret_cast<int16_t*>(slot + (size_t)sbs[k].count * sizeof(JpegFrameHdr) + (size_t)blk_off[i] * 128);
         st = st_jpeg_decode_scan(bufs_host[i], sizes[i], hd, coef, msg, sizeof msg);
       }
@@ -441,7 +417,8 @@ ST_EXPORT int st_jpeg_decode_batch(st_ctx* ctx, const uint8_t* const* bufs_host,
     for (int i = 0; i < n; ++i) a |= (unsigned)(uintptr_t)out_dev[i];
     return a;
   }();
-  const int px = (w % 16 == 0 && (align & 15) == 0) ? 16 : ((w % 4 == 0 && (align & 3) == 0) ? 4 : 1);
+  const int ow = (w + d - 1) / d;   // the width of the frames written
+  const int px = (ow % 16 == 0 && (align & 15) == 0) ? 16 : ((ow % 4 == 0 && (align & 3) == 0) ? 4 : 1);
   auto issue = [&]() -> int {
     for (int k = 0; k < nsb; ++k) {
       {
@@ -457,17 +434,17 @@ ST_EXPORT int st_jpeg_decode_batch(st_ctx* ctx, const uint8_t* const* bufs_host,
       js->busy[s] = true;
       JpegArgsK a;
       a.slot = d_slot; a.planes = d_planes; a.nf = sb.count; a.h = h; a.w = w; a.channels = channels;
-      size_t most = 0;
-      for (int i = sb.first; i < sb.first + sb.count; ++i) most = std::max(most, st_jpeg_blocks(hds[i]));
+      size_t most = 0, most1 = 0, mostlds = 0;
+      for (int i = sb.first; i < sb.first + sb.count; ++i) {
+        most = std::max(most, st_jpeg_blocks(hds[i]));
+        size_t n1, nlds;
+        st_jpeg_reduced_counts(reinterpret_cast<const JpegFrameHdr*>(js->pin[s])[i - sb.first], &n1, &nlds);
+        most1 = std::max(most1, n1);
+        mostlds = std::max(mostlds, nlds);
+      }
       {
         st_timed t(ctx, ST_K_JPEG);
-        hipLaunchKernelGGL(k_jpeg_idct, dim3((unsigned)((most + kIdctBlocks - 1) / kIdctBlocks), sb.count), dim3(256), 0, ctx->stream, a);
-        long long bx = ((long long)h * w / px + 255) / 256;
-        if (bx > 8192) bx = 8192;
-        const dim3 grid((unsigned)bx, sb.count);
-        if (px == 16) hipLaunchKernelGGL(k_jpeg_color<16>, grid, dim3(256), 0, ctx->stream, a);
-        else if (px == 4) hipLaunchKernelGGL(k_jpeg_color<4>, grid, dim3(256), 0, ctx->stream, a);
-        else hipLaunchKernelGGL(k_jpeg_color<1>, grid, dim3(256), 0, ctx->stream, a);
+        launch_dense(ctx, a, sb.count, d, px, most, most1, mostlds);
       }
       ST_HIP(ctx, hipGetLastError());
       if (k + 2 < nsb) {
@@ -490,6 +467,13 @@ ST_EXPORT int st_jpeg_decode_batch(st_ctx* ctx, const uint8_t* const* bufs_host,
   }
   for (std::thread& t : pool) t.join();
   return status;
+}
+}  // namespace
+
+ST_EXPORT int st_jpeg_decode_batch(st_ctx* ctx, const uint8_t* const* bufs_host, const size_t* sizes, int n, int h, int w, int channels,
+                                   uint8_t* const* out_dev) {
+  ST_TRY(st_enter(ctx));
+  return decode_batch_host(ctx, bufs_host, sizes, n, h, w, channels, out_dev, 1);
 }
 
 // ---- entropy decoding on the device -----------------------------------------------------------------------------------------
@@ -558,7 +542,7 @@ namespace {
 // st_jpeg_decode_batch_gpu (split = false: one lane per restart interval) and st_jpeg_decode_batch_gpu_split (split = true: one
 // lane per subsequence of S bytes, at most R round launches) share everything but the entropy launches.
 int decode_batch_gpu(st_ctx* ctx, const uint8_t* const* bufs_host, const size_t* sizes, int n, int h, int w, int channels, uint8_t* const* out_dev,
-                     const bool split, const uint32_t S, const int R) {
+                     const bool split, const uint32_t S, const int R, const int d) {
   if (n < 0 || h <= 0 || w <= 0 || h > 65535 || w > 65535 || (channels != 1 && channels != 3))
     return st_set_error(ctx, ST_ERR_INVALID, "jpeg: bad arguments (n=%d h=%d w=%d channels=%d)", n, h, w, channels);
   if (n == 0) return ST_OK;
@@ -603,7 +587,7 @@ int decode_batch_gpu(st_ctx* ctx, const uint8_t* const* bufs_host, const size_t*
           return;
         }
         if (!scan_ok) continue;   // a later stream of this run may still be refused, which comes first
-        jpeg_frame_hdr(hd, out_dev[i], 0, &g.fh);
+        jpeg_frame_hdr(hd, out_dev[i], 0, &g.fh, d);
         g.geom = st_jpeg_scan_geom(hd);
         g.scan_pos = hd.scan_pos;
         g.nblocks = st_jpeg_blocks(hd);
@@ -716,7 +700,8 @@ int decode_batch_gpu(st_ctx* ctx, const uint8_t* const* bufs_host, const size_t*
     for (int i = 0; i < n; ++i) a |= (unsigned)(uintptr_t)out_dev[i];
     return a;
   }();
-  const int px = (w % 16 == 0 && (align & 15) == 0) ? 16 : ((w % 4 == 0 && (align & 3) == 0) ? 4 : 1);
+  const int ow = (w + d - 1) / d;   // the width of the frames written
+  const int px = (ow % 16 == 0 && (align & 15) == 0) ? 16 : ((ow % 4 == 0 && (align & 3) == 0) ? 4 : 1);
 
   for (const GpuSubBatch& sb : sbs) {
     // 3. fill the slot on the threads (free: the previous sub-batch was waited for)
@@ -814,10 +799,14 @@ int decode_batch_gpu(st_ctx* ctx, const uint8_t* const* bufs_host, const size_t*
       ST_HIP(ctx, hipStreamSynchronize(ctx->stream));
       word = *js->gstatus;
       if (word == kStJpegEntClean) {
-        size_t most = 0;
-        for (int i = sb.first; i < sb.first + sb.count; ++i) most = std::max(most, gs[(size_t)i].nblocks);
-        long long bx = ((long long)h * w / px + 255) / 256;
-        if (bx > 8192) bx = 8192;
+        size_t most = 0, most1 = 0, mostlds = 0;
+        for (int i = sb.first; i < sb.first + sb.count; ++i) {
+          most = std::max(most, gs[(size_t)i].nblocks);
+          size_t n1, nlds;
+          st_jpeg_reduced_counts(gs[(size_t)i].fh, &n1, &nlds);
+          most1 = std::max(most1, n1);
+          mostlds = std::max(mostlds, nlds);
+        }
         // the dense kernels take the frame from blockIdx.y: at most 65 535 frames per launch, the headers offset so that the
         // coefficients stay where slot + nf * 512 points
         for (int f0 = 0; f0 < sb.count; f0 += 65535) {
@@ -825,11 +814,7 @@ int decode_batch_gpu(st_ctx* ctx, const uint8_t* const* bufs_host, const size_t*
           JpegArgsK a;
           a.slot = d_up + sb.hdr_off + (size_t)f0 * sizeof(JpegFrameHdr);
           a.planes = d_planes; a.nf = sb.count - f0; a.h = h; a.w = w; a.channels = channels;
-          hipLaunchKernelGGL(k_jpeg_idct, dim3((unsigned)((most + kIdctBlocks - 1) / kIdctBlocks), nfl), dim3(256), 0, ctx->stream, a);
-          const dim3 grid((unsigned)bx, nfl);
-          if (px == 16) hipLaunchKernelGGL(k_jpeg_color<16>, grid, dim3(256), 0, ctx->stream, a);
-          else if (px == 4) hipLaunchKernelGGL(k_jpeg_color<4>, grid, dim3(256), 0, ctx->stream, a);
-          else hipLaunchKernelGGL(k_jpeg_color<1>, grid, dim3(256), 0, ctx->stream, a);
+          launch_dense(ctx, a, nfl, d, px, most, most1, mostlds);
         }
       }
     }
@@ -851,18 +836,38 @@ int decode_batch_gpu(st_ctx* ctx, const uint8_t* const* bufs_host, const size_t*
 ST_EXPORT int st_jpeg_decode_batch_gpu(st_ctx* ctx, const uint8_t* const* bufs_host, const size_t* sizes, int n, int h, int w, int channels,
                                        uint8_t* const* out_dev) {
   ST_TRY(st_enter(ctx));
-  return decode_batch_gpu(ctx, bufs_host, sizes, n, h, w, channels, out_dev, false, 0, 0);
+  return decode_batch_gpu(ctx, bufs_host, sizes, n, h, w, channels, out_dev, false, 0, 0, 1);
 }
 
-ST_EXPORT int st_jpeg_decode_batch_gpu_split(st_ctx* ctx, const uint8_t* const* bufs_host, const size_t* sizes, int n, int h, int w, int channels,
-                                             uint8_t* const* out_dev, const st_jpeg_split_opts* opts) {
-  ST_TRY(st_enter(ctx));
+namespace {
+int decode_batch_split(st_ctx* ctx, const uint8_t* const* bufs_host, const size_t* sizes, int n, int h, int w, int channels, uint8_t* const* out_dev,
+                       const st_jpeg_split_opts* opts, const int d) {
   const int S = opts && opts->subseq_bytes ? opts->subseq_bytes : kStJsqDefaultSubseqBytes;
   const int R = opts && opts->max_rounds ? opts->max_rounds : kStJsqDefaultMaxRounds;
   if (S < 8 || S > 4096 || S % 8 != 0 || R < 0)
     return st_set_error(ctx, ST_ERR_INVALID, "jpeg: subseq_bytes %d / max_rounds %d: a multiple of 8 in 8..4096, and no negative cap", S, R);
   if (ctx->jpeg) ctx->jpeg->split_rounds = 0;
-  return decode_batch_gpu(ctx, bufs_host, sizes, n, h, w, channels, out_dev, true, (uint32_t)S, R);
+  return decode_batch_gpu(ctx, bufs_host, sizes, n, h, w, channels, out_dev, true, (uint32_t)S, R, d);
+}
+}  // namespace
+
+ST_EXPORT int st_jpeg_decode_batch_gpu_split(st_ctx* ctx, const uint8_t* const* bufs_host, const size_t* sizes, int n, int h, int w, int channels,
+                                             uint8_t* const* out_dev, const st_jpeg_split_opts* opts) {
+  ST_TRY(st_enter(ctx));
+  return decode_batch_split(ctx, bufs_host, sizes, n, h, w, channels, out_dev, opts, 1);
+}
+
+ST_EXPORT int st_jpeg_decode_batch_scaled(st_ctx* ctx, const uint8_t* const* bufs_host, const size_t* sizes, int n, int h, int w, int channels,
+                                          int scale_denom, int entropy, const st_jpeg_split_opts* opts, uint8_t* const* out_dev) {
+  ST_TRY(st_enter(ctx));
+  const int d = scale_denom;
+  if (d != 1 && d != 2 && d != 4 && d != 8) return st_set_error(ctx, ST_ERR_INVALID, "jpeg: scale_denom %d: 1, 2, 4 or 8", d);
+  switch (entropy) {
+    case ST_JPEG_ENTROPY_HOST: return decode_batch_host(ctx, bufs_host, sizes, n, h, w, channels, out_dev, d);
+    case ST_JPEG_ENTROPY_INTERVAL: return decode_batch_gpu(ctx, bufs_host, sizes, n, h, w, channels, out_dev, false, 0, 0, d);
+    case ST_JPEG_ENTROPY_SUBSEQUENCE: return decode_batch_split(ctx, bufs_host, sizes, n, h, w, channels, out_dev, opts, d);
+  }
+  return st_set_error(ctx, ST_ERR_INVALID, "jpeg: entropy %d: ST_JPEG_ENTROPY_HOST (0), _INTERVAL (1) or _SUBSEQUENCE (2)", entropy);
 }
 
 ST_EXPORT int st_jpeg_split_last_rounds(st_ctx* ctx) { return ctx && ctx->jpeg ? ctx->jpeg->split_rounds : 0; }

@@ -373,6 +373,29 @@ ST_JPEG_EXPORT int st_jpeg_probe(const uint8_t* buf, size_t size, st_jpeg_info* 
   return st;
 }
 
+ST_JPEG_EXPORT int st_jpeg_scaled_size(int h, int w, int scale_denom, int* oh, int* ow) {
+  const int d = scale_denom;
+  if ((d != 1 && d != 2 && d != 4 && d != 8) || h < 1 || w < 1 || h > 65535 || w > 65535 || !oh || !ow) return ST_ERR_INVALID;
+  *oh = (h + d - 1) / d;
+  *ow = (w + d - 1) / d;
+  return ST_OK;
+}
+
+ST_JPEG_EXPORT int st_jpeg_scaled_geometry(const uint8_t* buf, size_t size, int scale_denom, int S[3], int dw[3], int dh[3], st_jpeg_info* info) {
+  st_jpeg_info local;
+  if (!info) info = &local;
+  memset(info, 0, sizeof *info);
+  const int d = scale_denom;
+  if ((d != 1 && d != 2 && d != 4 && d != 8) || !S || !dw || !dh)
+    return fail(info->message, sizeof info->message, ST_ERR_INVALID, "scale_denom %d: 1, 2, 4 or 8, and no null pointer", d);
+  StJpegHeader hd;
+  const int st = st_jpeg_parse_header(buf, size, &hd, info->message, sizeof info->message);
+  if (st != ST_OK) return st;
+  fill_info(hd, info);
+  st_jpeg_reduced_geom(hd, d, S, dw, dh);
+  return ST_OK;
+}
+
 ST_JPEG_EXPORT int st_jpeg_coefficients(const uint8_t* buf, size_t size, int16_t* coef, size_t cap, uint16_t* quant, st_jpeg_info* info) {
   st_jpeg_info local;
   if (!info) info = &local;

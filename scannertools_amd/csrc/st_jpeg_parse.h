@@ -62,4 +62,20 @@ inline size_t st_jpeg_segment_count(const StJpegHeader& hd) { return hd.restart_
 // hd.scan_pos to the first marker that is neither FF00 nor a fill byte (or size).  ST_ERR_UNSUPPORTED: size >= 4 GiB.
 int st_jpeg_segments(const uint8_t* buf, size_t size, const StJpegHeader& hd, uint32_t* table, char* msg, size_t msg_len);
 
+// Decoding at 1/d (d = 2, 4, 8; m = 8 / d is libjpeg's min_DCT_scaled_size): jdmaster's inverse DCT size S of every component
+// (doubled from m while the component's remaining upsampling factor stays whole in both directions) and the extent
+// (dw, dh) of its reduced plane in samples.  d = 1 gives S = 8 and the component's own extent.
+inline void st_jpeg_reduced_geom(const StJpegHeader& hd, int d, int S[3], int dw[3], int dh[3]) {
+  const int m = 8 / d, hmax = hd.hs[0], vmax = hd.vs[0];   // luma carries the largest factors in every sampling accepted
+  for (int c = 0; c < 3; ++c) {
+    S[c] = dw[c] = dh[c] = 0;
+    if (c >= hd.ncomp) continue;
+    int s = m;
+    while (s < 8 && (hmax * m) % (hd.hs[c] * s * 2) == 0 && (vmax * m) % (hd.vs[c] * s * 2) == 0) s *= 2;
+    S[c] = s;
+    dw[c] = (int)(((long long)hd.w * hd.hs[c] * s + (long long)hmax * 8 - 1) / ((long long)hmax * 8));
+    dh[c] = (int)(((long long)hd.h * hd.vs[c] * s + (long long)vmax * 8 - 1) / ((long long)vmax * 8));
+  }
+}
+
 #endif  // ST_JPEG_PARSE_H_

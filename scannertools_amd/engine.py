@@ -910,10 +910,11 @@ class _Ops:
         (the last two fail validation: JPEG only) and / or entropy "host" / "gpu" / "auto" (ImageDecoderArgs.entropy = 2:
         where the Huffman decoder runs; "gpu" needs restart intervals in every row) and / or split "interval" / "subsequence"
         (ImageDecoderArgs.split = 3: with entropy "gpu" or "auto", "subsequence" decodes on the device by subsequence and needs no
-        restart intervals), or serialised bytes."""
+        restart intervals) and / or scale_denom 1, 2, 4 or 8 (ImageDecoderArgs.scale_denom = 4: the frames at 1 / scale_denom,
+        (ceil(h / d), ceil(w / d), c), libjpeg's scaled decoding; any other number fails validation), or serialised bytes."""
         from . import _proto
         if isinstance(args, dict):
-            args = _proto.image_decoder_args(args.get("image_type"), args.get("entropy"), args.get("split"))
+            args = _proto.image_decoder_args(args.get("image_type"), args.get("entropy"), args.get("split"), args.get("scale_denom"))
         return _ImageDecoderNode(self.sc, "ImageDecoder", [img], device, batch, args or b"")
 
     def ImageEncoder(self, frame, quality=95, subsampling="4:2:0", restart="row", device=None, batch=None):

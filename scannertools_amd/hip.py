@@ -437,7 +437,7 @@ class HipContext:
         self._check(self._L.st_cvt_color_u8_batch(self._h, tf, n, h, w, c, int(code), int(gray_bits), to))
         return out
 
-    def decode_jpeg(self, streams, out=None, entropy="host", split="interval", subseq_bytes=None, max_rounds=None):
+    def decode_jpeg(self, streams, out=None, entropy="host", split="interval", subseq_bytes=None, max_rounds=None, scale=1):
         """ImageDecoder op (image_decoder_kernel_cpu.cpp:16-29): a list of baseline JPEG streams (bytes) of one shape ->
         (n, h, w, c) uint8 CUDA tensor, c = 3 in R, G, B order or 1; bit-exact to libjpeg's defaults.  The shape is the first
         stream's; a stream of another shape, or one that is refused or malformed, raises StError naming it, and nothing is
@@ -447,7 +447,13 @@ class HipContext:
         entropy="auto": "gpu" when every stream's probe reports a restart interval, else "host".  Same frames either way.
         split="subsequence" (with entropy "gpu" or "auto", which then mean the same): st_jpeg_decode_batch_gpu_split, one lane
         per subsequence of ``subseq_bytes`` raw bytes, at most ``max_rounds`` round launches (None: the library's defaults);
-        streams need no restart intervals.  ``last_jpeg_rounds()`` then tells the round launches the call took."""
+        streams need no restart intervals.  ``last_jpeg_rounds()`` then tells the round launches the call took.
+        scale = 2, 4 or 8 (st_jpeg_decode_batch_scaled): the frames at 1/2, 1/4 or 1/8, (n, ceil(h / scale), ceil(w / scale), c),
+        bit-exact to libjpeg's scaled decoding (cv::IMREAD_REDUCED_COLOR_* / _GRAYSCALE_*, Pillow's draft()); anything but
+        1, 2, 4 or 8 raises ValueError.  It composes with every entropy and split."""
+        if isinstance(scale, bool) or scale not in JPEG_SCALES:
+            raise ValueError("scale must be one of 1, 2, 4, 8, got %r" % (scale,))
+        scale = int(scale)
         if entropy not in JPEG_ENTROPY_MODES:
             raise ValueError("entropy must be one of %s, got %r" % (", ".join(repr(m) for m in JPEG_ENTROPY_MODES), entropy))
         if split not in JPEG_ENTROPY_SPLITS:
@@ -460,19 +466,25 @@ class HipContext:
         if n == 0:
             return torch.zeros((0, 0, 0, 3), dtype=torch.uint8, device=self.device)
         info = probe_jpeg(streams[0])
-        shape = (n, info["h"], info["w"], info["channels"])
+        h, w = info["h"], info["w"]
+        shape = (n,) + jpeg_scaled_size(h, w, scale) + (info["channels"],)
         out = torch.empty(shape, dtype=torch.uint8, device=self.device) if out is None else _check_out(out, shape, torch.uint8, self.device)
         bufs = (ctypes.c_void_p * n)(*[ctypes.cast(ctypes.c_char_p(s), ctypes.c_void_p).value for s in streams])
         sizes = (ctypes.c_size_t * n)(*[len(s) for s in streams])
         to = (ctypes.c_void_p * n)(*[out[i].data_ptr() for i in range(n)])
+        if split != "subsequence" and entropy == "auto":
+            entropy = "gpu" if all(_jpeg_has_restarts(s) for s in streams) else "host"
+        if scale != 1:
+            opts = _native.JpegSplitOpts(int(subseq_bytes or 0), int(max_rounds or 0))
+            mode = 2 if split == "subsequence" else (1 if entropy == "gpu" else 0)   # ST_JPEG_ENTROPY_*
+            self._check(self._L.st_jpeg_decode_batch_scaled(self._h, bufs, sizes, n, h, w, shape[3], scale, mode, ctypes.byref(opts), to))
+            return out
         if split == "subsequence":
             opts = _native.JpegSplitOpts(int(subseq_bytes or 0), int(max_rounds or 0))
-            self._check(self._L.st_jpeg_decode_batch_gpu_split(self._h, bufs, sizes, n, shape[1], shape[2], shape[3], to, ctypes.byref(opts)))
+            self._check(self._L.st_jpeg_decode_batch_gpu_split(self._h, bufs, sizes, n, h, w, shape[3], to, ctypes.byref(opts)))
             return out
-        if entropy == "auto":
-            entropy = "gpu" if all(_jpeg_has_restarts(s) for s in streams) else "host"
         call = self._L.st_jpeg_decode_batch_gpu if entropy == "gpu" else self._L.st_jpeg_decode_batch
-        self._check(call(self._h, bufs, sizes, n, shape[1], shape[2], shape[3], to))
+        self._check(call(self._h, bufs, sizes, n, h, w, shape[3], to))
         return out
 
     def last_jpeg_rounds(self):
@@ -983,6 +995,32 @@ def probe_jpeg(stream):
 
 JPEG_ENTROPY_MODES = ("host", "gpu", "auto")   # decode_jpeg's entropy=; ImageDecoderArgs.entropy HOST = 0, GPU = 1, AUTO = 2
 JPEG_ENTROPY_SPLITS = ("interval", "subsequence")   # decode_jpeg's split=; ImageDecoderArgs.split INTERVAL = 0, SUBSEQUENCE = 1
+
+
+JPEG_SCALES = (1, 2, 4, 8)   # decode_jpeg's scale=; ImageDecoderArgs.scale_denom (0 or absent: 1)
+
+
+def jpeg_scaled_size(h, w, scale):
+    """st_jpeg_scaled_size (host only): (ceil(h / scale), ceil(w / scale)), the frame decode_jpeg(scale=scale) writes for an
+    (h, w) stream.  ValueError: a scale other than 1, 2, 4 or 8, or a size outside 1..65535."""
+    oh, ow = ctypes.c_int(0), ctypes.c_int(0)
+    if isinstance(scale, bool) or scale not in JPEG_SCALES or _native.lib().st_jpeg_scaled_size(int(h), int(w), int(scale), ctypes.byref(oh), ctypes.byref(ow)) != 0:
+        raise ValueError("jpeg_scaled_size(h=%r, w=%r, scale=%r): scale must be 1, 2, 4 or 8 and the size within 1..65535" % (h, w, scale))
+    return oh.value, ow.value
+
+
+def jpeg_scaled_geometry(stream, scale):
+    """st_jpeg_scaled_geometry (host only): per component of the stream its inverse DCT size and the extent of its reduced
+    plane at 1 / scale, as {'S': [...], 'dw': [...], 'dh': [...]} (one entry per channel).  Raises StError on a stream
+    st_jpeg_probe refuses or a scale other than 1, 2, 4 or 8."""
+    data = bytes(stream)
+    info = _native.JpegInfo()
+    S, dw, dh = (ctypes.c_int * 3)(), (ctypes.c_int * 3)(), (ctypes.c_int * 3)()
+    st = _native.lib().st_jpeg_scaled_geometry(data, len(data), int(scale), S, dw, dh, ctypes.byref(info))
+    if st != 0:
+        raise StError(st, info.message.decode(errors="replace"))
+    c = info.channels
+    return {"S": list(S)[:c], "dw": list(dw)[:c], "dh": list(dh)[:c]}
 
 
 def _jpeg_has_restarts(data):

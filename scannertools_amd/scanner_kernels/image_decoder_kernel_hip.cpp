@@ -26,6 +26,11 @@
 // one st_jpeg_decode_batch_gpu_split() call: one lane per fixed-size piece of the entropy-coded bytes, and a row without restart
 // intervals is no error.  SUBSEQUENCE with entropy HOST (or absent) fails validate(), as any other value of split does.
 //
+// ImageDecoderArgs { ..., scale_denom = 4 } (this build's own field too) decodes at 1 / scale_denom: 1, 2, 4 or 8, libjpeg's
+// scaled decoding (cv::IMREAD_REDUCED_COLOR_2 / _4 / _8), and the frame's FrameInfo is (ceil(h / d), ceil(w / d), channels).  Absent
+// or 0 means 1; any other value fails validate().  With 2, 4 or 8 execute() is one st_jpeg_decode_batch_scaled() call standing
+// for whichever of the three calls entropy and split select.
+//
 // The frame shape of an execute() is that of its first element.  Where the reference is undefined this fails instead: an
 // element of another shape (the reference's CPU kernel copies it into a frame of the first one's size, :46-50), and an element
 // that is not a baseline JPEG this library decodes ("Failed to decode image" there) are fatal with the row and the cause.
@@ -43,17 +48,19 @@ namespace scanner {
 namespace {
 enum { ENTROPY_HOST = 0, ENTROPY_GPU = 1, ENTROPY_AUTO = 2 };
 enum { SPLIT_INTERVAL = 0, SPLIT_SUBSEQUENCE = 1 };
-// false: not a message; *image_type: -1 when the field is absent; *entropy: ENTROPY_HOST, *split: SPLIT_INTERVAL when absent
-bool parse_image_decoder_args(const std::vector<u8>& args, int* image_type, long long* entropy, long long* split) {
+// false: not a message; *image_type: -1 when the field is absent; *entropy: ENTROPY_HOST, *split: SPLIT_INTERVAL, *scale: 1 when absent (or 0)
+bool parse_image_decoder_args(const std::vector<u8>& args, int* image_type, long long* entropy, long long* split, long long* scale) {
   std::vector<proto_lite::Field> fields;
   *image_type = -1;
   *entropy = ENTROPY_HOST;
   *split = SPLIT_INTERVAL;
+  *scale = 1;
   if (!proto_lite::parse(args.data(), args.size(), &fields)) return false;
   for (auto& f : fields) {
     if (f.number == 1 && f.wire == 0) *image_type = (int)f.value;
     if (f.number == 2 && f.wire == 0) *entropy = (long long)f.value;
     if (f.number == 3 && f.wire == 0) *split = (long long)f.value;
+    if (f.number == 4 && f.wire == 0) *scale = (int32_t)f.value == 0 ? 1 : (long long)(int32_t)f.value;   // an int32 field
   }
   return true;
 }
@@ -64,8 +71,8 @@ class ImageDecoderKernelHIPImpl : public BatchedKernel {
  public:
   ImageDecoderKernelHIPImpl(const KernelConfig& config) : BatchedKernel(config), core_(config, STAGED), stage_(core_.gpu) {
     int image_type = -1;
-    long long entropy = ENTROPY_HOST, split = SPLIT_INTERVAL;
-    if (!parse_image_decoder_args(config.args, &image_type, &entropy, &split)) RESULT_ERROR(&core_.valid, "ImageDecoder: could not parse ImageDecoderArgs");
+    long long entropy = ENTROPY_HOST, split = SPLIT_INTERVAL, scale = 1;
+    if (!parse_image_decoder_args(config.args, &image_type, &entropy, &split, &scale)) RESULT_ERROR(&core_.valid, "ImageDecoder: could not parse ImageDecoderArgs");
     else if (image_type == 0 || image_type == 2)
       RESULT_ERROR(&core_.valid, "ImageDecoder: image_type %s is not supported (JPEG only)", image_type == 0 ? "PNG" : "ANY");
     else if (image_type != -1 && image_type != 1) RESULT_ERROR(&core_.valid, "ImageDecoder: invalid image_type %d", image_type);
@@ -75,7 +82,10 @@ class ImageDecoderKernelHIPImpl : public BatchedKernel {
       RESULT_ERROR(&core_.valid, "ImageDecoder: invalid split %lld (INTERVAL = 0, SUBSEQUENCE = 1)", split);
     else if (split == SPLIT_SUBSEQUENCE && entropy == ENTROPY_HOST)
       RESULT_ERROR(&core_.valid, "ImageDecoder: split = SUBSEQUENCE decodes on the device: entropy must be GPU or AUTO, not HOST");
+    else if (scale != 1 && scale != 2 && scale != 4 && scale != 8)
+      RESULT_ERROR(&core_.valid, "ImageDecoder: invalid scale_denom %lld (1, 2, 4 or 8)", scale);
     else core_.open("ImageDecoderKernelHIP");
+    scale_ = scale == 2 || scale == 4 || scale == 8 ? (int)scale : 1;
     entropy_ = (int)entropy;
     by_subsequence_ = split == SPLIT_SUBSEQUENCE;
   }
@@ -101,7 +111,9 @@ class ImageDecoderKernelHIPImpl : public BatchedKernel {
       restarts = restarts && info.restart_interval > 0;
     }
     const bool on_gpu = entropy_ == ENTROPY_GPU || (entropy_ == ENTROPY_AUTO && restarts);
-    FrameInfo info(first.h, first.w, first.channels, FrameType::U8);
+    int oh = first.h, ow = first.w;
+    LOG_IF(FATAL, st_jpeg_scaled_size(first.h, first.w, scale_, &oh, &ow) != ST_OK) << "ImageDecoder: no frame size at scale 1/" << scale_;
+    FrameInfo info(oh, ow, first.channels, FrameType::U8);
     std::vector<Frame*> output_frames = new_frames(core_.device, info, n);
     bufs_.resize(n);
     sizes_.resize(n);
@@ -115,7 +127,10 @@ class ImageDecoderKernelHIPImpl : public BatchedKernel {
       output_ptrs(dst_, output_frames);
     }
     st_ctx* ctx = core_.ctx;
-    const int st = by_subsequence_ ? st_jpeg_decode_batch_gpu_split(ctx, bufs_.data(), sizes_.data(), n, first.h, first.w, first.channels, dst_.data(), nullptr)
+    const int st = scale_ != 1 ? st_jpeg_decode_batch_scaled(ctx, bufs_.data(), sizes_.data(), n, first.h, first.w, first.channels, scale_,
+                                                             by_subsequence_ ? ST_JPEG_ENTROPY_SUBSEQUENCE : on_gpu ? ST_JPEG_ENTROPY_INTERVAL : ST_JPEG_ENTROPY_HOST,
+                                                             nullptr, dst_.data())
+                   : by_subsequence_ ? st_jpeg_decode_batch_gpu_split(ctx, bufs_.data(), sizes_.data(), n, first.h, first.w, first.channels, dst_.data(), nullptr)
                    : on_gpu ? st_jpeg_decode_batch_gpu(ctx, bufs_.data(), sizes_.data(), n, first.h, first.w, first.channels, dst_.data())
                           : st_jpeg_decode_batch(ctx, bufs_.data(), sizes_.data(), n, first.h, first.w, first.channels, dst_.data());
     LOG_IF(FATAL, st != ST_OK) << "ImageDecoder: " << st_ctx_last_error(ctx);
@@ -128,6 +143,7 @@ class ImageDecoderKernelHIPImpl : public BatchedKernel {
   KernelCore core_;
   DeviceStage stage_;   // staged: the decoded frames
   int entropy_ = ENTROPY_HOST;
+  int scale_ = 1;
   bool by_subsequence_ = false;
   std::vector<const uint8_t*> bufs_;
   std::vector<size_t> sizes_;

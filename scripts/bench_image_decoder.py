@@ -36,6 +36,16 @@ the streams as Pillow writes them by default (no DRI) beside st_jpeg_decode_batc
 with one restart interval per MCU row beside st_jpeg_decode_batch_gpu (one lane per interval) and the host path.  It reports the
 round launches per call and the lanes per frame.  With --trace it makes three subsequence calls per quality, kind of stream and
 call size and times nothing.
+
+    python scripts/bench_image_decoder.py --scale 1 2 4 8 [--rounds 3]
+    rocprofv3 --kernel-trace --stats -d DIR -- python scripts/bench_image_decoder.py --scale 1 2 4 8 --trace
+
+--scale measures decode_jpeg(scale=d) (st_jpeg_decode_batch_scaled: libjpeg's scaled decoding, frames of ceil(1080 / d) x
+ceil(1920 / d)) for every denominator given, in one process, on the quality-75 pictures with one restart interval per MCU row:
+calls of 32 and 256 frames on the host path (ST_JPEG_THREADS=16) and on the interval path, frames/s end to end (synchronised) as
+the median and range of three medians of --rounds calls, and the ST_K_JPEG bracket per frame.  Denominator 1 is the yardstick:
+code the scale does not touch.  With 4 among them it also times decode + Resize to the 1/4 size beside decode(scale=4), for the
+reader only (the two do not produce the same pixels).  With --trace it makes three calls per denominator, path and call size.
 """
 import argparse
 import ctypes
@@ -197,6 +207,76 @@ def split_subsequence(args, Image):
     print(json.dumps(result))
 
 
+def scaled(args, Image):
+    import torch
+    from scannertools_amd import _native
+    from scannertools_amd.hip import HipContext, jpeg_scaled_size
+    os.environ["ST_JPEG_THREADS"] = "16"
+    ctx = HipContext(0)
+    quality = 75
+    result = {"bench": "image_decoder_scale", "h": H, "w": W, "sampling": "4:2:0", "quality": quality, "restart": "one interval per MCU row",
+              "host_threads": 16, "calls_per_median": args.rounds, "scales": {}}
+    streams = []
+    for s in make_streams(Image, quality):
+        buf = io.BytesIO()
+        Image.open(io.BytesIO(s)).save(buf, "JPEG", quality=quality, subsampling="4:2:0", restart_marker_rows=1)
+        streams.append(buf.getvalue())
+    result["stream_bytes"] = int(statistics.mean(len(s) for s in streams))
+    paths = (("host", dict()), ("interval", dict(entropy="gpu")))
+    for d in args.scale:
+        oh, ow = jpeg_scaled_size(H, W, d)
+        out = torch.empty((max(GPU_BATCHES), oh, ow, 3), dtype=torch.uint8, device=ctx.device)
+        im = Image.open(io.BytesIO(streams[0]))
+        if d > 1:
+            im.draft("RGB", (W // d, H // d))
+        want = np.asarray(im)
+        assert want.shape == (oh, ow, 3)
+
+        def call(n, kw):
+            ctx.decode_jpeg([streams[i % DISTINCT] for i in range(n)], out=out[:n], scale=d, **kw)
+            ctx.sync()
+
+        r = {"frame": [oh, ow, 3]}
+        for path, kw in paths:
+            call(1, kw)
+            assert np.array_equal(out[0].cpu().numpy(), want), "decode at 1/%d differs from Pillow (%s)" % (d, path)
+            if args.trace:
+                for n in GPU_BATCHES:
+                    for _ in range(3):
+                        call(n, kw)
+                continue
+            fps, kms = {}, {}
+            for n in GPU_BATCHES:
+                runs = [rate(lambda: call(n, kw), n, args.rounds) for _ in range(3)]     # three medians: the run-to-run range
+                fps["batch%d" % n] = {"median": round(statistics.median(runs), 1), "min": round(min(runs), 1), "max": round(max(runs), 1)}
+            ctx.timing_enable([_native.K_JPEG])
+            for n in GPU_BATCHES:
+                call(n, kw)
+                ctx.timing_reset()
+                for _ in range(args.rounds):
+                    call(n, kw)
+                _, ms = ctx.timing_read(_native.K_JPEG)
+                kms["batch%d" % n] = round(ms / (args.rounds * n), 4)
+            ctx.timing_enable([])
+            r[path + "_fps"], r[path + "_bracket_ms_per_frame"] = fps, kms
+        if d == 4 and not args.trace:
+            # what a pipeline without the scale does for the same size: the full decode, then Resize
+            full = torch.empty((32, H, W, 3), dtype=torch.uint8, device=ctx.device)
+            small = torch.empty((32, oh, ow, 3), dtype=torch.uint8, device=ctx.device)
+
+            def decode_resize():
+                ctx.decode_jpeg([streams[i % DISTINCT] for i in range(32)], out=full)
+                ctx.resize(full, ow, oh, out=small)
+                ctx.sync()
+
+            runs = [rate(decode_resize, 32, args.rounds) for _ in range(3)]
+            r["decode_then_resize_host_fps_batch32"] = {"median": round(statistics.median(runs), 1), "min": round(min(runs), 1), "max": round(max(runs), 1)}
+        result["scales"]["1/%d" % d] = r
+        del out
+    ctx.close()
+    print(json.dumps(result))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=5)
@@ -205,11 +285,15 @@ def main():
     ap.add_argument("--split", choices=("interval", "subsequence"), default="interval",
                     help="subsequence: measure st_jpeg_decode_batch_gpu_split beside the interval kernel and the host path")
     ap.add_argument("--subseq-bytes", type=int, default=None, help="with --split subsequence: bytes per lane (default: the library's)")
+    ap.add_argument("--scale", type=int, nargs="+", choices=(1, 2, 4, 8), default=None,
+                    help="measure decode_jpeg(scale=d) for each denominator given, on the host path and the interval path")
     args = ap.parse_args()
     try:
         from PIL import Image
     except ImportError:
         sys.exit("bench_image_decoder.py needs Pillow to make its 1080p streams and as its yardstick")
+    if args.scale:
+        return scaled(args, Image)
     if args.split == "subsequence":
         return split_subsequence(args, Image)
     if args.entropy == "gpu":
