@@ -770,7 +770,8 @@ int st_jpeg_decode_batch_scaled(st_ctx* ctx, const uint8_t* const* bufs_host, co
  * save(quality=q, subsampling=s, restart_marker_rows=1)): SOI, JFIF APP0, DQT luma, DQT chroma, SOF0, four DHT, DRI (= MCUs
  * per row), SOS, the scan with RST0..7 cycling between MCU rows, EOI.  Three YCbCr components, one interleaved scan, luma
  * sampling h_samp x v_samp = 1x1 (4:4:4), 2x1 (4:2:2) or 2x2 (4:2:0), chroma 1x1.  DESIGN.md section 4.16 restates the
- * arithmetic.  Not written: grayscale or 4-channel frames, optimised Huffman tables, progressive streams, EXIF / ICC.
+ * arithmetic.  Optimised Huffman tables are opt-in (st_jpeg_encode_batch_opt below).  Not written: grayscale or 4-channel frames, progressive
+ * streams, EXIF / ICC.
  *
  * Host only (no context, no GPU), re-entrant: */
 /* The quantisation tables of `quality` (1..100) in natural (row-major) order: the Annex K tables scaled as libjpeg's
@@ -815,6 +816,45 @@ int st_jpeg_encode_header_rst(int h, int w, int quality, int h_samp, int v_samp,
  * coded block is the same. */
 int st_jpeg_encode_batch_rst(st_ctx* ctx, const uint8_t* const* frames_dev, int n, int h, int w, int quality, int h_samp, int v_samp,
                              int restart);
+
+/* ---- ImageEncoder with optimised Huffman tables ----
+ * libjpeg's optimize_coding (Pillow: optimize=True; cjpeg -optimize): each frame's four Huffman tables are built from the
+ * frame's own symbol counts, on the device, and the stream is byte for byte what libjpeg-turbo writes at JDCT_ISLOW with
+ * optimize_coding = TRUE at the same quality, sampling and restart mode.  Only the four DHT segments and the scan coded with
+ * them differ from the streams above.
+ *
+ * Host only, re-entrant: jpeg_gen_optimal_table.  freq: the counts of symbols 0 .. 255 (the reserved pseudo-symbol is added
+ * inside); bits[k]: the codes of k + 1 bits; vals: the *nvals symbols that have a code, by code length, then by value.
+ * ST_ERR_INVALID: a null pointer.  ST_ERR_UNSUPPORTED: a code would have more than 32 bits before the limiting to 16 (counts that
+ * grow like Fibonacci numbers over 34 symbols or more), where libjpeg stops with JERR_HUFF_CLEN_OVERFLOW; bits and vals then
+ * hold a valid table of 9- and 10-bit codes, which is what the device path encodes such a frame with. */
+int st_jpeg_optimal_table(const uint64_t freq[256], uint8_t bits[16], uint8_t vals[256], int* nvals);
+/* Host only: the DHT segment (marker included, 21 + nvals bytes) of the table st_jpeg_optimal_table builds from freq, as table
+ * `table` = 0 DC luma, 1 AC luma, 2 DC chroma, 3 AC chroma (the order of the segments in the stream); *size (may be null) receives
+ * the bytes whenever freq and table are valid; codes (may be null): 16 (DC) or 256 (AC) words (code length << 16) | code by
+ * symbol, 0 for a symbol without a code.  ST_ERR_INVALID: a null freq, another table, buf null or cap too small. */
+int st_jpeg_optimal_dht(const uint64_t freq[256], int table, uint8_t* buf, size_t cap, size_t* size, uint32_t* codes);
+/* Host only: the 4 x 256 symbol counts (tables in the order above) of an (h, w, 3) frame's coefficients in st_jpeg_coefficients'
+ * layout, `cap` int16 behind coef: what jchuff's htest_one_block counts -- the DC category of each block's difference to its
+ * component's previous block, 0xF0 per run of 16 zeros, (run << 4) | size per non-zero coefficient, 0x00 where a block ends in
+ * zeros --, the DC predictors reset at each MCU row for ST_JPEG_RESTART_ROW and kept for ST_JPEG_RESTART_NONE.  The CPU twin of
+ * k_jpeg_sym_stats.  Refusals as st_jpeg_encode_header_rst; too few coefficients or a null pointer is ST_ERR_INVALID. */
+int st_jpeg_symbol_stats(const int16_t* coef, size_t cap, int h, int w, int h_samp, int v_samp, int restart, uint64_t freq[1024]);
+/* st_jpeg_encode_bound for streams written with optimize = 1: 418 bytes per coded block (any table of codes up to 16 bits: 1665
+ * bits at most, every byte stuffed); the header is never longer than the 629 bytes (at most 12 DC and 162 AC symbols occur). */
+long long st_jpeg_encode_bound_opt(int h, int w, int h_samp, int v_samp);
+/* st_jpeg_encode_batch_rst with `optimize`.  0: that call exactly -- the same launches, bytes and messages.  1: two launches
+ * more between the transform and the entropy coder -- k_jpeg_sym_stats counts each frame's symbols into 4 x 256 64-bit counters
+ * (zeroed by the call), k_jpeg_opt_tables builds each frame's tables, code words and header -- six launches for
+ * ST_JPEG_RESTART_ROW and seven for ST_JPEG_RESTART_NONE, with no host wait between them.  Any other `optimize` is
+ * ST_ERR_INVALID, the message naming the value, before anything is launched or uploaded.  st_jpeg_encode_fetch serves the call.
+ * Device memory: 128 bytes of coefficients and 2 x 418 bytes of stream space per coded block, 11 KiB per frame. */
+int st_jpeg_encode_batch_opt(st_ctx* ctx, const uint8_t* const* frames_dev, int n, int h, int w, int quality, int h_samp, int v_samp,
+                             int restart, int optimize);
+/* The symbol counts of the context's last st_jpeg_encode_batch_opt(optimize = 1) call, for tests and tools: n x 1024 counters
+ * (st_jpeg_symbol_stats' layout per frame) into freq[0, cap).  One wait for the kernels.  ST_ERR_INVALID: no such call to fetch
+ * from, freq null, cap < n x 1024. */
+int st_jpeg_encode_fetch_stats(st_ctx* ctx, uint64_t* freq, size_t cap);
 
 #ifdef __cplusplus
 }

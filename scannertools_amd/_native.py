@@ -209,6 +209,12 @@ SIGNATURES = {
     "st_jpeg_encode_fetch": (_i, [_vp, _c.POINTER(_vp), _c.POINTER(_sz), _sz]),
     "st_jpeg_encode_header_rst": (_i, [_i, _i, _i, _i, _i, _i, _vp, _sz, _c.POINTER(_sz)]),
     "st_jpeg_encode_batch_rst": (_i, [_vp, _c.POINTER(_vp), _i, _i, _i, _i, _i, _i, _i]),
+    "st_jpeg_optimal_table": (_i, [_vp, _vp, _vp, _c.POINTER(_i)]),
+    "st_jpeg_optimal_dht": (_i, [_vp, _i, _vp, _sz, _c.POINTER(_sz), _vp]),
+    "st_jpeg_symbol_stats": (_i, [_vp, _sz, _i, _i, _i, _i, _i, _vp]),
+    "st_jpeg_encode_bound_opt": (ctypes.c_longlong, [_i, _i, _i, _i]),
+    "st_jpeg_encode_batch_opt": (_i, [_vp, _c.POINTER(_vp), _i, _i, _i, _i, _i, _i, _i, _i]),
+    "st_jpeg_encode_fetch_stats": (_i, [_vp, _vp, _sz]),
 }
 
 _LIB = None
@@ -227,7 +233,7 @@ def source_hash():
     import hashlib
     srcs = ["st_context.hip", "st_hist.hip", "st_farneback.hip", "st_flowvis.hip", "st_imgproc.hip", "st_pose.hip", "st_conv.hip",
             "st_conv_tile_bf16x3.hip", "st_conv_tile_f32.hip", "st_framestats.hip", "st_jpeg.hip", "st_netinput.hip", "st_nn.hip", "st_detect.hip", "st_jpeg_enc.hip", "st_jpeg_entropy.hip", "st_jpeg_subseq.hip", "st_jpeg_reduced.hip", "st_jpeg_parse.cpp", "st_jpeg_enc_host.cpp", "st_internal.h",
-            "st_conv_tile.h", "st_jpeg_parse.h", "st_jpeg_enc_host.h", "st_jpeg_entropy.h", "st_jpeg_dense.h",
+            "st_conv_tile.h", "st_jpeg_parse.h", "st_jpeg_enc_host.h", "st_jpeg_entropy.h", "st_jpeg_dense.h", "st_jpeg_enc_opt.h",
             os.path.join("..", "..", "include", "scannertools_hip.h"), "Makefile"]
     hsh = hashlib.sha256()
     for f in srcs:

@@ -160,10 +160,13 @@ def parse_image_decoder_args(buf):
 ENCODER_RESTARTS = {"MCU_ROW": 0, "NONE": 1}   # ImageEncoderArgs.Restart
 
 
-def image_encoder_args(quality=0, subsampling="", restart=0):
+def image_encoder_args(quality=0, subsampling="", restart=0, optimize=False):
     """A serialised ImageEncoderArgs (scannertools_imgproc_amd.proto): quality = 1, subsampling = 2, restart = 3 (a number, or
-    "mcu_row" / "none" in either case).  The defaults (0, "", MCU_ROW = 0) are not written, as proto3 does; the op then takes
-    quality 95, "4:2:0" and one restart interval per MCU row."""
+    "mcu_row" / "none" in either case), optimize = 4 (False / True, or a number: any other than 0 / 1 fails the op's
+    validation).  The defaults (0, "", MCU_ROW = 0, false) are not written, as proto3 does; the op then takes quality 95,
+    "4:2:0", one restart interval per MCU row and the Annex K Huffman tables."""
+    if isinstance(optimize, str) or optimize is None or not isinstance(optimize, (bool, int)):
+        raise ValueError("optimize must be False, True or a number, got %r" % (optimize,))
     if isinstance(restart, str):
         if restart.upper() not in ENCODER_RESTARTS:
             raise ValueError("restart must be one of 'mcu_row', 'none' or a number, got %r" % (restart,))
@@ -171,12 +174,14 @@ def image_encoder_args(quality=0, subsampling="", restart=0):
     out = encode([(1, "int32", int(quality)), (2, "string", subsampling or "")])
     if int(restart) != 0:
         out += _varint(3 << 3 | 0) + _varint(int(restart) & ((1 << 64) - 1))
+    if int(optimize) != 0:
+        out += _varint(4 << 3 | 0) + _varint(int(optimize) & ((1 << 64) - 1))
     return out
 
 
 def parse_image_encoder_args(buf):
-    """{'quality': int, 'subsampling': str, 'restart': name or number} of a serialised ImageEncoderArgs; an absent field is left
-    out."""
+    """{'quality': int, 'subsampling': str, 'restart': name or number, 'optimize': bool or number} of a serialised
+    ImageEncoderArgs; an absent field is left out."""
     names = {v: k for k, v in ENCODER_RESTARTS.items()}
     out = {}
     for number, wt, value in fields(buf):
@@ -187,6 +192,9 @@ def parse_image_encoder_args(buf):
         elif number == 3 and wt == 0:
             value = value - (1 << 64) if value >> 63 else value
             out["restart"] = names.get(value, value)
+        elif number == 4 and wt == 0:
+            value = value - (1 << 64) if value >> 63 else value
+            out["optimize"] = bool(value) if value in (0, 1) else value
     return out
 
 

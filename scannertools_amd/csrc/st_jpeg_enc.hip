@@ -28,12 +28,22 @@
 //   k_jpeg_layout<false>    as above over the rows' stuffed lengths, nothing between rows, EOI at the end
 //   k_jpeg_pack_bits        one workgroup per MCU row: header, the owned bytes shifted into place, completed from the next row
 //                           (or with 1-bits) and stuffed, EOI
+//
+// st_jpeg_encode_batch_opt(..., optimize = 1) codes each frame with Huffman tables built from its own symbol counts, libjpeg's
+// optimize_coding: two launches more, between the transform and the entropy coder, and no host wait:
+//   k_jpeg_sym_stats        one wave per MCU row walks each block once and counts the symbols code_block will emit, per frame
+//   k_jpeg_opt_tables       one workgroup per frame, one wave per table: jpeg_gen_optimal_table (st_jpeg_enc_opt.h), the frame's
+//                           code words, its four DHT segments in its own header, the header's length
+// The kernels above then run as their <.., OPT = true> instances: the frame's table and header instead of the call's, 1665 bits
+// per block instead of 1660, and for streams without markers the ownership rule for rows as short as 6 bits (following_bits()).
+// With optimize = 0 the <.., false> instances run, which are the kernels as they were.
 #include <climits>
 #include <cstring>
 #include <vector>
 
 #include "st_internal.h"
 #include "st_jpeg_enc_host.h"
+#include "st_jpeg_enc_opt.h"
 
 struct st_jpeg_enc_state {
   // device: the header bytes at 0, the Huffman code words at kParamsHuff; what they were built for
@@ -50,6 +60,10 @@ struct st_jpeg_enc_state {
   uint8_t* pin = nullptr;
   size_t pin_cap = 0;
   std::vector<unsigned long long> offs_host;
+  // optimize = 1: each frame's 4 x 256 symbol counts, kept for st_jpeg_encode_fetch_stats
+  unsigned long long* stats = nullptr;
+  size_t stats_cap = 0;
+  int stats_n = -1;   // frames of the last call with optimised tables; -1: none
 };
 
 void st_jpeg_enc_release(st_ctx* ctx) {
@@ -58,6 +72,7 @@ void st_jpeg_enc_release(st_ctx* ctx) {
   if (s->params) (void)hipFree(s->params);
   if (s->blob) (void)hipFree(s->blob);
   if (s->offs) (void)hipFree(s->offs);
+  if (s->stats) (void)hipFree(s->stats);
   if (s->pin) (void)hipHostFree(s->pin);
   delete s;
   ctx->jpeg_enc = nullptr;
@@ -213,19 +228,23 @@ __global__ __launch_bounds__(256) void k_jpeg_fdct(EncTransformK a) {
 
 // ---- entropy coding -------------------------------------------------------------------------------------------------------
 constexpr int kChunk = 64;                                                     // blocks per pass of the wave, one per lane
-constexpr int kRawBits = kChunk * kJpegEncBlockBits + 7 + 7;                   // carried-in bits in front, padding behind
-constexpr int kRawWords = (kRawBits + 31) / 32 + 1;
-constexpr int kOutBytes = ((kRawBits + 7) / 8) * 2;                            // every byte stuffed
+// OPT: the frame's own tables, whose codes may all have 16 bits: 1665 bits per block instead of 1660
+template <bool OPT>
+struct EncBuf {
+  static constexpr int kRawBits = kChunk * (OPT ? kJpegEncBlockBitsOpt : kJpegEncBlockBits) + 7 + 7;   // carried-in bits in front, padding behind
+  static constexpr int kRawWords = (kRawBits + 31) / 32 + 1;
+  static constexpr int kOutBytes = ((kRawBits + 7) / 8) * 2;                   // every byte stuffed
+};
 constexpr int kCoefPitch = 33;                                                 // dwords per lane: 32 of coefficients + 1 against bank conflicts
 
 struct EncEntropyK {
   const int16_t* coef;
-  const uint32_t* huff;
+  const uint32_t* huff;   // OPT: kJpegEncHuffWords per frame
   uint8_t* slots;
   unsigned* ilen;
   size_t slot_bytes;
   int nblk, bpm, nluma;
-  int mrows;   // RESTART false: MCU rows per frame
+  int mrows;   // MCU rows per frame
 };
 
 // nb bits (the low ones of val) at bit p of the stream; bit 0 of the stream is the top bit of raw[0]
@@ -304,15 +323,18 @@ __device__ __forceinline__ unsigned raw_byte(const uint32_t* raw, int j) { retur
 // take their DC predecessors from the last MCU of the row above in the same frame -- the coefficient buffer holds it, rows of a
 // frame one after the other, so no workgroup depends on another --, nothing is padded with 1-bits or stuffed, the bits go to the
 // slot with a zero-filled last byte, and ilen receives the row's length in BITS (at most 49 152 blocks x 1660 bits < 2^32).
-template <bool RESTART>
+// OPT: the code words are the frame's own (k_jpeg_opt_tables), any code may have 16 bits, and the buffers hold 1665 bits per block.
+template <bool RESTART, bool OPT = false>
 __global__ __launch_bounds__(64) void k_jpeg_entropy(EncEntropyK a) {
+  constexpr int kRawWords = EncBuf<OPT>::kRawWords, kOutBytes = EncBuf<OPT>::kOutBytes;
   __shared__ uint32_t s_huff[kJpegEncHuffWords];
   __shared__ uint32_t s_coef[kChunk * kCoefPitch];
   __shared__ uint32_t s_raw[kRawWords];
   __shared__ uint8_t s_out[kOutBytes];
   const int lane = threadIdx.x;
   const size_t iv = blockIdx.x;
-  for (int i = lane; i < kJpegEncHuffWords; i += 64) s_huff[i] = a.huff[i];
+  const uint32_t* __restrict__ huff = OPT ? a.huff + (iv / (size_t)a.mrows) * kJpegEncHuffWords : a.huff;   // the frame's table, or the call's
+  for (int i = lane; i < kJpegEncHuffWords; i += 64) s_huff[i] = huff[i];
   const int16_t* __restrict__ C = a.coef + iv * (size_t)a.nblk * 64;
   uint8_t* __restrict__ slot = a.slots + iv * a.slot_bytes;
   uint32_t* mine = s_coef + lane * kCoefPitch;
@@ -402,11 +424,12 @@ struct EncLayoutK {
   const unsigned* ilen;
   u64* ioff;    // per interval: its offset in its stream
   u64* offs;    // n + 1: each stream's offset in the packed buffer, then the total
+  const unsigned* hlen;   // OPT: each frame's header bytes
   int n, mrows;
 };
 
 // RESTART false: ilen holds the stuffed bytes each MCU row owns (k_jpeg_ff_count); nothing stands between them, EOI ends the stream
-template <bool RESTART>
+template <bool RESTART, bool OPT = false>
 __global__ __launch_bounds__(1024) void k_jpeg_layout(EncLayoutK a) {
   __shared__ u64 part[1024];
   const int tid = threadIdx.x;
@@ -414,7 +437,7 @@ __global__ __launch_bounds__(1024) void k_jpeg_layout(EncLayoutK a) {
   const long long f0 = tid * per < a.n ? tid * per : a.n, f1 = f0 + per < a.n ? f0 + per : a.n;
   u64 sum = 0;
   for (long long f = f0; f < f1; ++f) {
-    u64 o = RESTART ? kJpegEncHeaderBytes : kJpegEncHeaderBytesNoRst;
+    u64 o = OPT ? (u64)a.hlen[f] : RESTART ? kJpegEncHeaderBytes : kJpegEncHeaderBytesNoRst;
     for (int r = 0; r < a.mrows; ++r) {
       const size_t iv = (size_t)f * a.mrows + r;
       a.ioff[iv] = o;
@@ -449,19 +472,24 @@ struct EncPackK {
   const unsigned* ilen;
   const u64* ioff;
   const u64* offs;
-  const uint8_t* header;
+  const uint8_t* header;   // OPT: kJpegEncHeaderStride bytes per frame, hlen[f] of them written
+  const unsigned* hlen;
   uint8_t* blob;
   size_t slot_bytes;
   int mrows;
 };
 
+template <bool OPT = false>
 __global__ __launch_bounds__(256) void k_jpeg_pack(EncPackK a) {
   const size_t iv = blockIdx.x;
   const size_t f = iv / (size_t)a.mrows;
   const int r = (int)(iv - f * (size_t)a.mrows);
   uint8_t* __restrict__ dst = a.blob + a.offs[f];
-  if (r == 0)
-    for (int j = threadIdx.x; j < (int)kJpegEncHeaderBytes; j += 256) dst[j] = a.header[j];
+  if (r == 0) {
+    const uint8_t* __restrict__ hd = OPT ? a.header + f * kJpegEncHeaderStride : a.header;
+    const int hb = OPT ? (int)a.hlen[f] : (int)kJpegEncHeaderBytes;
+    for (int j = threadIdx.x; j < hb; j += 256) dst[j] = hd[j];
+  }
   const uint8_t* __restrict__ src = a.slots + iv * a.slot_bytes;
   const unsigned len = a.ilen[iv];
   uint8_t* __restrict__ d = dst + a.ioff[iv];
@@ -488,11 +516,38 @@ struct EncMergeK {
   unsigned* slen;         // per row: the bytes it owns, stuffed zeros included
   const u64* ioff;
   const u64* offs;
-  const uint8_t* header;
+  const uint8_t* header;   // OPT: kJpegEncHeaderStride bytes per frame, hlen[f] of them written
+  const unsigned* hlen;
   uint8_t* blob;
   size_t slot_bytes, blob_bytes;
   int mrows;
 };
+
+// With a frame's own tables (OPT) a block may have as few as 2 bits -- a DC code of 1 bit or more and an EOB of 1 bit or more,
+// or an AC symbol and its magnitude bit -- so a row has at least 6 bits at 4:4:4, 8 at 4:2:2, 12 at 4:2:0, and "one next row is
+// enough" no longer holds: a byte can hold bits of three rows, a row can lie inside a byte an earlier row owns and own NO byte
+// (count == 0), and the frame's padding can fall into a byte that a row before the last owns.  The ownership rule itself does
+// not depend on the lengths: every byte of the scan starts in exactly one row (the rows tile the scan's bits, and the byte whose
+// first bit is past the last row does not exist), that row is its one writer, and of a row's owned bytes only the last can reach
+// past the row's end (the byte before it ends where the last begins, inside the row), by at most 7 bits.  Those bits are what
+// FOLLOWS the row in the frame's scan: the leading bits of the next rows, as many rows as it takes -- two suffice, 6 + 6 >= 7,
+// but the loop below asks only that a row has at least 1 bit and ends at the frame's last row at the latest --, then the 1-bits
+// of the padding.  Each next row's contribution is read from its slot's first byte, whose bits past the row's end are zeros.
+// All of it is the entropy launch's finished output, so still no workgroup waits for another.
+__device__ __forceinline__ unsigned following_bits(const EncMergeK& a, size_t iv, int r) {   // the 8 bits after row r, first bit on top
+  unsigned tail = 0;
+  int got = 0;
+  for (int rr = r + 1; rr < a.mrows && got < 8; ++rr) {
+    ++iv;
+    const unsigned L = a.bits[iv];
+    int take = 8 - got;
+    take = (unsigned)take > L ? (int)L : take;
+    if (take > 0) tail |= (((unsigned)a.slots[iv * a.slot_bytes] >> (8 - take)) << (8 - got - take)) & 0xffu;
+    got += take;
+  }
+  if (got < 8) tail |= (1u << (8 - got)) - 1u;   // past the frame's last row: the padding
+  return tail;
+}
 
 struct OwnedBytes {
   const uint8_t* slot;
@@ -500,9 +555,10 @@ struct OwnedBytes {
   unsigned nvalid;  // bytes of the slot that were written: ceil(L / 8)
   unsigned count;   // owned bytes
   unsigned sh;
-  unsigned tail;    // what follows the row: the next row's first byte, or 0xFF after the frame's last
+  unsigned tail;    // what follows the row: the next row's first byte, or 0xFF after the frame's last; OPT: following_bits()
 };
 
+template <bool OPT>
 __device__ __forceinline__ OwnedBytes owned_bytes(const EncMergeK& a, size_t iv, int r, u64 B) {
   OwnedBytes o;
   o.slot = a.slots + iv * a.slot_bytes;
@@ -511,7 +567,8 @@ __device__ __forceinline__ OwnedBytes owned_bytes(const EncMergeK& a, size_t iv,
   const u64 first = (B + 7) >> 3;
   o.count = (unsigned)(((B + o.bits + 7) >> 3) - first);
   o.sh = (unsigned)(first * 8 - B);
-  o.tail = r == a.mrows - 1 ? 0xffu : a.slots[(iv + 1) * a.slot_bytes];
+  if (OPT) o.tail = following_bits(a, iv, r);
+  else o.tail = r == a.mrows - 1 ? 0xffu : a.slots[(iv + 1) * a.slot_bytes];
   return o;
 }
 
@@ -537,6 +594,7 @@ __device__ __forceinline__ u64 block_sum(u64 v, u64* red) {   // 256 threads
 
 // One workgroup per MCU row: its bit offset in the frame's scan (the lengths above it summed; at most 8192 rows) and the
 // number of bytes it owns, a zero after every 0xFF among them counted in.
+template <bool OPT = false>
 __global__ __launch_bounds__(256) void k_jpeg_ff_count(EncMergeK a) {
   __shared__ u64 red[256];
   const size_t iv = blockIdx.x;
@@ -545,7 +603,7 @@ __global__ __launch_bounds__(256) void k_jpeg_ff_count(EncMergeK a) {
   u64 part = 0;
   for (int i = threadIdx.x; i < r; i += 256) part += a.bits[f * (size_t)a.mrows + i];
   const u64 B = block_sum(part, red);
-  const OwnedBytes o = owned_bytes(a, iv, r, B);
+  const OwnedBytes o = owned_bytes<OPT>(a, iv, r, B);
   u64 ff = 0;
   for (unsigned j = threadIdx.x; j < o.count; j += 256) ff += owned_byte(o, j) == 0xffu;
   ff = block_sum(ff, red);
@@ -557,6 +615,7 @@ __global__ __launch_bounds__(256) void k_jpeg_ff_count(EncMergeK a) {
 
 // One workgroup per MCU row: the header (the frame's first row), the row's owned bytes with their stuffed zeros -- computed
 // again, 256 at a time, a ballot and a prefix over the four waves placing them --, EOI after the frame's last row.
+template <bool OPT = false>
 __global__ __launch_bounds__(256) void k_jpeg_pack_bits(EncMergeK a) {
   __shared__ unsigned s_w[4];
   const size_t iv = blockIdx.x;
@@ -566,10 +625,13 @@ __global__ __launch_bounds__(256) void k_jpeg_pack_bits(EncMergeK a) {
   const u64 at = a.offs[f];
   const u64 room = at < a.blob_bytes ? a.blob_bytes - at : 0;   // every store below stays inside the blob
   uint8_t* __restrict__ dst = a.blob + at;
-  if (r == 0)
-    for (int j = tid; j < (int)kJpegEncHeaderBytesNoRst; j += 256)
-      if ((u64)j < room) dst[j] = a.header[j];
-  const OwnedBytes o = owned_bytes(a, iv, r, a.bitoff[iv]);
+  if (r == 0) {
+    const uint8_t* __restrict__ hd = OPT ? a.header + f * kJpegEncHeaderStride : a.header;
+    const int hb = OPT ? (int)a.hlen[f] : (int)kJpegEncHeaderBytesNoRst;
+    for (int j = tid; j < hb; j += 256)
+      if ((u64)j < room) dst[j] = hd[j];
+  }
+  const OwnedBytes o = owned_bytes<OPT>(a, iv, r, a.bitoff[iv]);
   const u64 base = a.ioff[iv];
   unsigned ff_run = 0;
   for (unsigned t0 = 0; t0 < o.count; t0 += 256) {
@@ -600,6 +662,134 @@ __global__ __launch_bounds__(256) void k_jpeg_pack_bits(EncMergeK a) {
   }
 }
 
+// ---- optimised Huffman tables: each frame's symbol counts and the tables built from them ---------------------
+struct EncStatsK {
+  const int16_t* coef;
+  u64* freq;   // per frame kJpegOptTables x 256 counters, zeroed by the call before this launch
+  int nblk, bpm, nluma, mrows;
+};
+
+// One wave per MCU row, the work unit and block numbering of k_jpeg_entropy: each lane walks its block once and counts the
+// symbols code_block would emit (st_jpeg_opt_block_symbols) in the workgroup's 4 x 256 LDS counters -- 32 bits are plenty for a
+// row: at most 49 152 blocks of 64 symbols --, which are then added to the frame's 64-bit counters.  Integer adds: the sums do
+// not depend on the order.  RESTART false: the row's first blocks take their DC predecessor from the row above.
+template <bool RESTART>
+__global__ __launch_bounds__(64) void k_jpeg_sym_stats(EncStatsK a) {
+  __shared__ uint32_t s_coef[kChunk * kCoefPitch];
+  __shared__ unsigned s_hist[kJpegOptTables * 256];
+  const int lane = threadIdx.x;
+  const size_t iv = blockIdx.x;
+  for (int i = lane; i < kJpegOptTables * 256; i += 64) s_hist[i] = 0;
+  const int16_t* __restrict__ C = a.coef + iv * (size_t)a.nblk * 64;
+  uint32_t* mine = s_coef + lane * kCoefPitch;
+  const int floor_blk = !RESTART && iv % (size_t)a.mrows != 0 ? -a.bpm : 0;
+  __syncthreads();
+  for (int b0 = 0; b0 < a.nblk; b0 += kChunk) {
+    const int b = b0 + lane;
+    if (b < a.nblk) {
+      const uint4* __restrict__ src = reinterpret_cast<const uint4*>(C + (size_t)b * 64);
+#pragma unroll
+      for (int s = 0; s < 8; ++s) {
+        const uint4 t = src[s];
+        mine[4 * s] = t.x; mine[4 * s + 1] = t.y; mine[4 * s + 2] = t.z; mine[4 * s + 3] = t.w;
+      }
+      const int k = b % a.bpm;
+      const bool luma = k < a.nluma;
+      const int prev = luma ? (k > 0 ? b - 1 : b - a.bpm + a.nluma - 1) : b - a.bpm;
+      const int diff = (int)C[(size_t)b * 64] - (prev >= floor_blk ? (int)C[(ptrdiff_t)prev * 64] : 0);
+      unsigned* hist = s_hist + (luma ? 0 : 2 * 256);   // the component's DC table; its AC table follows
+      st_jpeg_opt_block_symbols(
+          [mine](int p) {
+            const uint32_t wd = mine[p >> 1];
+            return (int)(short)((p & 1) ? (wd >> 16) : (wd & 0xffffu));
+          },
+          diff, [hist](int ac, int sym) { atomicAdd(&hist[ac * 256 + (sym & 255)], 1u); });
+    }
+  }
+  __syncthreads();
+  u64* __restrict__ F = a.freq + (iv / (size_t)a.mrows) * (size_t)(kJpegOptTables * 256);
+  for (int i = lane; i < kJpegOptTables * 256; i += 64) {
+    const unsigned c = s_hist[i];
+    if (c) atomicAdd(&F[i], (u64)c);
+  }
+}
+
+struct EncTablesK {
+  const u64* freq;
+  const uint8_t* fixed;   // the call's header with the Annex K tables: its prefix and what follows its DHT segments are copied
+  uint32_t* huff;         // per frame kJpegEncHuffWords code words
+  uint8_t* headers;       // per frame kJpegEncHeaderStride bytes
+  unsigned* hlen;         // per frame: the header's bytes
+  unsigned fixed_bytes;   // 623 or 629
+};
+
+__device__ __forceinline__ void wave_least(const uint64_t* freq, int lane, int exclude, int* idx) {
+  // 257 entries over 64 lanes, 5 each (the last lanes none); then a butterfly whose every step keeps the better candidate --
+  // the rule is a total order on (frequency, index), so all lanes end on the serial search's choice, ties included
+  const int lo = lane * 5 < kJpegOptSymbols ? lane * 5 : kJpegOptSymbols, hi = lo + 5 < kJpegOptSymbols ? lo + 5 : kJpegOptSymbols;
+  uint64_t v;
+  int i = st_jpeg_opt_least(freq, lo, hi, exclude, &v);
+#pragma unroll
+  for (int d = 32; d > 0; d >>= 1) {
+    const uint64_t ov = (uint64_t)__shfl_xor((u64)v, d);
+    const int oi = __shfl_xor(i, d);
+    if (!st_jpeg_opt_better(v, i, ov, oi)) {
+      v = ov;
+      i = oi;
+    }
+  }
+  *idx = i;
+}
+
+// One workgroup per frame, one wave per table (DC luma, AC luma, DC chroma, AC chroma): the merge loop of
+// jpeg_gen_optimal_table is serial -- at most 256 steps --, the wave shares each step's two searches for the least frequency
+// and lane 0 merges.  The steps are separated by workgroup barriers (the four waves take the same number of trips: until none
+// has two entries left), so nothing relies on the order of LDS accesses inside a wave.  When all four tables are known, their
+// lengths are, and each wave writes its code words and its DHT segment at its place in the frame's header: SOI .. SOF0 from the
+// call's header, DHT x 4, then DRI (MCU_ROW only) and SOS from the call's header.
+__global__ __launch_bounds__(256) void k_jpeg_opt_tables(EncTablesK a) {
+  __shared__ StJpegOptWork s_w[kJpegOptTables];
+  __shared__ uint8_t s_bits[kJpegOptTables][16];
+  __shared__ uint8_t s_vals[kJpegOptTables][256];
+  __shared__ int s_nvals[kJpegOptTables];
+  const size_t f = blockIdx.x;
+  const int lane = threadIdx.x & 63, t = threadIdx.x >> 6;
+  StJpegOptWork* w = &s_w[t];
+  for (int i = lane; i < kJpegOptSymbols; i += 64) st_jpeg_opt_begin(w, i, i < 256 ? a.freq[f * (size_t)(kJpegOptTables * 256) + t * 256 + i] : 1);
+  __syncthreads();
+  for (int step = 0; step < kJpegOptSymbols; ++step) {
+    int c1, c2;
+    wave_least(w->freq, lane, -1, &c1);
+    wave_least(w->freq, lane, c1, &c2);
+    if (!__syncthreads_or(c2 >= 0)) break;   // every search has read before any merge writes; no table has two entries left
+    if (lane == 0 && c2 >= 0) st_jpeg_opt_merge(w->freq, w->codesize, w->others, c1, c2);
+    __syncthreads();
+  }
+  if (lane == 0) {
+    int nv = 0;
+    (void)st_jpeg_opt_lengths(w->codesize, s_bits[t], s_vals[t], &nv);
+    s_nvals[t] = nv;
+    st_jpeg_opt_codes(s_bits[t], s_vals[t], nv, a.huff + f * kJpegEncHuffWords + st_jpeg_opt_tab_off(t), st_jpeg_opt_tab_words(t));
+  }
+  __syncthreads();
+  unsigned off = (unsigned)kJpegEncHeaderPrefix;
+  for (int u = 0; u < t; ++u) off += (unsigned)st_jpeg_opt_dht_bytes(s_nvals[u]);
+  const unsigned mine = (unsigned)st_jpeg_opt_dht_bytes(s_nvals[t]);
+  uint8_t* __restrict__ H = a.headers + f * kJpegEncHeaderStride;
+  // at most 12 DC and 162 AC symbols are ever counted, so off + mine + 20 <= 629; the checks keep the stores inside whatever
+  for (unsigned i = lane; i < mine; i += 64)
+    if (off + i < kJpegEncHeaderStride) H[off + i] = st_jpeg_opt_dht_byte(s_bits[t], s_vals[t], s_nvals[t], st_jpeg_opt_class_id(t), (int)i);
+  if (t == 0)
+    for (unsigned i = lane; i < kJpegEncHeaderPrefix; i += 64) H[i] = a.fixed[i];
+  if (t == kJpegOptTables - 1) {
+    const unsigned end = off + mine, from = (unsigned)kJpegEncHeaderBytesNoRst - 14u;   // where DRI or SOS begins in the call's header
+    const unsigned rest = a.fixed_bytes - from;
+    for (unsigned i = lane; i < rest; i += 64)
+      if (end + i < kJpegEncHeaderStride) H[end + i] = a.fixed[from + i];
+    if (lane == 0) a.hlen[f] = end + rest < kJpegEncHeaderStride ? end + rest : (unsigned)kJpegEncHeaderStride;
+  }
+}
+
 template <class T>
 int grow(st_ctx* ctx, T** p, size_t* cap, size_t want, const char* what) {
   if (want <= *cap) return ST_OK;
@@ -617,17 +807,17 @@ int grow(st_ctx* ctx, T** p, size_t* cap, size_t want, const char* what) {
   return ST_OK;
 }
 
-}  // namespace
-
-ST_EXPORT int st_jpeg_encode_batch_rst(st_ctx* ctx, const uint8_t* const* frames_dev, int n, int h, int w, int quality, int h_samp, int v_samp,
-                                       int restart) {
+// optimize = 0 is st_jpeg_encode_batch_rst as it always was: every `opt` below only adds to it
+int encode_batch(st_ctx* ctx, const uint8_t* const* frames_dev, int n, int h, int w, int quality, int h_samp, int v_samp, int restart, int optimize) {
   ST_TRY(st_enter(ctx));
   if (!ctx->jpeg_enc) ctx->jpeg_enc = new st_jpeg_enc_state();
   st_jpeg_enc_state* s = ctx->jpeg_enc;
   s->n = -1;   // a call that fails leaves nothing to fetch
+  s->stats_n = -1;
   char msg[160];
   if (st_jpeg_enc_check_restart(restart, msg, sizeof msg) != ST_OK) return st_set_error(ctx, ST_ERR_INVALID, "jpeg_encode: %s", msg);
-  const bool rst = restart == ST_JPEG_RESTART_ROW;
+  if (st_jpeg_enc_check_optimize(optimize, msg, sizeof msg) != ST_OK) return st_set_error(ctx, ST_ERR_INVALID, "jpeg_encode: %s", msg);
+  const bool rst = restart == ST_JPEG_RESTART_ROW, opt = optimize == 1;
   if (n < 0) return st_set_error(ctx, ST_ERR_INVALID, "jpeg_encode: n = %d is negative", n);
   const int chk = st_jpeg_enc_check(h, w, quality, h_samp, v_samp, msg, sizeof msg);
   if (chk != ST_OK) return st_set_error(ctx, chk, "jpeg_encode: %s", msg);
@@ -644,8 +834,10 @@ ST_EXPORT int st_jpeg_encode_batch_rst(st_ctx* ctx, const uint8_t* const* frames
   if (intervals > INT_MAX) return st_set_error(ctx, ST_ERR_UNSUPPORTED, "jpeg_encode: %lld restart intervals in one call (at most 2^31 - 1)", intervals);
   const int nblk = g.mcols * g.bpm;
   // without markers a slot holds the row's bits as they are, half of what they could take stuffed
-  const size_t slot_bytes = rst ? st_jpeg_enc_slot_bytes(g) : st_jpeg_enc_raw_slot_bytes(g);
-  const size_t bound = (size_t)st_jpeg_encode_bound(h, w, h_samp, v_samp);
+  // with the frame's own tables a block has up to 1665 bits: 418 / 209 bytes per block instead of 416 / 208
+  const size_t opt_slot = ((size_t)nblk * (rst ? kJpegEncBlockStuffedOpt : kJpegEncBlockBytesOpt) + 15) / 16 * 16;
+  const size_t slot_bytes = opt ? opt_slot : rst ? st_jpeg_enc_slot_bytes(g) : st_jpeg_enc_raw_slot_bytes(g);
+  const size_t bound = (size_t)(opt ? st_jpeg_encode_bound_opt(h, w, h_samp, v_samp) : st_jpeg_encode_bound(h, w, h_samp, v_samp));
 
   // header and code tables, when the call differs from the last one
   const int key[6] = {h, w, quality, h_samp, v_samp, restart};
@@ -665,11 +857,14 @@ ST_EXPORT int st_jpeg_encode_batch_rst(st_ctx* ctx, const uint8_t* const* frames
   }
   ST_TRY(grow(ctx, &s->blob, &s->blob_cap, (size_t)n * bound, "the streams"));
   ST_TRY(grow(ctx, &s->offs, &s->offs_cap, (size_t)n + 1, "the stream offsets"));
+  if (opt) ST_TRY(grow(ctx, &s->stats, &s->stats_cap, (size_t)n * (kJpegOptTables * 256), "the symbol counts"));
 
   const size_t tb = sizeof(void*) * (size_t)n, cb = (size_t)intervals * (size_t)nblk * 128, sb = (size_t)intervals * slot_bytes;
   const size_t lb = sizeof(unsigned) * (size_t)intervals, ob = sizeof(u64) * (size_t)intervals;
+  // the frames' own code words, headers and header lengths
+  const size_t hwb = sizeof(uint32_t) * kJpegEncHuffWords * (size_t)n, hdb = kJpegEncHeaderStride * (size_t)n, hlb = sizeof(unsigned) * (size_t)n;
   ST_TRY(st_ws_reserve(ctx, st_align_up(tb) + st_align_up(cb) + st_align_up(sb) + st_align_up(lb) + st_align_up(ob) +
-                                (rst ? 0 : st_align_up(lb) + st_align_up(ob))));
+                                (rst ? 0 : st_align_up(lb) + st_align_up(ob)) + (opt ? st_align_up(hwb) + st_align_up(hdb) + st_align_up(hlb) : 0)));
   const uint8_t** d_frames = (const uint8_t**)st_ws_alloc(ctx, tb);
   int16_t* d_coef = (int16_t*)st_ws_alloc(ctx, cb);
   uint8_t* d_slots = (uint8_t*)st_ws_alloc(ctx, sb);
@@ -677,7 +872,10 @@ ST_EXPORT int st_jpeg_encode_batch_rst(st_ctx* ctx, const uint8_t* const* frames
   u64* d_ioff = (u64*)st_ws_alloc(ctx, ob);
   unsigned* d_slen = rst ? d_ilen : (unsigned*)st_ws_alloc(ctx, lb);   // without markers: the rows' bits, and their stuffed bytes
   u64* d_bitoff = rst ? d_ioff : (u64*)st_ws_alloc(ctx, ob);
-  if (!d_frames || !d_coef || !d_slots || !d_ilen || !d_ioff || !d_slen || !d_bitoff)
+  uint32_t* d_huff = opt ? (uint32_t*)st_ws_alloc(ctx, hwb) : nullptr;
+  uint8_t* d_headers = opt ? (uint8_t*)st_ws_alloc(ctx, hdb) : nullptr;
+  unsigned* d_hlen = opt ? (unsigned*)st_ws_alloc(ctx, hlb) : nullptr;
+  if (!d_frames || !d_coef || !d_slots || !d_ilen || !d_ioff || !d_slen || !d_bitoff || (opt && (!d_huff || !d_headers || !d_hlen)))
     return st_set_error(ctx, ST_ERR_OOM, "jpeg_encode: workspace exhausted");
   ST_HIP(ctx, hipMemcpyAsync(d_frames, frames_dev, tb, hipMemcpyHostToDevice, ctx->stream));
 
@@ -697,47 +895,101 @@ ST_EXPORT int st_jpeg_encode_batch_rst(st_ctx* ctx, const uint8_t* const* frames
     else hipLaunchKernelGGL((k_jpeg_fdct<2, 2>), grid, dim3(256), 0, ctx->stream, t);
     ST_HIP(ctx, hipGetLastError());
   }
+  if (opt) {
+    // the counters are zeroed on the stream, in front of the launch that adds to them: nothing depends on an earlier call
+    ST_HIP(ctx, hipMemsetAsync(s->stats, 0, sizeof(u64) * (size_t)n * (kJpegOptTables * 256), ctx->stream));
+    EncStatsK c;
+    c.coef = d_coef; c.freq = s->stats; c.nblk = nblk; c.bpm = g.bpm; c.nluma = g.bpm - 2; c.mrows = g.mrows;
+    {
+      st_timed tm(ctx, ST_K_JPEG);
+      if (rst) hipLaunchKernelGGL(k_jpeg_sym_stats<true>, dim3((unsigned)intervals), dim3(64), 0, ctx->stream, c);
+      else hipLaunchKernelGGL(k_jpeg_sym_stats<false>, dim3((unsigned)intervals), dim3(64), 0, ctx->stream, c);
+      ST_HIP(ctx, hipGetLastError());
+    }
+    EncTablesK b;
+    b.freq = s->stats; b.fixed = s->params; b.huff = d_huff; b.headers = d_headers; b.hlen = d_hlen;
+    b.fixed_bytes = (unsigned)st_jpeg_enc_header_bytes(restart);
+    {
+      st_timed tm(ctx, ST_K_JPEG);
+      hipLaunchKernelGGL(k_jpeg_opt_tables, dim3((unsigned)n), dim3(256), 0, ctx->stream, b);
+      ST_HIP(ctx, hipGetLastError());
+    }
+  }
   EncEntropyK e;
-  e.coef = d_coef; e.huff = reinterpret_cast<const uint32_t*>(s->params + kParamsHuff); e.slots = d_slots; e.ilen = d_ilen;
+  e.coef = d_coef; e.huff = opt ? d_huff : reinterpret_cast<const uint32_t*>(s->params + kParamsHuff); e.slots = d_slots; e.ilen = d_ilen;
   e.slot_bytes = slot_bytes; e.nblk = nblk; e.bpm = g.bpm; e.nluma = g.bpm - 2; e.mrows = g.mrows;
   {
     st_timed tm(ctx, ST_K_JPEG);
-    if (rst) hipLaunchKernelGGL(k_jpeg_entropy<true>, dim3((unsigned)intervals), dim3(64), 0, ctx->stream, e);
-    else hipLaunchKernelGGL(k_jpeg_entropy<false>, dim3((unsigned)intervals), dim3(64), 0, ctx->stream, e);
+    const dim3 grid((unsigned)intervals);
+    if (opt && rst) hipLaunchKernelGGL((k_jpeg_entropy<true, true>), grid, dim3(64), 0, ctx->stream, e);
+    else if (opt) hipLaunchKernelGGL((k_jpeg_entropy<false, true>), grid, dim3(64), 0, ctx->stream, e);
+    else if (rst) hipLaunchKernelGGL(k_jpeg_entropy<true>, grid, dim3(64), 0, ctx->stream, e);
+    else hipLaunchKernelGGL(k_jpeg_entropy<false>, grid, dim3(64), 0, ctx->stream, e);
     ST_HIP(ctx, hipGetLastError());
   }
   EncMergeK m;
-  m.slots = d_slots; m.bits = d_ilen; m.bitoff = d_bitoff; m.slen = d_slen; m.ioff = d_ioff; m.offs = s->offs; m.header = s->params;
+  m.slots = d_slots; m.bits = d_ilen; m.bitoff = d_bitoff; m.slen = d_slen; m.ioff = d_ioff; m.offs = s->offs;
+  m.header = opt ? d_headers : s->params; m.hlen = d_hlen;
   m.blob = s->blob; m.slot_bytes = slot_bytes; m.blob_bytes = (size_t)n * bound; m.mrows = g.mrows;
   if (!rst) {
     st_timed tm(ctx, ST_K_JPEG);
-    hipLaunchKernelGGL(k_jpeg_ff_count, dim3((unsigned)intervals), dim3(256), 0, ctx->stream, m);
+    if (opt) hipLaunchKernelGGL(k_jpeg_ff_count<true>, dim3((unsigned)intervals), dim3(256), 0, ctx->stream, m);
+    else hipLaunchKernelGGL(k_jpeg_ff_count<false>, dim3((unsigned)intervals), dim3(256), 0, ctx->stream, m);
     ST_HIP(ctx, hipGetLastError());
   }
   EncLayoutK l;
-  l.ilen = d_slen; l.ioff = d_ioff; l.offs = s->offs; l.n = n; l.mrows = g.mrows;
+  l.ilen = d_slen; l.ioff = d_ioff; l.offs = s->offs; l.hlen = d_hlen; l.n = n; l.mrows = g.mrows;
   {
     st_timed tm(ctx, ST_K_JPEG);
-    if (rst) hipLaunchKernelGGL(k_jpeg_layout<true>, dim3(1), dim3(1024), 0, ctx->stream, l);
+    if (opt && rst) hipLaunchKernelGGL((k_jpeg_layout<true, true>), dim3(1), dim3(1024), 0, ctx->stream, l);
+    else if (opt) hipLaunchKernelGGL((k_jpeg_layout<false, true>), dim3(1), dim3(1024), 0, ctx->stream, l);
+    else if (rst) hipLaunchKernelGGL(k_jpeg_layout<true>, dim3(1), dim3(1024), 0, ctx->stream, l);
     else hipLaunchKernelGGL(k_jpeg_layout<false>, dim3(1), dim3(1024), 0, ctx->stream, l);
     ST_HIP(ctx, hipGetLastError());
   }
   if (!rst) {
     st_timed tm(ctx, ST_K_JPEG);
-    hipLaunchKernelGGL(k_jpeg_pack_bits, dim3((unsigned)intervals), dim3(256), 0, ctx->stream, m);
+    if (opt) hipLaunchKernelGGL(k_jpeg_pack_bits<true>, dim3((unsigned)intervals), dim3(256), 0, ctx->stream, m);
+    else hipLaunchKernelGGL(k_jpeg_pack_bits<false>, dim3((unsigned)intervals), dim3(256), 0, ctx->stream, m);
     ST_HIP(ctx, hipGetLastError());
     s->n = n;
+    if (opt) s->stats_n = n;
     return ST_OK;
   }
   EncPackK p;
-  p.slots = d_slots; p.ilen = d_ilen; p.ioff = d_ioff; p.offs = s->offs; p.header = s->params; p.blob = s->blob;
+  p.slots = d_slots; p.ilen = d_ilen; p.ioff = d_ioff; p.offs = s->offs; p.header = opt ? d_headers : s->params; p.hlen = d_hlen; p.blob = s->blob;
   p.slot_bytes = slot_bytes; p.mrows = g.mrows;
   {
     st_timed tm(ctx, ST_K_JPEG);
-    hipLaunchKernelGGL(k_jpeg_pack, dim3((unsigned)intervals), dim3(256), 0, ctx->stream, p);
+    if (opt) hipLaunchKernelGGL(k_jpeg_pack<true>, dim3((unsigned)intervals), dim3(256), 0, ctx->stream, p);
+    else hipLaunchKernelGGL(k_jpeg_pack<false>, dim3((unsigned)intervals), dim3(256), 0, ctx->stream, p);
     ST_HIP(ctx, hipGetLastError());
   }
   s->n = n;
+  if (opt) s->stats_n = n;
+  return ST_OK;
+}
+
+}  // namespace
+
+ST_EXPORT int st_jpeg_encode_batch_rst(st_ctx* ctx, const uint8_t* const* frames_dev, int n, int h, int w, int quality, int h_samp, int v_samp,
+                                       int restart) {
+  return encode_batch(ctx, frames_dev, n, h, w, quality, h_samp, v_samp, restart, 0);
+}
+
+ST_EXPORT int st_jpeg_encode_batch_opt(st_ctx* ctx, const uint8_t* const* frames_dev, int n, int h, int w, int quality, int h_samp, int v_samp,
+                                       int restart, int optimize) {
+  return encode_batch(ctx, frames_dev, n, h, w, quality, h_samp, v_samp, restart, optimize);
+}
+
+ST_EXPORT int st_jpeg_encode_fetch_stats(st_ctx* ctx, uint64_t* freq, size_t cap) {
+  ST_TRY(st_enter(ctx));
+  st_jpeg_enc_state* s = ctx->jpeg_enc;
+  if (!s || s->stats_n < 0) return st_set_error(ctx, ST_ERR_INVALID, "jpeg_encode_fetch_stats: no st_jpeg_encode_batch_opt call with optimize = 1 to fetch from");
+  const size_t count = (size_t)s->stats_n * (kJpegOptTables * 256);
+  if (!freq || cap < count) return st_set_error(ctx, ST_ERR_INVALID, "jpeg_encode_fetch_stats: %zu counters, room for %zu", count, freq ? cap : (size_t)0);
+  ST_HIP(ctx, hipMemcpyAsync(freq, s->stats, sizeof(uint64_t) * count, hipMemcpyDeviceToHost, ctx->stream));
+  ST_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return ST_OK;
 }
 

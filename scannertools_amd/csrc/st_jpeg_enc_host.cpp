@@ -8,6 +8,7 @@
 #include <initializer_list>
 
 #include "scannertools_hip.h"
+#include "st_jpeg_enc_opt.h"
 
 #define ST_JPEG_EXPORT extern "C" __attribute__((visibility("default")))
 
@@ -170,5 +171,77 @@ ST_JPEG_EXPORT long long st_jpeg_encode_bound(int h, int w, int h_samp, int v_sa
   st_jpeg_enc_geom(h, w, h_samp, v_samp, &g);
   // header, every interval at its worst case, an RST marker between intervals, EOI
   return (long long)kJpegEncHeaderBytes + (long long)g.mrows * (long long)g.mcols * g.bpm * (long long)kJpegEncBlockStuffed +
+         2LL * (g.mrows - 1) + 2;
+}
+
+// ---- optimised Huffman tables: the host twins of k_jpeg_sym_stats and k_jpeg_opt_tables ------------------
+int st_jpeg_enc_check_optimize(int optimize, char* msg, size_t msg_len) {
+  msg[0] = 0;
+  if (optimize != 0 && optimize != 1) {
+    snprintf(msg, msg_len, "optimize %d is not supported (0 or 1)", optimize);
+    return ST_ERR_INVALID;
+  }
+  return ST_OK;
+}
+
+ST_JPEG_EXPORT int st_jpeg_optimal_table(const uint64_t freq[256], uint8_t bits[16], uint8_t vals[256], int* nvals) {
+  if (!freq || !bits || !vals || !nvals) return ST_ERR_INVALID;
+  StJpegOptWork w;
+  // a code of more than 32 bits before the limiting: libjpeg stops there; the table returned is valid but not optimal
+  return st_jpeg_opt_table_serial(freq, &w, bits, vals, nvals) ? ST_ERR_UNSUPPORTED : ST_OK;
+}
+
+ST_JPEG_EXPORT int st_jpeg_optimal_dht(const uint64_t freq[256], int table, uint8_t* buf, size_t cap, size_t* size, uint32_t* codes) {
+  if (!freq || table < 0 || table >= kJpegOptTables) return ST_ERR_INVALID;
+  StJpegOptWork w;
+  uint8_t bits[16], vals[256];
+  int nvals = 0;
+  (void)st_jpeg_opt_table_serial(freq, &w, bits, vals, &nvals);
+  const size_t bytes = (size_t)st_jpeg_opt_dht_bytes(nvals);
+  if (size) *size = bytes;
+  if (!buf || cap < bytes) return ST_ERR_INVALID;
+  for (size_t i = 0; i < bytes; ++i) buf[i] = st_jpeg_opt_dht_byte(bits, vals, nvals, st_jpeg_opt_class_id(table), (int)i);
+  if (codes) st_jpeg_opt_codes(bits, vals, nvals, codes, st_jpeg_opt_tab_words(table));
+  return ST_OK;
+}
+
+ST_JPEG_EXPORT int st_jpeg_symbol_stats(const int16_t* coef, size_t cap, int h, int w, int h_samp, int v_samp, int restart, uint64_t* freq) {
+  char msg[160];
+  int st = st_jpeg_enc_check_restart(restart, msg, sizeof msg);
+  if (st == ST_OK) st = st_jpeg_enc_check(h, w, 50, h_samp, v_samp, msg, sizeof msg);
+  if (st != ST_OK) return st;
+  if (!coef || !freq) return ST_ERR_INVALID;
+  StJpegEncGeom g;
+  st_jpeg_enc_geom(h, w, h_samp, v_samp, &g);
+  const size_t luma_blocks = (size_t)g.mrows * v_samp * g.mcols * h_samp, chroma_blocks = (size_t)g.mrows * g.mcols;
+  if (cap < (luma_blocks + 2 * chroma_blocks) * 64) return ST_ERR_INVALID;
+  memset(freq, 0, sizeof(uint64_t) * kJpegOptTables * 256);
+  int pred[3] = {0, 0, 0};
+  auto block = [&](const int16_t* b, int comp) {
+    uint64_t* f = freq + (comp == 0 ? 0 : 2) * 256;   // DC table of the component; its AC table follows
+    const int diff = (int)b[0] - pred[comp];
+    pred[comp] = b[0];
+    st_jpeg_opt_block_symbols([b](int k) { return (int)b[st_jpeg_enc_zigzag[k]]; }, diff, [f](int ac, int sym) { f[ac * 256 + sym]++; });
+  };
+  for (int my = 0; my < g.mrows; ++my) {
+    if (restart == ST_JPEG_RESTART_ROW) pred[0] = pred[1] = pred[2] = 0;
+    for (int mx = 0; mx < g.mcols; ++mx) {
+      for (int k = 0; k < h_samp * v_samp; ++k) {
+        const size_t by = (size_t)my * v_samp + k / h_samp, bx = (size_t)mx * h_samp + k % h_samp;
+        block(coef + (by * ((size_t)g.mcols * h_samp) + bx) * 64, 0);
+      }
+      for (int c = 0; c < 2; ++c) block(coef + (luma_blocks + c * chroma_blocks + (size_t)my * g.mcols + mx) * 64, 1 + c);
+    }
+  }
+  return ST_OK;
+}
+
+ST_JPEG_EXPORT long long st_jpeg_encode_bound_opt(int h, int w, int h_samp, int v_samp) {
+  char msg[160];
+  if (st_jpeg_enc_check(h, w, 50, h_samp, v_samp, msg, sizeof msg) != ST_OK) return -1;
+  StJpegEncGeom g;
+  st_jpeg_enc_geom(h, w, h_samp, v_samp, &g);
+  // the header (four DHT segments of at most 12 / 162 symbols: never more than the 629 bytes), every block at 1665 bits stuffed
+  return (long long)kJpegEncHeaderBytes + (long long)g.mrows * (long long)g.mcols * g.bpm * (long long)kJpegEncBlockStuffedOpt +
          2LL * (g.mrows - 1) + 2;
 }

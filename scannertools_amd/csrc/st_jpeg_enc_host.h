@@ -28,6 +28,8 @@ constexpr size_t kJpegEncBlockStuffed = 416;        // after
 int st_jpeg_enc_check(int h, int w, int quality, int h_samp, int v_samp, char* msg, size_t msg_len);
 // The same for the restart mode (ST_JPEG_RESTART_*): ST_ERR_INVALID names any other value.
 int st_jpeg_enc_check_restart(int restart, char* msg, size_t msg_len);
+// The same for `optimize` (0: the Annex K tables, 1: per-frame optimal tables): ST_ERR_INVALID names any other value.
+int st_jpeg_enc_check_optimize(int optimize, char* msg, size_t msg_len);
 void st_jpeg_enc_geom(int h, int w, int h_samp, int v_samp, StJpegEncGeom* g);
 // Bytes of an interval's slot: its blocks at their stuffed worst case (the padding of the last byte only fills a byte counted
 // already), a multiple of 16.

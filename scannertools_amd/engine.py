@@ -917,17 +917,19 @@ class _Ops:
             args = _proto.image_decoder_args(args.get("image_type"), args.get("entropy"), args.get("split"), args.get("scale_denom"))
         return _ImageDecoderNode(self.sc, "ImageDecoder", [img], device, batch, args or b"")
 
-    def ImageEncoder(self, frame, quality=95, subsampling="4:2:0", restart="row", device=None, batch=None):
+    def ImageEncoder(self, frame, quality=95, subsampling="4:2:0", restart="row", device=None, batch=None, optimize=False):
         """sc.ops.ImageEncoder(frame=..., quality=..., subsampling=..., restart=..., device=..., batch=...): (h, w, 3) uint8 RGB
         frames -> the column img, one baseline JPEG stream (bytes) per row -- what sc.ops.ImageDecoder(img=...) reads.  Args
         ImageEncoderArgs{quality = 1, subsampling = 2, restart = 3} (scannertools_imgproc_amd.proto): quality 1..100,
         subsampling "4:4:4", "4:2:2" or "4:2:0", restart "row" (one restart interval per MCU row; also "mcu_row") or "none" (no
         restart markers: what cv::imencode and Pillow write by default), or the field's number; anything else fails validation.
-        The whole encoder, Huffman coding included, runs on the GPU."""
+        optimize (ImageEncoderArgs field 4): True writes each frame with Huffman tables built from its own symbol counts
+        (libjpeg's optimize_coding, Pillow's optimize=True); a number other than 0 / 1 fails validation.
+        The whole encoder, Huffman coding and table construction included, runs on the GPU."""
         from . import _proto
         if isinstance(restart, str):
             restart = {"row": 0, "mcu_row": 0, "none": 1}.get(restart.lower(), restart)
-        return _ImageEncoderNode(self.sc, "ImageEncoder", [frame], device, batch, _proto.image_encoder_args(quality, subsampling, restart))
+        return _ImageEncoderNode(self.sc, "ImageEncoder", [frame], device, batch, _proto.image_encoder_args(quality, subsampling, restart, optimize))
 
     def InfoFromFrame(self, frame):
         """sc.ops.InfoFromFrame(frame=frame): the frame's FrameInfo as a bytes column."""

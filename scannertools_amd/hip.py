@@ -493,14 +493,17 @@ class HipContext:
         self._bind()
         return int(self._L.st_jpeg_split_last_rounds(self._h))
 
-    def encode_jpeg(self, frames, quality=95, subsampling="4:2:0", restart="row"):
+    def encode_jpeg(self, frames, quality=95, subsampling="4:2:0", restart="row", optimize=False):
         """ImageEncoder op: (n, h, w, 3) uint8 CUDA frames (a tensor or a list of (h, w, 3) tensors of one shape), R, G, B
         order -> a list of n baseline JPEG streams (bytes), byte for byte what libjpeg writes at this quality and sampling
         with one restart interval per MCU row (restart="row") or without restart markers (restart="none": libjpeg's, Pillow's
         and cv::imencode's default).  Colour conversion, downsampling, DCT, quantisation and Huffman coding run in
-        HIP kernels on the current stream; only the streams cross to the host, in one copy."""
+        HIP kernels on the current stream; only the streams cross to the host, in one copy.  optimize=True: libjpeg's
+        optimize_coding (Pillow's optimize=True) -- each frame's Huffman tables are built from its own symbol counts, on the
+        device, and the stream is what libjpeg writes with that switch."""
         hs, vs = jpeg_sampling(subsampling)
         rst = jpeg_restart(restart)
+        opt = jpeg_optimize(optimize)
         self._bind()
         fr = list(frames) if isinstance(frames, (list, tuple)) else list(frames.unbind(0))
         n = len(fr)
@@ -514,7 +517,10 @@ class HipContext:
             if tuple(f.shape) != (h, w, 3):
                 raise ValueError("all frames must have the same (h,w,3) shape")
         tf = (ctypes.c_void_p * n)(*[f.data_ptr() for f in fr])
-        self._check(self._L.st_jpeg_encode_batch_rst(self._h, tf, n, h, w, int(quality), hs, vs, rst))
+        if opt:
+            self._check(self._L.st_jpeg_encode_batch_opt(self._h, tf, n, h, w, int(quality), hs, vs, rst, opt))
+        else:
+            self._check(self._L.st_jpeg_encode_batch_rst(self._h, tf, n, h, w, int(quality), hs, vs, rst))
         sizes = (ctypes.c_size_t * n)()
         self._check(self._L.st_jpeg_encode_fetch(self._h, None, sizes, 0))   # the sizes alone
         most = max(sizes)
@@ -522,6 +528,14 @@ class HipContext:
         bufs = (ctypes.c_void_p * n)(*[store[i].ctypes.data for i in range(n)])
         self._check(self._L.st_jpeg_encode_fetch(self._h, bufs, sizes, most))
         return [store[i, :sizes[i]].tobytes() for i in range(n)]
+
+    def last_jpeg_symbol_stats(self, n):
+        """st_jpeg_encode_fetch_stats: the (n, 4, 256) uint64 symbol counts of the last encode_jpeg(optimize=True) call of n
+        frames (tables DC luma, AC luma, DC chroma, AC chroma), as the device counted them."""
+        self._bind()
+        out = np.empty((int(n), 4, 256), np.uint64)
+        self._check(self._L.st_jpeg_encode_fetch_stats(self._h, out.ctypes.data, out.size))
+        return out
 
     # -- pose path (scannertools_caffe) -------------------------------------------------------
     def cpm2_input(self, frames, scale, out=None):
@@ -1093,6 +1107,53 @@ def jpeg_restart(restart):
     return JPEG_RESTARTS[restart]
 
 
+def jpeg_optimize(optimize):
+    """0 / 1 of False / True / 0 / 1; ValueError for anything else."""
+    if isinstance(optimize, (bool, int, np.integer)) and int(optimize) in (0, 1):
+        return int(optimize)
+    raise ValueError("optimize %r is not supported (False or True)" % (optimize,))
+
+
+def jpeg_optimal_table(freq):
+    """st_jpeg_optimal_table (host only): (bits, vals) of libjpeg's jpeg_gen_optimal_table for 256 symbol counts: bits[k] the
+    codes of k + 1 bits as a (16,) uint8 array, vals the symbols that have a code, by code length and then by value."""
+    f = np.ascontiguousarray(freq, np.uint64)
+    if f.shape != (256,):
+        raise ValueError("jpeg_optimal_table takes 256 counts, got shape %s" % (f.shape,))
+    bits, vals, n = np.zeros(16, np.uint8), np.zeros(256, np.uint8), ctypes.c_int()
+    st = _native.lib().st_jpeg_optimal_table(f.ctypes.data, bits.ctypes.data, vals.ctypes.data, ctypes.byref(n))
+    if st != 0:
+        raise StError(st, "st_jpeg_optimal_table")
+    return bits, vals[:n.value].copy()
+
+
+def jpeg_optimal_dht(freq, table):
+    """st_jpeg_optimal_dht (host only): (the DHT segment's bytes, the code words (length << 16 | code) by symbol) of the table
+    built from 256 counts, as table 0 DC luma, 1 AC luma, 2 DC chroma or 3 AC chroma."""
+    f = np.ascontiguousarray(freq, np.uint64)
+    if f.shape != (256,):
+        raise ValueError("jpeg_optimal_dht takes 256 counts, got shape %s" % (f.shape,))
+    buf, size = ctypes.create_string_buffer(21 + 256), ctypes.c_size_t()
+    codes = np.zeros(256 if int(table) & 1 else 16, np.uint32)
+    st = _native.lib().st_jpeg_optimal_dht(f.ctypes.data, int(table), buf, len(buf), ctypes.byref(size), codes.ctypes.data)
+    if st != 0:
+        raise StError(st, "st_jpeg_optimal_dht(table=%r): tables are 0..3" % (table,))
+    return buf.raw[:size.value], codes
+
+
+def jpeg_symbol_stats(coef, h, w, subsampling="4:2:0", restart="row"):
+    """st_jpeg_symbol_stats (host only): the (4, 256) uint64 symbol counts (DC luma, AC luma, DC chroma, AC chroma) of an
+    (h, w, 3) frame's int16 coefficients in jpeg_coefficients' layout, the DC predictors as the restart mode has them."""
+    hs, vs = jpeg_sampling(subsampling)
+    rst = jpeg_restart(restart)
+    c = np.ascontiguousarray(coef, np.int16).reshape(-1)
+    out = np.zeros((4, 256), np.uint64)
+    st = _native.lib().st_jpeg_symbol_stats(c.ctypes.data, c.size, int(h), int(w), hs, vs, rst, out.ctypes.data)
+    if st != 0:
+        raise StError(st, "st_jpeg_symbol_stats(h=%d, w=%d): size outside 1..65535 or too few coefficients (%d)" % (h, w, c.size))
+    return out
+
+
 def jpeg_quant_tables(quality):
     """st_jpeg_quant_tables (host only): the (luma, chroma) quantisation tables of ``quality``, (64,) uint16 each, natural order."""
     luma, chroma = np.empty(64, np.uint16), np.empty(64, np.uint16)
@@ -1119,6 +1180,15 @@ def jpeg_encode_bound(h, w, subsampling="4:2:0"):
     """st_jpeg_encode_bound (host only): no stream of an (h, w, 3) frame at this sampling is longer, whatever its content."""
     hs, vs = jpeg_sampling(subsampling)
     v = _native.lib().st_jpeg_encode_bound(int(h), int(w), hs, vs)
+    if v < 0:
+        raise StError(1, "frame size %dx%d is outside 1..65535" % (w, h))
+    return v
+
+
+def jpeg_encode_bound_opt(h, w, subsampling="4:2:0"):
+    """st_jpeg_encode_bound_opt (host only): jpeg_encode_bound for streams written with optimize=True."""
+    hs, vs = jpeg_sampling(subsampling)
+    v = _native.lib().st_jpeg_encode_bound_opt(int(h), int(w), hs, vs)
     if v < 0:
         raise StError(1, "frame size %dx%d is outside 1..65535" % (w, h))
     return v

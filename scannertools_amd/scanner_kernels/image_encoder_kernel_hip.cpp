@@ -7,9 +7,11 @@
 // subsampling means "4:2:0".  Those are cv::imencode's defaults for JPEG (IMWRITE_JPEG_QUALITY 95, 4:2:0 sampling) as restated
 // from OpenCV's documentation; OpenCV is not available to check them against, so they are unpinned.  restart: MCU_ROW (0 or
 // absent) writes one restart interval per MCU row, NONE (1) no DRI segment and no RSTn markers -- the stream cv::imencode,
-// Pillow and cjpeg write by default; any other value fails validate().
+// Pillow and cjpeg write by default; any other value fails validate().  optimize = 4 (a varint; declared as `bool optimize = 4`
+// in ImageEncoderArgsWithRestart): 1 writes each frame with Huffman tables built on the device from its own symbol counts
+// (libjpeg's optimize_coding); 0 or absent the Annex K tables; any other value fails validate().
 //
-// One st_jpeg_encode_batch_rst() call per execute(): colour conversion, downsampling, forward DCT, quantisation and Huffman coding
+// One st_jpeg_encode_batch_opt() call per execute(): colour conversion, downsampling, forward DCT, quantisation and Huffman coding
 // run in HIP kernels (include/scannertools_hip.h), the streams come back in one copy of exactly their bytes
 // (st_jpeg_encode_fetch).  A stream is byte for byte what libjpeg writes at the same settings with one restart interval per
 // MCU row, or with restart = NONE with none at all.  Registered twice like the other classes: DeviceType::GPU reads device frames, the staged DeviceType::CPU form
@@ -25,16 +27,19 @@
 namespace scanner {
 namespace {
 // false: not a message.  quality: 0 when the field is absent; subsampling: empty when absent; restart: 0 (MCU_ROW) when absent
-bool parse_image_encoder_args(const std::vector<u8>& args, int* quality, std::string* subsampling, long long* restart) {
+// optimize: 0 when absent
+bool parse_image_encoder_args(const std::vector<u8>& args, int* quality, std::string* subsampling, long long* restart, long long* optimize) {
   std::vector<proto_lite::Field> fields;
   *quality = 0;
   *restart = 0;
+  *optimize = 0;
   subsampling->clear();
   if (!proto_lite::parse(args.data(), args.size(), &fields)) return false;
   for (auto& f : fields) {
     if (f.number == 1 && f.wire == 0) *quality = (int)(int64_t)f.value;
     if (f.number == 2 && f.wire == 2) *subsampling = f.bytes;
     if (f.number == 3 && f.wire == 0) *restart = (long long)(int64_t)f.value;
+    if (f.number == 4 && f.wire == 0) *optimize = (long long)(int64_t)f.value;
   }
   return true;
 }
@@ -45,8 +50,8 @@ class ImageEncoderKernelHIPImpl : public BatchedKernel {
  public:
   ImageEncoderKernelHIPImpl(const KernelConfig& config) : BatchedKernel(config), core_(config, STAGED), stage_(core_.gpu) {
     std::string sub;
-    long long restart = 0;
-    if (!parse_image_encoder_args(config.args, &quality_, &sub, &restart)) {
+    long long restart = 0, optimize = 0;
+    if (!parse_image_encoder_args(config.args, &quality_, &sub, &restart, &optimize)) {
       RESULT_ERROR(&core_.valid, "ImageEncoder: could not parse ImageEncoderArgs");
       return;
     }
@@ -67,6 +72,11 @@ class ImageEncoderKernelHIPImpl : public BatchedKernel {
       return;
     }
     restart_ = (int)restart;
+    if (optimize != 0 && optimize != 1) {
+      RESULT_ERROR(&core_.valid, "ImageEncoder: optimize %lld is not supported (0 or 1)", optimize);
+      return;
+    }
+    optimize_ = (int)optimize;
     core_.open("ImageEncoderKernelHIP");
   }
   void validate(Result* result) override { core_.validate(result); }
@@ -94,7 +104,7 @@ class ImageEncoderKernelHIPImpl : public BatchedKernel {
       input_ptrs(src_, frame_col);
     }
     st_ctx* ctx = core_.ctx;
-    ST_CHECK(ctx, st_jpeg_encode_batch_rst(ctx, src_.data(), n, h, w, quality_, h_samp_, v_samp_, restart_));
+    ST_CHECK(ctx, st_jpeg_encode_batch_opt(ctx, src_.data(), n, h, w, quality_, h_samp_, v_samp_, restart_, optimize_));
     sizes_.assign(n, 0);
     ST_CHECK(ctx, st_jpeg_encode_fetch(ctx, nullptr, sizes_.data(), 0));   // the sizes alone
     size_t total = 0, most = 0;
@@ -116,7 +126,7 @@ class ImageEncoderKernelHIPImpl : public BatchedKernel {
  private:
   KernelCore core_;
   DeviceStage stage_;   // staged: the frames
-  int quality_ = 95, h_samp_ = 2, v_samp_ = 2, restart_ = ST_JPEG_RESTART_ROW;
+  int quality_ = 95, h_samp_ = 2, v_samp_ = 2, restart_ = ST_JPEG_RESTART_ROW, optimize_ = 0;
   std::vector<const uint8_t*> src_;
   std::vector<uint8_t*> dst_;
   std::vector<size_t> sizes_;

@@ -10,7 +10,7 @@ the only baseline there is -- the op has no predecessor.  Per batch size, after 
 The first stream is compared with Pillow's byte for byte before anything is timed.  The frames are synthetic (seeded smooth
 structure plus sensor-like noise), eight distinct ones repeated.
 
-    python scripts/bench_image_encoder.py [--rounds 7] [--restart row|none|both]
+    python scripts/bench_image_encoder.py [--rounds 7] [--restart row|none|both] [--optimize off|on|both]
     rocprofv3 --kernel-trace --stats --output-format csv -d DIR -- python scripts/bench_image_encoder.py --trace [--restart none]
 
 --trace makes three calls per batch size and times nothing: the kernel statistics of the trace then hold the four kernels'
@@ -21,6 +21,12 @@ measures streams without restart markers (five launches: k_jpeg_fdct, k_jpeg_ent
 k_jpeg_pack_bits; Pillow then encodes without markers too); both measures the two in ONE run on the same frames, their timed
 calls alternating, so that the difference between them can be set against the spread between repeats of the run.  The figures
 of "none" go under "batches_norst".
+
+--optimize off (the default) changes nothing; on measures the calls with per-frame optimised Huffman tables
+(st_jpeg_encode_batch_opt(..., optimize = 1): k_jpeg_sym_stats and k_jpeg_opt_tables between the transform and the entropy coder;
+Pillow then saves with optimize=True too); both measures the two settings in ONE run on the same frames, their timed calls
+alternating like those of --restart both, so that "off" is the unchanged path measured beside "on".  The figures with optimised
+tables go under "batches_opt" / "batches_norst_opt": frames/s, kernel ms per frame and stream bytes per frame as for the others.
 """
 import argparse
 import ctypes
@@ -59,6 +65,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--trace", action="store_true")
     ap.add_argument("--restart", choices=("row", "none", "both"), default="row")
+    ap.add_argument("--optimize", choices=("off", "on", "both"), default="off")
     args = ap.parse_args()
     try:
         from PIL import Image
@@ -72,19 +79,27 @@ def main():
     host = make_frames()
     dev = [torch.from_numpy(f).cuda() for f in host]
 
-    modes = ("row", "none") if args.restart == "both" else (args.restart,)
+    # a mode is (restart, optimised tables); without --optimize the modes and their keys are what they always were
+    modes = [(r, o) for r in (("row", "none") if args.restart == "both" else (args.restart,))
+             for o in {"off": (False,), "on": (True,), "both": (False, True)}[args.optimize]]
+    if any(o for _, o in modes):
+        from PIL import ImageFile
+        ImageFile.MAXBLOCK = max(ImageFile.MAXBLOCK, 1 << 24)   # optimize=True saves need the whole stream in one block
 
-    def pillow(i, mode="row"):
+    def pillow(i, mode=("row", False)):
         buf = io.BytesIO()
-        kw = {"restart_marker_rows": 1} if mode == "row" else {}
+        kw = {"restart_marker_rows": 1} if mode[0] == "row" else {}
+        if mode[1]:
+            kw["optimize"] = True
         Image.fromarray(host[i % DISTINCT]).save(buf, "JPEG", quality=QUALITY, subsampling=SUBSAMPLING, **kw)
         return buf.getvalue()
 
     for mode in modes:
-        assert ctx.encode_jpeg([dev[0]], QUALITY, SUBSAMPLING, restart=mode)[0] == pillow(0, mode), "the stream differs from Pillow's (restart=%s)" % mode
+        assert ctx.encode_jpeg([dev[0]], QUALITY, SUBSAMPLING, restart=mode[0], optimize=mode[1])[0] == pillow(0, mode), \
+            "the stream differs from Pillow's (restart=%s, optimize=%s)" % mode
     result = {"bench": "image_encoder", "h": H, "w": W, "quality": QUALITY, "sampling": SUBSAMPLING, "raw_frame_bytes": H * W * 3,
               "bound_bytes": jpeg_encode_bound(H, W, SUBSAMPLING), "rounds": args.rounds}
-    keys = {"row": "batches", "none": "batches_norst"}
+    keys = {("row", False): "batches", ("none", False): "batches_norst", ("row", True): "batches_opt", ("none", True): "batches_norst_opt"}
     for mode in modes:
         result[keys[mode]] = {}
     ctx._bind()
@@ -95,7 +110,9 @@ def main():
         bufs = (ctypes.c_void_p * n)(*[store[i].ctypes.data for i in range(n)])
 
         def call(mode):
-            if mode == "row":
+            if mode[1]:
+                ctx._check(L.st_jpeg_encode_batch_opt(ctx._h, tab, n, H, W, QUALITY, 2, 2, 0 if mode[0] == "row" else 1, 1))
+            elif mode[0] == "row":
                 ctx._check(L.st_jpeg_encode_batch(ctx._h, tab, n, H, W, QUALITY, 2, 2))
             else:
                 ctx._check(L.st_jpeg_encode_batch_rst(ctx._h, tab, n, H, W, QUALITY, 2, 2, 1))
