@@ -99,7 +99,7 @@ enum st_kernel_id {
   ST_K_CPM2_RESIZE = 14,
   ST_K_CPM2_NMS = 15,      /* the library's non-maximum suppressions: CPM2's peak search and the FacenetOutput launches (decode, sort + greedy NMS, pack) */
   ST_K_FRAME_STATS = 16, /* moments + finishing launches of the frame-statistics ops */
-  ST_K_JPEG = 17,        /* inverse DCT + upsample / colour launches of the ImageDecoder op; the ImageEncoder op's launches (four, or five without restart markers) */
+  ST_K_JPEG = 17,        /* inverse DCT + upsample / colour launches of the ImageDecoder op; the ImageEncoder op's launches (four, or five without restart markers); the PNG launches of st_png_decode_batch (unfilter, expand) */
   ST_K_NET_INPUT = 18,   /* the FacenetInput and CaffeInput launches */
   ST_K_COUNT = 19
 };
@@ -855,6 +855,48 @@ int st_jpeg_encode_batch_opt(st_ctx* ctx, const uint8_t* const* frames_dev, int 
  * (st_jpeg_symbol_stats' layout per frame) into freq[0, cap).  One wait for the kernels.  ST_ERR_INVALID: no such call to fetch
  * from, freq null, cap < n x 1024. */
 int st_jpeg_encode_fetch_stats(st_ctx* ctx, uint64_t* freq, size_t cap);
+
+/* ---- ImageDecoder: PNG (opt-in, ImageDecoderArgs.png = DECODE) ----------------------------------
+ * cv::imdecode(IMREAD_UNCHANGED) reads PNG as readily as JPEG (image_decoder_kernel_cpu.cpp).  Inflate is serial per stream and
+ * runs on host threads with the library's own inflater (no zlib, no libpng); undoing the row filters and expanding palette
+ * indices, sub-byte samples, gray+alpha and colour-key transparency run in HIP kernels.  Decoded: colour type 0 at bit depth
+ * 1 / 2 / 4 / 8 -> 1 channel (depth 1 / 2 / 4 scaled by 255 / 85 / 17, tRNS ignored); 2 at 8 -> R, G, B, with tRNS R, G, B, A
+ * (A = 0 where the pixel equals the key, else 255); 3 at 1 / 2 / 4 / 8 -> R, G, B, with tRNS R, G, B, A (entries past tRNS
+ * have A = 255; an index past the palette is opaque black); 4 at 8 -> g, g, g, a; 6 at 8 -> R, G, B, A.  That restates
+ * OpenCV's PNG reader followed by the reference's BGR(A) -> RGB(A) swap (unpinned: DESIGN.md 4.17).  ST_ERR_UNSUPPORTED:
+ * 16-bit samples, Adam7 interlace; of an APNG only the default image is decoded.  ST_ERR_INVALID: anything malformed. */
+typedef struct st_png_info {
+  int h, w, channels;            /* of the decoded frame */
+  int color_type, bit_depth, interlace;
+  int palette_entries, trns_entries;   /* 0: no such chunk */
+  char message[160];             /* why a stream is refused; empty on ST_OK */
+} st_png_info;
+/* Host only, re-entrant: reads the signature and the chunks up to the first IDAT (so that `channels` is known), CRCs checked. */
+int st_png_probe(const uint8_t* buf, size_t size, st_png_info* info);
+/* Host only, re-entrant, for tests and tools: inflates one zlib stream (RFC 1950 / 1951) into dst[0, cap) and never past it;
+ * *produced (may be null) receives the bytes written.  ST_ERR_INVALID with the cause in message (may be null): a bad zlib
+ * header, block type 3, stored LEN / NLEN mismatch, over-subscribed or incomplete code lengths, invalid length or distance
+ * symbols, a distance before the start of the output, truncated input, more output than cap, Adler-32 mismatch. */
+int st_zlib_inflate(const uint8_t* src, size_t n, uint8_t* dst, size_t cap, size_t* produced, char* message, size_t message_len);
+/* Host only, re-entrant: stage 1 alone -- the whole container is parsed and checked, the IDAT chunks are joined and inflated
+ * into raw[0, cap): h x (1 + rowbytes) bytes, every row its filter type and its still-filtered bytes.  cap too small, an
+ * inflated length other than exactly that, or a filter type above 4 is ST_ERR_INVALID.  The twin of st_jpeg_coefficients. */
+int st_png_filtered(const uint8_t* buf, size_t size, uint8_t* raw, size_t cap, st_png_info* info);
+/* Host only, re-entrant: the whole decode in plain C++, the way the device computes it: frame[0, cap) receives the
+ * (h, w, channels) frame.  The CPU twin of k_png_unfilter + k_png_expand. */
+int st_png_decode_host(const uint8_t* buf, size_t size, uint8_t* frame, size_t cap, st_png_info* info);
+/* st_jpeg_decode_batch's contract for PNG streams: every stream is probed and its container checked first (all but the CRCs of
+ * the IDAT chunks, which belong to the data), and one that is refused, malformed or of another decoded shape than
+ * (h, w, channels) fails the call naming it before anything is launched or written.  Then the streams are inflated on min(n, ST_PNG_THREADS) host threads (default and clamping as ST_JPEG_THREADS)
+ * into page-locked memory in sub-batches that alternate between two slots; each sub-batch is copied and its launches
+ * (k_png_unfilter: one workgroup per frame; k_png_expand where a frame needs it) enqueued on the context's stream while the
+ * next is inflated; the only host wait is the one for a slot's previous copy.  Streams of different colour types and depths
+ * may share a call when they decode to the same shape.  A stream whose data turns out corrupt (an IDAT CRC, the zlib stream, the
+ * inflated length, a filter type) fails the call under
+ * st_jpeg_decode_batch's rule: later sub-batches are not written, enqueued ones are.  out_dev: n device pointers to
+ * (h, w, channels) frames at any byte address.  Timed under ST_K_JPEG. */
+int st_png_decode_batch(st_ctx* ctx, const uint8_t* const* bufs_host, const size_t* sizes, int n, int h, int w, int channels,
+                        uint8_t* const* out_dev);
 
 #ifdef __cplusplus
 }

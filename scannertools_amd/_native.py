@@ -82,6 +82,13 @@ class JpegInfo(ctypes.Structure):
                 ("v_samp", ctypes.c_int), ("restart_interval", ctypes.c_int), ("message", ctypes.c_char * 160)]
 
 
+class PngInfo(ctypes.Structure):
+    """``st_png_info``: what st_png_probe reads from a stream's chunks, and the message of a refusal."""
+    _fields_ = [("h", ctypes.c_int), ("w", ctypes.c_int), ("channels", ctypes.c_int), ("color_type", ctypes.c_int),
+                ("bit_depth", ctypes.c_int), ("interlace", ctypes.c_int), ("palette_entries", ctypes.c_int),
+                ("trns_entries", ctypes.c_int), ("message", ctypes.c_char * 160)]
+
+
 class JpegSplitOpts(ctypes.Structure):
     """``st_jpeg_split_opts``: subsequence bytes and the cap on rounds of the decoding by subsequence; 0: the library's default."""
     _fields_ = [("subseq_bytes", ctypes.c_int), ("max_rounds", ctypes.c_int)]
@@ -215,6 +222,11 @@ SIGNATURES = {
     "st_jpeg_encode_bound_opt": (ctypes.c_longlong, [_i, _i, _i, _i]),
     "st_jpeg_encode_batch_opt": (_i, [_vp, _c.POINTER(_vp), _i, _i, _i, _i, _i, _i, _i, _i]),
     "st_jpeg_encode_fetch_stats": (_i, [_vp, _vp, _sz]),
+    "st_png_probe": (_i, [_vp, _sz, _c.POINTER(PngInfo)]),
+    "st_zlib_inflate": (_i, [_vp, _sz, _vp, _sz, _c.POINTER(_sz), _vp, _sz]),
+    "st_png_filtered": (_i, [_vp, _sz, _vp, _sz, _c.POINTER(PngInfo)]),
+    "st_png_decode_host": (_i, [_vp, _sz, _vp, _sz, _c.POINTER(PngInfo)]),
+    "st_png_decode_batch": (_i, [_vp, _c.POINTER(_vp), _c.POINTER(_sz), _i, _i, _i, _i, _c.POINTER(_vp)]),
 }
 
 _LIB = None
@@ -232,8 +244,8 @@ def source_hash():
     st_build_info() of a library built from THIS tree reports."""
     import hashlib
     srcs = ["st_context.hip", "st_hist.hip", "st_farneback.hip", "st_flowvis.hip", "st_imgproc.hip", "st_pose.hip", "st_conv.hip",
-            "st_conv_tile_bf16x3.hip", "st_conv_tile_f32.hip", "st_framestats.hip", "st_jpeg.hip", "st_netinput.hip", "st_nn.hip", "st_detect.hip", "st_jpeg_enc.hip", "st_jpeg_entropy.hip", "st_jpeg_subseq.hip", "st_jpeg_reduced.hip", "st_jpeg_parse.cpp", "st_jpeg_enc_host.cpp", "st_internal.h",
-            "st_conv_tile.h", "st_jpeg_parse.h", "st_jpeg_enc_host.h", "st_jpeg_entropy.h", "st_jpeg_dense.h", "st_jpeg_enc_opt.h",
+            "st_conv_tile_bf16x3.hip", "st_conv_tile_f32.hip", "st_framestats.hip", "st_jpeg.hip", "st_netinput.hip", "st_nn.hip", "st_detect.hip", "st_jpeg_enc.hip", "st_jpeg_entropy.hip", "st_jpeg_subseq.hip", "st_jpeg_reduced.hip", "st_png.hip", "st_jpeg_parse.cpp", "st_jpeg_enc_host.cpp", "st_png_host.cpp", "st_internal.h",
+            "st_conv_tile.h", "st_jpeg_parse.h", "st_jpeg_enc_host.h", "st_jpeg_entropy.h", "st_jpeg_dense.h", "st_jpeg_enc_opt.h", "st_png_host.h",
             os.path.join("..", "..", "include", "scannertools_hip.h"), "Makefile"]
     hsh = hashlib.sha256()
     for f in srcs:

@@ -112,13 +112,18 @@ ENTROPY_MODES = {"HOST": 0, "GPU": 1, "AUTO": 2}   # ImageDecoderArgs.Entropy
 ENTROPY_SPLITS = {"INTERVAL": 0, "SUBSEQUENCE": 1}   # ImageDecoderArgs.Split
 
 
-def image_decoder_args(image_type=None, entropy=None, split=None, scale_denom=None):
+PNG_MODES = {"REFUSE": 0, "DECODE": 1}   # ImageDecoderArgs.Png
+
+
+def image_decoder_args(image_type=None, entropy=None, split=None, scale_denom=None, png=None):
     """A serialised ImageDecoderArgs.  None: the empty message (the op then decodes JPEG).  A named or numeric type is
     written explicitly, PNG = 0 too (proto3 would omit it, and the kernel could not tell it from an absent field).
     entropy (field 2): None leaves the field out (HOST); "host" / "gpu" / "auto" in either case, or a number, is written.
     split (field 3): None leaves the field out (INTERVAL); "interval" / "subsequence" in either case, or a number, is written.
     scale_denom (field 4, int32): None or 0 leaves the field out (full size, as proto3 omits a zero); any other number is
-    written, 1, 2, 4 and 8 being the ones the op accepts."""
+    written, 1, 2, 4 and 8 being the ones the op accepts.
+    png (field 5): None leaves the field out (REFUSE: PNG rows are not decoded); "refuse" / "decode" in either case, or a
+    number, is written."""
     out = b""
     if image_type is not None:
         v = IMAGE_TYPES[image_type] if isinstance(image_type, str) else int(image_type)
@@ -135,12 +140,17 @@ def image_decoder_args(image_type=None, entropy=None, split=None, scale_denom=No
         out += _varint(3 << 3 | 0) + _varint(v)
     if scale_denom is not None and int(scale_denom) != 0:
         out += _varint(4 << 3 | 0) + _varint(int(scale_denom))
+    if png is not None:
+        if isinstance(png, str) and png.upper() not in PNG_MODES:
+            raise ValueError("png must be one of 'refuse', 'decode' or a number, got %r" % (png,))
+        v = PNG_MODES[png.upper()] if isinstance(png, str) else int(png)
+        out += _varint(5 << 3 | 0) + _varint(v)
     return out
 
 
 def parse_image_decoder_args(buf):
-    """{'image_type': name or number, 'entropy': name or number, 'split': name or number, 'scale_denom': number} of a
-    serialised ImageDecoderArgs; a key is missing when its field is absent."""
+    """{'image_type': name or number, 'entropy': name or number, 'split': name or number, 'scale_denom': number, 'png': name or
+    number} of a serialised ImageDecoderArgs; a key is missing when its field is absent."""
     names = {v: k for k, v in IMAGE_TYPES.items()}
     modes = {v: k for k, v in ENTROPY_MODES.items()}
     out = {}
@@ -154,6 +164,8 @@ def parse_image_decoder_args(buf):
         if number == 4 and wt == 0:
             value &= 0xFFFFFFFF                       # an int32 field: the low 32 bits, sign-extended
             out["scale_denom"] = value - (1 << 32) if value >> 31 else value
+        if number == 5 and wt == 0:
+            out["png"] = {v: k for k, v in PNG_MODES.items()}.get(value, value)
     return out
 
 

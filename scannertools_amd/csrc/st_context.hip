@@ -146,6 +146,7 @@ ST_EXPORT int st_ctx_destroy(st_ctx* ctx) {
   }
   if (ctx->ws) (void)hipFree(ctx->ws);
   st_jpeg_release(ctx);
+  st_png_release(ctx);
   st_jpeg_enc_release(ctx);
   st_netin_release(ctx);
   st_detect_release(ctx);

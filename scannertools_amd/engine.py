@@ -600,7 +600,10 @@ class _ImageDecoderNode(_CppMultiOpNode):
     """ImageDecoder (image_decoder_kernel_cpu.cpp / _gpu.cpp): a bytes column in, frames out.  Every requested row is probed
     on the host first (st_jpeg_probe): a row that is not a JPEG this library decodes, or whose shape differs from the first
     row's, or that has no restart intervals where the arguments say entropy = GPU with split = INTERVAL (or no split), is a
-    ValueError naming the row and the cause, before any kernel instance exists (the kernel class can only abort)."""
+    ValueError naming the row and the cause, before any kernel instance exists (the kernel class can only abort).  With
+    png = DECODE the rows the kernel class takes for PNG streams (all of them for image_type PNG, those that begin with the PNG
+    signature for ANY or no image_type) are probed with st_png_probe instead, and one in an execute() with scale_denom other
+    than 1 is such a ValueError too."""
 
     def rows(self, idx):
         if not idx:
@@ -612,21 +615,31 @@ class _ImageDecoderNode(_CppMultiOpNode):
         try:
             parsed = _proto.parse_image_decoder_args(self.args)
             on_gpu = parsed.get("entropy") == "GPU" and parsed.get("split", "INTERVAL") == "INTERVAL"   # by subsequence needs none
+            png, image_type, scale = parsed.get("png") == "DECODE", parsed.get("image_type"), parsed.get("scale_denom", 1)
         except Exception:
-            on_gpu = False   # not a message: the kernel's validate() reports it
+            on_gpu, png, image_type, scale = False, False, None, 1   # not a message: the kernel's validate() reports it
         for r, data in zip(idx, streams):
             if not isinstance(data, (bytes, bytearray)):
                 raise ValueError("%s: row %d is %s, not the bytes of an encoded image" % (self.name, r, type(data).__name__))
-            info = _native.JpegInfo()
-            if L.st_jpeg_probe(bytes(data), len(data), ctypes.byref(info)) != 0:
-                raise ValueError("%s: row %d: %s" % (self.name, r, info.message.decode()))
+            if png and (image_type == "PNG" or (image_type != "JPEG" and bytes(data[:8]) == b"\x89PNG\r\n\x1a\n")):
+                info = _native.PngInfo()
+                if L.st_png_probe(bytes(data), len(data), ctypes.byref(info)) != 0:
+                    raise ValueError("%s: row %d: %s" % (self.name, r, info.message.decode()))
+                if scale not in (0, 1):
+                    raise ValueError("%s: row %d: a PNG row cannot be decoded at scale_denom %s (scaled decoding is JPEG's)" % (self.name, r, scale))
+                restart_interval = 1
+            else:
+                info = _native.JpegInfo()
+                if L.st_jpeg_probe(bytes(data), len(data), ctypes.byref(info)) != 0:
+                    raise ValueError("%s: row %d: %s" % (self.name, r, info.message.decode()))
+                restart_interval = info.restart_interval
             shape = (info.h, info.w, info.channels)
             if first is None:
                 first = shape
             # the kernel takes the frame shape of an execute() from its first element: one stream, one shape
             if shape != first:
                 raise ValueError("%s: row %d changes shape inside a batch: %s after %s" % (self.name, r, shape, first))
-            if on_gpu and info.restart_interval <= 0:
+            if on_gpu and restart_interval <= 0:
                 raise ValueError("%s: row %d: no restart intervals: the stream has no DRI segment, entropy = GPU needs one" % (self.name, r))
         node = copy.copy(self)
         node.parents = [_RowsNode(dict(zip(idx, streams)), self.length())]
@@ -911,10 +924,14 @@ class _Ops:
         where the Huffman decoder runs; "gpu" needs restart intervals in every row) and / or split "interval" / "subsequence"
         (ImageDecoderArgs.split = 3: with entropy "gpu" or "auto", "subsequence" decodes on the device by subsequence and needs no
         restart intervals) and / or scale_denom 1, 2, 4 or 8 (ImageDecoderArgs.scale_denom = 4: the frames at 1 / scale_denom,
-        (ceil(h / d), ceil(w / d), c), libjpeg's scaled decoding; any other number fails validation), or serialised bytes."""
+        (ceil(h / d), ceil(w / d), c), libjpeg's scaled decoding; any other number fails validation) and / or png "refuse" /
+        "decode" (ImageDecoderArgs.png = 5: with "decode", image_type "PNG" and "ANY" pass validation, rows may be PNG streams --
+        all of them for "PNG", those that begin with the PNG signature for "ANY" or no image_type, mixed with JPEG rows in one
+        batch -- and frames may have 4 channels, R, G, B, A; entropy, split and scale_denom apply to the JPEG rows), or
+        serialised bytes."""
         from . import _proto
         if isinstance(args, dict):
-            args = _proto.image_decoder_args(args.get("image_type"), args.get("entropy"), args.get("split"), args.get("scale_denom"))
+            args = _proto.image_decoder_args(args.get("image_type"), args.get("entropy"), args.get("split"), args.get("scale_denom"), args.get("png"))
         return _ImageDecoderNode(self.sc, "ImageDecoder", [img], device, batch, args or b"")
 
     def ImageEncoder(self, frame, quality=95, subsampling="4:2:0", restart="row", device=None, batch=None, optimize=False):

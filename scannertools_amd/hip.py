@@ -487,6 +487,26 @@ class HipContext:
         self._check(call(self._h, bufs, sizes, n, h, w, shape[3], to))
         return out
 
+    def decode_png(self, streams, out=None):
+        """ImageDecoder op with png = DECODE (st_png_decode_batch): a list of PNG streams (bytes) that decode to one shape ->
+        (n, h, w, c) uint8 CUDA tensor, c = 1 (gray), 3 (R, G, B) or 4 (R, G, B, A); lossless, so exactly the stored picture.
+        The shape is the first stream's; a stream of another shape, or one that is refused or malformed, raises StError naming
+        it, and nothing is written.  Inflate runs on host threads (ST_PNG_THREADS), filter reconstruction and expansion in HIP
+        kernels on the current stream.  ``out`` may be any (n, h, w, c) uint8 tensor whose frames are dense, at any address."""
+        self._bind()
+        streams = [bytes(s) for s in streams]
+        n = len(streams)
+        if n == 0:
+            return torch.zeros((0, 0, 0, 3), dtype=torch.uint8, device=self.device)
+        info = probe_png(streams[0])
+        shape = (n, info["h"], info["w"], info["channels"])
+        out = torch.empty(shape, dtype=torch.uint8, device=self.device) if out is None else _check_out(out, shape, torch.uint8, self.device)
+        bufs = (ctypes.c_void_p * n)(*[ctypes.cast(ctypes.c_char_p(s), ctypes.c_void_p).value for s in streams])
+        sizes = (ctypes.c_size_t * n)(*[len(s) for s in streams])
+        to = (ctypes.c_void_p * n)(*[out[i].data_ptr() for i in range(n)])
+        self._check(self._L.st_png_decode_batch(self._h, bufs, sizes, n, shape[1], shape[2], shape[3], to))
+        return out
+
     def last_jpeg_rounds(self):
         """st_jpeg_split_last_rounds: the round launches the last decode_jpeg(split="subsequence") call took (the most over its
         sub-batches; the cap where a segment fell back to the interval decoder)."""
@@ -1005,6 +1025,67 @@ def probe_jpeg(stream):
     if st != 0:
         raise StError(st, info.message.decode())
     return {k: getattr(info, k) for k in ("h", "w", "channels", "h_samp", "v_samp", "restart_interval")}
+
+
+_PNG_INFO_KEYS = ("h", "w", "channels", "color_type", "bit_depth", "interlace", "palette_entries", "trns_entries")
+
+
+def probe_png(stream):
+    """st_png_probe (host only): {'h', 'w', 'channels', 'color_type', 'bit_depth', 'interlace', 'palette_entries',
+    'trns_entries'} of a PNG stream, read from its chunks up to the first IDAT (h, w, channels: of the decoded frame); StError
+    with the library's message for a stream that is refused or malformed."""
+    info = _native.PngInfo()
+    data = bytes(stream)
+    st = _native.lib().st_png_probe(data, len(data), ctypes.byref(info))
+    if st != 0:
+        raise StError(st, info.message.decode())
+    return {k: getattr(info, k) for k in _PNG_INFO_KEYS}
+
+
+def zlib_inflate(data, size):
+    """st_zlib_inflate (host only): the library's own inflater on one zlib stream, into a buffer of exactly ``size`` bytes;
+    returns the bytes produced (there may be fewer than ``size``).  StError with the cause for a malformed stream or one that
+    produces more than ``size`` bytes."""
+    data = bytes(data)
+    out = np.empty(max(int(size), 1), np.uint8)
+    produced = ctypes.c_size_t(0)
+    msg = ctypes.create_string_buffer(160)
+    st = _native.lib().st_zlib_inflate(data, len(data), out.ctypes.data, int(size), ctypes.byref(produced), msg, 160)
+    if st != 0:
+        raise StError(st, msg.value.decode())
+    return out[:produced.value].tobytes()
+
+
+def png_filtered(stream):
+    """st_png_filtered (host only): stage 1 alone, the (h, 1 + rowbytes) uint8 array of the stream's inflated scanlines, every
+    row its filter type and its still-filtered bytes."""
+    data = bytes(stream)
+    info = _native.PngInfo()
+    st = _native.lib().st_png_probe(data, len(data), ctypes.byref(info))
+    if st != 0:
+        raise StError(st, info.message.decode())
+    samples = {0: 1, 2: 3, 3: 1, 4: 2, 6: 4}[info.color_type]
+    rowbytes = (info.w * samples * info.bit_depth + 7) // 8
+    raw = np.empty((info.h, 1 + rowbytes), np.uint8)
+    st = _native.lib().st_png_filtered(data, len(data), raw.ctypes.data, raw.size, ctypes.byref(info))
+    if st != 0:
+        raise StError(st, info.message.decode())
+    return raw
+
+
+def png_decode_host(stream):
+    """st_png_decode_host (host only): the (h, w, c) uint8 frame of a PNG stream, decoded in plain C++ the way the device
+    computes it (the CPU twin of decode_png's kernels)."""
+    data = bytes(stream)
+    info = _native.PngInfo()
+    st = _native.lib().st_png_probe(data, len(data), ctypes.byref(info))
+    if st != 0:
+        raise StError(st, info.message.decode())
+    frame = np.empty((info.h, info.w, info.channels), np.uint8)
+    st = _native.lib().st_png_decode_host(data, len(data), frame.ctypes.data, frame.size, ctypes.byref(info))
+    if st != 0:
+        raise StError(st, info.message.decode())
+    return frame
 
 
 JPEG_ENTROPY_MODES = ("host", "gpu", "auto")   # decode_jpeg's entropy=; ImageDecoderArgs.entropy HOST = 0, GPU = 1, AUTO = 2

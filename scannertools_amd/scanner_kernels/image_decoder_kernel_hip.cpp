@@ -31,11 +31,23 @@
 // or 0 means 1; any other value fails validate().  With 2, 4 or 8 execute() is one st_jpeg_decode_batch_scaled() call standing
 // for whichever of the three calls entropy and split select.
 //
+// ImageDecoderArgs { ..., png = 5: REFUSE = 0 | DECODE = 1 } (this build's own field too) decides whether PNG rows are decoded.
+// REFUSE, and a message without the field, is all of the above, the validate() failures for image_type PNG / ANY included.
+// DECODE makes image_type mean what it means in the reference: PNG -- every row must be a PNG, and a JPEG row is fatal with the
+// row and the cause; JPEG -- as above; ANY or absent -- each row is told apart by its first 8 bytes, and an execute() may mix
+// PNG and JPEG rows.  The PNG rows then go to ONE st_png_decode_batch() call (inflate on host threads, filter reconstruction
+// and expansion in HIP kernels) and the JPEG rows to the JPEG call the other fields select: both take pointer
+// arrays, so a subset needs no copy.  entropy, split and scale_denom apply to JPEG rows; a PNG row in an execute() with
+// scale_denom other than 1 is fatal with the row and the cause.  Frames may then have 4 channels (R, G, B, A).  Any other
+// value of png fails validate().
+//
 // The frame shape of an execute() is that of its first element.  Where the reference is undefined this fails instead: an
 // element of another shape (the reference's CPU kernel copies it into a frame of the first one's size, :46-50), and an element
 // that is not a baseline JPEG this library decodes ("Failed to decode image" there) are fatal with the row and the cause.
 // Registered twice like the other classes: DeviceType::GPU reads host bytes and produces device frames, the staged
 // DeviceType::CPU form decodes into a device buffer and copies host frames out.
+#include <cstring>
+
 #include "scanner/api/kernel.h"
 #include "scanner/api/op.h"
 #include "scanner/util/hip.h"
@@ -48,19 +60,24 @@ namespace scanner {
 namespace {
 enum { ENTROPY_HOST = 0, ENTROPY_GPU = 1, ENTROPY_AUTO = 2 };
 enum { SPLIT_INTERVAL = 0, SPLIT_SUBSEQUENCE = 1 };
-// false: not a message; *image_type: -1 when the field is absent; *entropy: ENTROPY_HOST, *split: SPLIT_INTERVAL, *scale: 1 when absent (or 0)
-bool parse_image_decoder_args(const std::vector<u8>& args, int* image_type, long long* entropy, long long* split, long long* scale) {
+enum { PNG_REFUSE = 0, PNG_DECODE = 1 };
+enum { TYPE_PNG = 0, TYPE_JPEG = 1, TYPE_ANY = 2 };
+// false: not a message; *image_type: -1 when the field is absent; *entropy: ENTROPY_HOST, *split: SPLIT_INTERVAL, *scale: 1 when absent (or 0),
+// *png: PNG_REFUSE when absent
+bool parse_image_decoder_args(const std::vector<u8>& args, int* image_type, long long* entropy, long long* split, long long* scale, long long* png) {
   std::vector<proto_lite::Field> fields;
   *image_type = -1;
   *entropy = ENTROPY_HOST;
   *split = SPLIT_INTERVAL;
   *scale = 1;
+  *png = PNG_REFUSE;
   if (!proto_lite::parse(args.data(), args.size(), &fields)) return false;
   for (auto& f : fields) {
     if (f.number == 1 && f.wire == 0) *image_type = (int)f.value;
     if (f.number == 2 && f.wire == 0) *entropy = (long long)f.value;
     if (f.number == 3 && f.wire == 0) *split = (long long)f.value;
     if (f.number == 4 && f.wire == 0) *scale = (int32_t)f.value == 0 ? 1 : (long long)(int32_t)f.value;   // an int32 field
+    if (f.number == 5 && f.wire == 0) *png = (long long)f.value;
   }
   return true;
 }
@@ -71,11 +88,12 @@ class ImageDecoderKernelHIPImpl : public BatchedKernel {
  public:
   ImageDecoderKernelHIPImpl(const KernelConfig& config) : BatchedKernel(config), core_(config, STAGED), stage_(core_.gpu) {
     int image_type = -1;
-    long long entropy = ENTROPY_HOST, split = SPLIT_INTERVAL, scale = 1;
-    if (!parse_image_decoder_args(config.args, &image_type, &entropy, &split, &scale)) RESULT_ERROR(&core_.valid, "ImageDecoder: could not parse ImageDecoderArgs");
-    else if (image_type == 0 || image_type == 2)
+    long long entropy = ENTROPY_HOST, split = SPLIT_INTERVAL, scale = 1, png = PNG_REFUSE;
+    if (!parse_image_decoder_args(config.args, &image_type, &entropy, &split, &scale, &png)) RESULT_ERROR(&core_.valid, "ImageDecoder: could not parse ImageDecoderArgs");
+    else if (png < PNG_REFUSE || png > PNG_DECODE) RESULT_ERROR(&core_.valid, "ImageDecoder: invalid png %lld (REFUSE = 0, DECODE = 1)", png);
+    else if (png != PNG_DECODE && (image_type == 0 || image_type == 2))
       RESULT_ERROR(&core_.valid, "ImageDecoder: image_type %s is not supported (JPEG only)", image_type == 0 ? "PNG" : "ANY");
-    else if (image_type != -1 && image_type != 1) RESULT_ERROR(&core_.valid, "ImageDecoder: invalid image_type %d", image_type);
+    else if (image_type != -1 && (image_type < 0 || image_type > 2)) RESULT_ERROR(&core_.valid, "ImageDecoder: invalid image_type %d", image_type);
     else if (entropy < ENTROPY_HOST || entropy > ENTROPY_AUTO)
       RESULT_ERROR(&core_.valid, "ImageDecoder: invalid entropy %lld (HOST = 0, GPU = 1, AUTO = 2)", entropy);
     else if (split < SPLIT_INTERVAL || split > SPLIT_SUBSEQUENCE)
@@ -88,6 +106,8 @@ class ImageDecoderKernelHIPImpl : public BatchedKernel {
     scale_ = scale == 2 || scale == 4 || scale == 8 ? (int)scale : 1;
     entropy_ = (int)entropy;
     by_subsequence_ = split == SPLIT_SUBSEQUENCE;
+    png_ = png == PNG_DECODE;
+    image_type_ = image_type;
   }
   void validate(Result* result) override { core_.validate(result); }
 
@@ -96,28 +116,43 @@ class ImageDecoderKernelHIPImpl : public BatchedKernel {
     const i32 n = (i32)num_rows(img_col);
     if (n == 0) return;
     // the shape of the batch is that of its first element; every element is probed before anything is launched
-    st_jpeg_info first = {};
-    bool restarts = true;   // every row has restart intervals
+    static const u8 kPngSignature[8] = {0x89, 'P', 'N', 'G', 0x0d, 0x0a, 0x1a, 0x0a};
+    struct { int h, w, channels; } first = {0, 0, 0};
+    bool restarts = true;   // every JPEG row has restart intervals
+    is_png_.assign(n, 0);
+    i32 n_png = 0;
     for (i32 i = 0; i < n; ++i) {
-      st_jpeg_info info;
-      const int st = st_jpeg_probe(img_col[i].buffer, img_col[i].size, &info);
-      LOG_IF(FATAL, st != ST_OK) << "ImageDecoder: row " << i << " of the batch: " << info.message;
-      if (i == 0) first = info;
-      LOG_IF(FATAL, info.h != first.h || info.w != first.w || info.channels != first.channels)
-          << "ImageDecoder: row " << i << " of the batch changes shape inside a batch (" << info.w << "x" << info.h << "x" << info.channels
+      int h, w, channels;
+      // png = DECODE: image_type PNG takes every row for one, JPEG none, ANY (or absent) those that begin with the signature
+      const bool is_png = png_ && (image_type_ == TYPE_PNG || (image_type_ != TYPE_JPEG && img_col[i].size >= 8 && memcmp(img_col[i].buffer, kPngSignature, 8) == 0));
+      if (is_png) {
+        st_png_info info;
+        const int st = st_png_probe(img_col[i].buffer, img_col[i].size, &info);
+        LOG_IF(FATAL, st != ST_OK) << "ImageDecoder: row " << i << " of the batch: " << info.message;
+        LOG_IF(FATAL, scale_ != 1) << "ImageDecoder: row " << i << " of the batch: a PNG row cannot be decoded at scale_denom " << scale_
+                                   << " (scaled decoding is JPEG's)";
+        h = info.h; w = info.w; channels = info.channels;
+        is_png_[i] = 1;
+        ++n_png;
+      } else {
+        st_jpeg_info info;
+        const int st = st_jpeg_probe(img_col[i].buffer, img_col[i].size, &info);
+        LOG_IF(FATAL, st != ST_OK) << "ImageDecoder: row " << i << " of the batch: " << info.message;
+        LOG_IF(FATAL, entropy_ == ENTROPY_GPU && !by_subsequence_ && info.restart_interval <= 0)
+            << "ImageDecoder: row " << i << " of the batch: no restart intervals: the stream has no DRI segment, entropy = GPU needs one";
+        restarts = restarts && info.restart_interval > 0;
+        h = info.h; w = info.w; channels = info.channels;
+      }
+      if (i == 0) { first.h = h; first.w = w; first.channels = channels; }
+      LOG_IF(FATAL, h != first.h || w != first.w || channels != first.channels)
+          << "ImageDecoder: row " << i << " of the batch changes shape inside a batch (" << w << "x" << h << "x" << channels
           << " after " << first.w << "x" << first.h << "x" << first.channels << ")";
-      LOG_IF(FATAL, entropy_ == ENTROPY_GPU && !by_subsequence_ && info.restart_interval <= 0)
-          << "ImageDecoder: row " << i << " of the batch: no restart intervals: the stream has no DRI segment, entropy = GPU needs one";
-      restarts = restarts && info.restart_interval > 0;
     }
     const bool on_gpu = entropy_ == ENTROPY_GPU || (entropy_ == ENTROPY_AUTO && restarts);
     int oh = first.h, ow = first.w;
     LOG_IF(FATAL, st_jpeg_scaled_size(first.h, first.w, scale_, &oh, &ow) != ST_OK) << "ImageDecoder: no frame size at scale 1/" << scale_;
     FrameInfo info(oh, ow, first.channels, FrameType::U8);
     std::vector<Frame*> output_frames = new_frames(core_.device, info, n);
-    bufs_.resize(n);
-    sizes_.resize(n);
-    for (i32 i = 0; i < n; ++i) { bufs_[i] = img_col[i].buffer; sizes_[i] = img_col[i].size; }
     const size_t out_bytes = info.size(), out_stride = DeviceStage::align(out_bytes);
     u8* dev = nullptr;
     if (STAGED) {
@@ -126,14 +161,29 @@ class ImageDecoderKernelHIPImpl : public BatchedKernel {
     } else {
       output_ptrs(dst_, output_frames);
     }
+    // the JPEG rows first in the three arrays, then the PNG rows: each call takes its own run of pointers
+    const i32 n_jpeg = n - n_png;
+    bufs_.resize(n);
+    sizes_.resize(n);
+    sub_dst_.resize(n);
+    for (i32 i = 0, j = 0, p = n_jpeg; i < n; ++i) {
+      const i32 k = is_png_[i] ? p++ : j++;
+      bufs_[k] = img_col[i].buffer; sizes_[k] = img_col[i].size; sub_dst_[k] = dst_[i];
+    }
     st_ctx* ctx = core_.ctx;
-    const int st = scale_ != 1 ? st_jpeg_decode_batch_scaled(ctx, bufs_.data(), sizes_.data(), n, first.h, first.w, first.channels, scale_,
-                                                             by_subsequence_ ? ST_JPEG_ENTROPY_SUBSEQUENCE : on_gpu ? ST_JPEG_ENTROPY_INTERVAL : ST_JPEG_ENTROPY_HOST,
-                                                             nullptr, dst_.data())
-                   : by_subsequence_ ? st_jpeg_decode_batch_gpu_split(ctx, bufs_.data(), sizes_.data(), n, first.h, first.w, first.channels, dst_.data(), nullptr)
-                   : on_gpu ? st_jpeg_decode_batch_gpu(ctx, bufs_.data(), sizes_.data(), n, first.h, first.w, first.channels, dst_.data())
-                          : st_jpeg_decode_batch(ctx, bufs_.data(), sizes_.data(), n, first.h, first.w, first.channels, dst_.data());
-    LOG_IF(FATAL, st != ST_OK) << "ImageDecoder: " << st_ctx_last_error(ctx);
+    if (n_jpeg > 0) {
+      const int st = scale_ != 1 ? st_jpeg_decode_batch_scaled(ctx, bufs_.data(), sizes_.data(), n_jpeg, first.h, first.w, first.channels, scale_,
+                                                               by_subsequence_ ? ST_JPEG_ENTROPY_SUBSEQUENCE : on_gpu ? ST_JPEG_ENTROPY_INTERVAL : ST_JPEG_ENTROPY_HOST,
+                                                               nullptr, sub_dst_.data())
+                     : by_subsequence_ ? st_jpeg_decode_batch_gpu_split(ctx, bufs_.data(), sizes_.data(), n_jpeg, first.h, first.w, first.channels, sub_dst_.data(), nullptr)
+                     : on_gpu ? st_jpeg_decode_batch_gpu(ctx, bufs_.data(), sizes_.data(), n_jpeg, first.h, first.w, first.channels, sub_dst_.data())
+                            : st_jpeg_decode_batch(ctx, bufs_.data(), sizes_.data(), n_jpeg, first.h, first.w, first.channels, sub_dst_.data());
+      LOG_IF(FATAL, st != ST_OK) << "ImageDecoder: " << st_ctx_last_error(ctx);
+    }
+    if (n_png > 0) {
+      const int st = st_png_decode_batch(ctx, bufs_.data() + n_jpeg, sizes_.data() + n_jpeg, n_png, first.h, first.w, first.channels, sub_dst_.data() + n_jpeg);
+      LOG_IF(FATAL, st != ST_OK) << "ImageDecoder: " << st_ctx_last_error(ctx);
+    }
     core_.sync();
     if (STAGED) stage_.download_frames(output_frames, dev, out_stride, out_bytes);
     for (i32 i = 0; i < n; ++i) insert_frame(output_columns[0], output_frames[i]);
@@ -145,6 +195,10 @@ class ImageDecoderKernelHIPImpl : public BatchedKernel {
   int entropy_ = ENTROPY_HOST;
   int scale_ = 1;
   bool by_subsequence_ = false;
+  bool png_ = false;        // png = DECODE
+  int image_type_ = -1;     // -1: the field is absent
+  std::vector<char> is_png_;
+  std::vector<uint8_t*> sub_dst_;
   std::vector<const uint8_t*> bufs_;
   std::vector<size_t> sizes_;
   std::vector<uint8_t*> dst_;

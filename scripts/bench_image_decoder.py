@@ -46,6 +46,18 @@ calls of 32 and 256 frames on the host path (ST_JPEG_THREADS=16) and on the inte
 the median and range of three medians of --rounds calls, and the ST_K_JPEG bracket per frame.  Denominator 1 is the yardstick:
 code the scale does not touch.  With 4 among them it also times decode + Resize to the 1/4 size beside decode(scale=4), for the
 reader only (the two do not produce the same pixels).  With --trace it makes three calls per denominator, path and call size.
+
+    python scripts/bench_image_decoder.py --png [--rounds 3]
+    rocprofv3 --kernel-trace --stats -d DIR -- python scripts/bench_image_decoder.py --png --trace
+
+--png measures decode_png (st_png_decode_batch: inflate on ST_PNG_THREADS=16 host threads, filter reconstruction and expansion
+in HIP kernels) on the same 1080p pictures stored as RGB PNG at deflate levels 1 and 6, the rows' filter types cycling through
+Sub, Up, Average and Paeth, written by the writer of tests/png_cases.py (Pillow need not be there).  Calls of 1, 8, 32 and 256
+streams: frames/s end to end (synchronised), the wall time of a call, the wall time of inflating the call's streams alone on 16
+host threads (st_zlib_inflate), and the ST_K_JPEG kernel time of the call from the library's events.  Beside it, in the same
+run, Pillow's full decode of the same streams on 16 threads -- or, where Pillow is missing, zlib.decompress plus the library's
+CPU twin (st_png_decode_host) on 16 threads; "yardstick" in the output says which.  And the inflater alone on one thread in MB/s
+of output against zlib.decompress on the same streams.  With --trace it makes three calls per level and call size.
 """
 import argparse
 import ctypes
@@ -69,15 +81,19 @@ BLOCKS = (W // 16) * ((H + 15) // 16) * 6
 MODEL_BYTES = BLOCKS * 128 + 2 * BLOCKS * 64 + H * W * 3
 
 
+def picture(i):
+    rng = np.random.default_rng(100 + i)
+    y, x = np.mgrid[0:H, 0:W].astype(np.float32)
+    ph = rng.uniform(0, 6.28, 6)
+    img = np.stack([127 + 100 * np.sin(x / 37 + ph[0]) * np.cos(y / 23 + ph[1]), 127 + 100 * np.sin((x + y) / 51 + ph[2]) * np.cos(y / 9 + ph[3]),
+                    127 + 100 * np.cos(x / 13 + ph[4]) * np.sin((x - y) / 29 + ph[5])], axis=-1)
+    return np.clip(img + rng.normal(0, 12, img.shape), 0, 255).astype(np.uint8)   # sensor-like noise: a few hundred KB at q75
+
+
 def make_streams(Image, quality):
     out = []
     for i in range(DISTINCT):
-        rng = np.random.default_rng(100 + i)
-        y, x = np.mgrid[0:H, 0:W].astype(np.float32)
-        ph = rng.uniform(0, 6.28, 6)
-        img = np.stack([127 + 100 * np.sin(x / 37 + ph[0]) * np.cos(y / 23 + ph[1]), 127 + 100 * np.sin((x + y) / 51 + ph[2]) * np.cos(y / 9 + ph[3]),
-                        127 + 100 * np.cos(x / 13 + ph[4]) * np.sin((x - y) / 29 + ph[5])], axis=-1)
-        img = np.clip(img + rng.normal(0, 12, img.shape), 0, 255).astype(np.uint8)   # sensor-like noise: a few hundred KB at q75
+        img = picture(i)
         buf = io.BytesIO()
         Image.fromarray(img).save(buf, "JPEG", quality=quality, subsampling="4:2:0")
         out.append(buf.getvalue())
@@ -277,6 +293,93 @@ def scaled(args, Image):
     print(json.dumps(result))
 
 
+PNG_BATCHES = (1, 8, 32, 256)
+
+
+def png(args):
+    import zlib
+    import torch
+    from scannertools_amd import _native
+    from scannertools_amd.hip import HipContext, png_decode_host, zlib_inflate
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+    import png_cases as pc
+    try:
+        from PIL import Image
+    except ImportError:
+        Image = None
+    os.environ["ST_PNG_THREADS"] = "16"
+    ctx = HipContext(0)
+    L = _native.lib()
+    result = {"bench": "image_decoder_png", "h": H, "w": W, "colour_type": "RGB 8", "filters": "Sub, Up, Average, Paeth by row", "host_threads": 16,
+              "calls_per_median": args.rounds, "yardstick": "Pillow on 16 threads" if Image else "zlib.decompress + st_png_decode_host on 16 threads",
+              "levels": {}}
+    pictures = [picture(i) for i in range(DISTINCT)]
+    raws = [pc.filter_rows(pc.scanlines(p, 2, 8), 3, [1 + y % 4 for y in range(H)]).tobytes() for p in pictures]
+    out = torch.empty((max(PNG_BATCHES), H, W, 3), dtype=torch.uint8, device=ctx.device)
+    sink = [np.empty(len(raws[0]), np.uint8) for _ in range(16)]
+    for level in (1, 6):
+        zs = [pc.deflate(r, level) for r in raws]
+        streams = [pc.write_png(p, 2, zdata=z) for p, z in zip(pictures, zs)]
+        assert np.array_equal(ctx.decode_png(streams[:1]).cpu().numpy()[0], pictures[0]), "decode differs from the picture"
+        r = {"stream_bytes": int(statistics.mean(len(s) for s in streams)), "inflated_bytes": len(raws[0])}
+
+        def call(n):
+            ctx.decode_png([streams[i % DISTINCT] for i in range(n)], out=out[:n])
+            ctx.sync()
+
+        if args.trace:
+            for n in PNG_BATCHES:
+                for _ in range(3):
+                    call(n)
+            result["levels"]["z%d" % level] = r
+            continue
+        # the inflater alone, one thread, against zlib on the same streams
+        t0 = time.perf_counter()
+        for z, raw in zip(zs, raws):
+            assert zlib_inflate(z, len(raw)) == raw
+        ours = time.perf_counter() - t0
+        t0 = time.perf_counter()
+        for z in zs:
+            zlib.decompress(z)
+        theirs = time.perf_counter() - t0
+        mb = sum(len(x) for x in raws) / 1e6
+        r["inflate_one_thread_MBps"] = {"st_zlib_inflate": round(mb / ours, 1), "zlib_decompress": round(mb / theirs, 1), "ratio": round(theirs / ours, 3)}
+
+        def inflate_only(i):
+            z, buf = zs[i % DISTINCT], sink[i % 16]
+            assert L.st_zlib_inflate(z, len(z), buf.ctypes.data, buf.size, None, None, 0) == 0
+
+        def yardstick(i):
+            if Image:
+                Image.open(io.BytesIO(streams[i % DISTINCT])).load()
+            else:
+                zlib.decompress(zs[i % DISTINCT])
+                png_decode_host(streams[i % DISTINCT])
+
+        calls = {}
+        with ThreadPoolExecutor(16) as pool:
+            for n in PNG_BATCHES:
+                c = {"fps": round(rate(lambda: call(n), n, args.rounds), 1)}
+                c["call_ms"] = round(1e3 * n / c["fps"], 2)
+                c["inflate_alone_ms"] = round(1e3 * n / rate(lambda: list(pool.map(inflate_only, range(n))), n, args.rounds), 2)
+                c["yardstick_fps"] = round(rate(lambda: list(pool.map(yardstick, range(n))), n, args.rounds), 1)
+                calls["batch%d" % n] = c
+        ctx.timing_enable([_native.K_JPEG])
+        for n in PNG_BATCHES:
+            call(n)
+            ctx.timing_reset()
+            for _ in range(args.rounds):
+                call(n)
+            launches, ms = ctx.timing_read(_native.K_JPEG)
+            calls["batch%d" % n]["kernel_ms"] = round(ms / args.rounds, 3)
+            calls["batch%d" % n]["launches"] = launches / args.rounds
+        ctx.timing_enable([])
+        r["calls"] = calls
+        result["levels"]["z%d" % level] = r
+    ctx.close()
+    print(json.dumps(result))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=5)
@@ -287,7 +390,10 @@ def main():
     ap.add_argument("--subseq-bytes", type=int, default=None, help="with --split subsequence: bytes per lane (default: the library's)")
     ap.add_argument("--scale", type=int, nargs="+", choices=(1, 2, 4, 8), default=None,
                     help="measure decode_jpeg(scale=d) for each denominator given, on the host path and the interval path")
+    ap.add_argument("--png", action="store_true", help="measure decode_png on 1080p RGB PNG streams at deflate levels 1 and 6")
     args = ap.parse_args()
+    if args.png:
+        return png(args)
     try:
         from PIL import Image
     except ImportError:
