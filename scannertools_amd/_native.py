@@ -246,7 +246,7 @@ def source_hash():
     srcs = ["st_context.hip", "st_hist.hip", "st_farneback.hip", "st_flowvis.hip", "st_imgproc.hip", "st_pose.hip", "st_conv.hip",
             "st_conv_tile_bf16x3.hip", "st_conv_tile_f32.hip", "st_framestats.hip", "st_jpeg.hip", "st_netinput.hip", "st_nn.hip", "st_detect.hip", "st_jpeg_enc.hip", "st_jpeg_entropy.hip", "st_jpeg_subseq.hip", "st_jpeg_reduced.hip", "st_png.hip", "st_jpeg_parse.cpp", "st_jpeg_enc_host.cpp", "st_png_host.cpp", "st_internal.h",
             "st_conv_tile.h", "st_jpeg_parse.h", "st_jpeg_enc_host.h", "st_jpeg_entropy.h", "st_jpeg_dense.h", "st_jpeg_enc_opt.h", "st_png_host.h",
-            os.path.join("..", "..", "include", "scannertools_hip.h"), "Makefile"]
+            "st_host_pipeline.h", os.path.join("..", "..", "include", "scannertools_hip.h"), "Makefile"]
     hsh = hashlib.sha256()
     for f in srcs:
         hsh.update(open(os.path.join(CSRC, f), "rb").read())

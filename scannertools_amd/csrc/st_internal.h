@@ -95,6 +95,70 @@ int st_set_error(st_ctx* ctx, int status, const char* fmt, ...);
 // Enter an API call: null check + select device.
 int st_enter(st_ctx* ctx);
 
+// The checks a batch decoder begins with (codec: "jpeg" or "png"; channels_ok: bit c set where c channels can be asked
+// for).  The caller then returns ST_OK itself when n is 0.
+inline int st_decode_args(st_ctx* ctx, const char* codec, int n, int h, int w, int channels, unsigned channels_ok, const void* bufs_host,
+                          const void* sizes, const void* out_dev) {
+  if (n < 0 || h <= 0 || w <= 0 || h > 65535 || w > 65535 || channels < 0 || channels > 31 || !(channels_ok >> channels & 1))
+    return st_set_error(ctx, ST_ERR_INVALID, "%s: bad arguments (n=%d h=%d w=%d channels=%d)", codec, n, h, w, channels);
+  if (n > 0 && (!bufs_host || !sizes || !out_dev)) return st_set_error(ctx, ST_ERR_INVALID, "%s: null argument", codec);
+  return ST_OK;
+}
+constexpr const char* kStNoOutputFrame = "%s: stream %d has no output frame";   // (codec, stream), ST_ERR_INVALID
+
+// Grows a page-locked buffer to `bytes` (its contents are not kept); oom_fmt words the failure and may print the size (%zu).
+inline int st_pinned_grow(st_ctx* ctx, void** p, size_t* cap, size_t bytes, const char* oom_fmt) {
+  if (bytes <= *cap) return ST_OK;
+  if (*p) ST_HIP(ctx, hipHostFree(*p));
+  *p = nullptr;
+  *cap = 0;
+  if (hipHostMalloc(p, bytes, hipHostMallocDefault) != hipSuccess) {
+    (void)hipGetLastError();
+    *p = nullptr;
+    return st_set_error(ctx, ST_ERR_OOM, oom_fmt, bytes);
+  }
+  *cap = bytes;
+  return ST_OK;
+}
+
+// The two page-locked upload slots of a pipelined decoder (st_host_pipeline.h): sub-batch k is filled into slot k & 1 and
+// copied to the device from there.
+struct st_pinned_slots {
+  void* pin[2] = {nullptr, nullptr};
+  size_t cap[2] = {0, 0};
+  hipEvent_t copied[2] = {nullptr, nullptr};   // the slot's last copy has left host memory
+  bool busy[2] = {false, false};               // a copy was enqueued that `copied` has not been waited for since
+  uint8_t* at(int s) const { return static_cast<uint8_t*>(pin[s]); }
+};
+// A slot is refilled only after its previous copy (of this call or an earlier one) has read it.
+inline int st_slot_release(st_ctx* ctx, st_pinned_slots* sl, int s) {
+  if (sl->busy[s]) ST_HIP(ctx, hipEventSynchronize(sl->copied[s]));
+  sl->busy[s] = false;
+  return ST_OK;
+}
+// The first `count` slots ready to be filled with up to `bytes`.
+inline int st_slots_prepare(st_ctx* ctx, st_pinned_slots* sl, int count, size_t bytes, const char* oom_fmt) {
+  for (int s = 0; s < count; ++s) {
+    if (!sl->copied[s]) ST_HIP(ctx, hipEventCreateWithFlags(&sl->copied[s], hipEventDisableTiming));
+    ST_TRY(st_slot_release(ctx, sl, s));
+    ST_TRY(st_pinned_grow(ctx, &sl->pin[s], &sl->cap[s], bytes, oom_fmt));
+  }
+  return ST_OK;
+}
+// enqueues the copy of a filled slot
+inline int st_slot_upload(st_ctx* ctx, st_pinned_slots* sl, int s, void* dst_dev, size_t bytes) {
+  ST_HIP(ctx, hipMemcpyAsync(dst_dev, sl->pin[s], bytes, hipMemcpyHostToDevice, ctx->stream));
+  ST_HIP(ctx, hipEventRecord(sl->copied[s], ctx->stream));
+  sl->busy[s] = true;
+  return ST_OK;
+}
+inline void st_slots_free(st_pinned_slots* sl) {
+  for (int s = 0; s < 2; ++s) {
+    if (sl->copied[s]) (void)hipEventDestroy(sl->copied[s]);
+    if (sl->pin[s]) (void)hipHostFree(sl->pin[s]);
+  }
+}
+
 // Marks `ctx` as having an OpticalFlow call in flight and says whether TWO OR MORE other contexts of this process have one in
 // flight on the same device (entered within the last 50 ms and not synchronised since): then a small launch should not take a
 // whole CU per workgroup.  A scheduling decision only -- the kernels it chooses between agree bit for bit.

@@ -18,12 +18,11 @@
 #include <algorithm>
 #include <atomic>
 #include <climits>
-#include <condition_variable>
-#include <cstdlib>
 #include <cstring>
 #include <mutex>
 #include <thread>
 
+#include "st_host_pipeline.h"
 #include "st_internal.h"
 #include "st_jpeg_dense.h"
 #include "st_jpeg_entropy.h"
@@ -219,13 +218,9 @@ __global__ __launch_bounds__(256) void k_jpeg_color(JpegArgsK a) {
 }
 
 // ---- host ---------------------------------------------------------------------------------------------------------------
-struct SubBatch { int first, count; size_t blocks; };
+struct SubBatch : StPipeSubBatch { size_t blocks; };
 
-int jpeg_threads(int n) {
-  int t = (int)std::min(16u, std::max(1u, std::thread::hardware_concurrency()));
-  if (const char* e = getenv("ST_JPEG_THREADS")) t = atoi(e);
-  return std::max(1, std::min(std::min(t, 64), n));
-}
+int jpeg_threads(int n) { return st_pipe_threads("ST_JPEG_THREADS", n); }
 
 // the header the two dense kernels read, from a parsed stream; d: the scale denominator (1: full size)
 void jpeg_frame_hdr(const StJpegHeader& hd, uint8_t* out, int blk_off, JpegFrameHdr* fh, int d) {
@@ -254,15 +249,36 @@ void jpeg_frame_hdr(const StJpegHeader& hd, uint8_t* out, int blk_off, JpegFrame
   for (int c = 0; c < hd.ncomp; ++c) memcpy(fh->quant[c], hd.quant[hd.tq[c]], 128);
 }
 
+// output pixels per lane of the colour kernels: 16 or 4 where the width written and every frame's address are multiples of it
+int store_width(int ow, uint8_t* const* out_dev, int n) {
+  unsigned align = 0;
+  for (int i = 0; i < n; ++i) align |= (unsigned)(uintptr_t)out_dev[i];
+  return (ow % 16 == 0 && (align & 15) == 0) ? 16 : ((ow % 4 == 0 && (align & 3) == 0) ? 4 : 1);
+}
+
+// what sizes the dense grids of a sub-batch: the most blocks any frame has, and the most of st_jpeg_reduced_counts
+struct DenseMost { size_t most = 0, most1 = 0, mostlds = 0; };
+DenseMost dense_most(const JpegFrameHdr* fh, int count) {
+  DenseMost m;
+  for (int j = 0; j < count; ++j) {
+    m.most = std::max(m.most, (size_t)fh[j].nblk_y + 2 * (size_t)fh[j].nblk_c);
+    size_t n1, nlds;
+    st_jpeg_reduced_counts(fh[j], &n1, &nlds);
+    m.most1 = std::max(m.most1, n1);
+    m.mostlds = std::max(m.mostlds, nlds);
+  }
+  return m;
+}
+
 // the dense launches of nfl frames whose headers start at a.slot: the full-size pair, or the reduced ones
-void launch_dense(st_ctx* ctx, JpegArgsK a, int nfl, int d, int px, size_t most, size_t most1, size_t mostlds) {
+void launch_dense(st_ctx* ctx, JpegArgsK a, int nfl, int d, int px, const DenseMost& m) {
   if (d > 1) {
     a.h = (a.h + d - 1) / d;
     a.w = (a.w + d - 1) / d;
-    st_jpeg_reduced_launch(ctx, a, nfl, most1, mostlds, px);
+    st_jpeg_reduced_launch(ctx, a, nfl, m.most1, m.mostlds, px);
     return;
   }
-  hipLaunchKernelGGL(k_jpeg_idct, dim3((unsigned)((most + kIdctBlocks - 1) / kIdctBlocks), nfl), dim3(256), 0, ctx->stream, a);
+  hipLaunchKernelGGL(k_jpeg_idct, dim3((unsigned)((m.most + kIdctBlocks - 1) / kIdctBlocks), nfl), dim3(256), 0, ctx->stream, a);
   long long bx = ((long long)a.h * a.w / px + 255) / 256;
   if (bx > 8192) bx = 8192;
   const dim3 grid((unsigned)bx, nfl);
@@ -276,24 +292,19 @@ constexpr size_t kSlotCoefBytes = (size_t)64 << 20;   // coefficients of one sub
 }  // namespace
 
 struct st_jpeg_state {
-  uint8_t* pin[2] = {nullptr, nullptr};
-  size_t cap[2] = {0, 0};
-  hipEvent_t copied[2] = {nullptr, nullptr};   // the slot's last copy has left host memory
-  bool busy[2] = {false, false};
+  st_pinned_slots slots;   // of st_jpeg_decode_batch
   // st_jpeg_decode_batch_gpu: its one upload slot (the call waits for every sub-batch, so the slot is free when it is
-  // refilled) and the page-locked word the status comes back in
-  uint8_t* gpin = nullptr;
+  // refilled) and the page-locked words the status comes back in
+  void* gpin = nullptr;
   size_t gcap = 0;
-  unsigned long long* gstatus = nullptr;
+  void* gstatus = nullptr;
+  size_t gstatus_cap = 0;
   int split_rounds = 0;   // st_jpeg_split_last_rounds
 };
 
 void st_jpeg_release(st_ctx* ctx) {
   if (!ctx->jpeg) return;
-  for (int s = 0; s < 2; ++s) {
-    if (ctx->jpeg->copied[s]) (void)hipEventDestroy(ctx->jpeg->copied[s]);
-    if (ctx->jpeg->pin[s]) (void)hipHostFree(ctx->jpeg->pin[s]);
-  }
+  st_slots_free(&ctx->jpeg->slots);
   if (ctx->jpeg->gpin) (void)hipHostFree(ctx->jpeg->gpin);
   if (ctx->jpeg->gstatus) (void)hipHostFree(ctx->jpeg->gstatus);
   delete ctx->jpeg;
@@ -301,18 +312,26 @@ void st_jpeg_release(st_ctx* ctx) {
 }
 
 namespace {
+constexpr unsigned kJpegChannels = 1u << 1 | 1u << 3;
+
+// ctx->jpeg, made at the first call
+int jpeg_state(st_ctx* ctx, st_jpeg_state** js) {
+  if (!ctx->jpeg) ctx->jpeg = new (std::nothrow) st_jpeg_state();
+  if (!ctx->jpeg) return st_set_error(ctx, ST_ERR_OOM, "jpeg: out of host memory");
+  *js = ctx->jpeg;
+  return ST_OK;
+}
+
 // st_jpeg_decode_batch, the frames written at 1/d
 int decode_batch_host(st_ctx* ctx, const uint8_t* const* bufs_host, const size_t* sizes, int n, int h, int w, int channels, uint8_t* const* out_dev,
                       const int d) {
-  if (n < 0 || h <= 0 || w <= 0 || h > 65535 || w > 65535 || (channels != 1 && channels != 3))
-    return st_set_error(ctx, ST_ERR_INVALID, "jpeg: bad arguments (n=%d h=%d w=%d channels=%d)", n, h, w, channels);
+  ST_TRY(st_decode_args(ctx, "jpeg", n, h, w, channels, kJpegChannels, bufs_host, sizes, out_dev));
   if (n == 0) return ST_OK;
-  if (!bufs_host || !sizes || !out_dev) return st_set_error(ctx, ST_ERR_INVALID, "jpeg: null argument");
   // every stream's markers first: nothing is launched or written unless all of them are streams this decodes, of one shape
   std::vector<StJpegHeader> hds((size_t)n);
   for (int i = 0; i < n; ++i) {
     char msg[160];
-    if (!out_dev[i]) return st_set_error(ctx, ST_ERR_INVALID, "jpeg: stream %d has no output frame", i);
+    if (!out_dev[i]) return st_set_error(ctx, ST_ERR_INVALID, kStNoOutputFrame, "jpeg", i);
     const int st = st_jpeg_parse_header(bufs_host[i], sizes[i], &hds[i], msg, sizeof msg);
     if (st != ST_OK) return st_set_error(ctx, st, "jpeg: stream %d: %s", i, msg);
     if (hds[i].h != h || hds[i].w != w || hds[i].ncomp != channels)
@@ -321,152 +340,52 @@ int decode_batch_host(st_ctx* ctx, const uint8_t* const* bufs_host, const size_t
   }
   const int T = jpeg_threads(n);
   std::vector<SubBatch> sbs;
-  std::vector<int> sb_of((size_t)n), blk_off((size_t)n);
+  std::vector<int> blk_off((size_t)n);
   for (int i = 0; i < n; ++i) {
     const size_t nb = st_jpeg_blocks(hds[i]);
-    if (sbs.empty() || sbs.back().count >= T || (sbs.back().blocks + nb) * 128 > kSlotCoefBytes) sbs.push_back(SubBatch{i, 0, 0});
-    sb_of[i] = (int)sbs.size() - 1;
+    if (sbs.empty() || sbs.back().count >= T || (sbs.back().blocks + nb) * 128 > kSlotCoefBytes) sbs.push_back(SubBatch{{i, 0}, 0});
     blk_off[i] = (int)sbs.back().blocks;
     sbs.back().count++;
     sbs.back().blocks += nb;
   }
-  const int nsb = (int)sbs.size();
+  auto upload_bytes = [](const SubBatch& sb) { return (size_t)sb.count * sizeof(JpegFrameHdr) + sb.blocks * 128; };
   size_t slot_bytes = 0, plane_bytes = 0;
   for (const SubBatch& sb : sbs) {
-    slot_bytes = std::max(slot_bytes, (size_t)sb.count * sizeof(JpegFrameHdr) + sb.blocks * 128);
+    slot_bytes = std::max(slot_bytes, upload_bytes(sb));
     plane_bytes = std::max(plane_bytes, sb.blocks * 64);
   }
-  if (!ctx->jpeg) {
-    ctx->jpeg = new (std::nothrow) st_jpeg_state();
-    if (!ctx->jpeg) return st_set_error(ctx, ST_ERR_OOM, "jpeg: out of host memory");
-  }
-  st_jpeg_state* js = ctx->jpeg;
-  for (int s = 0; s < std::min(2, nsb); ++s) {
-    if (!js->copied[s]) ST_HIP(ctx, hipEventCreateWithFlags(&js->copied[s], hipEventDisableTiming));
-    // a slot is refilled only after its previous copy (of this call or an earlier one) has read it
-    if (js->busy[s]) { ST_HIP(ctx, hipEventSynchronize(js->copied[s])); js->busy[s] = false; }
-    if (slot_bytes > js->cap[s]) {
-      if (js->pin[s]) ST_HIP(ctx, hipHostFree(js->pin[s]));
-      js->pin[s] = nullptr;
-      js->cap[s] = 0;
-      if (hipHostMalloc((void**)&js->pin[s], slot_bytes, hipHostMallocDefault) != hipSuccess) {
-        (void)hipGetLastError();
-        js->pin[s] = nullptr;
-        return st_set_error(ctx, ST_ERR_OOM, "jpeg: cannot page-lock %zu bytes for the coefficients", slot_bytes);
-      }
-      js->cap[s] = slot_bytes;
-    }
-  }
+  st_jpeg_state* js;
+  ST_TRY(jpeg_state(ctx, &js));
+  st_pinned_slots* sl = &js->slots;
+  ST_TRY(st_slots_prepare(ctx, sl, std::min(2, (int)sbs.size()), slot_bytes, "jpeg: cannot page-lock %zu bytes for the coefficients"));
   ST_TRY(st_ws_reserve(ctx, st_align_up(slot_bytes) + st_align_up(plane_bytes)));
   uint8_t* d_slot = (uint8_t*)st_ws_alloc(ctx, slot_bytes);
   uint8_t* d_planes = (uint8_t*)st_ws_alloc(ctx, plane_bytes);
   if (!d_slot || !d_planes) return st_set_error(ctx, ST_ERR_OOM, "jpeg: workspace exhausted");
+  const int px = store_width((w + d - 1) / d, out_dev, n);
 
-  // workers take streams in order; sub-batch k may be filled once `allowed` > k
-  struct Shared {
-    std::mutex mu;
-    std::condition_variable cv;
-    int allowed = 2;
-    std::vector<int> remaining;
-    bool failed = false;
-    int fail_status = ST_OK, fail_stream = -1;
-    char fail_msg[160];
-  } sh;
-  sh.remaining.resize((size_t)nsb);
-  for (int k = 0; k < nsb; ++k) sh.remaining[k] = sbs[k].count;
-  std::atomic<int> next{0};
-  auto work = [&]() {
-    for (;;) {
-      const int i = next.fetch_add(1);
-      if (i >= n) return;
-      const int k = sb_of[i];
-      bool skip;
-      {
-        std::unique_lock<std::mutex> lk(sh.mu);
-        sh.cv.wait(lk, [&] { return sh.allowed > k; });
-        skip = sh.failed;
-      }
-      int st = ST_OK;
-      char msg[160];
-      msg[0] = 0;
-      if (!skip) {
-        const StJpegHeader& hd = hds[i];
-        uint8_t* slot = js->pin[k & 1];
-        JpegFrameHdr* fh = reinterpret_cast<JpegFrameHdr*>(slot) + (i - sbs[k].first);
-        jpeg_frame_hdr(hd, out_dev[i], blk_off[i], fh, d);
-        int16_t* coef = reinterpret_cast<int16_t*>(slot + (size_t)sbs[k].count * sizeof(JpegFrameHdr) + (size_t)blk_off[i] * 128);
-        st = st_jpeg_decode_scan(bufs_host[i], sizes[i], hd, coef, msg, sizeof msg);
-      }
-      std::lock_guard<std::mutex> lk(sh.mu);
-      if (st != ST_OK && (!sh.failed || i < sh.fail_stream)) {
-        sh.failed = true;
-        sh.fail_status = st;
-        sh.fail_stream = i;
-        memcpy(sh.fail_msg, msg, sizeof msg);
-      }
-      --sh.remaining[k];
-      sh.cv.notify_all();
-    }
+  // a stream's header and coefficients into its sub-batch's slot
+  auto fill = [&](int i, int k, int s, char* msg, size_t msg_len) {
+    JpegFrameHdr* fh = reinterpret_cast<JpegFrameHdr*>(sl->at(s)) + (i - sbs[k].first);
+    jpeg_frame_hdr(hds[i], out_dev[i], blk_off[i], fh, d);
+    int16_t* coef = reinterpret_cast<int16_t*>(sl->at(s) + (size_t)sbs[k].count * sizeof(JpegFrameHdr) + (size_t)blk_off[i] * 128);
+    return st_jpeg_decode_scan(bufs_host[i], sizes[i], hds[i], coef, msg, msg_len);
   };
-  std::vector<std::thread> pool;
-  pool.reserve((size_t)T);
-  for (int t = 0; t < T; ++t) pool.emplace_back(work);
-
-  const unsigned align = [&] {
-    unsigned a = 0;
-    for (int i = 0; i < n; ++i) a |= (unsigned)(uintptr_t)out_dev[i];
-    return a;
-  }();
-  const int ow = (w + d - 1) / d;   // the width of the frames written
-  const int px = (ow % 16 == 0 && (align & 15) == 0) ? 16 : ((ow % 4 == 0 && (align & 3) == 0) ? 4 : 1);
-  auto issue = [&]() -> int {
-    for (int k = 0; k < nsb; ++k) {
-      {
-        std::unique_lock<std::mutex> lk(sh.mu);
-        sh.cv.wait(lk, [&] { return sh.remaining[k] == 0; });
-        if (sh.failed) return st_set_error(ctx, sh.fail_status, "jpeg: stream %d: %s", sh.fail_stream, sh.fail_msg);
-      }
-      const SubBatch& sb = sbs[k];
-      const int s = k & 1;
-      const size_t bytes = (size_t)sb.count * sizeof(JpegFrameHdr) + sb.blocks * 128;
-      ST_HIP(ctx, hipMemcpyAsync(d_slot, js->pin[s], bytes, hipMemcpyHostToDevice, ctx->stream));
-      ST_HIP(ctx, hipEventRecord(js->copied[s], ctx->stream));
-      js->busy[s] = true;
-      JpegArgsK a;
-      a.slot = d_slot; a.planes = d_planes; a.nf = sb.count; a.h = h; a.w = w; a.channels = channels;
-      size_t most = 0, most1 = 0, mostlds = 0;
-      for (int i = sb.first; i < sb.first + sb.count; ++i) {
-        most = std::max(most, st_jpeg_blocks(hds[i]));
-        size_t n1, nlds;
-        st_jpeg_reduced_counts(reinterpret_cast<const JpegFrameHdr*>(js->pin[s])[i - sb.first], &n1, &nlds);
-        most1 = std::max(most1, n1);
-        mostlds = std::max(mostlds, nlds);
-      }
-      {
-        st_timed t(ctx, ST_K_JPEG);
-        launch_dense(ctx, a, sb.count, d, px, most, most1, mostlds);
-      }
-      ST_HIP(ctx, hipGetLastError());
-      if (k + 2 < nsb) {
-        ST_HIP(ctx, hipEventSynchronize(js->copied[s]));
-        js->busy[s] = false;
-        std::lock_guard<std::mutex> lk(sh.mu);
-        sh.allowed = k + 3;
-        sh.cv.notify_all();
-      }
+  // one copy and the dense launches
+  auto issue = [&](int k, int s) -> int {
+    const SubBatch& sb = sbs[k];
+    ST_TRY(st_slot_upload(ctx, sl, s, d_slot, upload_bytes(sb)));
+    JpegArgsK a;
+    a.slot = d_slot; a.planes = d_planes; a.nf = sb.count; a.h = h; a.w = w; a.channels = channels;
+    {
+      st_timed t(ctx, ST_K_JPEG);
+      launch_dense(ctx, a, sb.count, d, px, dense_most(reinterpret_cast<const JpegFrameHdr*>(sl->at(s)), sb.count));
     }
+    ST_HIP(ctx, hipGetLastError());
     return ST_OK;
   };
-  const int status = issue();
-  {
-    // on an error the workers run out of streams without decoding them
-    std::lock_guard<std::mutex> lk(sh.mu);
-    if (status != ST_OK) sh.failed = true;
-    sh.allowed = INT_MAX;
-    sh.cv.notify_all();
-  }
-  for (std::thread& t : pool) t.join();
-  return status;
+  const StPipeResult r = st_pipe_run(sbs, T, fill, issue, [&](int s) { return st_slot_release(ctx, sl, s); });
+  return r.stream >= 0 ? st_set_error(ctx, r.status, "jpeg: stream %d: %s", r.stream, r.message) : r.status;
 }
 }  // namespace
 
@@ -536,23 +455,34 @@ void run_threads(int T, F&& f) {
   for (std::thread& t : pool) t.join();
 }
 
-}  // namespace
+// A call of st_jpeg_decode_batch_gpu (split = false: one lane per restart interval) or st_jpeg_decode_batch_gpu_split (split =
+// true: one lane per subsequence of S bytes, at most R round launches), which share everything but the entropy launches: its
+// arguments, what the steps below make of them in turn, and the steps.
+struct GpuPlan {
+  st_ctx* ctx;
+  const uint8_t* const* bufs_host;
+  const size_t* sizes;
+  int n, h, w, channels;
+  uint8_t* const* out_dev;
+  bool split;
+  uint32_t S;
+  int R, d, T;
+  std::vector<GpuStream> gs;
+  std::vector<std::vector<uint32_t>> ivs;   // the intervals (or segments) each scanning thread found
+  std::vector<GpuSubBatch> sbs;
+  size_t upload_most = 0, dev_most = 0, plane_most = 0;
 
-namespace {
-// st_jpeg_decode_batch_gpu (split = false: one lane per restart interval) and st_jpeg_decode_batch_gpu_split (split = true: one
-// lane per subsequence of S bytes, at most R round launches) share everything but the entropy launches.
-int decode_batch_gpu(st_ctx* ctx, const uint8_t* const* bufs_host, const size_t* sizes, int n, int h, int w, int channels, uint8_t* const* out_dev,
-                     const bool split, const uint32_t S, const int R, const int d) {
-  if (n < 0 || h <= 0 || w <= 0 || h > 65535 || w > 65535 || (channels != 1 && channels != 3))
-    return st_set_error(ctx, ST_ERR_INVALID, "jpeg: bad arguments (n=%d h=%d w=%d channels=%d)", n, h, w, channels);
-  if (n == 0) return ST_OK;
-  if (!bufs_host || !sizes || !out_dev) return st_set_error(ctx, ST_ERR_INVALID, "jpeg: null argument");
-  const int T = jpeg_threads(n);
+  int probe_and_scan();
+  void lay_out();
+  int fill_slot(const GpuSubBatch& sb, uint8_t* slot) const;
+  int run_sub_batch(const GpuSubBatch& sb, st_jpeg_state* js, uint8_t* d_up, uint8_t* d_planes, int px) const;
+};
 
-  // 1. every stream's markers and its restart intervals, on T threads over contiguous runs of streams.  The lowest stream
-  // that is refused wins; only when none is, the lowest stream whose scan is broken.  Nothing is launched or written before.
-  std::vector<GpuStream> gs((size_t)n);
-  std::vector<std::vector<uint32_t>> ivs((size_t)T);
+// 1. every stream's markers and its restart intervals, on T threads over contiguous runs of streams.  The lowest stream
+// that is refused wins; only when none is, the lowest stream whose scan is broken.  Nothing is launched or written before.
+int GpuPlan::probe_and_scan() {
+  gs.resize((size_t)n);
+  ivs.resize((size_t)T);
   struct Fail { int stream = INT_MAX, status = ST_OK; char msg[224]; };
   Fail probe_fail, scan_fail;
   std::mutex mu;
@@ -573,7 +503,7 @@ int decode_batch_gpu(st_ctx* ctx, const uint8_t* const* bufs_host, const size_t*
       char msg[160];
       for (int i = lo; i < hi; ++i) {
         GpuStream& g = gs[(size_t)i];
-        if (!out_dev[i]) { note(probe_fail, i, ST_ERR_INVALID, "jpeg: stream %d has no output frame", i); return; }
+        if (!out_dev[i]) { note(probe_fail, i, ST_ERR_INVALID, kStNoOutputFrame, "jpeg", i); return; }
         const int st = st_jpeg_parse_header(bufs_host[i], sizes[i], &hd, msg, sizeof msg);
         if (st != ST_OK) { note(probe_fail, i, st, "jpeg: stream %d: %s", i, msg); return; }
         if (hd.h != h || hd.w != w || hd.ncomp != channels) {
@@ -615,219 +545,206 @@ int decode_batch_gpu(st_ctx* ctx, const uint8_t* const* bufs_host, const size_t*
   }
   if (probe_fail.stream != INT_MAX) return st_set_error(ctx, probe_fail.status, "%s", probe_fail.msg);
   if (scan_fail.stream != INT_MAX) return st_set_error(ctx, scan_fail.status, "%s", scan_fail.msg);
+  return ST_OK;
+}
 
-  // 2. sub-batches and the layout of each one's upload
-  std::vector<GpuSubBatch> sbs;
-  size_t upload_most = 0, dev_most = 0, plane_most = 0;
+// 2. sub-batches and the layout of each one's upload
+void GpuPlan::lay_out() {
+  auto close = [&]() {
+    if (sbs.empty()) return;
+    GpuSubBatch& sb = sbs.back();
+    sb.tables_off = 16;
+    sb.frames_off = up16(sb.tables_off + (size_t)sb.nsets * sizeof(StJpegFrameTables));
+    size_t o = sb.frames_off + (size_t)sb.count * sizeof(StJpegEntFrame);
+    if (split) { sb.sq_off = o; o += (size_t)sb.count * sizeof(StJsqFrame); }
+    for (int i = sb.first; i < sb.first + sb.count; ++i) { gs[(size_t)i].iv_off = o; o += (size_t)gs[(size_t)i].nint * 8; }
+    if (split)
+      for (int i = sb.first; i < sb.first + sb.count; ++i) { gs[(size_t)i].subpre_off = o; o += ((size_t)gs[(size_t)i].nint + 1) * 4; }
+    o = up16(o);
+    for (int i = sb.first; i < sb.first + sb.count; ++i) { gs[(size_t)i].bytes_off = o; o += up16(gs[(size_t)i].nbytes + 16); }
+    sb.hdr_off = st_align_up(o);
+    sb.upload_bytes = sb.hdr_off + (size_t)sb.count * sizeof(JpegFrameHdr);
+    upload_most = std::max(upload_most, sb.upload_bytes);
+    // behind the coefficients: per lane two exit states, the entered-from state and four counts; per segment a flag; four
+    // counters of changed exits
+    sb.scratch_off = up16(sb.upload_bytes + sb.blocks * 128);
+    dev_most = std::max(dev_most, split ? sb.scratch_off + sb.lanes * 40 + up16(sb.nint * 4) + 16 : sb.upload_bytes + sb.blocks * 128);
+    plane_most = std::max(plane_most, sb.blocks * 64);
+  };
+  for (int i = 0; i < n; ++i) {
+    GpuStream& g = gs[(size_t)i];
+    if (sbs.empty() || (sbs.back().blocks + g.nblocks) * 128 > kGpuCoefBytes || sbs.back().lanes + g.nlanes > ((size_t)1 << 31) ||
+        sbs.back().nint + g.nint > ((size_t)1 << 31)) {
+      close();
+      sbs.push_back(GpuSubBatch());
+      sbs.back().first = i;
+    }
+    GpuSubBatch& sb = sbs.back();
+    g.sb = (int)sbs.size() - 1;
+    g.writes_tabs = sb.count == 0 || !g.same_tabs || gs[(size_t)i - 1].owner != g.owner;
+    if (g.writes_tabs) sb.nsets++;
+    g.tabs = sb.nsets - 1;
+    g.fh.blk_off = (int)sb.blocks;
+    g.lane_off = sb.lanes;
+    g.seg_off = sb.nint;
+    sb.lanes += g.nlanes;
+    sb.max_lane_groups = std::max(sb.max_lane_groups, (unsigned)((g.nlanes + (size_t)kStJsqLanes - 1) / (size_t)kStJsqLanes));
+    sb.max_segments = std::max(sb.max_segments, g.nint);
+    sb.count++;
+    sb.blocks += g.nblocks;
+    sb.nint += g.nint;
+    sb.max_groups = std::max(sb.max_groups, (g.nint + (unsigned)kStJpegEntLanes - 1) / (unsigned)kStJpegEntLanes);
+  }
+  close();
+}
+
+// 3. fill the slot on the threads (free: the previous sub-batch was waited for)
+int GpuPlan::fill_slot(const GpuSubBatch& sb, uint8_t* slot) const {
+  memset(slot, 0xFF, 16);   // the status word: clean
+  std::atomic<int> next{sb.first};
+  std::atomic<bool> bad{false};
+  run_threads(std::min(T, sb.count), [&](int) {
+    std::vector<StJpegHeader> hdv;
+    char msg[160];
+    for (;;) {
+      const int i = next.fetch_add(1);
+      if (i >= sb.first + sb.count) return;
+      const GpuStream& g = gs[(size_t)i];
+      const int j = i - sb.first;
+      StJpegEntFrame* ef = reinterpret_cast<StJpegEntFrame*>(slot + sb.frames_off) + j;
+      ef->geom = g.geom;
+      ef->nint = g.nint;
+      ef->tables = (uint32_t)g.tabs;
+      ef->intervals_off = g.iv_off;
+      ef->bytes_off = g.bytes_off;
+      ef->nbytes = (uint32_t)g.nbytes;
+      ef->blk_off = (uint32_t)g.fh.blk_off;
+      if (g.writes_tabs) {
+        if (hdv.empty()) hdv.resize(1);
+        if (st_jpeg_parse_header(bufs_host[i], sizes[i], &hdv[0], msg, sizeof msg) != ST_OK) { bad = true; return; }   // the caller changed the stream
+        frame_tables(hdv[0], reinterpret_cast<StJpegFrameTables*>(slot + sb.tables_off) + g.tabs);
+      }
+      const uint32_t* iv = ivs[(size_t)g.owner].data() + g.iv_at;
+      uint32_t* dv = reinterpret_cast<uint32_t*>(slot + g.iv_off);
+      for (size_t k = 0; k < 2 * (size_t)g.nint; ++k) dv[k] = iv[k] - (uint32_t)g.scan_pos;
+      if (split) {
+        StJsqFrame* qf = reinterpret_cast<StJsqFrame*>(slot + sb.sq_off) + j;
+        memset(qf, 0, sizeof *qf);
+        qf->subpre_off = g.subpre_off;
+        qf->lane_off = (uint32_t)g.lane_off;
+        qf->seg_off = (uint32_t)g.seg_off;
+        qf->nlanes = (uint32_t)g.nlanes;
+        uint32_t* pre = reinterpret_cast<uint32_t*>(slot + g.subpre_off);
+        uint32_t sum = 0;
+        for (size_t k = 0; k < g.nint; ++k) { pre[k] = sum; sum += st_jsq_count(iv[2 * k + 1] - iv[2 * k], S); }
+        pre[g.nint] = sum;
+      }
+      memcpy(slot + g.bytes_off, bufs_host[i] + g.scan_pos, g.nbytes);
+      memset(slot + g.bytes_off + g.nbytes, 0, up16(g.nbytes + 16) - g.nbytes);
+      memcpy(slot + sb.hdr_off + (size_t)j * sizeof(JpegFrameHdr), &g.fh, sizeof(JpegFrameHdr));
+    }
+  });
+  if (bad) return st_set_error(ctx, ST_ERR_INVALID, "jpeg: a stream changed during the call");
+  return ST_OK;
+}
+
+// 4. one copy of the filled slot (js->gpin), the entropy launch, the ONE host wait of the sub-batch (its status word), then the
+// dense kernels
+int GpuPlan::run_sub_batch(const GpuSubBatch& sb, st_jpeg_state* js, uint8_t* d_up, uint8_t* d_planes, int px) const {
+  unsigned long long* const gstatus = static_cast<unsigned long long*>(js->gstatus);
+  unsigned long long word = kStJpegEntClean;
   {
-    auto close = [&]() {
-      if (sbs.empty()) return;
-      GpuSubBatch& sb = sbs.back();
-      sb.tables_off = 16;
-      sb.frames_off = up16(sb.tables_off + (size_t)sb.nsets * sizeof(StJpegFrameTables));
-      size_t o = sb.frames_off + (size_t)sb.count * sizeof(StJpegEntFrame);
-      if (split) { sb.sq_off = o; o += (size_t)sb.count * sizeof(StJsqFrame); }
-      for (int i = sb.first; i < sb.first + sb.count; ++i) { gs[(size_t)i].iv_off = o; o += (size_t)gs[(size_t)i].nint * 8; }
-      if (split)
-        for (int i = sb.first; i < sb.first + sb.count; ++i) { gs[(size_t)i].subpre_off = o; o += ((size_t)gs[(size_t)i].nint + 1) * 4; }
-      o = up16(o);
-      for (int i = sb.first; i < sb.first + sb.count; ++i) { gs[(size_t)i].bytes_off = o; o += up16(gs[(size_t)i].nbytes + 16); }
-      sb.hdr_off = st_align_up(o);
-      sb.upload_bytes = sb.hdr_off + (size_t)sb.count * sizeof(JpegFrameHdr);
-      upload_most = std::max(upload_most, sb.upload_bytes);
-      // behind the coefficients: per lane two exit states, the entered-from state and four counts; per segment a flag; four
-      // counters of changed exits
-      sb.scratch_off = up16(sb.upload_bytes + sb.blocks * 128);
-      dev_most = std::max(dev_most, split ? sb.scratch_off + sb.lanes * 40 + up16(sb.nint * 4) + 16 : sb.upload_bytes + sb.blocks * 128);
-      plane_most = std::max(plane_most, sb.blocks * 64);
-    };
-    for (int i = 0; i < n; ++i) {
-      GpuStream& g = gs[(size_t)i];
-      if (sbs.empty() || (sbs.back().blocks + g.nblocks) * 128 > kGpuCoefBytes || sbs.back().lanes + g.nlanes > ((size_t)1 << 31) ||
-          sbs.back().nint + g.nint > ((size_t)1 << 31)) {
-        close();
-        sbs.push_back(GpuSubBatch());
-        sbs.back().first = i;
+    st_timed timed(ctx, ST_K_JPEG);
+    ST_HIP(ctx, hipMemcpyAsync(d_up, js->gpin, sb.upload_bytes, hipMemcpyHostToDevice, ctx->stream));
+    StJpegEntArgs ea;
+    ea.upload = d_up;
+    ea.frames = reinterpret_cast<const StJpegEntFrame*>(d_up + sb.frames_off);
+    ea.tables = reinterpret_cast<const StJpegFrameTables*>(d_up + sb.tables_off);
+    ea.coef = reinterpret_cast<int16_t*>(d_up + sb.upload_bytes);
+    ea.status = reinterpret_cast<unsigned long long*>(d_up);
+    ea.nf = sb.count;
+    ea.first_stream = sb.first;
+    if (!split) {
+      ST_TRY(st_jpeg_entropy_launch(ctx, ea, sb.max_groups));
+    } else {
+      StJsqArgs qa;
+      qa.ent = ea;
+      qa.sq = reinterpret_cast<const StJsqFrame*>(d_up + sb.sq_off);
+      uint8_t* scratch = d_up + sb.scratch_off;
+      qa.exits[0] = reinterpret_cast<uint64_t*>(scratch + sb.lanes * 16);
+      qa.exits[1] = reinterpret_cast<uint64_t*>(scratch + sb.lanes * 24);
+      qa.entered = reinterpret_cast<uint64_t*>(scratch + sb.lanes * 32);
+      qa.counts = reinterpret_cast<uint32_t*>(scratch);   // 16 bytes per lane, 16-byte aligned
+      qa.unconverged = reinterpret_cast<uint32_t*>(scratch + sb.lanes * 40);
+      qa.changed = reinterpret_cast<unsigned*>(scratch + sb.lanes * 40 + up16(sb.nint * 4));
+      qa.S = S;
+      // round launches in groups (three, then two at a time), one host wait per group for its counts of changed exits: a
+      // launch that changed none has verified the chain.  Launches behind it in its group change nothing either.
+      int launches = 0, rounds = R;
+      bool converged = false;
+      unsigned* back = reinterpret_cast<unsigned*>(gstatus + 1);
+      while (launches < R && !converged) {
+        const int group = std::min(launches == 0 ? 3 : 2, R - launches);
+        ST_HIP(ctx, hipMemsetAsync(qa.changed, 0, 16, ctx->stream));
+        for (int q = 0; q < group; ++q, ++launches) ST_TRY(st_jsq_round_launch(ctx, qa, sb.max_lane_groups, launches == 0, launches & 1, qa.changed + q));
+        ST_HIP(ctx, hipMemcpyAsync(back, qa.changed, 16, hipMemcpyDeviceToHost, ctx->stream));
+        ST_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        for (int q = 0; q < group && !converged; ++q)
+          if (back[q] == 0) { converged = true; rounds = launches - group + q; }
       }
-      GpuSubBatch& sb = sbs.back();
-      g.sb = (int)sbs.size() - 1;
-      g.writes_tabs = sb.count == 0 || !g.same_tabs || gs[(size_t)i - 1].owner != g.owner;
-      if (g.writes_tabs) sb.nsets++;
-      g.tabs = sb.nsets - 1;
-      g.fh.blk_off = (int)sb.blocks;
-      g.lane_off = sb.lanes;
-      g.seg_off = sb.nint;
-      sb.lanes += g.nlanes;
-      sb.max_lane_groups = std::max(sb.max_lane_groups, (unsigned)((g.nlanes + (size_t)kStJsqLanes - 1) / (size_t)kStJsqLanes));
-      sb.max_segments = std::max(sb.max_segments, g.nint);
-      sb.count++;
-      sb.blocks += g.nblocks;
-      sb.nint += g.nint;
-      sb.max_groups = std::max(sb.max_groups, (g.nint + (unsigned)kStJpegEntLanes - 1) / (unsigned)kStJpegEntLanes);
+      js->split_rounds = std::max(js->split_rounds, rounds);
+      ST_TRY(st_jsq_finish_launch(ctx, qa, sb.max_lane_groups, sb.max_segments, (launches - 1) & 1, sb.blocks * 128));
     }
-    close();
+    ST_HIP(ctx, hipMemcpyAsync(gstatus, d_up, sizeof word, hipMemcpyDeviceToHost, ctx->stream));
+    ST_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    word = *gstatus;
+    if (word == kStJpegEntClean) {
+      const DenseMost m = dense_most(reinterpret_cast<const JpegFrameHdr*>(static_cast<const uint8_t*>(js->gpin) + sb.hdr_off), sb.count);
+      // the dense kernels take the frame from blockIdx.y: at most 65 535 frames per launch, the headers offset so that the
+      // coefficients stay where slot + nf * 512 points
+      for (int f0 = 0; f0 < sb.count; f0 += 65535) {
+        const int nfl = std::min(65535, sb.count - f0);
+        JpegArgsK a;
+        a.slot = d_up + sb.hdr_off + (size_t)f0 * sizeof(JpegFrameHdr);
+        a.planes = d_planes; a.nf = sb.count - f0; a.h = h; a.w = w; a.channels = channels;
+        launch_dense(ctx, a, nfl, d, px, m);
+      }
+    }
   }
+  ST_HIP(ctx, hipGetLastError());
+  if (word != kStJpegEntClean) {
+    const int stream = (int)(word >> 32);
+    const unsigned interval = (unsigned)((word >> 4) & 0xfffffffu);
+    const unsigned nint = stream >= 0 && stream < n ? gs[(size_t)stream].nint : 0u;
+    if (split && stream >= 0 && stream < n && gs[(size_t)stream].geom.restart_interval <= 0)
+      return st_set_error(ctx, ST_ERR_INVALID, "jpeg: stream %d: corrupt scan: the scan: %s", stream, st_jpeg_entropy_cause((int)(word & 15)));
+    return st_set_error(ctx, ST_ERR_INVALID, "jpeg: stream %d: corrupt scan: restart interval %u of %u: %s", stream, interval, nint,
+                        st_jpeg_entropy_cause((int)(word & 15)));
+  }
+  return ST_OK;
+}
 
-  if (!ctx->jpeg) {
-    ctx->jpeg = new (std::nothrow) st_jpeg_state();
-    if (!ctx->jpeg) return st_set_error(ctx, ST_ERR_OOM, "jpeg: out of host memory");
-  }
-  st_jpeg_state* js = ctx->jpeg;
-  if (!js->gstatus && hipHostMalloc((void**)&js->gstatus, 64, hipHostMallocDefault) != hipSuccess) {
-    (void)hipGetLastError();
-    js->gstatus = nullptr;
-    return st_set_error(ctx, ST_ERR_OOM, "jpeg: cannot page-lock the status word");
-  }
-  if (upload_most > js->gcap) {
-    if (js->gpin) ST_HIP(ctx, hipHostFree(js->gpin));
-    js->gpin = nullptr;
-    js->gcap = 0;
-    const size_t want = upload_most + upload_most / 8;
-    if (hipHostMalloc((void**)&js->gpin, want, hipHostMallocDefault) != hipSuccess) {
-      (void)hipGetLastError();
-      js->gpin = nullptr;
-      return st_set_error(ctx, ST_ERR_OOM, "jpeg: cannot page-lock %zu bytes for the streams", want);
-    }
-    js->gcap = want;
-  }
-  ST_TRY(st_ws_reserve(ctx, st_align_up(dev_most) + st_align_up(plane_most)));
-  uint8_t* d_up = (uint8_t*)st_ws_alloc(ctx, dev_most);
-  uint8_t* d_planes = (uint8_t*)st_ws_alloc(ctx, plane_most);
+int decode_batch_gpu(st_ctx* ctx, const uint8_t* const* bufs_host, const size_t* sizes, int n, int h, int w, int channels, uint8_t* const* out_dev,
+                     const bool split, const uint32_t S, const int R, const int d) {
+  ST_TRY(st_decode_args(ctx, "jpeg", n, h, w, channels, kJpegChannels, bufs_host, sizes, out_dev));
+  if (n == 0) return ST_OK;
+  GpuPlan p{ctx, bufs_host, sizes, n, h, w, channels, out_dev, split, S, R, d, jpeg_threads(n)};
+  ST_TRY(p.probe_and_scan());
+  p.lay_out();
+  st_jpeg_state* js;
+  ST_TRY(jpeg_state(ctx, &js));
+  ST_TRY(st_pinned_grow(ctx, &js->gstatus, &js->gstatus_cap, 64, "jpeg: cannot page-lock the status word"));
+  // (an eighth more than this call needs, so that calls of slowly growing size do not each allocate again)
+  if (p.upload_most > js->gcap)
+    ST_TRY(st_pinned_grow(ctx, &js->gpin, &js->gcap, p.upload_most + p.upload_most / 8, "jpeg: cannot page-lock %zu bytes for the streams"));
+  ST_TRY(st_ws_reserve(ctx, st_align_up(p.dev_most) + st_align_up(p.plane_most)));
+  uint8_t* d_up = (uint8_t*)st_ws_alloc(ctx, p.dev_most);
+  uint8_t* d_planes = (uint8_t*)st_ws_alloc(ctx, p.plane_most);
   if (!d_up || !d_planes) return st_set_error(ctx, ST_ERR_OOM, "jpeg: workspace exhausted");
-
-  const unsigned align = [&] {
-    unsigned a = 0;
-    for (int i = 0; i < n; ++i) a |= (unsigned)(uintptr_t)out_dev[i];
-    return a;
-  }();
-  const int ow = (w + d - 1) / d;   // the width of the frames written
-  const int px = (ow % 16 == 0 && (align & 15) == 0) ? 16 : ((ow % 4 == 0 && (align & 3) == 0) ? 4 : 1);
-
-  for (const GpuSubBatch& sb : sbs) {
-    // 3. fill the slot on the threads (free: the previous sub-batch was waited for)
-    uint8_t* slot = js->gpin;
-    memset(slot, 0xFF, 16);   // the status word: clean
-    std::atomic<int> next{sb.first};
-    std::atomic<bool> bad{false};
-    run_threads(std::min(T, sb.count), [&](int) {
-      std::vector<StJpegHeader> hdv;
-      char msg[160];
-      for (;;) {
-        const int i = next.fetch_add(1);
-        if (i >= sb.first + sb.count) return;
-        const GpuStream& g = gs[(size_t)i];
-        const int j = i - sb.first;
-        StJpegEntFrame* ef = reinterpret_cast<StJpegEntFrame*>(slot + sb.frames_off) + j;
-        ef->geom = g.geom;
-        ef->nint = g.nint;
-        ef->tables = (uint32_t)g.tabs;
-        ef->intervals_off = g.iv_off;
-        ef->bytes_off = g.bytes_off;
-        ef->nbytes = (uint32_t)g.nbytes;
-        ef->blk_off = (uint32_t)g.fh.blk_off;
-        if (g.writes_tabs) {
-          if (hdv.empty()) hdv.resize(1);
-          if (st_jpeg_parse_header(bufs_host[i], sizes[i], &hdv[0], msg, sizeof msg) != ST_OK) { bad = true; return; }   // the caller changed the stream
-          frame_tables(hdv[0], reinterpret_cast<StJpegFrameTables*>(slot + sb.tables_off) + g.tabs);
-        }
-        const uint32_t* iv = ivs[(size_t)g.owner].data() + g.iv_at;
-        uint32_t* dv = reinterpret_cast<uint32_t*>(slot + g.iv_off);
-        for (size_t k = 0; k < 2 * (size_t)g.nint; ++k) dv[k] = iv[k] - (uint32_t)g.scan_pos;
-        if (split) {
-          StJsqFrame* qf = reinterpret_cast<StJsqFrame*>(slot + sb.sq_off) + j;
-          memset(qf, 0, sizeof *qf);
-          qf->subpre_off = g.subpre_off;
-          qf->lane_off = (uint32_t)g.lane_off;
-          qf->seg_off = (uint32_t)g.seg_off;
-          qf->nlanes = (uint32_t)g.nlanes;
-          uint32_t* pre = reinterpret_cast<uint32_t*>(slot + g.subpre_off);
-          uint32_t sum = 0;
-          for (size_t k = 0; k < g.nint; ++k) { pre[k] = sum; sum += st_jsq_count(iv[2 * k + 1] - iv[2 * k], S); }
-          pre[g.nint] = sum;
-        }
-        memcpy(slot + g.bytes_off, bufs_host[i] + g.scan_pos, g.nbytes);
-        memset(slot + g.bytes_off + g.nbytes, 0, up16(g.nbytes + 16) - g.nbytes);
-        memcpy(slot + sb.hdr_off + (size_t)j * sizeof(JpegFrameHdr), &g.fh, sizeof(JpegFrameHdr));
-      }
-    });
-    if (bad) return st_set_error(ctx, ST_ERR_INVALID, "jpeg: a stream changed during the call");
-    // 4. one copy, the entropy launch, the ONE host wait of the sub-batch (its status word), then the dense kernels
-    unsigned long long word = kStJpegEntClean;
-    {
-      st_timed timed(ctx, ST_K_JPEG);
-      ST_HIP(ctx, hipMemcpyAsync(d_up, slot, sb.upload_bytes, hipMemcpyHostToDevice, ctx->stream));
-      StJpegEntArgs ea;
-      ea.upload = d_up;
-      ea.frames = reinterpret_cast<const StJpegEntFrame*>(d_up + sb.frames_off);
-      ea.tables = reinterpret_cast<const StJpegFrameTables*>(d_up + sb.tables_off);
-      ea.coef = reinterpret_cast<int16_t*>(d_up + sb.upload_bytes);
-      ea.status = reinterpret_cast<unsigned long long*>(d_up);
-      ea.nf = sb.count;
-      ea.first_stream = sb.first;
-      if (!split) {
-        ST_TRY(st_jpeg_entropy_launch(ctx, ea, sb.max_groups));
-      } else {
-        StJsqArgs qa;
-        qa.ent = ea;
-        qa.sq = reinterpret_cast<const StJsqFrame*>(d_up + sb.sq_off);
-        uint8_t* scratch = d_up + sb.scratch_off;
-        qa.exits[0] = reinterpret_cast<uint64_t*>(scratch + sb.lanes * 16);
-        qa.exits[1] = reinterpret_cast<uint64_t*>(scratch + sb.lanes * 24);
-        qa.entered = reinterpret_cast<uint64_t*>(scratch + sb.lanes * 32);
-        qa.counts = reinterpret_cast<uint32_t*>(scratch);   // 16 bytes per lane, 16-byte aligned
-        qa.unconverged = reinterpret_cast<uint32_t*>(scratch + sb.lanes * 40);
-        qa.changed = reinterpret_cast<unsigned*>(scratch + sb.lanes * 40 + up16(sb.nint * 4));
-        qa.S = S;
-        // round launches in groups (three, then two at a time), one host wait per group for its counts of changed exits: a
-        // launch that changed none has verified the chain.  Launches behind it in its group change nothing either.
-        int launches = 0, rounds = R;
-        bool converged = false;
-        unsigned* back = reinterpret_cast<unsigned*>(js->gstatus + 1);
-        while (launches < R && !converged) {
-          const int group = std::min(launches == 0 ? 3 : 2, R - launches);
-          ST_HIP(ctx, hipMemsetAsync(qa.changed, 0, 16, ctx->stream));
-          for (int q = 0; q < group; ++q, ++launches) ST_TRY(st_jsq_round_launch(ctx, qa, sb.max_lane_groups, launches == 0, launches & 1, qa.changed + q));
-          ST_HIP(ctx, hipMemcpyAsync(back, qa.changed, 16, hipMemcpyDeviceToHost, ctx->stream));
-          ST_HIP(ctx, hipStreamSynchronize(ctx->stream));
-          for (int q = 0; q < group && !converged; ++q)
-            if (back[q] == 0) { converged = true; rounds = launches - group + q; }
-        }
-        js->split_rounds = std::max(js->split_rounds, rounds);
-        ST_TRY(st_jsq_finish_launch(ctx, qa, sb.max_lane_groups, sb.max_segments, (launches - 1) & 1, sb.blocks * 128));
-      }
-      ST_HIP(ctx, hipMemcpyAsync(js->gstatus, d_up, sizeof word, hipMemcpyDeviceToHost, ctx->stream));
-      ST_HIP(ctx, hipStreamSynchronize(ctx->stream));
-      word = *js->gstatus;
-      if (word == kStJpegEntClean) {
-        size_t most = 0, most1 = 0, mostlds = 0;
-        for (int i = sb.first; i < sb.first + sb.count; ++i) {
-          most = std::max(most, gs[(size_t)i].nblocks);
-          size_t n1, nlds;
-          st_jpeg_reduced_counts(gs[(size_t)i].fh, &n1, &nlds);
-          most1 = std::max(most1, n1);
-          mostlds = std::max(mostlds, nlds);
-        }
-        // the dense kernels take the frame from blockIdx.y: at most 65 535 frames per launch, the headers offset so that the
-        // coefficients stay where slot + nf * 512 points
-        for (int f0 = 0; f0 < sb.count; f0 += 65535) {
-          const int nfl = std::min(65535, sb.count - f0);
-          JpegArgsK a;
-          a.slot = d_up + sb.hdr_off + (size_t)f0 * sizeof(JpegFrameHdr);
-          a.planes = d_planes; a.nf = sb.count - f0; a.h = h; a.w = w; a.channels = channels;
-          launch_dense(ctx, a, nfl, d, px, most, most1, mostlds);
-        }
-      }
-    }
-    ST_HIP(ctx, hipGetLastError());
-    if (word != kStJpegEntClean) {
-      const int stream = (int)(word >> 32);
-      const unsigned interval = (unsigned)((word >> 4) & 0xfffffffu);
-      const unsigned nint = stream >= 0 && stream < n ? gs[(size_t)stream].nint : 0u;
-      if (split && stream >= 0 && stream < n && gs[(size_t)stream].geom.restart_interval <= 0)
-        return st_set_error(ctx, ST_ERR_INVALID, "jpeg: stream %d: corrupt scan: the scan: %s", stream, st_jpeg_entropy_cause((int)(word & 15)));
-      return st_set_error(ctx, ST_ERR_INVALID, "jpeg: stream %d: corrupt scan: restart interval %u of %u: %s", stream, interval, nint,
-                          st_jpeg_entropy_cause((int)(word & 15)));
-    }
+  const int px = store_width((w + d - 1) / d, out_dev, n);
+  for (const GpuSubBatch& sb : p.sbs) {
+    ST_TRY(p.fill_slot(sb, static_cast<uint8_t*>(js->gpin)));
+    ST_TRY(p.run_sub_batch(sb, js, d_up, d_planes, px));
   }
   return ST_OK;
 }

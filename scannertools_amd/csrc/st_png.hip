@@ -9,15 +9,10 @@
 // same wave stored: it drains its stores (vmcnt(0)) and passes a barrier before the next band, and reads that row past L1.
 // k_png_expand: elementwise, for the frames whose layout is not the scanlines' (palette, depth < 8, gray + alpha, RGB + tRNS).
 #include <algorithm>
-#include <atomic>
-#include <climits>
-#include <condition_variable>
-#include <cstdlib>
 #include <cstring>
-#include <mutex>
 #include <new>
-#include <thread>
 
+#include "st_host_pipeline.h"
 #include "st_internal.h"
 #include "st_png_host.h"
 
@@ -192,13 +187,7 @@ __global__ __launch_bounds__(256) void k_png_expand(PngArgsK a) {
   }
 }
 
-int png_threads(int n) {
-  int t = (int)std::min(16u, std::max(1u, std::thread::hardware_concurrency()));
-  if (const char* e = getenv("ST_PNG_THREADS")) t = atoi(e);
-  return std::max(1, std::min(std::min(t, 64), n));
-}
-
-struct PngSubBatch { int first, count; size_t data, planes; };
+struct PngSubBatch : StPipeSubBatch { size_t data, planes; };
 // Inflated bytes of one sub-batch, unless a single frame has more: sixteen 1080p RGBA frames.  A frame is one wave, so a
 // sub-batch's unfilter launch takes as long as its slowest frame however many frames it has: at 64 MB (ten 1080p RGB frames) a
 // 256-stream call made 26 launches of 20 ms and the device was as busy as the inflating threads; at sixteen it makes 16.
@@ -207,19 +196,11 @@ inline size_t pad16(size_t v) { return (v + 15) / 16 * 16 + 16; }   // 16-byte a
 
 }  // namespace
 
-struct st_png_state {
-  uint8_t* pin[2] = {nullptr, nullptr};
-  size_t cap[2] = {0, 0};
-  hipEvent_t copied[2] = {nullptr, nullptr};   // the slot's last copy has left host memory
-  bool busy[2] = {false, false};
-};
+struct st_png_state { st_pinned_slots slots; };
 
 void st_png_release(st_ctx* ctx) {
   if (!ctx->png) return;
-  for (int s = 0; s < 2; ++s) {
-    if (ctx->png->copied[s]) (void)hipEventDestroy(ctx->png->copied[s]);
-    if (ctx->png->pin[s]) (void)hipHostFree(ctx->png->pin[s]);
-  }
+  st_slots_free(&ctx->png->slots);
   delete ctx->png;
   ctx->png = nullptr;
 }
@@ -227,169 +208,82 @@ void st_png_release(st_ctx* ctx) {
 ST_EXPORT int st_png_decode_batch(st_ctx* ctx, const uint8_t* const* bufs_host, const size_t* sizes, int n, int h, int w, int channels,
                                   uint8_t* const* out_dev) {
   ST_TRY(st_enter(ctx));
-  if (n < 0 || h <= 0 || w <= 0 || h > 65535 || w > 65535 || (channels != 1 && channels != 3 && channels != 4))
-    return st_set_error(ctx, ST_ERR_INVALID, "png: bad arguments (n=%d h=%d w=%d channels=%d)", n, h, w, channels);
+  ST_TRY(st_decode_args(ctx, "png", n, h, w, channels, 1u << 1 | 1u << 3 | 1u << 4, bufs_host, sizes, out_dev));
   if (n == 0) return ST_OK;
-  if (!bufs_host || !sizes || !out_dev) return st_set_error(ctx, ST_ERR_INVALID, "png: null argument");
   // every stream's container first: nothing is launched or written unless all of them are streams this decodes, of one shape
   std::vector<StPngHeader> hds((size_t)n);
   for (int i = 0; i < n; ++i) {
     char msg[160];
-    if (!out_dev[i]) return st_set_error(ctx, ST_ERR_INVALID, "png: stream %d has no output frame", i);
+    if (!out_dev[i]) return st_set_error(ctx, ST_ERR_INVALID, kStNoOutputFrame, "png", i);
     const int st = st_png_parse(bufs_host[i], sizes[i], true, &hds[i], msg, sizeof msg);
     if (st != ST_OK) return st_set_error(ctx, st, "png: stream %d: %s", i, msg);
     if (hds[i].h != h || hds[i].w != w || hds[i].channels != channels)
       return st_set_error(ctx, ST_ERR_INVALID, "png: stream %d is %dx%d with %d channel(s), the call decodes %dx%d with %d", i, hds[i].w, hds[i].h,
                           hds[i].channels, w, h, channels);
   }
-  const int T = png_threads(n);
+  const int T = st_pipe_threads("ST_PNG_THREADS", n);
   std::vector<PngSubBatch> sbs;
-  std::vector<int> sb_of((size_t)n);
   std::vector<size_t> data_off((size_t)n), plane_off((size_t)n);
   for (int i = 0; i < n; ++i) {
     const size_t nb = pad16(st_png_raw_bytes(hds[i]));
-    if (sbs.empty() || sbs.back().count >= T || sbs.back().data + nb > kSlotDataBytes) sbs.push_back(PngSubBatch{i, 0, 0, 0});
-    sb_of[i] = (int)sbs.size() - 1;
+    if (sbs.empty() || sbs.back().count >= T || sbs.back().data + nb > kSlotDataBytes) sbs.push_back(PngSubBatch{{i, 0}, 0, 0});
     data_off[i] = sbs.back().data;
     plane_off[i] = sbs.back().planes;
     sbs.back().count++;
     sbs.back().data += nb;
     if (hds[i].kind != ST_PNG_DIRECT) sbs.back().planes += pad16((size_t)hds[i].h * hds[i].rowbytes);
   }
-  const int nsb = (int)sbs.size();
+  auto upload_bytes = [](const PngSubBatch& sb) { return (size_t)sb.count * sizeof(PngFrameHdr) + sb.data; };
   size_t slot_bytes = 0, plane_bytes = 16;
   for (const PngSubBatch& sb : sbs) {
-    slot_bytes = std::max(slot_bytes, (size_t)sb.count * sizeof(PngFrameHdr) + sb.data);
+    slot_bytes = std::max(slot_bytes, upload_bytes(sb));
     plane_bytes = std::max(plane_bytes, sb.planes);
   }
-  if (!ctx->png) {
-    ctx->png = new (std::nothrow) st_png_state();
-    if (!ctx->png) return st_set_error(ctx, ST_ERR_OOM, "png: out of host memory");
-  }
-  st_png_state* ps = ctx->png;
-  for (int s = 0; s < std::min(2, nsb); ++s) {
-    if (!ps->copied[s]) ST_HIP(ctx, hipEventCreateWithFlags(&ps->copied[s], hipEventDisableTiming));
-    // a slot is refilled only after its previous copy (of this call or an earlier one) has read it
-    if (ps->busy[s]) { ST_HIP(ctx, hipEventSynchronize(ps->copied[s])); ps->busy[s] = false; }
-    if (slot_bytes > ps->cap[s]) {
-      if (ps->pin[s]) ST_HIP(ctx, hipHostFree(ps->pin[s]));
-      ps->pin[s] = nullptr;
-      ps->cap[s] = 0;
-      if (hipHostMalloc((void**)&ps->pin[s], slot_bytes, hipHostMallocDefault) != hipSuccess) {
-        (void)hipGetLastError();
-        ps->pin[s] = nullptr;
-        return st_set_error(ctx, ST_ERR_OOM, "png: cannot page-lock %zu bytes for the scanlines", slot_bytes);
-      }
-      ps->cap[s] = slot_bytes;
-    }
-  }
+  if (!ctx->png) ctx->png = new (std::nothrow) st_png_state();
+  if (!ctx->png) return st_set_error(ctx, ST_ERR_OOM, "png: out of host memory");
+  st_pinned_slots* sl = &ctx->png->slots;
+  ST_TRY(st_slots_prepare(ctx, sl, std::min(2, (int)sbs.size()), slot_bytes, "png: cannot page-lock %zu bytes for the scanlines"));
   ST_TRY(st_ws_reserve(ctx, st_align_up(slot_bytes) + st_align_up(plane_bytes)));
   uint8_t* d_slot = (uint8_t*)st_ws_alloc(ctx, slot_bytes);
   uint8_t* d_planes = (uint8_t*)st_ws_alloc(ctx, plane_bytes);
   if (!d_slot || !d_planes) return st_set_error(ctx, ST_ERR_OOM, "png: workspace exhausted");
 
-  // workers take streams in order; sub-batch k may be filled once `allowed` > k
-  struct Shared {
-    std::mutex mu;
-    std::condition_variable cv;
-    int allowed = 2;
-    std::vector<int> remaining;
-    bool failed = false;
-    int fail_status = ST_OK, fail_stream = -1;
-    char fail_msg[160];
-  } sh;
-  sh.remaining.resize((size_t)nsb);
-  for (int k = 0; k < nsb; ++k) sh.remaining[k] = sbs[k].count;
-  std::atomic<int> next{0};
-  auto work = [&]() {
-    for (;;) {
-      const int i = next.fetch_add(1);
-      if (i >= n) return;
-      const int k = sb_of[i];
-      bool skip;
-      {
-        std::unique_lock<std::mutex> lk(sh.mu);
-        sh.cv.wait(lk, [&] { return sh.allowed > k; });
-        skip = sh.failed;
-      }
-      int st = ST_OK;
-      char msg[160];
-      msg[0] = 0;
-      if (!skip) {
-        const StPngHeader& hd = hds[i];
-        uint8_t* slot = ps->pin[k & 1];
-        PngFrameHdr* fh = reinterpret_cast<PngFrameHdr*>(slot) + (i - sbs[k].first);
-        memset(fh, 0, sizeof *fh);
-        fh->out = out_dev[i];
-        fh->data_off = (size_t)sbs[k].count * sizeof(PngFrameHdr) + data_off[i];
-        fh->plane_off = plane_off[i];
-        fh->h = hd.h; fh->w = hd.w; fh->bpp = hd.bpp; fh->rowbytes = hd.rowbytes; fh->kind = hd.kind; fh->depth = hd.bit_depth;
-        fh->channels = hd.channels;
-        memcpy(fh->key, hd.key, 3);
-        memcpy(fh->pal, hd.pal, sizeof fh->pal);
-        uint8_t* raw = slot + fh->data_off;
-        st = st_png_inflate_rows(bufs_host[i], hd, raw, msg, sizeof msg);
-        memset(raw + st_png_raw_bytes(hd), 0, pad16(st_png_raw_bytes(hd)) - st_png_raw_bytes(hd));
-      }
-      std::lock_guard<std::mutex> lk(sh.mu);
-      if (st != ST_OK && (!sh.failed || i < sh.fail_stream)) {
-        sh.failed = true;
-        sh.fail_status = st;
-        sh.fail_stream = i;
-        memcpy(sh.fail_msg, msg, sizeof msg);
-      }
-      --sh.remaining[k];
-      sh.cv.notify_all();
-    }
+  // a stream's header and its inflated scanlines into its sub-batch's slot
+  auto fill = [&](int i, int k, int s, char* msg, size_t msg_len) {
+    const StPngHeader& hd = hds[i];
+    PngFrameHdr* fh = reinterpret_cast<PngFrameHdr*>(sl->at(s)) + (i - sbs[k].first);
+    memset(fh, 0, sizeof *fh);
+    fh->out = out_dev[i];
+    fh->data_off = (size_t)sbs[k].count * sizeof(PngFrameHdr) + data_off[i];
+    fh->plane_off = plane_off[i];
+    fh->h = hd.h; fh->w = hd.w; fh->bpp = hd.bpp; fh->rowbytes = hd.rowbytes; fh->kind = hd.kind; fh->depth = hd.bit_depth;
+    fh->channels = hd.channels;
+    memcpy(fh->key, hd.key, 3);
+    memcpy(fh->pal, hd.pal, sizeof fh->pal);
+    uint8_t* raw = sl->at(s) + fh->data_off;
+    const int st = st_png_inflate_rows(bufs_host[i], hd, raw, msg, msg_len);
+    memset(raw + st_png_raw_bytes(hd), 0, pad16(st_png_raw_bytes(hd)) - st_png_raw_bytes(hd));
+    return st;
   };
-  std::vector<std::thread> pool;
-  pool.reserve((size_t)T);
-  for (int t = 0; t < T; ++t) pool.emplace_back(work);
-
-  auto issue = [&]() -> int {
-    for (int k = 0; k < nsb; ++k) {
-      {
-        std::unique_lock<std::mutex> lk(sh.mu);
-        sh.cv.wait(lk, [&] { return sh.remaining[k] == 0; });
-        if (sh.failed) return st_set_error(ctx, sh.fail_status, "png: stream %d: %s", sh.fail_stream, sh.fail_msg);
-      }
-      const PngSubBatch& sb = sbs[k];
-      const int s = k & 1;
-      const size_t bytes = (size_t)sb.count * sizeof(PngFrameHdr) + sb.data;
-      ST_HIP(ctx, hipMemcpyAsync(d_slot, ps->pin[s], bytes, hipMemcpyHostToDevice, ctx->stream));
-      ST_HIP(ctx, hipEventRecord(ps->copied[s], ctx->stream));
-      ps->busy[s] = true;
-      PngArgsK a;
-      a.slot = d_slot; a.planes = d_planes; a.nf = sb.count;
-      {
-        st_timed t(ctx, ST_K_JPEG);
-        hipLaunchKernelGGL(k_png_unfilter, dim3(1, (unsigned)sb.count), dim3(64), 0, ctx->stream, a);
-      }
-      if (sb.planes) {
-        long long bx = ((long long)h * w + 255) / 256;
-        if (bx > 4096) bx = 4096;
-        st_timed t(ctx, ST_K_JPEG);
-        hipLaunchKernelGGL(k_png_expand, dim3((unsigned)bx, (unsigned)sb.count), dim3(256), 0, ctx->stream, a);
-      }
-      ST_HIP(ctx, hipGetLastError());
-      if (k + 2 < nsb) {
-        ST_HIP(ctx, hipEventSynchronize(ps->copied[s]));
-        ps->busy[s] = false;
-        std::lock_guard<std::mutex> lk(sh.mu);
-        sh.allowed = k + 3;
-        sh.cv.notify_all();
-      }
+  // one copy, the unfilter launch and, where a frame's layout is not the scanlines', the expansion
+  auto issue = [&](int k, int s) -> int {
+    const PngSubBatch& sb = sbs[k];
+    ST_TRY(st_slot_upload(ctx, sl, s, d_slot, upload_bytes(sb)));
+    PngArgsK a;
+    a.slot = d_slot; a.planes = d_planes; a.nf = sb.count;
+    {
+      st_timed t(ctx, ST_K_JPEG);
+      hipLaunchKernelGGL(k_png_unfilter, dim3(1, (unsigned)sb.count), dim3(64), 0, ctx->stream, a);
     }
+    if (sb.planes) {
+      long long bx = ((long long)h * w + 255) / 256;
+      if (bx > 4096) bx = 4096;
+      st_timed t(ctx, ST_K_JPEG);
+      hipLaunchKernelGGL(k_png_expand, dim3((unsigned)bx, (unsigned)sb.count), dim3(256), 0, ctx->stream, a);
+    }
+    ST_HIP(ctx, hipGetLastError());
     return ST_OK;
   };
-  const int status = issue();
-  {
-    // on an error the workers run out of streams without inflating them
-    std::lock_guard<std::mutex> lk(sh.mu);
-    if (status != ST_OK) sh.failed = true;
-    sh.allowed = INT_MAX;
-    sh.cv.notify_all();
-  }
-  for (std::thread& t : pool) t.join();
-  return status;
+  const StPipeResult r = st_pipe_run(sbs, T, fill, issue, [&](int s) { return st_slot_release(ctx, sl, s); });
+  return r.stream >= 0 ? st_set_error(ctx, r.status, "png: stream %d: %s", r.stream, r.message) : r.status;
 }

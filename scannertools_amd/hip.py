@@ -442,15 +442,16 @@ class HipContext:
         (n, h, w, c) uint8 CUDA tensor, c = 3 in R, G, B order or 1; bit-exact to libjpeg's defaults.  The shape is the first
         stream's; a stream of another shape, or one that is refused or malformed, raises StError naming it, and nothing is
         written.  entropy="host" (the default): entropy decoding runs on host threads (ST_JPEG_THREADS), the rest in HIP
-        kernels on the current stream.  entropy="gpu": st_jpeg_decode_batch_gpu, the Huffman decoder is a HIP kernel too, one
-        lane per restart interval; every stream must have restart intervals (StError naming the one that has none).
+        kernels on the current stream.  entropy="gpu": the Huffman decoder is a HIP kernel too, one lane per restart interval
+        (what st_jpeg_decode_batch_gpu does); every stream must have restart intervals (StError naming the one that has none).
         entropy="auto": "gpu" when every stream's probe reports a restart interval, else "host".  Same frames either way.
-        split="subsequence" (with entropy "gpu" or "auto", which then mean the same): st_jpeg_decode_batch_gpu_split, one lane
-        per subsequence of ``subseq_bytes`` raw bytes, at most ``max_rounds`` round launches (None: the library's defaults);
-        streams need no restart intervals.  ``last_jpeg_rounds()`` then tells the round launches the call took.
-        scale = 2, 4 or 8 (st_jpeg_decode_batch_scaled): the frames at 1/2, 1/4 or 1/8, (n, ceil(h / scale), ceil(w / scale), c),
+        split="subsequence" (with entropy "gpu" or "auto", which then mean the same): one lane per subsequence of
+        ``subseq_bytes`` raw bytes, at most ``max_rounds`` round launches (None: the library's defaults), what
+        st_jpeg_decode_batch_gpu_split does; streams need no restart intervals.  ``last_jpeg_rounds()`` then tells the round
+        launches the call took.  scale = 2, 4 or 8: the frames at 1/2, 1/4 or 1/8, (n, ceil(h / scale), ceil(w / scale), c),
         bit-exact to libjpeg's scaled decoding (cv::IMREAD_REDUCED_COLOR_* / _GRAYSCALE_*, Pillow's draft()); anything but
-        1, 2, 4 or 8 raises ValueError.  It composes with every entropy and split."""
+        1, 2, 4 or 8 raises ValueError.  It composes with every entropy and split: whatever the arguments, the call made is
+        ONE st_jpeg_decode_batch_scaled(scale, ST_JPEG_ENTROPY_HOST | _INTERVAL | _SUBSEQUENCE, opts)."""
         if isinstance(scale, bool) or scale not in JPEG_SCALES:
             raise ValueError("scale must be one of 1, 2, 4, 8, got %r" % (scale,))
         scale = int(scale)
@@ -474,17 +475,9 @@ class HipContext:
         to = (ctypes.c_void_p * n)(*[out[i].data_ptr() for i in range(n)])
         if split != "subsequence" and entropy == "auto":
             entropy = "gpu" if all(_jpeg_has_restarts(s) for s in streams) else "host"
-        if scale != 1:
-            opts = _native.JpegSplitOpts(int(subseq_bytes or 0), int(max_rounds or 0))
-            mode = 2 if split == "subsequence" else (1 if entropy == "gpu" else 0)   # ST_JPEG_ENTROPY_*
-            self._check(self._L.st_jpeg_decode_batch_scaled(self._h, bufs, sizes, n, h, w, shape[3], scale, mode, ctypes.byref(opts), to))
-            return out
-        if split == "subsequence":
-            opts = _native.JpegSplitOpts(int(subseq_bytes or 0), int(max_rounds or 0))
-            self._check(self._L.st_jpeg_decode_batch_gpu_split(self._h, bufs, sizes, n, h, w, shape[3], to, ctypes.byref(opts)))
-            return out
-        call = self._L.st_jpeg_decode_batch_gpu if entropy == "gpu" else self._L.st_jpeg_decode_batch
-        self._check(call(self._h, bufs, sizes, n, h, w, shape[3], to))
+        opts = _native.JpegSplitOpts(int(subseq_bytes or 0), int(max_rounds or 0))
+        mode = 2 if split == "subsequence" else (1 if entropy == "gpu" else 0)   # ST_JPEG_ENTROPY_*
+        self._check(self._L.st_jpeg_decode_batch_scaled(self._h, bufs, sizes, n, h, w, shape[3], scale, mode, ctypes.byref(opts), to))
         return out
 
     def decode_png(self, streams, out=None):

@@ -6,8 +6,9 @@
 // Same op declaration (input("img") -> frame_output("frame"); the GPU file adds protobuf_name("ImageDecoderArgs")), same
 // elements: `img` is the bytes of one encoded image, `frame` the decoded U8 frame in R, G, B order (cv::imdecode(
 // IMREAD_UNCHANGED) + COLOR_BGR2RGB, :23-29) or with one channel.  The per-image cv::imdecode calls of the reference's
-// 32-thread pool become ONE st_jpeg_decode_batch() call per execute(): Huffman decoding on host threads, everything dense in
-// HIP kernels, bit-exact to libjpeg's defaults (include/scannertools_hip.h).
+// 32-thread pool become ONE st_jpeg_decode_batch_scaled() call per execute(), whose scale_denom, entropy mode and opts the
+// fields below map to once.  Without them it does what st_jpeg_decode_batch() does: Huffman decoding on host threads,
+// everything dense in HIP kernels, bit-exact to libjpeg's defaults (include/scannertools_hip.h).
 //
 // JPEG only, as the reference's GPU kernel (:78-88 is fatal on PNG and ANY).  ImageDecoderArgs { image_type: PNG = 0 | JPEG = 1
 // | ANY = 2 }: JPEG and a message without the field (the reference's CPU kernel takes no arguments at all) are accepted; the
@@ -16,20 +17,19 @@
 // fails in execute() as any stream that is not a JPEG does.)
 //
 // ImageDecoderArgs { ..., entropy = 2: HOST = 0 | GPU = 1 | AUTO = 2 } (this build's own field, scannertools_imgproc_amd.proto)
-// chooses where the Huffman decoder runs: HOST, and a message without the field, is st_jpeg_decode_batch() as above; GPU is
-// st_jpeg_decode_batch_gpu(), the Huffman decoder a HIP kernel with one lane per restart interval, and a row without restart
+// chooses where the Huffman decoder runs: HOST, and a message without the field, is ST_JPEG_ENTROPY_HOST as above; GPU is
+// ST_JPEG_ENTROPY_INTERVAL (st_jpeg_decode_batch_gpu()'s), the Huffman decoder a HIP kernel with one lane per restart interval, and a row without restart
 // intervals is then fatal with the row and the cause; AUTO takes GPU for an execute() whose rows all have restart intervals
 // and HOST otherwise.  Any other value fails validate().  The frames are the same bytes either way.
 //
 // ImageDecoderArgs { ..., split = 3: INTERVAL = 0 | SUBSEQUENCE = 1 } (this build's own field too) chooses how the device decoder
-// cuts the work.  INTERVAL, and a message without the field, is the above.  SUBSEQUENCE with entropy GPU or AUTO makes execute()
-// one st_jpeg_decode_batch_gpu_split() call: one lane per fixed-size piece of the entropy-coded bytes, and a row without restart
+// cuts the work.  INTERVAL, and a message without the field, is the above.  SUBSEQUENCE with entropy GPU or AUTO is
+// ST_JPEG_ENTROPY_SUBSEQUENCE (st_jpeg_decode_batch_gpu_split()'s): one lane per fixed-size piece of the entropy-coded bytes, and a row without restart
 // intervals is no error.  SUBSEQUENCE with entropy HOST (or absent) fails validate(), as any other value of split does.
 //
 // ImageDecoderArgs { ..., scale_denom = 4 } (this build's own field too) decodes at 1 / scale_denom: 1, 2, 4 or 8, libjpeg's
 // scaled decoding (cv::IMREAD_REDUCED_COLOR_2 / _4 / _8), and the frame's FrameInfo is (ceil(h / d), ceil(w / d), channels).  Absent
-// or 0 means 1; any other value fails validate().  With 2, 4 or 8 execute() is one st_jpeg_decode_batch_scaled() call standing
-// for whichever of the three calls entropy and split select.
+// or 0 means 1; any other value fails validate().  It composes with whatever entropy and split select.
 //
 // ImageDecoderArgs { ..., png = 5: REFUSE = 0 | DECODE = 1 } (this build's own field too) decides whether PNG rows are decoded.
 // REFUSE, and a message without the field, is all of the above, the validate() failures for image_type PNG / ANY included.
@@ -172,12 +172,8 @@ class ImageDecoderKernelHIPImpl : public BatchedKernel {
     }
     st_ctx* ctx = core_.ctx;
     if (n_jpeg > 0) {
-      const int st = scale_ != 1 ? st_jpeg_decode_batch_scaled(ctx, bufs_.data(), sizes_.data(), n_jpeg, first.h, first.w, first.channels, scale_,
-                                                               by_subsequence_ ? ST_JPEG_ENTROPY_SUBSEQUENCE : on_gpu ? ST_JPEG_ENTROPY_INTERVAL : ST_JPEG_ENTROPY_HOST,
-                                                               nullptr, sub_dst_.data())
-                     : by_subsequence_ ? st_jpeg_decode_batch_gpu_split(ctx, bufs_.data(), sizes_.data(), n_jpeg, first.h, first.w, first.channels, sub_dst_.data(), nullptr)
-                     : on_gpu ? st_jpeg_decode_batch_gpu(ctx, bufs_.data(), sizes_.data(), n_jpeg, first.h, first.w, first.channels, sub_dst_.data())
-                            : st_jpeg_decode_batch(ctx, bufs_.data(), sizes_.data(), n_jpeg, first.h, first.w, first.channels, sub_dst_.data());
+      const int mode = by_subsequence_ ? ST_JPEG_ENTROPY_SUBSEQUENCE : on_gpu ? ST_JPEG_ENTROPY_INTERVAL : ST_JPEG_ENTROPY_HOST;
+      const int st = st_jpeg_decode_batch_scaled(ctx, bufs_.data(), sizes_.data(), n_jpeg, first.h, first.w, first.channels, scale_, mode, nullptr, sub_dst_.data());
       LOG_IF(FATAL, st != ST_OK) << "ImageDecoder: " << st_ctx_last_error(ctx);
     }
     if (n_png > 0) {

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import ref_jpeg_np as ref
+from util import env_threads
 
 pytestmark = pytest.mark.gpu
 
@@ -39,23 +40,6 @@ def _has_dri(jpg):
 
 
 GOLD_DRI = [str(c) for c in GOLD["cases"] if _has_dri(GOLD[str(c) + "__jpg"].tobytes())]
-
-
-class _threads:
-    """ST_JPEG_THREADS for the calls inside the block (the library reads it at each call)."""
-
-    def __init__(self, n):
-        self.n = n
-
-    def __enter__(self):
-        self.old = os.environ.get("ST_JPEG_THREADS")
-        os.environ["ST_JPEG_THREADS"] = str(self.n)
-
-    def __exit__(self, *a):
-        if self.old is None:
-            os.environ.pop("ST_JPEG_THREADS", None)
-        else:
-            os.environ["ST_JPEG_THREADS"] = self.old
 
 
 def test_new_golden_cases_are_byte_exact_and_one_bracket_each(hip_ctx):
@@ -103,7 +87,7 @@ def test_batches_equal_singles(hip_ctx):
         assert np.array_equal(got, ENC[n + "__dec"]), n
     for count in (1, 8, 33):
         for threads in (16, 3):
-            with _threads(threads):
+            with env_threads("ST_JPEG_THREADS", threads):
                 got = hip_ctx.decode_jpeg(streams[:count], entropy="gpu").cpu().numpy()
             assert np.array_equal(got, np.stack(singles[:count])), (count, threads)
 
@@ -114,7 +98,7 @@ def test_mixed_sampling_and_mixed_tables_in_one_call(hip_ctx):
         assert np.array_equal(got[i], GOLD[n + "__img"]), n
     names = [MIXED[0], GOOD[0], MIXED[1], MIXED[1], MIXED[0], GOOD[1], MIXED[1]]         # standard and optimised tables alternate
     for threads in (16, 2):
-        with _threads(threads):
+        with env_threads("ST_JPEG_THREADS", threads):
             got = hip_ctx.decode_jpeg([_rjpg(n) for n in names], entropy="gpu").cpu().numpy()
         for i, n in enumerate(names):
             assert np.array_equal(got[i], _rimg(n)), (threads, i, n)

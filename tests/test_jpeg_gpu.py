@@ -6,6 +6,8 @@ import os
 import numpy as np
 import pytest
 
+from util import env_threads
+
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -20,23 +22,6 @@ def _jpg(name):
 
 def _img(name):
     return GOLD[name + "__img"]
-
-
-class _threads:
-    """ST_JPEG_THREADS for the calls inside the block (the library reads it at each call)."""
-
-    def __init__(self, n):
-        self.n = n
-
-    def __enter__(self):
-        self.old = os.environ.get("ST_JPEG_THREADS")
-        os.environ["ST_JPEG_THREADS"] = str(self.n)
-
-    def __exit__(self, *a):
-        if self.old is None:
-            os.environ.pop("ST_JPEG_THREADS", None)
-        else:
-            os.environ["ST_JPEG_THREADS"] = self.old
 
 
 def test_every_golden_case_is_byte_exact(hip_ctx):
@@ -78,7 +63,7 @@ def test_batches_equal_singles_at_any_thread_count(hip_ctx):
     for count in (1, 8, 33):
         results = {}
         for threads in (16, 1, 3):           # 1: one stream per sub-batch, the two page-locked slots alternate 33 times
-            with _threads(threads):
+            with env_threads("ST_JPEG_THREADS", threads):
                 results[threads] = hip_ctx.decode_jpeg([_jpg(n) for n in BATCH[:count]]).cpu().numpy()
         assert np.array_equal(results[16], np.stack(singles[:count])), count
         assert np.array_equal(results[1], results[16]) and np.array_equal(results[3], results[16]), count
@@ -87,7 +72,7 @@ def test_batches_equal_singles_at_any_thread_count(hip_ctx):
 def test_mixed_subsampling_in_one_call(hip_ctx):
     names = BATCH[:3] + ["32x24_batch_444"] + BATCH[3:5]
     for threads in (16, 2):
-        with _threads(threads):
+        with env_threads("ST_JPEG_THREADS", threads):
             got = hip_ctx.decode_jpeg([_jpg(n) for n in names]).cpu().numpy()
         for i, n in enumerate(names):
             assert np.array_equal(got[i], _img(n)), (threads, n)
@@ -107,7 +92,7 @@ def test_bad_stream_fails_the_call_and_writes_nothing(hip_ctx):
                    (_jpg("48x24_vec_420"), _native.ST_ERR_INVALID, b"stream 2 is 48x24"),            # another shape
                    (_jpg("32x24_batch_444")[:200], _native.ST_ERR_INVALID, b"stream 2"),           # cut inside the tables
                    (good[1][:scan + (len(good[1]) - scan) // 2], _native.ST_ERR_INVALID, b"scan")]  # cut inside the scan
-    with _threads(16):
+    with env_threads("ST_JPEG_THREADS", 16):
         for bad, status, cause in bad_streams:
             streams = good[:2] + [bad] + good[2:]
             n = len(streams)
@@ -141,6 +126,37 @@ def test_bad_stream_fails_the_call_and_writes_nothing(hip_ctx):
     got = hip_ctx.decode_jpeg(good).cpu().numpy()
     assert all(np.array_equal(got[i], _img(BATCH[i])) for i in range(4))
     assert hip_ctx.decode_jpeg([]).shape[0] == 0
+
+
+def test_corrupt_scan_in_a_later_sub_batch_fails_the_call_and_both_decoders_slots_survive(hip_ctx):
+    """Seven 16 x 16 streams on two threads are four sub-batches, so both page-locked slots are refilled; stream 5 (the third
+    sub-batch, slot 0's second filling) has whole markers and a scan cut in the middle, which shows only while a worker
+    decodes it.  The context then decodes the good streams: the slots' events and busy flags survive a failed call.  The same
+    with PNG streams afterwards: the two decoders' slots are separate."""
+    import png_cases as pc
+    from scannertools_amd import _native, hip
+    from scannertools_amd.hip import StError
+    names = [c for c in CASES if c.startswith("16x16_") and "gray" not in c][:7]
+    good = [_jpg(n) for n in names]
+    scan = good[5].index(b"\xff\xda")
+    bad = good[5][:scan + (len(good[5]) - scan) // 2]
+    assert len(good) == 7 and hip.probe_jpeg(bad) == hip.probe_jpeg(good[5])             # header parsing passes
+    with env_threads("ST_JPEG_THREADS", 2):
+        with pytest.raises(StError, match="jpeg: stream 5: ") as e:
+            hip_ctx.decode_jpeg(good[:5] + [bad] + good[6:])
+        assert e.value.status == _native.ST_ERR_INVALID and "scan" in str(e.value)
+        got = hip_ctx.decode_jpeg(good).cpu().numpy()
+    assert all(np.array_equal(got[i], _img(n)) for i, n in enumerate(names))
+    rng = np.random.default_rng(13)
+    pxs = [pc.picture(rng, 12, 11, 6) for _ in range(7)]
+    pngs = [pc.write_png(p, 6) for p in pxs]
+    z = pc.deflate(pc.filter_rows(pc.scanlines(pxs[5], 6, 8), 4, [1] * 12).tobytes())
+    with env_threads("ST_PNG_THREADS", 2):
+        with pytest.raises(StError, match="png: stream 5: png: zlib: Adler-32 mismatch") as e:
+            hip_ctx.decode_png(pngs[:5] + [pc.write_png(pxs[5], 6, zdata=z[:-1] + bytes([z[-1] ^ 1]))] + pngs[6:])
+        assert e.value.status == _native.ST_ERR_INVALID
+        got = hip_ctx.decode_png(pngs).cpu().numpy()
+    assert all(np.array_equal(got[i], pc.expected(p, 6, 8)) for i, p in enumerate(pxs))
 
 
 def _run_decoder(device, names, batch, args=None):

@@ -21,6 +21,7 @@ import jpeg_large_cases as lc
 import ref_jpeg_encode_norst_np as ref_norst
 import ref_jpeg_encode_np as ref_row
 import ref_jpeg_np
+from util import env_threads
 
 pytestmark = pytest.mark.gpu
 
@@ -114,23 +115,6 @@ def _assert_frames(got, want, what):
         n, at = int(bad[0, 0]), int(bad[0, 1])
         c = got.shape[3]
         raise AssertionError((what, "wrong bytes: %d" % len(bad), "first: frame %d, y %d, x %d" % (n, at // c // got.shape[2], at // c % got.shape[2])))
-
-
-class _threads:
-    """ST_JPEG_THREADS for the calls inside the block (the library reads it at each call)."""
-
-    def __init__(self, n):
-        self.n = n
-
-    def __enter__(self):
-        self.old = os.environ.get("ST_JPEG_THREADS")
-        os.environ["ST_JPEG_THREADS"] = str(self.n)
-
-    def __exit__(self, *a):
-        if self.old is None:
-            os.environ.pop("ST_JPEG_THREADS", None)
-        else:
-            os.environ["ST_JPEG_THREADS"] = self.old
 
 
 # ---- encoder ---------------------------------------------------------------------------------------------------------------
@@ -247,7 +231,7 @@ def test_sub_batches_cut_by_bytes(hip_ctx):
         for threads, sub_batches in ((16, 2), (2, 4)):
             for kw, regions in ((dict(), sub_batches), (dict(entropy="gpu", split="interval"), 1), (dict(entropy="gpu", split="subsequence"), 1)):
                 hip_ctx.timing_reset()
-                with _threads(threads):
+                with env_threads("ST_JPEG_THREADS", threads):
                     got = hip_ctx.decode_jpeg(streams, **kw)
                 _assert_frames(got, want, (threads, kw))
                 counts = [hip_ctx.timing_read(k)[0] for k in range(_native.K_COUNT)]

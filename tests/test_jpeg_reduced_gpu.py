@@ -10,6 +10,8 @@ import os
 import numpy as np
 import pytest
 
+from util import env_threads
+
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -34,23 +36,6 @@ def _same(name, d, got):
     if key in GOLD.files:
         return got.shape == GOLD[key].shape and np.array_equal(got, GOLD[key])
     return got.shape == tuple(GOLD[key + "_shape"]) and hashlib.sha256(np.ascontiguousarray(got).tobytes()).hexdigest() == str(GOLD[key + "_sha"])
-
-
-class _threads:
-    """ST_JPEG_THREADS for the calls inside the block (the library reads it at each call)."""
-
-    def __init__(self, n):
-        self.n = n
-
-    def __enter__(self):
-        self.old = os.environ.get("ST_JPEG_THREADS")
-        os.environ["ST_JPEG_THREADS"] = str(self.n)
-
-    def __exit__(self, *a):
-        if self.old is None:
-            os.environ.pop("ST_JPEG_THREADS", None)
-        else:
-            os.environ["ST_JPEG_THREADS"] = self.old
 
 
 @pytest.mark.parametrize("mode", ["host", "gpu", "subsequence"])
@@ -85,7 +70,7 @@ def test_mixed_subsampling_in_one_call(hip_ctx):
     names = [_stream("37x53_%s_q%d" % (s, q)) for s, q in (("420", 95), ("444", 30), ("422", 95), ("420", 30), ("444", 95))]
     for d in (2, 4, 8):
         for threads in (16, 2):
-            with _threads(threads):
+            with env_threads("ST_JPEG_THREADS", threads):
                 got = hip_ctx.decode_jpeg([_jpg(n) for n in names], scale=d).cpu().numpy()
             for i, n in enumerate(names):
                 assert _same(n, d, got[i]), (d, threads, n)
@@ -101,7 +86,7 @@ def test_seventy_tiny_frames(hip_ctx):
         names = [pool[i % len(pool)] for i in range(70)]
         for d in (2, 8):
             for threads in (16, 1, 3):
-                with _threads(threads):
+                with env_threads("ST_JPEG_THREADS", threads):
                     got = hip_ctx.decode_jpeg([_jpg(n) for n in names], scale=d).cpu().numpy()
                 assert all(_same(n, d, got[i]) for i, n in enumerate(names)), (size, d, threads)
             got = hip_ctx.decode_jpeg([_jpg(n) for n in names], scale=d, entropy="auto", split="subsequence").cpu().numpy()

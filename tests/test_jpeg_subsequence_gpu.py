@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import ref_jpeg_np as ref
+from util import env_threads
 
 pytestmark = pytest.mark.gpu
 
@@ -43,23 +44,6 @@ GOLD_PLAIN = [str(c) for c in GOLD["cases"] if not _has_dri(GOLD[str(c) + "__jpg
 def _rimg(name):
     key = name + "__img"
     return RST[key] if key in RST.files else RST[str(RST[name + "__same_as"]) + "__img"]
-
-
-class _threads:
-    """ST_JPEG_THREADS for the calls inside the block (the library reads it at each call)."""
-
-    def __init__(self, n):
-        self.n = n
-
-    def __enter__(self):
-        self.old = os.environ.get("ST_JPEG_THREADS")
-        os.environ["ST_JPEG_THREADS"] = str(self.n)
-
-    def __exit__(self, *a):
-        if self.old is None:
-            os.environ.pop("ST_JPEG_THREADS", None)
-        else:
-            os.environ["ST_JPEG_THREADS"] = self.old
 
 
 def _split(hip_ctx, streams, shape, opts, fill=0xA5):
@@ -123,7 +107,7 @@ def test_batches_equal_singles(hip_ctx):
         assert np.array_equal(got, GOLD[n + "__img"]), n
     for count in (1, 8, 33):
         for threads in (16, 3):
-            with _threads(threads):
+            with env_threads("ST_JPEG_THREADS", threads):
                 got = hip_ctx.decode_jpeg(streams[:count], entropy="auto", split="subsequence").cpu().numpy()
             assert np.array_equal(got, np.stack(singles[:count])), (count, threads)
 
@@ -131,7 +115,7 @@ def test_batches_equal_singles(hip_ctx):
 def test_mixed_streams_in_one_call(hip_ctx):
     """With and without DRI, 4:2:0 and 4:2:2, standard and optimised tables, in one call."""
     for threads in (16, 2):
-        with _threads(threads):
+        with env_threads("ST_JPEG_THREADS", threads):
             got = hip_ctx.decode_jpeg([GOLD[n + "__jpg"].tobytes() for n in TINY_MIXED], entropy="gpu", split="subsequence").cpu().numpy()
         for i, n in enumerate(TINY_MIXED):
             assert np.array_equal(got[i], GOLD[n + "__img"]), (threads, n)

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import png_cases as pc
+from util import env_threads
 
 pytestmark = pytest.mark.gpu
 
@@ -68,12 +69,8 @@ def test_calls_of_1_17_and_70_mixed_streams(hip_ctx, n):
     streams, want = _four_channel_streams(n, seed=n)
     hip_ctx.timing_enable(list(range(_native.K_COUNT)))
     hip_ctx.timing_reset()
-    old = os.environ.get("ST_PNG_THREADS")
-    os.environ["ST_PNG_THREADS"] = "16"                                      # the default, whatever this machine has
-    try:
+    with env_threads("ST_PNG_THREADS", 16):                                  # the default, whatever this machine has
         got = hip_ctx.decode_png(streams).cpu().numpy()
-    finally:
-        os.environ.pop("ST_PNG_THREADS") if old is None else os.environ.update(ST_PNG_THREADS=old)
     counts = [hip_ctx.timing_read(k)[0] for k in range(_native.K_COUNT)]
     hip_ctx.timing_enable([])
     assert np.array_equal(got, want), [k for k in range(n) if not np.array_equal(got[k], want[k])]

@@ -1,5 +1,25 @@
 """Shared synthetic-input helpers for the test-suite (deterministic, seeded)."""
+import os
+
 import numpy as np
+
+
+class env_threads:
+    """The environment variable `name` (ST_JPEG_THREADS, ST_PNG_THREADS) set to n for the calls inside the block: the library
+    reads it at each call."""
+
+    def __init__(self, name, n):
+        self.name, self.n = name, n
+
+    def __enter__(self):
+        self.old = os.environ.get(self.name)
+        os.environ[self.name] = str(self.n)
+
+    def __exit__(self, *a):
+        if self.old is None:
+            os.environ.pop(self.name, None)
+        else:
+            os.environ[self.name] = self.old
 
 
 def random_frames(seed, n, h, w):
