@@ -307,9 +307,10 @@ ST_EXPORT int st_facenet_output_batch(st_ctx* ctx, const float* const* maps_dev,
   g.net_w = (float)nw; g.net_h = (float)nh; g.fw = (float)w; g.fh = (float)h;
   g.thr = (double)threshold;
   const long long C = (long long)g.nvalid * g.G;   // < 2^30
-  const size_t tb = st_align_up(sizeof(void*) * (size_t)n), cb = st_align_up(sizeof(int) * (size_t)n), total = (size_t)C * n;
-  ST_TRY(st_ws_reserve(ctx, 3 * tb + 2 * cb + st_align_up(total * sizeof(u64)) + st_align_up(total * sizeof(float4)) + st_align_up(total * sizeof(int))));
-  const float** d_maps = (const float**)st_ws_alloc(ctx, tb);
+  const size_t tb = st_align_up(sizeof(long long) * (size_t)n), cb = st_align_up(sizeof(int) * (size_t)n), total = (size_t)C * n;
+  const float** d_maps;
+  ST_TRY(st_upload_tables(ctx, n, 2 * tb + 2 * cb + st_align_up(total * sizeof(u64)) + st_align_up(total * sizeof(float4)) + st_align_up(total * sizeof(int)),
+                          maps_dev, &d_maps));
   long long* d_first = (long long*)st_ws_alloc(ctx, tb);
   long long* d_rowfirst = (long long*)st_ws_alloc(ctx, tb);
   unsigned* d_count = (unsigned*)st_ws_alloc(ctx, cb);
@@ -317,22 +318,21 @@ ST_EXPORT int st_facenet_output_batch(st_ctx* ctx, const float* const* maps_dev,
   u64* d_keys = (u64*)st_ws_alloc(ctx, total * sizeof(u64));
   float4* d_boxes = (float4*)st_ws_alloc(ctx, total * sizeof(float4));
   int* d_kept = (int*)st_ws_alloc(ctx, total * sizeof(int));
-  if (!d_maps || !d_first || !d_rowfirst || !d_count || !d_kept_count || !d_keys || !d_boxes || !d_kept)
+  if (!d_first || !d_rowfirst || !d_count || !d_kept_count || !d_keys || !d_boxes || !d_kept)
     return st_set_error(ctx, ST_ERR_OOM, "facenet_output: workspace exhausted");
   std::vector<long long> first(n);
   for (int i = 0; i < n; ++i) first[i] = C * i;
-  ST_HIP(ctx, hipMemcpyAsync(d_maps, maps_dev, sizeof(void*) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
   ST_HIP(ctx, hipMemcpyAsync(d_first, first.data(), sizeof(long long) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
   ST_HIP(ctx, hipMemsetAsync(d_count, 0, sizeof(unsigned) * (size_t)n, ctx->stream));
   FoDecodeK d;
   d.keys = d_keys; d.stride = C; d.g = g;
-  for (int f0 = 0; f0 < n; f0 += 65535) {
-    const int nf = n - f0 < 65535 ? n - f0 : 65535;
+  ST_TRY(st_for_launches(n, [&](int f0, int nf) -> int {
     d.maps = d_maps + f0; d.count = d_count + f0; d.keys = d_keys + (size_t)C * f0;
     st_timed t(ctx, ST_K_CPM2_NMS);
     hipLaunchKernelGGL(k_fo_decode, dim3((g.G + 255) / 256, g.nvalid, nf), dim3(256), 0, ctx->stream, d);
     ST_HIP(ctx, hipGetLastError());
-  }
+    return ST_OK;
+  }));
   NmsK k;
   k.count = d_count; k.first = d_first; k.keys = d_keys; k.boxes = d_boxes; k.kept = d_kept; k.kept_count = d_kept_count;
   k.rows = nullptr; k.maps = d_maps; k.overlap = overlap; k.offset = offset; k.g = g;

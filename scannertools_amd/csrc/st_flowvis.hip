@@ -229,16 +229,23 @@ int flow_hist_launch(st_ctx* ctx, FlowSrc src, int n, int h, int w, int32_t* out
   const long long npx = (long long)h * w;
   const long long chunks = chunks_for_grid(ctx->num_cus, n, npx / 2, 8 * kT);
   ST_HIP(ctx, hipMemsetAsync(out_dev, 0, sizeof(int32_t) * 2 * kFlowBins * (size_t)n, ctx->stream));
-  for (int f0 = 0; f0 < n; f0 += 65535) {
-    const int nf = n - f0 < 65535 ? n - f0 : 65535;
+  return st_for_launches(n, [&](int f0, int nf) -> int {
     FlowSrc s = src;
     if (s.ptrs) s.ptrs += f0; else s.base = reinterpret_cast<const float*>(reinterpret_cast<const char*>(s.base) + (size_t)f0 * s.stride);
     st_timed t(ctx, ST_K_FLOW_HIST);
     hipLaunchKernelGGL(k_flow_hist, dim3((unsigned)chunks, (unsigned)nf), dim3(kT), 0, ctx->stream, s, npx, (int)chunks,
                        out_dev + (size_t)f0 * 2 * kFlowBins);
     ST_HIP(ctx, hipGetLastError());
-  }
-  return ST_OK;
+    return ST_OK;
+  });
+}
+
+// The lowest row whose flow is not 8-byte aligned (n: none).  Rows are refused in index order, a null row ahead of a
+// misaligned flow in the same row: the caller checks rows 0 .. min(m + 1, n) - 1 for null pointers, then refuses row m.
+int first_misaligned_flow(const float* const* flows, int n) {
+  int m = 0;
+  while (m < n && !((uintptr_t)flows[m] & 7)) ++m;
+  return m;
 }
 
 int flow_check(st_ctx* ctx, const char* what, int n, int h, int w) {
@@ -254,13 +261,11 @@ ST_EXPORT int st_flow_hist_batch(st_ctx* ctx, const float* const* flows_dev, int
   ST_TRY(flow_check(ctx, "flow histogram", n, h, w));
   if (n == 0) return ST_OK;
   if (!flows_dev || !out_dev) return st_set_error(ctx, ST_ERR_INVALID, "flow histogram: null argument");
-  for (int i = 0; i < n; ++i) {
-    if (!flows_dev[i]) return st_set_error(ctx, ST_ERR_INVALID, "flow histogram: flow %d is null", i);
-    if ((uintptr_t)flows_dev[i] & 7) return st_set_error(ctx, ST_ERR_INVALID, "flow histogram: flow %d is not 8-byte aligned", i);
-  }
-  ST_TRY(st_ws_reserve(ctx, st_align_up(sizeof(void*) * (size_t)n)));
-  const float** table = (const float**)st_ws_alloc(ctx, sizeof(void*) * (size_t)n);
-  ST_HIP(ctx, hipMemcpyAsync(table, flows_dev, sizeof(void*) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+  const int m = first_misaligned_flow(flows_dev, n);
+  ST_TRY(st_check_rows(ctx, "flow histogram: flow %d is null", m < n ? m + 1 : n, false, flows_dev));
+  if (m < n) return st_set_error(ctx, ST_ERR_INVALID, "flow histogram: flow %d is not 8-byte aligned", m);
+  const float** table;
+  ST_TRY(st_upload_tables(ctx, n, 0, flows_dev, &table));
   FlowSrc src{table, nullptr, 0};
   return flow_hist_launch(ctx, src, n, h, w, out_dev);
 }
@@ -282,25 +287,20 @@ ST_EXPORT int st_draw_flow_batch(st_ctx* ctx, const uint8_t* const* frames_dev, 
   ST_TRY(flow_check(ctx, "draw flow", n, h, w));
   if (n == 0) return ST_OK;
   if (!frames_dev || !flows_dev || !out_dev) return st_set_error(ctx, ST_ERR_INVALID, "draw flow: null argument");
+  const int m = first_misaligned_flow(flows_dev, n);
+  ST_TRY(st_check_rows(ctx, "draw flow: row %d is null", m < n ? m + 1 : n, false, frames_dev, flows_dev, out_dev));
+  if (m < n) return st_set_error(ctx, ST_ERR_INVALID, "draw flow: flow %d is not 8-byte aligned", m);
   bool aligned = (w % 4) == 0;
-  for (int i = 0; i < n; ++i) {
-    if (!frames_dev[i] || !flows_dev[i] || !out_dev[i]) return st_set_error(ctx, ST_ERR_INVALID, "draw flow: row %d is null", i);
-    if ((uintptr_t)flows_dev[i] & 7) return st_set_error(ctx, ST_ERR_INVALID, "draw flow: flow %d is not 8-byte aligned", i);
+  for (int i = 0; i < n; ++i)
     if (((uintptr_t)frames_dev[i] & 3) || ((uintptr_t)out_dev[i] & 3) || ((uintptr_t)flows_dev[i] & 15)) aligned = false;
-  }
-  const size_t tb = st_align_up(sizeof(void*) * (size_t)n);
-  ST_TRY(st_ws_reserve(ctx, 3 * tb + st_align_up(sizeof(int) * 2 * (size_t)n)));
-  const uint8_t** d_frames = (const uint8_t**)st_ws_alloc(ctx, tb);
-  const float** d_flows = (const float**)st_ws_alloc(ctx, tb);
-  uint8_t** d_outs = (uint8_t**)st_ws_alloc(ctx, tb);
+  const uint8_t** d_frames;
+  const float** d_flows;
+  uint8_t** d_outs;
+  ST_TRY(st_upload_tables(ctx, n, st_align_up(sizeof(int) * 2 * (size_t)n), frames_dev, &d_frames, flows_dev, &d_flows, out_dev, &d_outs));
   int* stats = (int*)st_ws_alloc(ctx, sizeof(int) * 2 * (size_t)n);
-  ST_HIP(ctx, hipMemcpyAsync(d_frames, frames_dev, sizeof(void*) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
-  ST_HIP(ctx, hipMemcpyAsync(d_flows, flows_dev, sizeof(void*) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
-  ST_HIP(ctx, hipMemcpyAsync(d_outs, out_dev, sizeof(void*) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
   const long long npx = (long long)h * w;
   st_timed t(ctx, ST_K_DRAW_FLOW);
-  for (int f0 = 0; f0 < n; f0 += 65535) {
-    const int nf = n - f0 < 65535 ? n - f0 : 65535;
+  return st_for_launches(n, [&](int f0, int nf) -> int {
     hipLaunchKernelGGL(k_init_stats, dim3((nf + 255) / 256), dim3(256), 0, ctx->stream, stats + 2 * (size_t)f0, nf);
     FlowSrc src{d_flows + f0, nullptr, 0};
     const long long chunks = chunks_for_grid(ctx->num_cus, nf, npx, 4 * kT);
@@ -313,6 +313,6 @@ ST_EXPORT int st_draw_flow_batch(st_ctx* ctx, const uint8_t* const* frames_dev, 
     else
       hipLaunchKernelGGL(k_draw_flow1, dim3((w + kT - 1) / kT, h, nf), dim3(kT), 0, ctx->stream, a);
     ST_HIP(ctx, hipGetLastError());
-  }
-  return ST_OK;
+    return ST_OK;
+  });
 }

@@ -542,9 +542,7 @@ int fm_launch(st_ctx* ctx, FrameSrc src, int n, int h, int w, int what, int64_t*
   const int rows = fm_band_rows(ctx, n, h, w);
   const int lg = fm_ring_log2(what, w);
   const unsigned bands = (unsigned)((h + rows - 1) / rows);
-  // grid.y is limited to 65535 frames per launch
-  for (int f0 = 0; f0 < n; f0 += 65535) {
-    const int nf = n - f0 < 65535 ? n - f0 : 65535;
+  return st_for_launches(n, [&](int f0, int nf) -> int {   // the frame index is grid.y
     FrameSrc s = src;
     if (s.ptrs) s.ptrs += f0; else s.base += (size_t)f0 * s.stride;
     unsigned long long* o = reinterpret_cast<unsigned long long*>(out_dev) + (size_t)f0 * 8;
@@ -555,8 +553,8 @@ int fm_launch(st_ctx* ctx, FrameSrc src, int n, int h, int w, int what, int64_t*
     else if (what == ST_FM_LAPLACIAN) fm_launch_one<ST_FM_LAPLACIAN>(lg, grid, ctx->stream, e0, e1, s, h, w, rows, o);
     else fm_launch_one<ST_FM_LUMA | ST_FM_LAPLACIAN>(lg, grid, ctx->stream, e0, e1, s, h, w, rows, o);
     ST_HIP(ctx, hipGetLastError());
-  }
-  return ST_OK;
+    return ST_OK;
+  });
 }
 
 // Checks every box of a call and plans its resize; nothing has been enqueued when this fails
@@ -593,13 +591,14 @@ int bb_run(st_ctx* ctx, const uint8_t* const* frames_host, FrameSrc src, int n, 
   bands = bands < 1 ? 1 : (bands > BB_MAX_BANDS ? BB_MAX_BANDS : bands);
   const int band_rows = (BB_S + bands - 1) / bands;
   bands = (BB_S + band_rows - 1) / band_rows;
-  const size_t tb = frames_host ? st_align_up(sizeof(void*) * (size_t)n) : 0, bb = st_align_up(sizeof(BoxK) * (size_t)m);
+  const size_t bb = st_align_up(sizeof(BoxK) * (size_t)m);
   const size_t pb = bands > 1 ? st_align_up(sizeof(unsigned long long) * 6 * (size_t)m * bands) : 0;
-  ST_TRY(st_ws_reserve(ctx, tb + bb + pb));
   if (frames_host) {
-    const uint8_t** table = (const uint8_t**)st_ws_alloc(ctx, tb);
-    ST_HIP(ctx, hipMemcpyAsync(table, frames_host, sizeof(void*) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+    const uint8_t** table;
+    ST_TRY(st_upload_tables(ctx, n, bb + pb, frames_host, &table));
     src.ptrs = table;
+  } else {
+    ST_TRY(st_ws_reserve(ctx, bb + pb));
   }
   BoxK* boxes = (BoxK*)st_ws_alloc(ctx, bb);
   unsigned long long* part = bands > 1 ? (unsigned long long*)st_ws_alloc(ctx, pb) : nullptr;
@@ -626,8 +625,7 @@ int bb_batch(st_ctx* ctx, const uint8_t* const* frames_dev, int n, int h, int w,
   ST_TRY(st_enter(ctx));
   if (n > 0 && m > 0) {
     if (!frames_dev) return st_set_error(ctx, ST_ERR_INVALID, "bbox moments: null frame table");
-    for (int i = 0; i < n; ++i)
-      if (!frames_dev[i]) return st_set_error(ctx, ST_ERR_INVALID, "bbox moments: frame %d is null", i);
+    ST_TRY(st_check_rows(ctx, "bbox moments: frame %d is null", n, false, frames_dev));
   }
   return bb_run(ctx, frames_dev, FrameSrc{nullptr, nullptr, 0}, n, h, w, boxes_host, m, moments_dev, kind, stat_dev);
 }
@@ -655,11 +653,9 @@ ST_EXPORT int st_frame_moments_u8c3_batch(st_ctx* ctx, const uint8_t* const* fra
   ST_TRY(fm_check(ctx, n, h, w, what, moments_dev));
   if (n == 0) return ST_OK;
   if (!frames_dev) return st_set_error(ctx, ST_ERR_INVALID, "frame moments: null frame table");
-  for (int i = 0; i < n; ++i)
-    if (!frames_dev[i]) return st_set_error(ctx, ST_ERR_INVALID, "frame moments: frame %d is null", i);
-  ST_TRY(st_ws_reserve(ctx, st_align_up(sizeof(void*) * (size_t)n)));
-  const uint8_t** table = (const uint8_t**)st_ws_alloc(ctx, sizeof(void*) * (size_t)n);
-  ST_HIP(ctx, hipMemcpyAsync(table, frames_dev, sizeof(void*) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+  ST_TRY(st_check_rows(ctx, "frame moments: frame %d is null", n, false, frames_dev));
+  const uint8_t** table;
+  ST_TRY(st_upload_tables(ctx, n, 0, frames_dev, &table));
   return fm_launch(ctx, FrameSrc{table, nullptr, 0}, n, h, w, what, moments_dev);
 }
 

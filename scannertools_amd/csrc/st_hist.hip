@@ -243,7 +243,7 @@ HistPlan hist_plan(st_ctx* ctx, int n, int h, int w, int bins) {
   const long long nvec = nbytes / 16;
   HistPlan p;
   p.half_steps = false;
-  const int nl = n < 65535 ? n : 65535;   // frames per launch (grid.y)
+  const int nl = n < kStMaxGridFrames ? n : kStMaxGridFrames;   // frames per launch (grid.y)
   // the reference's own bin count (16) gets counters for byte >> 4 directly: 6 KB of LDS instead of 96 KB, 256-thread workgroups,
   // eight resident per CU -- clearing and folding shrink 16-fold and overlap with other workgroups' streaming
   p.bins16 = bins == 16;
@@ -270,9 +270,7 @@ int hist_launch(st_ctx* ctx, FrameSrc src, int n, int h, int w, int bins, int32_
   const long long chunks = plan.chunks;
   const HistCommit hc{plan.mode};
   if (plan.mode == HC_ATOMIC) ST_HIP(ctx, hipMemsetAsync(out_dev, 0, sizeof(int32_t) * 3 * (size_t)bins * n, ctx->stream));
-  // grid.y is limited to 65535 frames per launch
-  for (int f0 = 0; f0 < n; f0 += 65535) {
-    int nf = n - f0 < 65535 ? n - f0 : 65535;
+  return st_for_launches(n, [&](int f0, int nf) -> int {   // the frame index is grid.y
     FrameSrc s = src;
     if (s.ptrs) s.ptrs += f0; else s.base += (size_t)f0 * s.stride;
     int32_t* o = out_dev + (size_t)f0 * 3 * bins;
@@ -287,8 +285,8 @@ int hist_launch(st_ctx* ctx, FrameSrc src, int n, int h, int w, int bins, int32_
     else
       hipExtLaunchKernelGGL((k_hist_u8c3_v2<32, 1024>), grid, dim3(1024), 0, ctx->stream, e0, e1, 0, s, nbytes, (int)chunks, bins, o, hc);
     ST_HIP(ctx, hipGetLastError());
-  }
-  return ST_OK;
+    return ST_OK;
+  });
 }
 
 int hist_check(st_ctx* ctx, int n, int h, int w, int bins, const void* out) {
@@ -431,12 +429,10 @@ ST_EXPORT int st_hist_u8c3_batch(st_ctx* ctx, const uint8_t* const* frames_dev, 
   ST_TRY(hist_check(ctx, n, h, w, bins, out_dev));
   if (n == 0) return ST_OK;
   if (!frames_dev) return st_set_error(ctx, ST_ERR_INVALID, "histogram: null frame table");
-  for (int i = 0; i < n; ++i)
-    if (!frames_dev[i]) return st_set_error(ctx, ST_ERR_INVALID, "histogram: frame %d is null", i);
+  ST_TRY(st_check_rows(ctx, "histogram: frame %d is null", n, false, frames_dev));
   const HistPlan plan = hist_plan(ctx, n, h, w, bins);
-  ST_TRY(st_ws_reserve(ctx, st_align_up(sizeof(void*) * (size_t)n)));
-  const uint8_t** table = (const uint8_t**)st_ws_alloc(ctx, sizeof(void*) * (size_t)n);
-  ST_HIP(ctx, hipMemcpyAsync(table, frames_dev, sizeof(void*) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+  const uint8_t** table;
+  ST_TRY(st_upload_tables(ctx, n, 0, frames_dev, &table));
   FrameSrc src{table, nullptr, 0};
   return hist_launch(ctx, src, n, h, w, bins, out_dev, plan);
 }

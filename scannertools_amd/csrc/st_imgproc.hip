@@ -1323,16 +1323,13 @@ ST_EXPORT int st_box_blur_u8c3_batch(st_ctx* ctx, const uint8_t* const* frames_d
     return st_set_error(ctx, ST_ERR_UNSUPPORTED, "blur: kernel_size %d outside [1, %d]", kernel_size, BL_MAXK);
   if (n == 0) return ST_OK;
   if (!frames_dev || !out_dev) return st_set_error(ctx, ST_ERR_INVALID, "blur: null argument");
-  for (int i = 0; i < n; ++i) {
-    if (!frames_dev[i] || !out_dev[i]) return st_set_error(ctx, ST_ERR_INVALID, "blur: row %d is null", i);
-    if (frames_dev[i] == out_dev[i]) return st_set_error(ctx, ST_ERR_INVALID, "blur: row %d aliases its output", i);
-  }
-  const size_t tb = st_align_up(sizeof(void*) * (size_t)n);
-  ST_TRY(st_ws_reserve(ctx, 2 * tb));
-  const uint8_t** d_src = (const uint8_t**)st_ws_alloc(ctx, tb);
-  uint8_t** d_dst = (uint8_t**)st_ws_alloc(ctx, tb);
-  ST_HIP(ctx, hipMemcpyAsync(d_src, frames_dev, sizeof(void*) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
-  ST_HIP(ctx, hipMemcpyAsync(d_dst, out_dev, sizeof(void*) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+  int m = 0;   // the lowest row that aliases its output; rows up to it are checked for null pointers first
+  while (m < n && frames_dev[m] != out_dev[m]) ++m;
+  ST_TRY(st_check_rows(ctx, "blur: row %d is null", m < n ? m + 1 : n, false, frames_dev, out_dev));
+  if (m < n) return st_set_error(ctx, ST_ERR_INVALID, "blur: row %d aliases its output", m);
+  const uint8_t** d_src;
+  uint8_t** d_dst;
+  ST_TRY(st_upload_tables(ctx, n, 0, frames_dev, &d_src, out_dev, &d_dst));
   BlurArgsK a;
   a.h = h; a.w = w; a.k = kernel_size;
   a.left = (kernel_size + 1) / 2 - 1;  // ceil(k/2.0) - 1
@@ -1354,16 +1351,15 @@ ST_EXPORT int st_box_blur_u8c3_batch(st_ctx* ctx, const uint8_t* const* frames_d
   // of the specialisation no longer fits -- 310+ registers, one wave per SIMD -- and the generic path is faster)
   ST_HIP(ctx, hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   const int nb = 3 * w;
-  for (int f0 = 0; f0 < n; f0 += 65535) {
-    const int nf = n - f0 < 65535 ? n - f0 : 65535;
+  return st_for_launches(n, [&](int f0, int nf) -> int {
     a.src = d_src + f0; a.dst = d_dst + f0;
     dim3 grid((nb + BL_TILEB - 1) / BL_TILEB, (h + BL_ROWS - 1) / BL_ROWS, nf);
     if (grid.y > 65535) return st_set_error(ctx, ST_ERR_UNSUPPORTED, "blur: frame too tall");
     st_timed t(ctx, ST_K_BLUR_OP);
     hipLaunchKernelGGL(kern, grid, dim3(BL_T), lds, ctx->stream, a);
     ST_HIP(ctx, hipGetLastError());
-  }
-  return ST_OK;
+    return ST_OK;
+  });
 }
 
 // cv::resize's scale factors for (h, w) -> (out_h, out_w) (st_internal.h)
@@ -1444,17 +1440,13 @@ ST_EXPORT int st_resize_u8_batch(st_ctx* ctx, const uint8_t* const* frames_dev, 
   if (out_h > 65535) return st_set_error(ctx, ST_ERR_UNSUPPORTED, "resize: output taller than 65535 rows");
   if (n == 0) return ST_OK;
   if (!frames_dev || !out_dev) return st_set_error(ctx, ST_ERR_INVALID, "resize: null argument");
-  for (int i = 0; i < n; ++i)
-    if (!frames_dev[i] || !out_dev[i] || frames_dev[i] == out_dev[i]) return st_set_error(ctx, ST_ERR_INVALID, "resize: row %d is null or aliased", i);
-  const size_t tb = st_align_up(sizeof(void*) * (size_t)n);
+  ST_TRY(st_check_rows(ctx, "resize: row %d is null or aliased", n, true, frames_dev, out_dev));
   const bool lanczos = interpolation == ST_INTER_LANCZOS4 && !(h == out_h && w == out_w);
   const size_t lz = lanczos ? st_align_up(sizeof(int) * (size_t)out_w) + st_align_up(sizeof(short) * 8 * (size_t)out_w) +
                               st_align_up(sizeof(int) * (size_t)out_h) + st_align_up(sizeof(short) * 8 * (size_t)out_h) : 0;
-  ST_TRY(st_ws_reserve(ctx, 2 * tb + lz));
-  const uint8_t** d_src = (const uint8_t**)st_ws_alloc(ctx, tb);
-  uint8_t** d_dst = (uint8_t**)st_ws_alloc(ctx, tb);
-  ST_HIP(ctx, hipMemcpyAsync(d_src, frames_dev, sizeof(void*) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
-  ST_HIP(ctx, hipMemcpyAsync(d_dst, out_dev, sizeof(void*) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+  const uint8_t** d_src;
+  uint8_t** d_dst;
+  ST_TRY(st_upload_tables(ctx, n, lz, frames_dev, &d_src, out_dev, &d_dst));
   ResizeArgsK a;
   memset(&a, 0, sizeof(a));
   rs_plan(&a, h, w, channels, out_h, out_w, interpolation);
@@ -1476,8 +1468,7 @@ ST_EXPORT int st_resize_u8_batch(st_ctx* ctx, const uint8_t* const* frames_dev, 
     ST_HIP(ctx, hipMemcpyAsync(db_, hb.data(), sizeof(short) * hb.size(), hipMemcpyHostToDevice, ctx->stream));
     a.xofs = dx_; a.ialpha = da_; a.yofs = dy_; a.ibeta = db_;
   }
-  for (int f0 = 0; f0 < n; f0 += 65535) {
-    const int nf = n - f0 < 65535 ? n - f0 : 65535;
+  return st_for_launches(n, [&](int f0, int nf) -> int {
     a.src = d_src + f0; a.dst = d_dst + f0;
     st_timed t(ctx, ST_K_RESIZE);
     const bool fast = a.mode == RS_LINEAR && channels == 3;
@@ -1507,8 +1498,8 @@ ST_EXPORT int st_resize_u8_batch(st_ctx* ctx, const uint8_t* const* frames_dev, 
     else
       hipLaunchKernelGGL(k_resize_u8, dim3((out_w + 255) / 256, out_h, nf), dim3(256), 0, ctx->stream, a);
     ST_HIP(ctx, hipGetLastError());
-  }
-  return ST_OK;
+    return ST_OK;
+  });
 }
 
 ST_EXPORT int st_montage_geometry(int frame_h, int frame_w, int64_t num_frames, int target_width, int frames_per_row,
@@ -1549,20 +1540,16 @@ ST_EXPORT int st_montage_u8c3_batch(st_ctx* ctx, const uint8_t* const* frames_de
   if (target_h > 65535) return st_set_error(ctx, ST_ERR_UNSUPPORTED, "montage: tiles taller than 65535 rows");
   if (n == 0) return ST_OK;
   if (!frames_dev || !montage_dev) return st_set_error(ctx, ST_ERR_INVALID, "montage: null argument");
-  for (int i = 0; i < n; ++i)
-    if (!frames_dev[i]) return st_set_error(ctx, ST_ERR_INVALID, "montage: row %d is null", i);
-  const size_t tb = st_align_up(sizeof(void*) * (size_t)n);
-  ST_TRY(st_ws_reserve(ctx, tb));
-  const uint8_t** d_src = (const uint8_t**)st_ws_alloc(ctx, tb);
-  ST_HIP(ctx, hipMemcpyAsync(d_src, frames_dev, sizeof(void*) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+  ST_TRY(st_check_rows(ctx, "montage: row %d is null", n, false, frames_dev));
+  const uint8_t** d_src;
+  ST_TRY(st_upload_tables(ctx, n, 0, frames_dev, &d_src));
   ResizeTileArgsK a;
   memset(&a, 0, sizeof(a));
   rs_plan(&a, h, w, 3, target_h, target_w, ST_INTER_LINEAR);
   a.canvas = montage_dev;
   a.pitch = (size_t)montage_w * 3;
   a.per_row = frames_per_row;
-  for (int f0 = 0; f0 < n; f0 += 65535) {  // one launch up to 65535 frames
-    const int nf = n - f0 < 65535 ? n - f0 : 65535;
+  return st_for_launches(n, [&](int f0, int nf) -> int {
     a.src = d_src + f0;
     a.first_slot = first_slot + f0;
     st_timed t(ctx, ST_K_RESIZE);
@@ -1574,8 +1561,8 @@ ST_EXPORT int st_montage_u8c3_batch(st_ctx* ctx, const uint8_t* const* frames_de
       hipLaunchKernelGGL((k_resize_linear_c3_v4<false, ResizeTileArgsK>), dim3(((target_w + 3) / 4 + 255) / 256, (target_h + RL_ROWS - 1) / RL_ROWS, nf),
                          dim3(256), 0, ctx->stream, a);
     ST_HIP(ctx, hipGetLastError());
-  }
-  return ST_OK;
+    return ST_OK;
+  });
 }
 
 ST_EXPORT int st_cvt_color_out_channels(int code, int in_channels) {
@@ -1630,20 +1617,17 @@ ST_EXPORT int st_cvt_color_u8_batch(st_ctx* ctx, const uint8_t* const* frames_de
   if (gray_bits != 14 && gray_bits != 15) return st_set_error(ctx, ST_ERR_INVALID, "cvt_color: gray_bits must be 14 or 15");
   if (n == 0) return ST_OK;
   if (!frames_dev || !out_dev) return st_set_error(ctx, ST_ERR_INVALID, "cvt_color: null argument");
-  for (int i = 0; i < n; ++i)
-    if (!frames_dev[i] || !out_dev[i] || frames_dev[i] == out_dev[i]) return st_set_error(ctx, ST_ERR_INVALID, "cvt_color: row %d is null or aliased", i);
-  const size_t tb = st_align_up(sizeof(void*) * (size_t)n);
-  ST_TRY(st_ws_reserve(ctx, 2 * tb));
-  const uint8_t** d_src = (const uint8_t**)st_ws_alloc(ctx, tb);
-  uint8_t** d_dst = (uint8_t**)st_ws_alloc(ctx, tb);
-  ST_HIP(ctx, hipMemcpyAsync(d_src, frames_dev, sizeof(void*) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
-  ST_HIP(ctx, hipMemcpyAsync(d_dst, out_dev, sizeof(void*) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+  ST_TRY(st_check_rows(ctx, "cvt_color: row %d is null or aliased", n, true, frames_dev, out_dev));
+  const uint8_t** d_src;
+  uint8_t** d_dst;
+  ST_TRY(st_upload_tables(ctx, n, 0, frames_dev, &d_src, out_dev, &d_dst));
+  // the whole-dword kernels need every frame of the call, source and destination, to start on their boundary
+  unsigned align = 0;
+  for (int i = 0; i < n; ++i) align |= (unsigned)((uintptr_t)frames_dev[i] | (uintptr_t)out_dev[i]);
   YuvDesc yd;
   if (cvt_yuv_of(code, &yd)) {
     YuvArgsK ya;
     ya.H = oh; ya.W = ow; ya.d = yd;
-    unsigned align = 0;
-    for (int i = 0; i < n; ++i) align |= (unsigned)((uintptr_t)frames_dev[i] | (uintptr_t)out_dev[i]);
     // 16 pixels per thread need 16-byte aligned rows of luma AND of chroma (planar chroma rows are W / 2 bytes: W % 32)
     const bool planar = yd.kind == 1;
     const bool packed422 = yd.kind == 2 || yd.kind == 4;  // 80 bytes per thread at 16 pixels: measured slower than 4 (3.3 vs 4.0 TB/s)
@@ -1651,8 +1635,7 @@ ST_EXPORT int st_cvt_color_u8_batch(st_ctx* ctx, const uint8_t* const* frames_de
                    : ((ow % 4 == 0 && (align & 3) == 0) ? 4 : 1);
     long long by = (((long long)oh * ow) / px + 255) / 256;
     if (by > 8192) by = 8192;
-    for (int f0 = 0; f0 < n; f0 += 65535) {
-      const int nf = n - f0 < 65535 ? n - f0 : 65535;
+    return st_for_launches(n, [&](int f0, int nf) -> int {
       ya.src = d_src + f0; ya.dst = d_dst + f0;
       st_timed t(ctx, ST_K_CVT_COLOR);
       const dim3 grid((unsigned)by, nf);
@@ -1667,8 +1650,8 @@ ST_EXPORT int st_cvt_color_u8_batch(st_ctx* ctx, const uint8_t* const* frames_de
       else YUV_VEC(4);
 #undef YUV_VEC
       ST_HIP(ctx, hipGetLastError());
-    }
-    return ST_OK;
+      return ST_OK;
+    });
   }
   CvtArgsK a;
   a.npix = (long long)h * w; a.code = code;
@@ -1681,13 +1664,10 @@ ST_EXPORT int st_cvt_color_u8_batch(st_ctx* ctx, const uint8_t* const* frames_de
   a.scn = channels; a.dcn = oc;
   // whole-dword paths: 16 (4) pixels per thread when every frame starts on a 16- (4-) byte boundary and holds a multiple of
   // 16 (4) pixels
-  unsigned align = 0;
-  for (int i = 0; i < n; ++i) align |= (unsigned)((uintptr_t)frames_dev[i] | (uintptr_t)out_dev[i]);
   const int px = (a.npix % 16 == 0 && (align & 15) == 0) ? 16 : ((a.npix % 4 == 0 && (align & 3) == 0) ? 4 : 1);
   long long bx = (a.npix / px + 255) / 256;
   if (bx > 8192) bx = 8192;
-  for (int f0 = 0; f0 < n; f0 += 65535) {
-    const int nf = n - f0 < 65535 ? n - f0 : 65535;
+  return st_for_launches(n, [&](int f0, int nf) -> int {
     a.src = d_src + f0; a.dst = d_dst + f0;
     st_timed t(ctx, ST_K_CVT_COLOR);
     const dim3 grid((unsigned)bx, nf);
@@ -1716,6 +1696,6 @@ ST_EXPORT int st_cvt_color_u8_batch(st_ctx* ctx, const uint8_t* const* frames_de
     }
 #undef CVT_V4
     ST_HIP(ctx, hipGetLastError());
-  }
-  return ST_OK;
+    return ST_OK;
+  });
 }

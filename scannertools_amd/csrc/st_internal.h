@@ -171,6 +171,44 @@ void st_ws_reset(st_ctx* ctx);
 void* st_ws_alloc(st_ctx* ctx, size_t bytes);  // nullptr if the reservation is exhausted
 inline size_t st_align_up(size_t v, size_t a = 256) { return (v + a - 1) / a * a; }
 
+// ---- The host-side frame of a batched entry point: row checks, pointer tables, launch cuts.
+// A kernel that takes its frame index from gridDim.y or gridDim.z serves at most this many frames per launch.
+constexpr int kStMaxGridFrames = 65535;
+
+// Cuts a call of n frames into launches: body(f0, nf) -> status for frames f0 .. f0 + nf - 1, nf <= kStMaxGridFrames;
+// stops at the first status that is not ST_OK and returns it.
+template <class Body>
+inline int st_for_launches(int n, Body&& body) {
+  for (int f0 = 0; f0 < n; f0 += kStMaxGridFrames) ST_TRY(body(f0, n - f0 < kStMaxGridFrames ? n - f0 : kStMaxGridFrames));
+  return ST_OK;
+}
+
+// Refuses the lowest row i at which one of the host tables a, b, c (b and c may be absent) holds a null pointer, or, with
+// no_alias, at which a[i] == b[i]: ST_ERR_INVALID, with `fmt` taking the row index.
+template <class A, class B = void, class C = void>
+inline int st_check_rows(st_ctx* ctx, const char* fmt, int n, bool no_alias, A* const* a, B* const* b = nullptr, C* const* c = nullptr) {
+  for (int i = 0; i < n; ++i)
+    if (!a[i] || (b && !b[i]) || (c && !c[i]) || (no_alias && (const void*)a[i] == (const void*)b[i]))
+      return st_set_error(ctx, ST_ERR_INVALID, fmt, i);
+  return ST_OK;
+}
+
+// Device copies of one to three host tables of n pointers each: reserves the tables' workspace plus `extra` bytes (which
+// the caller allocates afterwards), then per (host table, device table out) pair allocates and enqueues the copy on ctx->stream.
+inline int st_upload_table(st_ctx*, size_t) { return ST_OK; }
+template <class D, class... Rest>
+inline int st_upload_table(st_ctx* ctx, size_t bytes, const void* host, D** dev, Rest... rest) {
+  if (!(*dev = (D*)st_ws_alloc(ctx, bytes))) return st_set_error(ctx, ST_ERR_OOM, "pointer table: workspace exhausted");
+  ST_HIP(ctx, hipMemcpyAsync(*dev, host, bytes, hipMemcpyHostToDevice, ctx->stream));
+  return st_upload_table(ctx, bytes, rest...);
+}
+template <class... Pairs>
+inline int st_upload_tables(st_ctx* ctx, int n, size_t extra, Pairs... pairs) {
+  const size_t bytes = sizeof(void*) * (size_t)n;
+  ST_TRY(st_ws_reserve(ctx, sizeof...(Pairs) / 2 * st_align_up(bytes) + extra));
+  return st_upload_table(ctx, bytes, pairs...);
+}
+
 // Timing brackets for kernel class `id` (no-ops unless enabled in timing_mask).
 int st_time_begin(st_ctx* ctx, int id);
 int st_time_end(st_ctx* ctx, int id);

@@ -700,15 +700,15 @@ int GpuPlan::run_sub_batch(const GpuSubBatch& sb, st_jpeg_state* js, uint8_t* d_
     word = *gstatus;
     if (word == kStJpegEntClean) {
       const DenseMost m = dense_most(reinterpret_cast<const JpegFrameHdr*>(static_cast<const uint8_t*>(js->gpin) + sb.hdr_off), sb.count);
-      // the dense kernels take the frame from blockIdx.y: at most 65 535 frames per launch, the headers offset so that the
-      // coefficients stay where slot + nf * 512 points
-      for (int f0 = 0; f0 < sb.count; f0 += 65535) {
-        const int nfl = std::min(65535, sb.count - f0);
+      // the dense kernels take the frame from blockIdx.y: the headers of a launch are offset so that the coefficients stay
+      // where slot + nf * 512 points
+      (void)st_for_launches(sb.count, [&](int f0, int nfl) -> int {
         JpegArgsK a;
         a.slot = d_up + sb.hdr_off + (size_t)f0 * sizeof(JpegFrameHdr);
         a.planes = d_planes; a.nf = sb.count - f0; a.h = h; a.w = w; a.channels = channels;
         launch_dense(ctx, a, nfl, d, px, m);
-      }
+        return ST_OK;
+      });
     }
   }
   ST_HIP(ctx, hipGetLastError());

@@ -826,8 +826,7 @@ int encode_batch(st_ctx* ctx, const uint8_t* const* frames_dev, int n, int h, in
     return ST_OK;
   }
   if (!frames_dev) return st_set_error(ctx, ST_ERR_INVALID, "jpeg_encode: null frame table");
-  for (int i = 0; i < n; ++i)
-    if (!frames_dev[i]) return st_set_error(ctx, ST_ERR_INVALID, "jpeg_encode: frame %d is a null pointer", i);
+  ST_TRY(st_check_rows(ctx, "jpeg_encode: frame %d is a null pointer", n, false, frames_dev));
   StJpegEncGeom g;
   st_jpeg_enc_geom(h, w, h_samp, v_samp, &g);
   const long long intervals = (long long)n * g.mrows;
@@ -859,13 +858,13 @@ int encode_batch(st_ctx* ctx, const uint8_t* const* frames_dev, int n, int h, in
   ST_TRY(grow(ctx, &s->offs, &s->offs_cap, (size_t)n + 1, "the stream offsets"));
   if (opt) ST_TRY(grow(ctx, &s->stats, &s->stats_cap, (size_t)n * (kJpegOptTables * 256), "the symbol counts"));
 
-  const size_t tb = sizeof(void*) * (size_t)n, cb = (size_t)intervals * (size_t)nblk * 128, sb = (size_t)intervals * slot_bytes;
+  const size_t cb = (size_t)intervals * (size_t)nblk * 128, sb = (size_t)intervals * slot_bytes;
   const size_t lb = sizeof(unsigned) * (size_t)intervals, ob = sizeof(u64) * (size_t)intervals;
   // the frames' own code words, headers and header lengths
   const size_t hwb = sizeof(uint32_t) * kJpegEncHuffWords * (size_t)n, hdb = kJpegEncHeaderStride * (size_t)n, hlb = sizeof(unsigned) * (size_t)n;
-  ST_TRY(st_ws_reserve(ctx, st_align_up(tb) + st_align_up(cb) + st_align_up(sb) + st_align_up(lb) + st_align_up(ob) +
-                                (rst ? 0 : st_align_up(lb) + st_align_up(ob)) + (opt ? st_align_up(hwb) + st_align_up(hdb) + st_align_up(hlb) : 0)));
-  const uint8_t** d_frames = (const uint8_t**)st_ws_alloc(ctx, tb);
+  const uint8_t** d_frames;
+  ST_TRY(st_upload_tables(ctx, n, st_align_up(cb) + st_align_up(sb) + st_align_up(lb) + st_align_up(ob) + (rst ? 0 : st_align_up(lb) + st_align_up(ob)) +
+                                  (opt ? st_align_up(hwb) + st_align_up(hdb) + st_align_up(hlb) : 0), frames_dev, &d_frames));
   int16_t* d_coef = (int16_t*)st_ws_alloc(ctx, cb);
   uint8_t* d_slots = (uint8_t*)st_ws_alloc(ctx, sb);
   unsigned* d_ilen = (unsigned*)st_ws_alloc(ctx, lb);
@@ -875,9 +874,8 @@ int encode_batch(st_ctx* ctx, const uint8_t* const* frames_dev, int n, int h, in
   uint32_t* d_huff = opt ? (uint32_t*)st_ws_alloc(ctx, hwb) : nullptr;
   uint8_t* d_headers = opt ? (uint8_t*)st_ws_alloc(ctx, hdb) : nullptr;
   unsigned* d_hlen = opt ? (unsigned*)st_ws_alloc(ctx, hlb) : nullptr;
-  if (!d_frames || !d_coef || !d_slots || !d_ilen || !d_ioff || !d_slen || !d_bitoff || (opt && (!d_huff || !d_headers || !d_hlen)))
+  if (!d_coef || !d_slots || !d_ilen || !d_ioff || !d_slen || !d_bitoff || (opt && (!d_huff || !d_headers || !d_hlen)))
     return st_set_error(ctx, ST_ERR_OOM, "jpeg_encode: workspace exhausted");
-  ST_HIP(ctx, hipMemcpyAsync(d_frames, frames_dev, tb, hipMemcpyHostToDevice, ctx->stream));
 
   EncTransformK t;
   t.frames = d_frames; t.coef = d_coef; t.total = intervals * nblk;

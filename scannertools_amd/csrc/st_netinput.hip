@@ -461,30 +461,25 @@ ST_EXPORT int st_facenet_input_batch(st_ctx* ctx, const uint8_t* const* frames_d
   if ((nh + FN_ROWS - 1) / FN_ROWS > 65535) return st_set_error(ctx, ST_ERR_UNSUPPORTED, "facenet_input: network input too tall");
   if (n == 0) return ST_OK;
   if (!frames_dev || !out_dev) return st_set_error(ctx, ST_ERR_INVALID, "facenet_input: null argument");
-  for (int i = 0; i < n; ++i)
-    if (!frames_dev[i] || !out_dev[i]) return st_set_error(ctx, ST_ERR_INVALID, "facenet_input: row %d is null", i);
+  ST_TRY(st_check_rows(ctx, "facenet_input: row %d is null", n, false, frames_dev, out_dev));
   ST_TRY(facenet_plan(ctx, h, w, nh, nw));
   const st_netin_plan& p = ctx->netin->facenet;
-  const size_t tb = st_align_up(sizeof(void*) * (size_t)n);
-  ST_TRY(st_ws_reserve(ctx, 2 * tb));
-  const uint8_t** d_src = (const uint8_t**)st_ws_alloc(ctx, tb);
-  float** d_dst = (float**)st_ws_alloc(ctx, tb);
-  ST_HIP(ctx, hipMemcpyAsync(d_src, frames_dev, sizeof(void*) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
-  ST_HIP(ctx, hipMemcpyAsync(d_dst, out_dev, sizeof(void*) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+  const uint8_t** d_src;
+  float** d_dst;
+  ST_TRY(st_upload_tables(ctx, n, 0, frames_dev, &d_src, out_dev, &d_dst));
   FacenetK a;
   a.xt = (const FnX*)p.dev; a.yt = (const FnY*)((const char*)p.dev + p.y_off);
   a.sh = h; a.sw = w; a.nh = nh; a.nw = nw; a.cx = p.cx; a.mode = p.mode;
   a.vec_in = (3 * (long long)w) % 16 == 0 && all_aligned16((const void* const*)frames_dev, n);
   a.vec_out = all_aligned16((const void* const*)out_dev, n);
   a.mean[0] = mean[0]; a.mean[1] = mean[1]; a.mean[2] = mean[2];
-  for (int f0 = 0; f0 < n; f0 += 65535) {
-    const int nf = n - f0 < 65535 ? n - f0 : 65535;
+  return st_for_launches(n, [&](int f0, int nf) -> int {
     a.src = d_src + f0; a.dst = d_dst + f0;
     st_timed t(ctx, ST_K_NET_INPUT);
     hipLaunchKernelGGL(k_facenet_input, dim3((nw + p.cx - 1) / p.cx, (nh + FN_ROWS - 1) / FN_ROWS, nf), dim3(256), 0, ctx->stream, a);
     ST_HIP(ctx, hipGetLastError());
-  }
-  return ST_OK;
+    return ST_OK;
+  });
 }
 
 ST_EXPORT int st_caffe_input_axis(int n_in, int n_out, int* begin, int* first, int* count) {
@@ -526,27 +521,22 @@ ST_EXPORT int st_caffe_input_batch(st_ctx* ctx, const uint8_t* const* frames_dev
   if (st != ST_OK) return st;
   if (n == 0) return ST_OK;
   if (!frames_dev || !out_dev) return st_set_error(ctx, ST_ERR_INVALID, "caffe_input: null argument");
-  for (int i = 0; i < n; ++i)
-    if (!frames_dev[i] || !out_dev[i]) return st_set_error(ctx, ST_ERR_INVALID, "caffe_input: row %d is null", i);
+  ST_TRY(st_check_rows(ctx, "caffe_input: row %d is null", n, false, frames_dev, out_dev));
   const st_netin_plan& p = ctx->netin->caffe;
-  const size_t tb = st_align_up(sizeof(void*) * (size_t)n);
-  ST_TRY(st_ws_reserve(ctx, 2 * tb));
-  const uint8_t** d_src = (const uint8_t**)st_ws_alloc(ctx, tb);
-  float** d_dst = (float**)st_ws_alloc(ctx, tb);
-  ST_HIP(ctx, hipMemcpyAsync(d_src, frames_dev, sizeof(void*) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
-  ST_HIP(ctx, hipMemcpyAsync(d_dst, out_dev, sizeof(void*) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+  const uint8_t** d_src;
+  float** d_dst;
+  ST_TRY(st_upload_tables(ctx, n, 0, frames_dev, &d_src, out_dev, &d_dst));
   CaffeK a;
   a.xt = (const CfTap*)p.dev; a.yt = (const CfTap*)((const char*)p.dev + p.y_off);
   a.sh = h; a.sw = w; a.nh = net_h; a.nw = net_w; a.cx = p.cx; a.orows = p.orows; a.seg = p.seg; a.smax = p.smax;
   a.vec_in = (3 * (long long)w) % 16 == 0 && all_aligned16((const void* const*)frames_dev, n);
   a.normalize = normalize != 0;
   a.mean[0] = mean_bgr[0]; a.mean[1] = mean_bgr[1]; a.mean[2] = mean_bgr[2];
-  for (int f0 = 0; f0 < n; f0 += 65535) {
-    const int nf = n - f0 < 65535 ? n - f0 : 65535;
+  return st_for_launches(n, [&](int f0, int nf) -> int {
     a.src = d_src + f0; a.dst = d_dst + f0;
     st_timed t(ctx, ST_K_NET_INPUT);
     hipLaunchKernelGGL(k_caffe_input, dim3((net_w + p.cx - 1) / p.cx, (net_h + p.orows - 1) / p.orows, nf), dim3(256), p.lds, ctx->stream, a);
     ST_HIP(ctx, hipGetLastError());
-  }
-  return ST_OK;
+    return ST_OK;
+  });
 }

@@ -413,12 +413,9 @@ ST_EXPORT int st_nhwc_to_planar_f32(st_ctx* ctx, const float* x_dev, int n, int 
   ST_TRY(st_enter(ctx));
   if (!x_dev || !out_dev || n <= 0 || h <= 0 || w <= 0 || !slice_ok(c, x_stride, x_offset))
     return st_set_error(ctx, ST_ERR_INVALID, "nhwc_to_planar: bad arguments");
-  for (int i = 0; i < n; ++i)
-    if (!out_dev[i]) return st_set_error(ctx, ST_ERR_INVALID, "nhwc_to_planar: row %d is null", i);
-  const size_t tb = st_align_up(sizeof(void*) * (size_t)n);
-  ST_TRY(st_ws_reserve(ctx, tb));
-  float** d_out = (float**)st_ws_alloc(ctx, tb);
-  ST_HIP(ctx, hipMemcpyAsync(d_out, out_dev, sizeof(void*) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+  ST_TRY(st_check_rows(ctx, "nhwc_to_planar: row %d is null", n, false, out_dev));
+  float** d_out;
+  ST_TRY(st_upload_tables(ctx, n, 0, out_dev, &d_out));
   PlanarOutArgs a;
   a.x = x_dev; a.out = d_out; a.hw = (long long)h * w; a.n = n; a.c = c; a.xs = x_stride; a.xoff = x_offset;
   st_timed t(ctx, ST_K_CONV);

@@ -399,26 +399,21 @@ ST_EXPORT int st_cpm2_input_batch(st_ctx* ctx, const uint8_t* const* frames_dev,
   if (nh > 65535) return st_set_error(ctx, ST_ERR_UNSUPPORTED, "cpm2_input: network input taller than 65535 rows");
   if (n == 0) return ST_OK;
   if (!frames_dev || !out_dev) return st_set_error(ctx, ST_ERR_INVALID, "cpm2_input: null argument");
-  for (int i = 0; i < n; ++i)
-    if (!frames_dev[i] || !out_dev[i]) return st_set_error(ctx, ST_ERR_INVALID, "cpm2_input: row %d is null", i);
-  const size_t tb = st_align_up(sizeof(void*) * (size_t)n);
-  ST_TRY(st_ws_reserve(ctx, 2 * tb));
-  const uint8_t** d_src = (const uint8_t**)st_ws_alloc(ctx, tb);
-  float** d_dst = (float**)st_ws_alloc(ctx, tb);
-  ST_HIP(ctx, hipMemcpyAsync(d_src, frames_dev, sizeof(void*) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
-  ST_HIP(ctx, hipMemcpyAsync(d_dst, out_dev, sizeof(void*) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+  ST_TRY(st_check_rows(ctx, "cpm2_input: row %d is null", n, false, frames_dev, out_dev));
+  const uint8_t** d_src;
+  float** d_dst;
+  ST_TRY(st_upload_tables(ctx, n, 0, frames_dev, &d_src, out_dev, &d_dst));
   Cpm2InArgs a;
   a.sh = h; a.sw = w; a.rh = rh; a.rw = rw; a.nh = nh; a.nw = nw;
   a.scale_x = 1. / ((double)rw / w);
   a.scale_y = 1. / ((double)rh / h);
-  for (int f0 = 0; f0 < n; f0 += 65535) {
-    const int nf = n - f0 < 65535 ? n - f0 : 65535;
+  return st_for_launches(n, [&](int f0, int nf) -> int {
     a.src = d_src + f0; a.dst = d_dst + f0;
     st_timed t(ctx, ST_K_CPM2_INPUT);
     hipLaunchKernelGGL(k_cpm2_input, dim3((nw + 255) / 256, nh, nf), dim3(256), 0, ctx->stream, a);
     ST_HIP(ctx, hipGetLastError());
-  }
-  return ST_OK;
+    return ST_OK;
+  });
 }
 
 ST_EXPORT int st_cpm2_limb_scores(st_ctx* ctx, const float* const* heatmaps_dev, const float* const* peaks_dev, int n,
@@ -429,32 +424,27 @@ ST_EXPORT int st_cpm2_limb_scores(st_ctx* ctx, const float* const* heatmaps_dev,
     return st_set_error(ctx, ST_ERR_INVALID, "cpm2_limb_scores: bad arguments (n=%d %dx%d max_peaks=%d)", n, net_h, net_w, max_peaks);
   if (n == 0) return ST_OK;
   if (!heatmaps_dev || !peaks_dev || !scores_dev) return st_set_error(ctx, ST_ERR_INVALID, "cpm2_limb_scores: null argument");
-  for (int i = 0; i < n; ++i)
-    if (!heatmaps_dev[i] || !peaks_dev[i]) return st_set_error(ctx, ST_ERR_INVALID, "cpm2_limb_scores: row %d is null", i);
-  const size_t tb = st_align_up(sizeof(void*) * (size_t)n);
-  ST_TRY(st_ws_reserve(ctx, 2 * tb));
-  const float** d_hm = (const float**)st_ws_alloc(ctx, tb);
-  const float** d_pk = (const float**)st_ws_alloc(ctx, tb);
-  ST_HIP(ctx, hipMemcpyAsync(d_hm, heatmaps_dev, sizeof(void*) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
-  ST_HIP(ctx, hipMemcpyAsync(d_pk, peaks_dev, sizeof(void*) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+  ST_TRY(st_check_rows(ctx, "cpm2_limb_scores: row %d is null", n, false, heatmaps_dev, peaks_dev));
+  const float** d_hm;
+  const float** d_pk;
+  ST_TRY(st_upload_tables(ctx, n, 0, heatmaps_dev, &d_hm, peaks_dev, &d_pk));
   LimbArgs a;
   a.h = net_h; a.w = net_w; a.max_peaks = max_peaks; a.min_above = min_above; a.threshold = inter_threshold;
-  for (int f0 = 0; f0 < n; f0 += 65535) {
-    const int nf = n - f0 < 65535 ? n - f0 : 65535;
+  return st_for_launches(n, [&](int f0, int nf) -> int {
     a.heatmaps = d_hm + f0; a.peaks = d_pk + f0;
     a.scores = scores_dev + (size_t)f0 * 19 * max_peaks * max_peaks;
     st_timed t(ctx, ST_K_CPM2_LIMBS);
     hipLaunchKernelGGL(k_cpm2_limb_scores, dim3(19, nf), dim3(256), 0, ctx->stream, a);
     ST_HIP(ctx, hipGetLastError());
-  }
-  return ST_OK;
+    return ST_OK;
+  });
 }
 
 ST_EXPORT int st_cpm2_resize_maps(st_ctx* ctx, const float* src_dev, int n, int src_h, int src_w, int src_stride,
                                   const int* chan_map, int nmaps, int dst_h, int dst_w, float* const* out_dev) {
   ST_TRY(st_enter(ctx));
   if (n < 0 || src_h <= 0 || src_w <= 0 || src_stride <= 0 || nmaps <= 0 || nmaps > 64 || dst_h <= 0 || dst_w <= 0 ||
-      (long long)dst_h * dst_w > 35000000LL || n > 65535)
+      (long long)dst_h * dst_w > 35000000LL || n > kStMaxGridFrames)
     return st_set_error(ctx, ST_ERR_INVALID, "cpm2_resize_maps: bad arguments (n=%d %dx%d -> %dx%d, %d maps)", n, src_h, src_w, dst_h, dst_w, nmaps);
   if (n == 0) return ST_OK;
   if (!src_dev || !out_dev) return st_set_error(ctx, ST_ERR_INVALID, "cpm2_resize_maps: null argument");
@@ -463,12 +453,9 @@ ST_EXPORT int st_cpm2_resize_maps(st_ctx* ctx, const float* src_dev, int n, int 
     a.chan[c] = chan_map ? chan_map[c] : c;
     if (a.chan[c] < 0 || a.chan[c] >= src_stride) return st_set_error(ctx, ST_ERR_INVALID, "cpm2_resize_maps: channel %d outside the source pixel", a.chan[c]);
   }
-  for (int i = 0; i < n; ++i)
-    if (!out_dev[i]) return st_set_error(ctx, ST_ERR_INVALID, "cpm2_resize_maps: row %d is null", i);
-  const size_t tb = st_align_up(sizeof(void*) * (size_t)n);
-  ST_TRY(st_ws_reserve(ctx, tb));
-  float** d_dst = (float**)st_ws_alloc(ctx, tb);
-  ST_HIP(ctx, hipMemcpyAsync(d_dst, out_dev, sizeof(void*) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+  ST_TRY(st_check_rows(ctx, "cpm2_resize_maps: row %d is null", n, false, out_dev));
+  float** d_dst;
+  ST_TRY(st_upload_tables(ctx, n, 0, out_dev, &d_dst));
   a.src = src_dev; a.dst = d_dst;
   a.sh = src_h; a.sw = src_w; a.stride = src_stride; a.nmaps = nmaps; a.th = dst_h; a.tw = dst_w;
   // the layer's own arithmetic: `tw/float(ow)/2 - 0.5` is a float quotient minus a double constant, stored as float
@@ -487,7 +474,7 @@ ST_EXPORT int st_cpm2_resize_merge_maps(st_ctx* ctx, const float* const* src_dev
                                         int dst_w, float* const* out_dev) {
   ST_TRY(st_enter(ctx));
   if (scales < 1 || scales > RM_MAX_SCALES || n < 0 || src_stride <= 0 || nmaps <= 0 || nmaps > 64 || dst_h <= 0 || dst_w <= 0 ||
-      (long long)dst_h * dst_w > 35000000LL || n > 65535 || !src_h || !src_w || !eff_h || !eff_w)
+      (long long)dst_h * dst_w > 35000000LL || n > kStMaxGridFrames || !src_h || !src_w || !eff_h || !eff_w)
     return st_set_error(ctx, ST_ERR_INVALID, "cpm2_resize_merge_maps: bad arguments (%d scales, n=%d -> %dx%d, %d maps)", scales, n, dst_h, dst_w, nmaps);
   if (n == 0) return ST_OK;
   if (!src_dev || !out_dev) return st_set_error(ctx, ST_ERR_INVALID, "cpm2_resize_merge_maps: null argument");
@@ -507,12 +494,9 @@ ST_EXPORT int st_cpm2_resize_merge_maps(st_ctx* ctx, const float* const* src_dev
     a.rx[s] = eff_w[s] / (float)dst_w;
     a.ry[s] = eff_h[s] / (float)dst_h;
   }
-  for (int i = 0; i < n; ++i)
-    if (!out_dev[i]) return st_set_error(ctx, ST_ERR_INVALID, "cpm2_resize_merge_maps: row %d is null", i);
-  const size_t tb = st_align_up(sizeof(void*) * (size_t)n);
-  ST_TRY(st_ws_reserve(ctx, tb));
-  float** d_dst = (float**)st_ws_alloc(ctx, tb);
-  ST_HIP(ctx, hipMemcpyAsync(d_dst, out_dev, sizeof(void*) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+  ST_TRY(st_check_rows(ctx, "cpm2_resize_merge_maps: row %d is null", n, false, out_dev));
+  float** d_dst;
+  ST_TRY(st_upload_tables(ctx, n, 0, out_dev, &d_dst));
   a.dst = d_dst; a.stride = src_stride; a.nmaps = nmaps; a.th = dst_h; a.tw = dst_w; a.scales = scales;
   st_timed t(ctx, ST_K_CPM2_RESIZE);
   hipLaunchKernelGGL(k_cpm2_resize_merge, dim3((dst_w + 255) / 256, (dst_h + RM_ROWS - 1) / RM_ROWS, n), dim3(256), 0, ctx->stream, a);
@@ -527,22 +511,17 @@ ST_EXPORT int st_cpm2_nms(st_ctx* ctx, const float* const* maps_dev, int n, int 
     return st_set_error(ctx, ST_ERR_INVALID, "cpm2_nms: bad arguments (n=%d %dx%d parts=%d max_peaks=%d)", n, h, w, parts, max_peaks);
   if (n == 0) return ST_OK;
   if (!maps_dev || !joints_dev) return st_set_error(ctx, ST_ERR_INVALID, "cpm2_nms: null argument");
-  for (int i = 0; i < n; ++i)
-    if (!maps_dev[i] || !joints_dev[i]) return st_set_error(ctx, ST_ERR_INVALID, "cpm2_nms: row %d is null", i);
-  const size_t tb = st_align_up(sizeof(void*) * (size_t)n);
-  ST_TRY(st_ws_reserve(ctx, 2 * tb));
-  const float** d_maps = (const float**)st_ws_alloc(ctx, tb);
-  float** d_j = (float**)st_ws_alloc(ctx, tb);
-  ST_HIP(ctx, hipMemcpyAsync(d_maps, maps_dev, sizeof(void*) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
-  ST_HIP(ctx, hipMemcpyAsync(d_j, joints_dev, sizeof(void*) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+  ST_TRY(st_check_rows(ctx, "cpm2_nms: row %d is null", n, false, maps_dev, joints_dev));
+  const float** d_maps;
+  float** d_j;
+  ST_TRY(st_upload_tables(ctx, n, 0, maps_dev, &d_maps, joints_dev, &d_j));
   NmsArgs a;
   a.h = h; a.w = w; a.parts = parts; a.max_peaks = max_peaks; a.threshold = threshold;
-  for (int f0 = 0; f0 < n; f0 += 65535) {
-    const int nf = n - f0 < 65535 ? n - f0 : 65535;
+  return st_for_launches(n, [&](int f0, int nf) -> int {
     a.maps = d_maps + f0; a.joints = d_j + f0;
     st_timed t(ctx, ST_K_CPM2_NMS);
     hipLaunchKernelGGL(k_cpm2_nms, dim3(parts, nf), dim3(256), 0, ctx->stream, a);
     ST_HIP(ctx, hipGetLastError());
-  }
-  return ST_OK;
+    return ST_OK;
+  });
 }

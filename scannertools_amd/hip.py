@@ -33,6 +33,12 @@ def _check_out(out, shape, dtype, device):
     return out
 
 
+def _ptr_table(addresses):
+    """A ctypes array of the given addresses (at least one entry, so that an empty batch still hands over a table)."""
+    addresses = list(addresses)
+    return (ctypes.c_void_p * max(len(addresses), 1))(*addresses)
+
+
 class HipContext:
     """One ``st_ctx``: per-kernel-instance state (stream binding, scratch).  Mirrors the role of
     a Scanner kernel instance's private GPU state (optical_flow_kernel_gpu.cpp:101-107)."""
@@ -105,6 +111,32 @@ class HipContext:
         self._check(self._L.st_ctx_timing_read(self._h, kernel_id, ctypes.byref(n), ctypes.byref(ms)))
         return n.value, ms.value
 
+    # -- the front of a batched method: rows, pointer tables, the output ---------------------------
+    def _rows(self, x, dtype, what, tail=None, shaped=True):
+        """(rows, n, shape) of a batch given as a list / tuple of per-row tensors or as one tensor, which is split along its
+        first dimension.  Every row is a contiguous CUDA tensor of ``dtype`` on this device; unless ``shaped`` is False, all
+        are (h, w, c) of one shape, with c == ``tail`` when given.  An empty batch has shape ()."""
+        rows = list(x) if isinstance(x, (list, tuple)) else list(x.unbind(0))
+        for r in rows:
+            _require_cuda(r, dtype, what, self.device)
+        shape = tuple(rows[0].shape) if rows else ()
+        if shaped and rows and (len(shape) != 3 or tail not in (None, shape[2]) or any(tuple(r.shape) != shape for r in rows)):
+            raise ValueError("all %ss must be (h,w,%s) with equal shape" % (what, "c" if tail is None else tail))
+        return rows, len(rows), shape
+
+    @staticmethod
+    def _table(rows):
+        """The host pointer table of a batch: ``rows`` is a list of tensors, or one tensor whose rows along the first
+        dimension are the entries (an output that the kernels write frame by frame)."""
+        if isinstance(rows, torch.Tensor):
+            step = rows.stride(0) * rows.element_size()
+            return _ptr_table(rows.data_ptr() + i * step for i in range(rows.shape[0]))
+        return _ptr_table(r.data_ptr() for r in rows)
+
+    def _out(self, out, shape, dtype):
+        """The output of a call: a new tensor, or the caller's once it is found to be exactly that dense device array."""
+        return torch.empty(shape, dtype=dtype, device=self.device) if out is None else _check_out(out, shape, dtype, self.device)
+
     # -- Histogram --------------------------------------------------------------------------
     def histogram(self, frames, bins=16, out=None):
         """Per-channel histograms of U8 RGB frames.
@@ -114,31 +146,9 @@ class HipContext:
         192-byte element the reference's Histogram op emits for bins=16
         (histogram_kernel_cpu.cpp:20,40-44)."""
         self._bind()
-        if isinstance(frames, (list, tuple)):
-            n = len(frames)
-            if n == 0:
-                return torch.zeros((0, 3, bins), dtype=torch.int32, device=self.device)
-            for f in frames:
-                _require_cuda(f, torch.uint8, "frame", self.device)
-            h, w, c = frames[0].shape
-            if any(tuple(f.shape) != (h, w, 3) for f in frames):
-                raise ValueError("all frames must be (h,w,3) with equal shape")
-            out = (torch.empty((n, 3, bins), dtype=torch.int32, device=self.device) if out is None
-                   else _check_out(out, (n, 3, bins), torch.int32, self.device))
-            table = (ctypes.c_void_p * n)(*[f.data_ptr() for f in frames])
-            self._check(self._L.st_hist_u8c3_batch(self._h, table, n, h, w, bins, ctypes.c_void_p(out.data_ptr())))
-            return out
-        _require_cuda(frames, torch.uint8, "frames", self.device)
-        if frames.dim() != 4 or frames.shape[3] != 3:
-            raise ValueError("frames must be (n,h,w,3)")
-        n, h, w, _ = frames.shape
-        out = (torch.empty((n, 3, bins), dtype=torch.int32, device=self.device) if out is None
-               else _check_out(out, (n, 3, bins), torch.int32, self.device))
-        if n == 0:
-            return out
-        self._check(self._L.st_hist_u8c3_strided(self._h, ctypes.c_void_p(frames.data_ptr()), 3 * h * w, n, h, w,
-                                                 bins, ctypes.c_void_p(out.data_ptr())))
-        return out
+        front = self._rows_or_strided(frames, torch.uint8, "frame", 3)
+        out = self._out(out, (front[1], 3, bins), torch.int32)
+        return self._call_rows("st_hist_u8c3", front, 3, out, bins, ctypes.c_void_p(out.data_ptr()))
 
     # -- frame statistics -------------------------------------------------------------------
     def frame_moments(self, frames, luma=True, laplacian=True, out=None):
@@ -148,33 +158,9 @@ class HipContext:
         (n,h,w,3) or a list of (h,w,3) tensors of one shape."""
         self._bind()
         what = (_native.FM_LUMA if luma else 0) | (_native.FM_LAPLACIAN if laplacian else 0)
-        if isinstance(frames, (list, tuple)):
-            n = len(frames)
-            if n == 0:
-                return torch.zeros((0, 8), dtype=torch.int64, device=self.device)
-            for f in frames:
-                _require_cuda(f, torch.uint8, "frame", self.device)
-            if frames[0].dim() != 3 or frames[0].shape[2] != 3:
-                raise ValueError("frames must be (h,w,3)")
-            h, w, _ = frames[0].shape
-            if any(tuple(f.shape) != (h, w, 3) for f in frames):
-                raise ValueError("all frames must be (h,w,3) with equal shape")
-            out = (torch.empty((n, 8), dtype=torch.int64, device=self.device) if out is None
-                   else _check_out(out, (n, 8), torch.int64, self.device))
-            table = (ctypes.c_void_p * n)(*[f.data_ptr() for f in frames])
-            self._check(self._L.st_frame_moments_u8c3_batch(self._h, table, n, h, w, what, ctypes.c_void_p(out.data_ptr())))
-            return out
-        _require_cuda(frames, torch.uint8, "frames", self.device)
-        if frames.dim() != 4 or frames.shape[3] != 3:
-            raise ValueError("frames must be (n,h,w,3)")
-        n, h, w, _ = frames.shape
-        out = (torch.empty((n, 8), dtype=torch.int64, device=self.device) if out is None
-               else _check_out(out, (n, 8), torch.int64, self.device))
-        if n == 0:
-            return out
-        self._check(self._L.st_frame_moments_u8c3_strided(self._h, ctypes.c_void_p(frames.data_ptr()), 3 * h * w, n, h, w, what,
-                                                          ctypes.c_void_p(out.data_ptr())))
-        return out
+        front = self._rows_or_strided(frames, torch.uint8, "frame", 3)
+        out = self._out(out, (front[1], 8), torch.int64)
+        return self._call_rows("st_frame_moments_u8c3", front, 3, out, what, ctypes.c_void_p(out.data_ptr()))
 
     def frame_stats(self, frames, kind):
         """One frame statistic per frame (st_frame_stats_finish over st_frame_moments_u8c3_*): ``kind`` is a name of
@@ -194,33 +180,42 @@ class HipContext:
         self._check(self._L.st_frame_stats_finish(self._h, ctypes.c_void_p(m.data_ptr()), n, h, w, k, ctypes.c_void_p(out.data_ptr())))
         return out
 
+    def _rows_or_strided(self, x, dtype, what, tail):
+        """The front of an op with a *_batch and a *_strided entry point: x is a list of (h,w,tail) rows, one buffer per Scanner
+        element, or one (n,h,w,tail) tensor.  Returns (is a list?, n, h, w, the pointer table or the base pointer); an empty
+        list has h = w = 1."""
+        if isinstance(x, (list, tuple)):
+            rows, n, shape = self._rows(x, dtype, what, tail)
+            return (True, n) + (tuple(int(v) for v in shape[:2]) if n else (1, 1)) + (self._table(rows),)
+        _require_cuda(x, dtype, what + "s", self.device)
+        if x.dim() != 4 or x.shape[3] != tail:
+            raise ValueError("%ss must be (n,h,w,%d)" % (what, tail))
+        return (False,) + tuple(int(v) for v in x.shape[:3]) + (ctypes.c_void_p(x.data_ptr()),)
+
+    def _call_rows(self, name, front, pixel_bytes, out, *rest):
+        """name_batch or name_strided (dense frames of pixel_bytes * h * w bytes) on a front of _rows_or_strided, unless
+        ``out`` is empty; returns out."""
+        is_list, n, h, w, arg = front
+        if out.shape[0]:
+            if is_list:
+                self._check(getattr(self._L, name + "_batch")(self._h, arg, n, h, w, *rest))
+            else:
+                self._check(getattr(self._L, name + "_strided")(self._h, arg, pixel_bytes * h * w, n, h, w, *rest))
+        return out
+
     def _bbox_args(self, frames, boxes):
-        """(list-of-frames?, n, h, w, frame argument, int32 (m, 5) box records) of a bbox_* call.  Every box is checked
-        here, against the frame count and size, before the library is entered."""
+        """(front of the frames, int32 (m, 5) box records) of a bbox_* call.  Every box is checked here, against the frame
+        count and size, before the library is entered."""
         boxes = np.ascontiguousarray(np.asarray(boxes, dtype=np.int64).reshape(-1, 5))
-        if isinstance(frames, (list, tuple)):
-            n = len(frames)
-            for f in frames:
-                _require_cuda(f, torch.uint8, "frame", self.device)
-            if n and (frames[0].dim() != 3 or frames[0].shape[2] != 3):
-                raise ValueError("frames must be (h,w,3)")
-            h, w = (int(frames[0].shape[0]), int(frames[0].shape[1])) if n else (1, 1)
-            if any(tuple(f.shape) != (h, w, 3) for f in frames):
-                raise ValueError("all frames must be (h,w,3) with equal shape")
-            arg = (ctypes.c_void_p * max(n, 1))(*[f.data_ptr() for f in frames])
-        else:
-            _require_cuda(frames, torch.uint8, "frames", self.device)
-            if frames.dim() != 4 or frames.shape[3] != 3:
-                raise ValueError("frames must be (n,h,w,3)")
-            n, h, w = int(frames.shape[0]), int(frames.shape[1]), int(frames.shape[2])
-            arg = ctypes.c_void_p(frames.data_ptr())
+        front = self._rows_or_strided(frames, torch.uint8, "frame", 3)
+        _, n, h, w, _ = front
         f, x1, y1, x2, y2 = boxes.T
         bad = ~((0 <= f) & (f < n) & (0 <= x1) & (x1 < x2) & (x2 <= w) & (0 <= y1) & (y1 < y2) & (y2 <= h))
         if bad.any():
             i = int(np.argmax(bad))
             raise ValueError("box %d {frame %d, x %d..%d, y %d..%d} is empty or not inside one of %d frames of %dx%d"
                              % ((i,) + tuple(boxes[i].tolist()[k] for k in (0, 1, 3, 2, 4)) + (n, w, h)))
-        return isinstance(frames, (list, tuple)), n, h, w, arg, np.ascontiguousarray(boxes.astype(np.int32))
+        return front, np.ascontiguousarray(boxes.astype(np.int32))
 
     def bbox_moments(self, frames, boxes, out=None):
         """Exact Laplacian moments of boxes of U8 RGB frames, each box resized to 200 x 200 with the Resize op's INTER_LINEAR
@@ -230,18 +225,11 @@ class HipContext:
         [frame index, x1, y1, x2, y2], the region being rows y1 .. y2-1 and columns x1 .. x2-1 of that frame; a box that is
         empty or not inside its frame is a ValueError and nothing is launched.  One launch for all boxes."""
         self._bind()
-        is_list, n, h, w, arg, rec = self._bbox_args(frames, boxes)
+        front, rec = self._bbox_args(frames, boxes)
         m = rec.shape[0]
-        out = (torch.empty((m, 8), dtype=torch.int64, device=self.device) if out is None
-               else _check_out(out, (m, 8), torch.int64, self.device))
-        if m == 0:
-            return out
-        bp = rec.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))
-        if is_list:
-            self._check(self._L.st_bbox_moments_u8c3_batch(self._h, arg, n, h, w, bp, m, ctypes.c_void_p(out.data_ptr())))
-        else:
-            self._check(self._L.st_bbox_moments_u8c3_strided(self._h, arg, 3 * h * w, n, h, w, bp, m, ctypes.c_void_p(out.data_ptr())))
-        return out
+        out = self._out(out, (m, 8), torch.int64)
+        return self._call_rows("st_bbox_moments_u8c3", front, 3, out, rec.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), m,
+                               ctypes.c_void_p(out.data_ptr()))
 
     def bbox_sharpness(self, frames, boxes, kind):
         """One sharpness value per box (st_bbox_sharpness_u8c3_*: the moments launch with the finishing formula fused):
@@ -251,17 +239,11 @@ class HipContext:
         if k not in (_native.FS_KINDS["SharpnessCPP"], _native.FS_KINDS["Sharpness"]):
             raise ValueError("bbox_sharpness: kind must be SharpnessCPP or Sharpness, not %r" % (kind,))
         self._bind()
-        is_list, n, h, w, arg, rec = self._bbox_args(frames, boxes)
+        front, rec = self._bbox_args(frames, boxes)
         m = rec.shape[0]
         out = torch.empty((m,), dtype=torch.float32 if k < 3 else torch.float64, device=self.device)
-        if m == 0:
-            return out
-        bp = rec.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))
-        if is_list:
-            self._check(self._L.st_bbox_sharpness_u8c3_batch(self._h, arg, n, h, w, bp, m, k, ctypes.c_void_p(out.data_ptr())))
-        else:
-            self._check(self._L.st_bbox_sharpness_u8c3_strided(self._h, arg, 3 * h * w, n, h, w, bp, m, k, ctypes.c_void_p(out.data_ptr())))
-        return out
+        return self._call_rows("st_bbox_sharpness_u8c3", front, 3, out, rec.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), m, k,
+                               ctypes.c_void_p(out.data_ptr()))
 
     # -- flow consumers ---------------------------------------------------------------------
     def shot_boundaries(self, hist, window=500, k_std=2.5, return_diffs=False):
@@ -289,55 +271,25 @@ class HipContext:
         flows: CUDA float32 tensor (n,h,w,2) or a list of (h,w,2) tensors.  Returns int32
         (n,2,64): row i is the 512-byte element the reference op emits."""
         self._bind()
-        if isinstance(flows, (list, tuple)):
-            n = len(flows)
-            if n == 0:
-                return torch.zeros((0, 2, 64), dtype=torch.int32, device=self.device)
-            for f in flows:
-                _require_cuda(f, torch.float32, "flow", self.device)
-            h, w, _ = flows[0].shape
-            if any(tuple(f.shape) != (h, w, 2) for f in flows):
-                raise ValueError("all flows must be (h,w,2) with equal shape")
-            out = (torch.empty((n, 2, 64), dtype=torch.int32, device=self.device) if out is None
-                   else _check_out(out, (n, 2, 64), torch.int32, self.device))
-            table = (ctypes.c_void_p * n)(*[f.data_ptr() for f in flows])
-            self._check(self._L.st_flow_hist_batch(self._h, table, n, h, w, ctypes.c_void_p(out.data_ptr())))
-            return out
-        _require_cuda(flows, torch.float32, "flows", self.device)
-        if flows.dim() != 4 or flows.shape[3] != 2:
-            raise ValueError("flows must be (n,h,w,2)")
-        n, h, w, _ = flows.shape
-        out = (torch.empty((n, 2, 64), dtype=torch.int32, device=self.device) if out is None
-               else _check_out(out, (n, 2, 64), torch.int32, self.device))
-        if n == 0:
-            return out
-        self._check(self._L.st_flow_hist_strided(self._h, ctypes.c_void_p(flows.data_ptr()), 8 * h * w, n, h, w,
-                                                 ctypes.c_void_p(out.data_ptr())))
-        return out
+        front = self._rows_or_strided(flows, torch.float32, "flow", 2)
+        out = self._out(out, (front[1], 2, 64), torch.int32)
+        return self._call_rows("st_flow_hist", front, 8, out, ctypes.c_void_p(out.data_ptr()))
 
     def draw_flow(self, frames, flows, out=None):
         """DrawFlow (scannertools/vis.py:8-12): frames (n,h,w,3) uint8 and flows (n,h,w,2) float32
         (tensors or lists of per-row tensors) -> (n,h,2w,3) uint8, the frame beside its flow map."""
         self._bind()
-        fr = list(frames) if isinstance(frames, (list, tuple)) else list(frames.unbind(0))
-        fl = list(flows) if isinstance(flows, (list, tuple)) else list(flows.unbind(0))
-        n = len(fr)
-        if len(fl) != n:
+        fr, n, shape = self._rows(frames, torch.uint8, "frame", 3)
+        fl, nfl, fshape = self._rows(flows, torch.float32, "flow", 2)
+        if nfl != n:
             raise ValueError("frames and flows must have the same number of rows")
         if n == 0:
             return torch.zeros((0, 0, 0, 3), dtype=torch.uint8, device=self.device)
-        h, w, _ = fr[0].shape
-        for f, g in zip(fr, fl):
-            _require_cuda(f, torch.uint8, "frame", self.device)
-            _require_cuda(g, torch.float32, "flow", self.device)
-            if tuple(f.shape) != (h, w, 3) or tuple(g.shape) != (h, w, 2):
-                raise ValueError("frames must be (h,w,3) and flows (h,w,2) with equal h,w")
-        out = (torch.empty((n, h, 2 * w, 3), dtype=torch.uint8, device=self.device) if out is None
-               else _check_out(out, (n, h, 2 * w, 3), torch.uint8, self.device))
-        tf = (ctypes.c_void_p * n)(*[f.data_ptr() for f in fr])
-        tg = (ctypes.c_void_p * n)(*[g.data_ptr() for g in fl])
-        to = (ctypes.c_void_p * n)(*[out[i].data_ptr() for i in range(n)])
-        self._check(self._L.st_draw_flow_batch(self._h, tf, tg, n, h, w, to))
+        h, w, _ = shape
+        if fshape[:2] != (h, w):
+            raise ValueError("frames must be (h,w,3) and flows (h,w,2) with equal h,w")
+        out = self._out(out, (n, h, 2 * w, 3), torch.uint8)
+        self._check(self._L.st_draw_flow_batch(self._h, self._table(fr), self._table(fl), n, h, w, self._table(out)))
         return out
 
     # -- sibling imgproc ops ----------------------------------------------------------------
@@ -345,41 +297,26 @@ class HipContext:
         """Blur op (blur_kernel_cpu.cpp:50-81): k x k integer box filter of (n,h,w,3) uint8 frames
         (a tensor or a list of (h,w,3) tensors); border pixels are 0."""
         self._bind()
-        fr = list(frames) if isinstance(frames, (list, tuple)) else list(frames.unbind(0))
-        n = len(fr)
+        fr, n, shape = self._rows(frames, torch.uint8, "frame", 3)
         if n == 0:
             return torch.zeros((0, 0, 0, 3), dtype=torch.uint8, device=self.device)
-        h, w, _ = fr[0].shape
-        for f in fr:
-            _require_cuda(f, torch.uint8, "frame", self.device)
-            if tuple(f.shape) != (h, w, 3):
-                raise ValueError("all frames must be (h,w,3) with equal shape")
-        out = (torch.empty((n, h, w, 3), dtype=torch.uint8, device=self.device) if out is None
-               else _check_out(out, (n, h, w, 3), torch.uint8, self.device))
-        tf = (ctypes.c_void_p * n)(*[f.data_ptr() for f in fr])
-        to = (ctypes.c_void_p * n)(*[out[i].data_ptr() for i in range(n)])
-        self._check(self._L.st_box_blur_u8c3_batch(self._h, tf, n, h, w, int(kernel_size), to))
+        h, w, _ = shape
+        out = self._out(out, (n, h, w, 3), torch.uint8)
+        self._check(self._L.st_box_blur_u8c3_batch(self._h, self._table(fr), n, h, w, int(kernel_size), self._table(out)))
         return out
 
     def resize(self, frames, width, height, interpolation=_native.INTER_LINEAR, out=None):
         """Resize op (resize_kernel.cpp:68-73): (n,h,w,c) uint8 frames (a tensor or a list of (h,w,c)
         tensors) -> (n,height,width,c) uint8, cv::resize semantics for 8-bit frames."""
         self._bind()
-        fr = list(frames) if isinstance(frames, (list, tuple)) else list(frames.unbind(0))
-        n = len(fr)
+        fr, n, shape = self._rows(frames, torch.uint8, "frame")
         if n == 0:
             c = frames.shape[3] if isinstance(frames, torch.Tensor) and frames.dim() == 4 else 3
             return torch.zeros((0, height, width, c), dtype=torch.uint8, device=self.device)
-        h, w, c = fr[0].shape
-        for f in fr:
-            _require_cuda(f, torch.uint8, "frame", self.device)
-            if tuple(f.shape) != (h, w, c):
-                raise ValueError("all frames must have the same (h,w,c) shape")
-        out = (torch.empty((n, height, width, c), dtype=torch.uint8, device=self.device) if out is None
-               else _check_out(out, (n, height, width, c), torch.uint8, self.device))
-        tf = (ctypes.c_void_p * n)(*[f.data_ptr() for f in fr])
-        to = (ctypes.c_void_p * n)(*[out[i].data_ptr() for i in range(n)])
-        self._check(self._L.st_resize_u8_batch(self._h, tf, n, h, w, c, int(height), int(width), int(interpolation), to))
+        h, w, c = shape
+        out = self._out(out, (n, height, width, c), torch.uint8)
+        self._check(self._L.st_resize_u8_batch(self._h, self._table(fr), n, h, w, c, int(height), int(width), int(interpolation),
+                                               self._table(out)))
         return out
 
     def montage(self, frames, canvas, target_width, target_height, frames_per_row, first_slot=0):
@@ -388,26 +325,20 @@ class HipContext:
         (montage_h, montage_w, 3) uint8 tensor, tile s at ((s % frames_per_row) * target_width, (s // frames_per_row) *
         target_height).  One launch; the rest of the canvas is left as it is.  Returns canvas."""
         self._bind()
-        fr = list(frames) if isinstance(frames, (list, tuple)) else list(frames.unbind(0))
         _require_cuda(canvas, torch.uint8, "canvas", self.device)
         if canvas.dim() != 3 or canvas.shape[2] != 3 or not canvas.is_contiguous():
             raise ValueError("canvas must be a contiguous (montage_h, montage_w, 3) tensor")
-        n = len(fr)
+        fr, n, shape = self._rows(frames, torch.uint8, "frame", 3)
         if n == 0:
             return canvas
-        h, w, c = fr[0].shape
-        for f in fr:
-            _require_cuda(f, torch.uint8, "frame", self.device)
-            if tuple(f.shape) != (h, w, 3):
-                raise ValueError("all frames must have the same (h,w,3) shape")
+        h, w, _ = shape
         last = int(first_slot) + n - 1
         if (frames_per_row * target_width > canvas.shape[1] or
                 (last // frames_per_row + 1) * target_height > canvas.shape[0]):
             raise ValueError("tiles %d..%d of %dx%d do not fit a %dx%d canvas" % (first_slot, last, target_width, target_height,
                                                                                   canvas.shape[1], canvas.shape[0]))
-        tf = (ctypes.c_void_p * n)(*[f.data_ptr() for f in fr])
-        self._check(self._L.st_montage_u8c3_batch(self._h, tf, n, h, w, canvas.data_ptr(), int(canvas.shape[1]), int(target_width),
-                                                  int(target_height), int(frames_per_row), int(first_slot)))
+        self._check(self._L.st_montage_u8c3_batch(self._h, self._table(fr), n, h, w, canvas.data_ptr(), int(canvas.shape[1]),
+                                                  int(target_width), int(target_height), int(frames_per_row), int(first_slot)))
         return canvas
 
     def cvt_color(self, frames, code, gray_bits=15, out=None):
@@ -418,23 +349,15 @@ class HipContext:
             if code not in _native.COLOR_CODES:
                 raise ValueError("conversion %r is not implemented" % code)
             code = _native.COLOR_CODES[code]
-        fr = list(frames) if isinstance(frames, (list, tuple)) else list(frames.unbind(0))
-        n = len(fr)
+        fr, n, shape = self._rows(frames, torch.uint8, "frame")
         if n == 0:
             return torch.zeros((0, 0, 0, 3), dtype=torch.uint8, device=self.device)
-        h, w, c = fr[0].shape
-        for f in fr:
-            _require_cuda(f, torch.uint8, "frame", self.device)
-            if tuple(f.shape) != (h, w, c):
-                raise ValueError("all frames must have the same (h,w,c) shape")
+        h, w, c = shape
         oh, ow, oc = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
         if self._L.st_cvt_color_out_shape(int(code), h, w, c, ctypes.byref(oh), ctypes.byref(ow), ctypes.byref(oc)) != 0:
             raise ValueError("conversion code %d on %dx%d frames of %d channel(s) is not implemented" % (code, w, h, c))
-        shape = (n, oh.value, ow.value, oc.value)
-        out = torch.empty(shape, dtype=torch.uint8, device=self.device) if out is None else _check_out(out, shape, torch.uint8, self.device)
-        tf = (ctypes.c_void_p * n)(*[f.data_ptr() for f in fr])
-        to = (ctypes.c_void_p * n)(*[out[i].data_ptr() for i in range(n)])
-        self._check(self._L.st_cvt_color_u8_batch(self._h, tf, n, h, w, c, int(code), int(gray_bits), to))
+        out = self._out(out, (n, oh.value, ow.value, oc.value), torch.uint8)
+        self._check(self._L.st_cvt_color_u8_batch(self._h, self._table(fr), n, h, w, c, int(code), int(gray_bits), self._table(out)))
         return out
 
     def decode_jpeg(self, streams, out=None, entropy="host", split="interval", subseq_bytes=None, max_rounds=None, scale=1):
@@ -469,10 +392,10 @@ class HipContext:
         info = probe_jpeg(streams[0])
         h, w = info["h"], info["w"]
         shape = (n,) + jpeg_scaled_size(h, w, scale) + (info["channels"],)
-        out = torch.empty(shape, dtype=torch.uint8, device=self.device) if out is None else _check_out(out, shape, torch.uint8, self.device)
-        bufs = (ctypes.c_void_p * n)(*[ctypes.cast(ctypes.c_char_p(s), ctypes.c_void_p).value for s in streams])
+        out = self._out(out, shape, torch.uint8)
+        bufs = _ptr_table(ctypes.cast(ctypes.c_char_p(s), ctypes.c_void_p).value for s in streams)
         sizes = (ctypes.c_size_t * n)(*[len(s) for s in streams])
-        to = (ctypes.c_void_p * n)(*[out[i].data_ptr() for i in range(n)])
+        to = self._table(out)
         if split != "subsequence" and entropy == "auto":
             entropy = "gpu" if all(_jpeg_has_restarts(s) for s in streams) else "host"
         opts = _native.JpegSplitOpts(int(subseq_bytes or 0), int(max_rounds or 0))
@@ -493,10 +416,10 @@ class HipContext:
             return torch.zeros((0, 0, 0, 3), dtype=torch.uint8, device=self.device)
         info = probe_png(streams[0])
         shape = (n, info["h"], info["w"], info["channels"])
-        out = torch.empty(shape, dtype=torch.uint8, device=self.device) if out is None else _check_out(out, shape, torch.uint8, self.device)
-        bufs = (ctypes.c_void_p * n)(*[ctypes.cast(ctypes.c_char_p(s), ctypes.c_void_p).value for s in streams])
+        out = self._out(out, shape, torch.uint8)
+        bufs = _ptr_table(ctypes.cast(ctypes.c_char_p(s), ctypes.c_void_p).value for s in streams)
         sizes = (ctypes.c_size_t * n)(*[len(s) for s in streams])
-        to = (ctypes.c_void_p * n)(*[out[i].data_ptr() for i in range(n)])
+        to = self._table(out)
         self._check(self._L.st_png_decode_batch(self._h, bufs, sizes, n, shape[1], shape[2], shape[3], to))
         return out
 
@@ -518,18 +441,11 @@ class HipContext:
         rst = jpeg_restart(restart)
         opt = jpeg_optimize(optimize)
         self._bind()
-        fr = list(frames) if isinstance(frames, (list, tuple)) else list(frames.unbind(0))
-        n = len(fr)
+        fr, n, shape = self._rows(frames, torch.uint8, "frame", 3)
         if n == 0:
             return []
-        if fr[0].dim() != 3 or fr[0].shape[2] != 3:
-            raise ValueError("encode_jpeg takes (h, w, 3) frames, got %s" % (tuple(fr[0].shape),))
-        h, w, _ = fr[0].shape
-        for f in fr:
-            _require_cuda(f, torch.uint8, "frame", self.device)
-            if tuple(f.shape) != (h, w, 3):
-                raise ValueError("all frames must have the same (h,w,3) shape")
-        tf = (ctypes.c_void_p * n)(*[f.data_ptr() for f in fr])
+        h, w, _ = shape
+        tf = self._table(fr)
         if opt:
             self._check(self._L.st_jpeg_encode_batch_opt(self._h, tf, n, h, w, int(quality), hs, vs, rst, opt))
         else:
@@ -538,7 +454,7 @@ class HipContext:
         self._check(self._L.st_jpeg_encode_fetch(self._h, None, sizes, 0))   # the sizes alone
         most = max(sizes)
         store = np.empty((n, most), np.uint8)
-        bufs = (ctypes.c_void_p * n)(*[store[i].ctypes.data for i in range(n)])
+        bufs = _ptr_table(store[i].ctypes.data for i in range(n))
         self._check(self._L.st_jpeg_encode_fetch(self._h, bufs, sizes, most))
         return [store[i, :sizes[i]].tobytes() for i in range(n)]
 
@@ -556,34 +472,16 @@ class HipContext:
         -> (n,3,net_h,net_w) float32 network input (planes B,G,R; bicubic resize by ``scale``, padded to
         a multiple of 8 with 128, x/256 - 0.5)."""
         self._bind()
-        fr = list(frames) if isinstance(frames, (list, tuple)) else list(frames.unbind(0))
-        n = len(fr)
+        fr, n, shape = self._rows(frames, torch.uint8, "frame", 3)
         if n == 0:
             return torch.zeros((0, 3, 0, 0), dtype=torch.float32, device=self.device)
-        h, w, _ = fr[0].shape
-        for f in fr:
-            _require_cuda(f, torch.uint8, "frame", self.device)
-            if tuple(f.shape) != (h, w, 3):
-                raise ValueError("all frames must be (h,w,3) with equal shape")
+        h, w, _ = shape
         _, _, nh, nw = cpm2_geometry(h, w, scale)
-        out = (torch.empty((n, 3, nh, nw), dtype=torch.float32, device=self.device) if out is None
-               else _check_out(out, (n, 3, nh, nw), torch.float32, self.device))
-        tf = (ctypes.c_void_p * n)(*[f.data_ptr() for f in fr])
-        to = (ctypes.c_void_p * n)(*[out[i].data_ptr() for i in range(n)])
-        self._check(self._L.st_cpm2_input_batch(self._h, tf, n, h, w, float(scale), to))
+        out = self._out(out, (n, 3, nh, nw), torch.float32)
+        self._check(self._L.st_cpm2_input_batch(self._h, self._table(fr), n, h, w, float(scale), self._table(out)))
         return out
 
     # -- network inputs (scannertools_caffe) ----------------------------------------------------
-    def _net_input_frames(self, frames):
-        fr = list(frames) if isinstance(frames, (list, tuple)) else list(frames.unbind(0))
-        if fr:
-            h, w, _ = fr[0].shape
-            for f in fr:
-                _require_cuda(f, torch.uint8, "frame", self.device)
-                if tuple(f.shape) != (h, w, 3):
-                    raise ValueError("all frames must be (h,w,3) with equal shape")
-        return fr
-
     def facenet_input(self, frames, scale, mean_colors, out=None):
         """FacenetInput (scannertools_caffe_cpp/facenet_input_kernel_cpu.cpp:81-117): (n,h,w,3) uint8 RGB frames (a tensor or a
         list of (h,w,3) tensors) -> (n,3,net_w,net_h) float32: INTER_LINEAR resize to `facenet_geometry(h, w, scale)`, minus
@@ -592,17 +490,13 @@ class HipContext:
         mean = [float(v) for v in mean_colors]
         if len(mean) != 3:
             raise ValueError("mean_colors must hold 3 values, got %d" % len(mean))
-        fr = self._net_input_frames(frames)
-        n = len(fr)
+        fr, n, shape = self._rows(frames, torch.uint8, "frame", 3)
         if n == 0:
             return torch.zeros((0, 3, 0, 0), dtype=torch.float32, device=self.device)
-        h, w, _ = fr[0].shape
+        h, w, _ = shape
         nh, nw = facenet_geometry(h, w, scale)
-        out = (torch.empty((n, 3, nw, nh), dtype=torch.float32, device=self.device) if out is None
-               else _check_out(out, (n, 3, nw, nh), torch.float32, self.device))
-        tf = (ctypes.c_void_p * n)(*[f.data_ptr() for f in fr])
-        to = (ctypes.c_void_p * n)(*[out[i].data_ptr() for i in range(n)])
-        self._check(self._L.st_facenet_input_batch(self._h, tf, n, h, w, float(scale), (ctypes.c_float * 3)(*mean), to))
+        out = self._out(out, (n, 3, nw, nh), torch.float32)
+        self._check(self._L.st_facenet_input_batch(self._h, self._table(fr), n, h, w, float(scale), (ctypes.c_float * 3)(*mean), self._table(out)))
         return out
 
     def caffe_input(self, frames, input_width, input_height, mean_colors, normalize=False, out=None):
@@ -615,17 +509,14 @@ class HipContext:
         mean = [float(v) for v in mean_colors]
         if len(mean) != 3:
             raise ValueError("mean_colors must hold 3 values, got %d" % len(mean))
-        fr = self._net_input_frames(frames)
-        n = len(fr)
+        fr, n, shape = self._rows(frames, torch.uint8, "frame", 3)
         if n == 0:
             return torch.zeros((0, 3, 0, 0), dtype=torch.float32, device=self.device)
-        h, w, _ = fr[0].shape
+        h, w, _ = shape
         nw, nh = (w, h) if int(input_width) == -1 else (int(input_width), int(input_height))
-        out = (torch.empty((n, 3, nh, nw), dtype=torch.float32, device=self.device) if out is None
-               else _check_out(out, (n, 3, nh, nw), torch.float32, self.device))
-        tf = (ctypes.c_void_p * n)(*[f.data_ptr() for f in fr])
-        to = (ctypes.c_void_p * n)(*[out[i].data_ptr() for i in range(n)])
-        self._check(self._L.st_caffe_input_batch(self._h, tf, n, h, w, nh, nw, (ctypes.c_float * 3)(*mean), int(bool(normalize)), to))
+        out = self._out(out, (n, 3, nh, nw), torch.float32)
+        self._check(self._L.st_caffe_input_batch(self._h, self._table(fr), n, h, w, nh, nw, (ctypes.c_float * 3)(*mean), int(bool(normalize)),
+                                                 self._table(out)))
         return out
 
     # -- FacenetOutput (scannertools_caffe) -----------------------------------------------------
@@ -636,21 +527,18 @@ class HipContext:
         grid_h) or a list of contiguous tensors of 125 * grid_w * grid_h values each; templates: the 25 x 4 floats of the
         templates file; overlap / offset: best_nms's threshold and the formula's pixel offset (the op passes 0.1 and 0)."""
         self._bind()
-        fr = list(maps) if isinstance(maps, (list, tuple)) else list(maps.unbind(0))
         tpl = np.ascontiguousarray(np.asarray(templates, dtype=np.float32).reshape(-1))
         if tpl.size != 100:
             raise ValueError("templates must hold 25 x 4 values, got %d" % tpl.size)
         nh, nw = facenet_geometry(h, w, scale)
         cells = 125 * ((nw + 7) // 8) * ((nh + 7) // 8)
+        fr, n, _ = self._rows(maps, torch.float32, "map", shaped=False)
         for f in fr:
-            _require_cuda(f, torch.float32, "map", self.device)
             if f.numel() != cells:
                 raise ValueError("a map of a %dx%d frame at scale %g holds 125 x %d x %d values, got %d"
                                  % (w, h, scale, (nw + 7) // 8, (nh + 7) // 8, f.numel()))
-        n = len(fr)
         counts = (ctypes.c_int32 * max(n, 1))()
-        tm = (ctypes.c_void_p * max(n, 1))(*[f.data_ptr() for f in fr])
-        self._check(self._L.st_facenet_output_batch(self._h, tm, n, int(h), int(w), float(scale), tpl.ctypes.data_as(ctypes.POINTER(ctypes.c_float)),
+        self._check(self._L.st_facenet_output_batch(self._h, self._table(fr), n, int(h), int(w), float(scale), tpl.ctypes.data_as(ctypes.POINTER(ctypes.c_float)),
                                                     float(threshold), float(overlap), float(offset), counts))
         counts = [int(c) for c in counts[:n]]
         rows = np.empty((sum(counts), 5), np.float32)
@@ -691,10 +579,8 @@ class HipContext:
         out = torch.empty((n, 19, mp, mp), dtype=torch.float32, device=self.device)
         if n == 0:
             return out
-        th = (ctypes.c_void_p * n)(*[heatmaps[i].data_ptr() for i in range(n)])
-        tp = (ctypes.c_void_p * n)(*[peaks[i].data_ptr() for i in range(n)])
-        self._check(self._L.st_cpm2_limb_scores(self._h, th, tp, n, H, W, mp, float(inter_threshold), int(min_above),
-                                                ctypes.c_void_p(out.data_ptr())))
+        self._check(self._L.st_cpm2_limb_scores(self._h, self._table(heatmaps), self._table(peaks), n, H, W, mp, float(inter_threshold),
+                                                int(min_above), ctypes.c_void_p(out.data_ptr())))
         return out
 
     def cpm2_resize_maps(self, maps, dst_h, dst_w, chan_map=None, nmaps=None, out=None):
@@ -711,12 +597,12 @@ class HipContext:
         elif nmaps is None:
             nmaps = C
         shape = (n, nmaps, int(dst_h), int(dst_w))
-        out = torch.empty(shape, dtype=torch.float32, device=self.device) if out is None else _check_out(out, shape, torch.float32, self.device)
+        out = self._out(out, shape, torch.float32)
         if n == 0:
             return out
         cm = (ctypes.c_int * nmaps)(*[int(v) for v in chan_map]) if chan_map is not None else None
-        to = (ctypes.c_void_p * n)(*[out[i].data_ptr() for i in range(n)])
-        self._check(self._L.st_cpm2_resize_maps(self._h, ctypes.c_void_p(maps.data_ptr()), n, h, w, C, cm, nmaps, int(dst_h), int(dst_w), to))
+        self._check(self._L.st_cpm2_resize_maps(self._h, ctypes.c_void_p(maps.data_ptr()), n, h, w, C, cm, nmaps, int(dst_h), int(dst_w),
+                                                self._table(out)))
         return out
 
     def cpm2_resize_merge_maps(self, maps_list, eff_sizes, dst_h, dst_w, chan_map=None, nmaps=None):
@@ -737,13 +623,12 @@ class HipContext:
         if n == 0:
             return out
         cm = (ctypes.c_int * nmaps)(*[int(v) for v in chan_map]) if chan_map is not None else None
-        src = (ctypes.c_void_p * S)(*[m.data_ptr() for m in maps_list])
+        src = self._table(maps_list)
         sh = (ctypes.c_int * S)(*[m.shape[1] for m in maps_list])
         sw = (ctypes.c_int * S)(*[m.shape[2] for m in maps_list])
         eh = (ctypes.c_float * S)(*[float(e[0]) for e in eff_sizes])
         ew = (ctypes.c_float * S)(*[float(e[1]) for e in eff_sizes])
-        to = (ctypes.c_void_p * n)(*[out[i].data_ptr() for i in range(n)])
-        self._check(self._L.st_cpm2_resize_merge_maps(self._h, src, sh, sw, eh, ew, S, n, C, cm, nmaps, int(dst_h), int(dst_w), to))
+        self._check(self._L.st_cpm2_resize_merge_maps(self._h, src, sh, sw, eh, ew, S, n, C, cm, nmaps, int(dst_h), int(dst_w), self._table(out)))
         return out
 
     def cpm2_nms(self, maps, parts=18, max_peaks=64, threshold=0.05, out=None):
@@ -755,12 +640,10 @@ class HipContext:
             raise ValueError("maps must be (n,>=parts,H,W)")
         n, _, H, W = maps.shape
         shape = (n, parts, max_peaks + 1, 3)
-        out = torch.empty(shape, dtype=torch.float32, device=self.device) if out is None else _check_out(out, shape, torch.float32, self.device)
+        out = self._out(out, shape, torch.float32)
         if n == 0:
             return out
-        tm = (ctypes.c_void_p * n)(*[maps[i].data_ptr() for i in range(n)])
-        to = (ctypes.c_void_p * n)(*[out[i].data_ptr() for i in range(n)])
-        self._check(self._L.st_cpm2_nms(self._h, tm, n, H, W, int(parts), int(max_peaks), float(threshold), to))
+        self._check(self._L.st_cpm2_nms(self._h, self._table(maps), n, H, W, int(parts), int(max_peaks), float(threshold), self._table(out)))
         return out
 
     # -- OpticalFlow ------------------------------------------------------------------------
@@ -856,9 +739,8 @@ class HipContext:
         """(n, h, w, stride) -> (n, c, h, w), every frame through its own pointer as the Caffe op writes its output frames."""
         n, h, wd, xs = self._nhwc(x)
         out = torch.empty((n, c, h, wd), dtype=torch.float32, device=self.device)
-        ptrs = (ctypes.c_void_p * n)(*[out[i].data_ptr() for i in range(n)])
         self._bind()
-        self._check(self._L.st_nhwc_to_planar_f32(self._h, self._vp(x), n, h, wd, c, xs, x_offset, ptrs))
+        self._check(self._L.st_nhwc_to_planar_f32(self._h, self._vp(x), n, h, wd, c, xs, x_offset, self._table(out)))
         return out
 
     def optical_flow(self, frames, pairs=None, params=None, out=None):
@@ -891,15 +773,12 @@ class HipContext:
             if p:
                 raise ValueError("pairs given but no frames")
             return torch.zeros((0, 0, 0, 2), dtype=torch.float32, device=self.device)
-        out = (torch.empty((p, h, w, 2), dtype=torch.float32, device=self.device) if out is None
-               else _check_out(out, (p, h, w, 2), torch.float32, self.device))
+        out = self._out(out, (p, h, w, 2), torch.float32)
         if p == 0:
             return out
         prm = params if params is not None else default_params()
-        ftab = (ctypes.c_void_p * n)(*[f.data_ptr() for f in fl])
-        otab = (ctypes.c_void_p * p)(*[out[i].data_ptr() for i in range(p)])
         self._check(self._L.st_farneback_pairs(
-            self._h, ftab, n, pairs.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), p, h, w, ctypes.byref(prm), otab))
+            self._h, self._table(fl), n, pairs.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), p, h, w, ctypes.byref(prm), self._table(out)))
         return out
 
     # -- stage-level entry points (used by the parity tests) ----------------------------------

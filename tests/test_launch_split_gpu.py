@@ -7,13 +7,17 @@ index (a misplaced frame shows), and must equal
   * the C oracle at frames 0, 65 534, 65 535, 65 536 and 65 537 (the last of the first launch and the second launch).
 
 st_cpm2_resize_maps / st_cpm2_resize_merge_maps launch one grid over n and refuse n > 65 535: that refusal must be a
-clean StError that leaves the context usable."""
+clean StError that leaves the context usable.
+
+Three of the calls of N frames (one per source file: FlowHistogram, Blur, CPM2Input) are also counted: with timing enabled
+for the op's kernel class they record exactly two launches."""
 import ctypes
 
 import numpy as np
 import pytest
 
 import oracle
+from scannertools_amd import _native
 
 N = 65538
 LIMIT = 65535
@@ -48,6 +52,17 @@ def split(fn, x, *more):
     """fn over calls of at most LIMIT frames, concatenated along the frame axis."""
     import torch
     return torch.cat([fn(x[lo:lo + LIMIT], *[m[lo:lo + LIMIT] for m in more]) for lo in range(0, N, LIMIT)])
+
+
+def counted(ctx, kernel_id, call):
+    """(call(), the launches of kernel class kernel_id it recorded)."""
+    ctx.timing_enable([kernel_id])
+    ctx.timing_reset()
+    try:
+        got = call()
+        return got, ctx.timing_read(kernel_id)[0]
+    finally:
+        ctx.timing_enable([])
 
 
 def same(a, b, what):
@@ -91,7 +106,8 @@ def test_flow_histogram_pointer_table_and_strided(hip_ctx):
     import torch
     h, w = 3, 5
     fl = flows_f32(h, w)
-    whole = hip_ctx.flow_histogram(list(fl.unbind(0)))
+    whole, launches = counted(hip_ctx, _native.K_FLOW_HIST, lambda: hip_ctx.flow_histogram(list(fl.unbind(0))))
+    assert launches == 2, "flow histogram of %d frames: %d launches" % (N, launches)
     same(whole, split(lambda x: hip_ctx.flow_histogram(list(x.unbind(0))), fl), "flow histogram table")
     stride = 136                                                # > 120 bytes of flow, 8-aligned, not a multiple of 16
     buf = torch.zeros((N * stride // 4,), dtype=torch.float32, device="cuda")
@@ -125,7 +141,8 @@ def test_draw_flow(hip_ctx, w):
 # -- Blur, Resize, Montage, ConvertColor -------------------------------------------------------------------------------
 def test_box_blur(hip_ctx):
     fr = frames_u8((5, 7, 3), 3)
-    whole = hip_ctx.box_blur(fr, 3)
+    whole, launches = counted(hip_ctx, _native.K_BLUR_OP, lambda: hip_ctx.box_blur(fr, 3))
+    assert launches == 2, "blur of %d frames: %d launches" % (N, launches)
     same(whole, split(lambda x: hip_ctx.box_blur(x, 3), fr), "blur")
     frc, got = fr.cpu().numpy(), whole.cpu().numpy()
     for i in IDX:
@@ -184,7 +201,8 @@ def test_cvt_color(hip_ctx, code, shape):
 # -- pose ----------------------------------------------------------------------------------------------------------
 def test_cpm2_input(hip_ctx):
     fr = frames_u8((6, 5, 3), 9)                                # 6 x 5 at scale 1 -> padded to an 8 x 8 network input
-    whole = hip_ctx.cpm2_input(fr, 1.0)
+    whole, launches = counted(hip_ctx, _native.K_CPM2_INPUT, lambda: hip_ctx.cpm2_input(fr, 1.0))
+    assert launches == 2, "cpm2_input of %d frames: %d launches" % (N, launches)
     same(whole, split(lambda x: hip_ctx.cpm2_input(x, 1.0), fr), "cpm2_input")
     frc, got = fr.cpu().numpy(), whole.cpu().numpy()
     for i in IDX:
