@@ -99,7 +99,7 @@ enum st_kernel_id {
   ST_K_CPM2_RESIZE = 14,
   ST_K_CPM2_NMS = 15,      /* the library's non-maximum suppressions: CPM2's peak search and the FacenetOutput launches (decode, sort + greedy NMS, pack) */
   ST_K_FRAME_STATS = 16, /* moments + finishing launches of the frame-statistics ops */
-  ST_K_JPEG = 17,        /* inverse DCT + upsample / colour launches of the ImageDecoder op; the ImageEncoder op's launches (four, or five without restart markers); the PNG launches of st_png_decode_batch (unfilter, expand) */
+  ST_K_JPEG = 17,        /* inverse DCT + upsample / colour launches of the ImageDecoder op; the ImageEncoder op's launches (four, or five without restart markers); the PNG launches of st_png_decode_batch (unfilter, expand) and of st_png_encode_batch (filter, deflate, layout, pack) */
   ST_K_NET_INPUT = 18,   /* the FacenetInput and CaffeInput launches */
   ST_K_COUNT = 19
 };
@@ -897,6 +897,36 @@ int st_png_decode_host(const uint8_t* buf, size_t size, uint8_t* frame, size_t c
  * (h, w, channels) frames at any byte address.  Timed under ST_K_JPEG. */
 int st_png_decode_batch(st_ctx* ctx, const uint8_t* const* bufs_host, const size_t* sizes, int n, int h, int w, int channels,
                         uint8_t* const* out_dev);
+
+/* ---- ImageEncoder: PNG (opt-in, ImageEncoderArgs.format = PNG) -----------------------------------
+ * Lossless streams of (h, w, c) uint8 frames, c = 1 (gray), 3 (R, G, B) or 4 (R, G, B, A): colour types 0, 2, 6 at bit depth
+ * 8, not interlaced, no ancillary chunks.  Rows are filtered on the device (k_png_filter), the filtered bytes are cut into
+ * pieces of 32 768 that are deflated independently (k_png_deflate: runs as distance-1 matches, one dynamic-Huffman block per
+ * piece, stored where that is not shorter), every piece is one IDAT chunk, and a last IDAT carries the final empty block and
+ * the Adler-32.  The bytes are defined by tests/ref_png_encode_np.py; any PNG reader decodes them. */
+enum { ST_PNG_FILTER_NONE = 0, ST_PNG_FILTER_SUB = 1, ST_PNG_FILTER_UP = 2, ST_PNG_FILTER_AVERAGE = 3, ST_PNG_FILTER_PAETH = 4,
+       ST_PNG_FILTER_ADAPTIVE = 5 };   /* ADAPTIVE: per row the type with the least sum of min(b, 256 - b), ties to the lowest */
+/* Host only.  ST_OK, or ST_ERR_INVALID with the refusal's words in msg (may be null): c outside {1, 3, 4}, a size outside
+ * 1..65535, a filter outside the enum. */
+int st_png_encode_check(int h, int w, int c, int filter, char* msg, size_t msg_len);
+/* Host only.  No stream of an (h, w, c) frame is longer: every piece stored.  -1 for what st_png_encode_check refuses. */
+long long st_png_encode_bound(int h, int w, int c);
+/* Host only, re-entrant: the stream of one dense host frame in plain C++, byte for byte what st_png_encode_batch writes.  *size
+ * receives its bytes; buf may be null for the size alone, else cap must hold it (ST_ERR_INVALID). */
+int st_png_encode_host(const uint8_t* frame, int h, int w, int c, int filter, uint8_t* buf, size_t cap, size_t* size);
+/* Host only, for tests: the encoder's length-limited code construction on any histogram.  counts[symbols] (2 <= symbols <= 286,
+ * their sum below 2^32), limit 1..15 with 2^limit >= symbols -> lengths[symbols], 0 for a symbol without a code.  The code is
+ * complete; with fewer than two counted symbols the lowest-numbered others receive a code too. */
+int st_png_huff_limited(const uint32_t* counts, int symbols, int limit, uint8_t* lengths);
+/* n device frames (h, w, c), dense, at any byte address -> n streams kept on the device until the context's next
+ * st_png_encode_batch call; st_png_encode_fetch copies them.  Refused before anything is launched, written or uploaded, with
+ * the context's previous streams still fetchable: n < 1, what st_png_encode_check refuses, a null table or frame, more than
+ * 2^31 - 1 rows or pieces in the call.  Four launches -- filter, deflate, layout, pack --, timed under ST_K_JPEG. */
+int st_png_encode_batch(st_ctx* ctx, const uint8_t* const* frames_dev, int n, int h, int w, int c, int filter);
+/* The streams of the context's last st_png_encode_batch call, with st_jpeg_encode_fetch's contract: sizes[i] receives stream
+ * i's bytes; bufs_host may be null for the sizes alone, else n host buffers of `capacity` bytes each.  One copy of the packed
+ * streams; the host does not touch their bytes otherwise. */
+int st_png_encode_fetch(st_ctx* ctx, uint8_t* const* bufs_host, size_t* sizes, size_t capacity);
 
 #ifdef __cplusplus
 }

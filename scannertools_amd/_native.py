@@ -227,6 +227,12 @@ SIGNATURES = {
     "st_png_filtered": (_i, [_vp, _sz, _vp, _sz, _c.POINTER(PngInfo)]),
     "st_png_decode_host": (_i, [_vp, _sz, _vp, _sz, _c.POINTER(PngInfo)]),
     "st_png_decode_batch": (_i, [_vp, _c.POINTER(_vp), _c.POINTER(_sz), _i, _i, _i, _i, _c.POINTER(_vp)]),
+    "st_png_encode_check": (_i, [_i, _i, _i, _i, _vp, _sz]),
+    "st_png_encode_bound": (ctypes.c_longlong, [_i, _i, _i]),
+    "st_png_encode_host": (_i, [_vp, _i, _i, _i, _i, _vp, _sz, _c.POINTER(_sz)]),
+    "st_png_huff_limited": (_i, [_vp, _i, _i, _vp]),
+    "st_png_encode_batch": (_i, [_vp, _c.POINTER(_vp), _i, _i, _i, _i, _i]),
+    "st_png_encode_fetch": (_i, [_vp, _c.POINTER(_vp), _c.POINTER(_sz), _sz]),
 }
 
 _LIB = None
@@ -244,9 +250,9 @@ def source_hash():
     st_build_info() of a library built from THIS tree reports."""
     import hashlib
     srcs = ["st_context.hip", "st_hist.hip", "st_farneback.hip", "st_flowvis.hip", "st_imgproc.hip", "st_pose.hip", "st_conv.hip",
-            "st_conv_tile_bf16x3.hip", "st_conv_tile_f32.hip", "st_framestats.hip", "st_jpeg.hip", "st_netinput.hip", "st_nn.hip", "st_detect.hip", "st_jpeg_enc.hip", "st_jpeg_entropy.hip", "st_jpeg_subseq.hip", "st_jpeg_reduced.hip", "st_png.hip", "st_jpeg_parse.cpp", "st_jpeg_enc_host.cpp", "st_png_host.cpp", "st_internal.h",
+            "st_conv_tile_bf16x3.hip", "st_conv_tile_f32.hip", "st_framestats.hip", "st_jpeg.hip", "st_netinput.hip", "st_nn.hip", "st_detect.hip", "st_jpeg_enc.hip", "st_jpeg_entropy.hip", "st_jpeg_subseq.hip", "st_jpeg_reduced.hip", "st_png.hip", "st_png_enc.hip", "st_jpeg_parse.cpp", "st_jpeg_enc_host.cpp", "st_png_host.cpp", "st_png_enc_host.cpp", "st_internal.h",
             "st_conv_tile.h", "st_jpeg_parse.h", "st_jpeg_enc_host.h", "st_jpeg_entropy.h", "st_jpeg_dense.h", "st_jpeg_enc_opt.h", "st_png_host.h",
-            "st_host_pipeline.h", os.path.join("..", "..", "include", "scannertools_hip.h"), "Makefile"]
+            "st_host_pipeline.h", "st_png_enc.h", os.path.join("..", "..", "include", "scannertools_hip.h"), "Makefile"]
     hsh = hashlib.sha256()
     for f in srcs:
         hsh.update(open(os.path.join(CSRC, f), "rb").read())

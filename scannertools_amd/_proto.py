@@ -172,11 +172,31 @@ def parse_image_decoder_args(buf):
 ENCODER_RESTARTS = {"MCU_ROW": 0, "NONE": 1}   # ImageEncoderArgs.Restart
 
 
-def image_encoder_args(quality=0, subsampling="", restart=0, optimize=False):
+ENCODER_FORMATS = {"JPEG": 0, "PNG": 1}        # ImageEncoderArgsWithFormat.Format
+ENCODER_PNG_FILTERS = {"ADAPTIVE": 0, "NONE": 1, "SUB": 2, "UP": 3, "AVERAGE": 4, "PAETH": 5}   # ImageEncoderArgsWithFormat.PngFilter
+
+
+def _enum_field(what, names, value):
+    if isinstance(value, str):
+        if value.upper() not in names:
+            raise ValueError("%s must be one of %s or a number, got %r" % (what, ", ".join(repr(k.lower()) for k in names), value))
+        return names[value.upper()]
+    if value is None or isinstance(value, bool) or not isinstance(value, int):
+        raise ValueError("%s must be one of %s or a number, got %r" % (what, ", ".join(repr(k.lower()) for k in names), value))
+    return value
+
+
+def image_encoder_args(quality=0, subsampling="", restart=0, optimize=False, format=0, png_filter=0):
     """A serialised ImageEncoderArgs (scannertools_imgproc_amd.proto): quality = 1, subsampling = 2, restart = 3 (a number, or
     "mcu_row" / "none" in either case), optimize = 4 (False / True, or a number: any other than 0 / 1 fails the op's
     validation).  The defaults (0, "", MCU_ROW = 0, false) are not written, as proto3 does; the op then takes quality 95,
-    "4:2:0", one restart interval per MCU row and the Annex K Huffman tables."""
+    "4:2:0", one restart interval per MCU row and the Annex K Huffman tables.  format = 5 ("jpeg" / "png" or a number) and
+    png_filter = 6 ("adaptive", "none", "sub", "up", "average", "paeth" or a number) likewise: absent when JPEG / ADAPTIVE, so a
+    message without them is byte for byte what it was before they existed.  A number for png_filter is the message's PngFilter
+    enum (ADAPTIVE = 0, NONE = 1, SUB = 2, UP = 3, AVERAGE = 4, PAETH = 5), NOT the library's ST_PNG_FILTER_* that
+    HipContext.encode_png(filter=<number>) takes (PNG's types 0..4, adaptive = 5): 3 is UP here and AVERAGE there."""
+    format = _enum_field("format", ENCODER_FORMATS, format)
+    png_filter = _enum_field("png_filter", ENCODER_PNG_FILTERS, png_filter)
     if isinstance(optimize, str) or optimize is None or not isinstance(optimize, (bool, int)):
         raise ValueError("optimize must be False, True or a number, got %r" % (optimize,))
     if isinstance(restart, str):
@@ -188,12 +208,16 @@ def image_encoder_args(quality=0, subsampling="", restart=0, optimize=False):
         out += _varint(3 << 3 | 0) + _varint(int(restart) & ((1 << 64) - 1))
     if int(optimize) != 0:
         out += _varint(4 << 3 | 0) + _varint(int(optimize) & ((1 << 64) - 1))
+    if format != 0:
+        out += _varint(5 << 3 | 0) + _varint(format & ((1 << 64) - 1))
+    if png_filter != 0:
+        out += _varint(6 << 3 | 0) + _varint(png_filter & ((1 << 64) - 1))
     return out
 
 
 def parse_image_encoder_args(buf):
-    """{'quality': int, 'subsampling': str, 'restart': name or number, 'optimize': bool or number} of a serialised
-    ImageEncoderArgs; an absent field is left out."""
+    """{'quality': int, 'subsampling': str, 'restart': name or number, 'optimize': bool or number, 'format': name or number,
+    'png_filter': name or number} of a serialised ImageEncoderArgs; an absent field is left out."""
     names = {v: k for k, v in ENCODER_RESTARTS.items()}
     out = {}
     for number, wt, value in fields(buf):
@@ -207,6 +231,10 @@ def parse_image_encoder_args(buf):
         elif number == 4 and wt == 0:
             value = value - (1 << 64) if value >> 63 else value
             out["optimize"] = bool(value) if value in (0, 1) else value
+        elif number in (5, 6) and wt == 0:
+            value = value - (1 << 64) if value >> 63 else value
+            table = ENCODER_FORMATS if number == 5 else ENCODER_PNG_FILTERS
+            out["format" if number == 5 else "png_filter"] = {v: k for k, v in table.items()}.get(value, value)
     return out
 
 

@@ -148,6 +148,7 @@ ST_EXPORT int st_ctx_destroy(st_ctx* ctx) {
   st_jpeg_release(ctx);
   st_png_release(ctx);
   st_jpeg_enc_release(ctx);
+  st_png_enc_release(ctx);
   st_netin_release(ctx);
   st_detect_release(ctx);
   if (ctx->own_stream) (void)hipStreamDestroy(ctx->own_stream);

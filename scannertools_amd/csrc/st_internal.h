@@ -58,6 +58,7 @@ struct st_ctx {
   struct st_detect_state* detect = nullptr; // the kept rows of the last st_facenet_output_batch call (st_detect.hip)
   struct st_png_state* png = nullptr;     // page-locked slots of st_png_decode_batch (st_png.hip), made at its first call
   struct st_jpeg_enc_state* jpeg_enc = nullptr; // tables and the packed streams of the last st_jpeg_encode_batch call (st_jpeg_enc.hip)
+  struct st_png_enc_state* png_enc = nullptr;   // the packed streams of the last st_png_encode_batch call (st_png_enc.hip)
 };
 void st_jpeg_release(st_ctx* ctx);   // frees ctx->jpeg (st_ctx_destroy)
 struct StJpegEntArgs;
@@ -73,6 +74,7 @@ int st_jsq_round_launch(st_ctx* ctx, const StJsqArgs& a, unsigned max_groups, bo
 int st_jsq_finish_launch(st_ctx* ctx, const StJsqArgs& a, unsigned max_groups, unsigned max_segments, int par, size_t coef_bytes);
 void st_png_release(st_ctx* ctx);    // frees ctx->png (st_ctx_destroy)
 void st_jpeg_enc_release(st_ctx* ctx); // frees ctx->jpeg_enc (st_ctx_destroy)
+void st_png_enc_release(st_ctx* ctx);  // frees ctx->png_enc (st_ctx_destroy)
 void st_netin_release(st_ctx* ctx);  // frees ctx->netin (st_ctx_destroy)
 void st_detect_release(st_ctx* ctx); // frees ctx->detect (st_ctx_destroy)
 

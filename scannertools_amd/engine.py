@@ -648,7 +648,9 @@ class _ImageDecoderNode(_CppMultiOpNode):
 
 class _ImageEncoderNode(_CppMultiOpNode):
     """ImageEncoder: frames in, a bytes column out.  A requested row that is not an (h, w, 3) uint8 frame, or whose shape differs
-    from the first row's, is a ValueError naming the row, before any kernel instance exists (the kernel class can only abort)."""
+    from the first row's, is a ValueError naming the row, before any kernel instance exists (the kernel class can only abort).
+    With format = PNG (``png`` set by sc.ops.ImageEncoder) frames of 1, 3 or 4 channels pass."""
+    png = False
 
     def rows(self, idx):
         import torch
@@ -656,10 +658,11 @@ class _ImageEncoderNode(_CppMultiOpNode):
             return []
         frames = self.parents[0].rows(idx)
         first = None
+        channels = (1, 3, 4) if self.png else (3,)
         for r, f in zip(idx, frames):
-            if isinstance(f, (bytes, bytearray)) or len(f.shape) != 3 or f.shape[2] != 3 or f.dtype not in (np.uint8, torch.uint8):
+            if isinstance(f, (bytes, bytearray)) or len(f.shape) != 3 or f.shape[2] not in channels or f.dtype not in (np.uint8, torch.uint8):
                 what = "%d bytes" % len(f) if isinstance(f, (bytes, bytearray)) else "%s %s" % (tuple(f.shape), f.dtype)
-                raise ValueError("%s: row %d is %s, not an (h, w, 3) uint8 frame" % (self.name, r, what))
+                raise ValueError("%s: row %d is %s, not an (h, w, %s) uint8 frame" % (self.name, r, what, "1 | 3 | 4" if self.png else "3"))
             first = tuple(f.shape) if first is None else first
             if tuple(f.shape) != first:
                 raise ValueError("%s: row %d changes shape inside a batch: %s after %s" % (self.name, r, tuple(f.shape), first))
@@ -934,7 +937,8 @@ class _Ops:
             args = _proto.image_decoder_args(args.get("image_type"), args.get("entropy"), args.get("split"), args.get("scale_denom"), args.get("png"))
         return _ImageDecoderNode(self.sc, "ImageDecoder", [img], device, batch, args or b"")
 
-    def ImageEncoder(self, frame, quality=95, subsampling="4:2:0", restart="row", device=None, batch=None, optimize=False):
+    def ImageEncoder(self, frame, quality=95, subsampling="4:2:0", restart="row", device=None, batch=None, optimize=False, format="jpeg",
+                     png_filter="adaptive"):
         """sc.ops.ImageEncoder(frame=..., quality=..., subsampling=..., restart=..., device=..., batch=...): (h, w, 3) uint8 RGB
         frames -> the column img, one baseline JPEG stream (bytes) per row -- what sc.ops.ImageDecoder(img=...) reads.  Args
         ImageEncoderArgs{quality = 1, subsampling = 2, restart = 3} (scannertools_imgproc_amd.proto): quality 1..100,
@@ -942,11 +946,18 @@ class _Ops:
         restart markers: what cv::imencode and Pillow write by default), or the field's number; anything else fails validation.
         optimize (ImageEncoderArgs field 4): True writes each frame with Huffman tables built from its own symbol counts
         (libjpeg's optimize_coding, Pillow's optimize=True); a number other than 0 / 1 fails validation.
-        The whole encoder, Huffman coding and table construction included, runs on the GPU."""
+        The whole encoder, Huffman coding and table construction included, runs on the GPU.
+        format (field 5): "jpeg", or "png" for lossless PNG streams of (h, w, 1 | 3 | 4) frames, rows filtered as png_filter (field
+        6) says: "adaptive", "none", "sub", "up", "average" or "paeth"; numbers pass as they are and unknown ones fail validation
+        (a number is the message's enum, ADAPTIVE = 0, NONE = 1 .. PAETH = 5 -- not HipContext.encode_png's ST_PNG_FILTER_* numbering).
+        With "png" the JPEG arguments are checked as ever and otherwise ignored."""
         from . import _proto
         if isinstance(restart, str):
             restart = {"row": 0, "mcu_row": 0, "none": 1}.get(restart.lower(), restart)
-        return _ImageEncoderNode(self.sc, "ImageEncoder", [frame], device, batch, _proto.image_encoder_args(quality, subsampling, restart, optimize))
+        args = _proto.image_encoder_args(quality, subsampling, restart, optimize, format, png_filter)
+        node = _ImageEncoderNode(self.sc, "ImageEncoder", [frame], device, batch, args)
+        node.png = _proto.parse_image_encoder_args(args).get("format") == "PNG"
+        return node
 
     def InfoFromFrame(self, frame):
         """sc.ops.InfoFromFrame(frame=frame): the frame's FrameInfo as a bytes column."""

@@ -458,6 +458,30 @@ class HipContext:
         self._check(self._L.st_jpeg_encode_fetch(self._h, bufs, sizes, most))
         return [store[i, :sizes[i]].tobytes() for i in range(n)]
 
+    def encode_png(self, frames, filter="adaptive"):
+        """ImageEncoder op with format = PNG (st_png_encode_batch): (n, h, w, c) uint8 CUDA frames (a tensor or a list of
+        (h, w, c) tensors of one shape), c = 1 (gray), 3 (R, G, B) or 4 (R, G, B, A) -> a list of n PNG streams (bytes), lossless,
+        byte for byte what png_encode_host writes.  ``filter``: "adaptive" (per row the type with the least sum of
+        min(b, 256 - b)) or one of "none", "sub", "up", "average", "paeth" for every row.  Filtering, deflate (runs only, one
+        dynamic-Huffman block per 32 768 filtered bytes), the CRCs and the Adler-32 run in HIP kernels on the current stream;
+        only the streams cross to the host, in one copy.  A number for ``filter`` is an ST_PNG_FILTER_* value (PNG's filter types
+        0..4, adaptive = 5), NOT the argument message's PngFilter enum that sc.ops.ImageEncoder(png_filter=<number>) takes (ADAPTIVE = 0,
+        NONE = 1 .. PAETH = 5): 3 is AVERAGE here and UP there.  Names mean the same at both."""
+        flt = png_filter(filter)
+        self._bind()
+        fr, n, shape = self._rows(frames, torch.uint8, "frame")
+        if n == 0:
+            return []
+        h, w, c = shape
+        self._check(self._L.st_png_encode_batch(self._h, self._table(fr), n, h, w, c, flt))
+        sizes = (ctypes.c_size_t * n)()
+        self._check(self._L.st_png_encode_fetch(self._h, None, sizes, 0))   # the sizes alone
+        most = max(sizes)
+        store = np.empty((n, most), np.uint8)
+        bufs = _ptr_table(store[i].ctypes.data for i in range(n))
+        self._check(self._L.st_png_encode_fetch(self._h, bufs, sizes, most))
+        return [store[i, :sizes[i]].tobytes() for i in range(n)]
+
     def last_jpeg_symbol_stats(self, n):
         """st_jpeg_encode_fetch_stats: the (n, 4, 256) uint64 symbol counts of the last encode_jpeg(optimize=True) call of n
         frames (tables DC luma, AC luma, DC chroma, AC chroma), as the device counted them."""
@@ -958,6 +982,65 @@ def png_decode_host(stream):
     if st != 0:
         raise StError(st, info.message.decode())
     return frame
+
+
+PNG_FILTERS = ("none", "sub", "up", "average", "paeth", "adaptive")   # encode_png's filter=; ImageEncoderArgs.png_filter, ST_PNG_FILTER_*
+
+
+def png_filter(filter):
+    """The ST_PNG_FILTER_* value of a filter name (or of the value itself: none = 0 .. paeth = 4 as in PNG, adaptive = 5 -- not the
+    numbering of ImageEncoderArgs.png_filter, where ADAPTIVE is 0); ValueError for anything else."""
+    if isinstance(filter, str) and filter.lower() in PNG_FILTERS:
+        return PNG_FILTERS.index(filter.lower())
+    if isinstance(filter, int) and not isinstance(filter, bool) and 0 <= filter < len(PNG_FILTERS):
+        return filter
+    raise ValueError("png filter must be one of %s, got %r" % (", ".join(PNG_FILTERS), filter))
+
+
+def _png_encode_refusal(h, w, c, flt):
+    msg = ctypes.create_string_buffer(160)
+    st = _native.lib().st_png_encode_check(int(h), int(w), int(c), int(flt), msg, 160)
+    return st, msg.value.decode()
+
+
+def png_encode_bound(h, w, c):
+    """st_png_encode_bound (host only): no PNG stream of an (h, w, c) frame is longer, whatever its content and filter."""
+    v = _native.lib().st_png_encode_bound(int(h), int(w), int(c))
+    if v < 0:
+        raise StError(*_png_encode_refusal(h, w, c, 5))
+    return v
+
+
+def png_encode_host(frame, filter="adaptive"):
+    """st_png_encode_host (host only): the PNG stream of one (h, w, c) or (h, w) uint8 host frame in plain C++, byte for byte
+    what encode_png writes for it (the CPU twin of its kernels)."""
+    flt = png_filter(filter)
+    f = np.ascontiguousarray(frame, np.uint8)
+    if f.ndim == 2:
+        f = f[:, :, None]
+    if f.ndim != 3:
+        raise ValueError("png_encode_host takes an (h, w, c) frame, got shape %s" % (f.shape,))
+    h, w, c = f.shape
+    st, msg = _png_encode_refusal(h, w, c, flt)
+    if st != 0:
+        raise StError(st, "png_encode: " + msg)
+    cap = png_encode_bound(h, w, c)
+    buf, size = np.empty(cap, np.uint8), ctypes.c_size_t()
+    st = _native.lib().st_png_encode_host(f.ctypes.data, h, w, c, flt, buf.ctypes.data, cap, ctypes.byref(size))
+    if st != 0:
+        raise StError(st, "st_png_encode_host(h=%d, w=%d, c=%d)" % (h, w, c))
+    return buf[:size.value].tobytes()
+
+
+def png_huff_limited(counts, limit):
+    """st_png_huff_limited (host only): the code lengths (uint8, 0: no code) the PNG encoder's length-limited construction
+    gives a histogram of 2..286 counts at ``limit`` bits (15: literal/length codes, 7: the code-length code)."""
+    f = np.ascontiguousarray(counts, np.uint32)
+    out = np.zeros(f.shape, np.uint8)
+    st = _native.lib().st_png_huff_limited(f.ctypes.data, f.size, int(limit), out.ctypes.data) if f.ndim == 1 else 1
+    if st != 0:
+        raise StError(st, "st_png_huff_limited(%d symbols, limit %r): 2..286 symbols, limit 1..15 with 2^limit >= symbols, counts below 2^32 in all" % (f.size, limit))
+    return out
 
 
 JPEG_ENTROPY_MODES = ("host", "gpu", "auto")   # decode_jpeg's entropy=; ImageDecoderArgs.entropy HOST = 0, GPU = 1, AUTO = 2

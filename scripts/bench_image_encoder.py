@@ -27,6 +27,14 @@ of "none" go under "batches_norst".
 Pillow then saves with optimize=True too); both measures the two settings in ONE run on the same frames, their timed calls
 alternating like those of --restart both, so that "off" is the unchanged path measured beside "on".  The figures with optimised
 tables go under "batches_opt" / "batches_norst_opt": frames/s, kernel ms per frame and stream bytes per frame as for the others.
+
+--format png measures the lossless PNG output instead (st_png_encode_batch + st_png_encode_fetch) on two kinds of
+resident 1080p RGB frames: the noisy frames above ("photo") and Montage-like sheets, the same pictures at quarter size tiled 2 x 2
+inside flat borders ("sheet").  Per kind and batch size: frames/s of the whole call, the four kernels' ms per frame from the
+library's events, stream bytes per frame, and in the same run Pillow's save(format="PNG") on 16 threads at its default and at
+compress_level=1.  The first stream of each kind is decoded back with the library's own decoder before anything is timed.  With
+--trace it makes three calls per kind and batch size for a rocprofv3 --kernel-trace --stats run of its own (k_png_filter,
+k_png_deflate, k_png_enc_layout, k_png_enc_pack).
 """
 import argparse
 import ctypes
@@ -60,8 +68,94 @@ def make_frames():
     return out
 
 
+def make_sheets(host):
+    """Montage-like: four quarter-size pictures in a 2 x 2 grid with flat borders and gutters"""
+    out = []
+    for i in range(DISTINCT):
+        sheet = np.zeros((H, W, 3), np.uint8)
+        th, tw = H // 2 - 60, W // 2 - 80
+        for k in range(4):
+            tile = host[(i + k) % DISTINCT][::2, ::2][:th, :tw]
+            y0, x0 = 40 + (k // 2) * (H // 2), 60 + (k % 2) * (W // 2)
+            sheet[y0:y0 + th, x0:x0 + tw] = tile
+        out.append(sheet)
+    return out
+
+
+def main_png(args):
+    from PIL import Image
+    import torch
+    from scannertools_amd import _native
+    from scannertools_amd.hip import HipContext, png_encode_bound
+    L = _native.lib()
+    ctx = HipContext(0)
+    photos = make_frames()
+    kinds = {"photo": photos, "sheet": make_sheets(photos)}
+    bound = png_encode_bound(H, W, 3)
+    result = {"bench": "image_encoder_png", "h": H, "w": W, "filter": "adaptive", "raw_frame_bytes": H * W * 3, "bound_bytes": bound,
+              "rounds": args.rounds}
+    ctx._bind()
+    for kind, host in kinds.items():
+        dev = [torch.from_numpy(f).cuda() for f in host]
+        (first,) = ctx.encode_png([dev[0]])
+        assert np.array_equal(ctx.decode_png([first]).cpu().numpy()[0], host[0]), "the stream does not decode back to the frame"
+        result[kind] = {}
+
+        def pillow(i, level):
+            buf = io.BytesIO()
+            Image.fromarray(host[i % DISTINCT]).save(buf, "PNG", **({} if level is None else {"compress_level": level}))
+            return len(buf.getvalue())
+
+        for n in BATCHES:
+            tab = (ctypes.c_void_p * n)(*[dev[i % DISTINCT].data_ptr() for i in range(n)])
+            sizes = (ctypes.c_size_t * n)()
+            store = np.empty((n, bound), np.uint8)   # pages are touched only where written
+            bufs = (ctypes.c_void_p * n)(*[store[i].ctypes.data for i in range(n)])
+
+            def call():
+                ctx._check(L.st_png_encode_batch(ctx._h, tab, n, H, W, 3, 5))
+                ctx._check(L.st_png_encode_fetch(ctx._h, bufs, sizes, bound))
+
+            if args.trace:
+                for _ in range(3):
+                    call()
+                continue
+            call()   # warm-up: workspace, stream buffer and staging grow here
+            b = {"stream_bytes_per_frame": int(statistics.mean(sizes))}
+            t = []
+            for _ in range(args.rounds):
+                t0 = time.perf_counter()
+                call()
+                t.append(time.perf_counter() - t0)
+            b.update({"fps_median": round(n / statistics.median(t), 1), "fps_min": round(n / max(t), 1), "fps_max": round(n / min(t), 1)})
+            ctx.timing_enable([_native.K_JPEG])
+            ctx.timing_reset()
+            for _ in range(args.rounds):
+                call()
+            launches, ms = ctx.timing_read(_native.K_JPEG)
+            ctx.timing_enable([])
+            b["kernel_ms_per_frame"] = round(ms / (args.rounds * n), 4)
+            b["kernel_launches_per_call"] = launches // args.rounds
+            with ThreadPoolExecutor(THREADS) as pool:
+                for level, key in ((None, "pillow_default"), (1, "pillow_level1")):
+                    t, got = [], []
+                    for _ in range(2):
+                        t0 = time.perf_counter()
+                        got = list(pool.map(lambda i: pillow(i, level), range(n)))
+                        t.append(time.perf_counter() - t0)
+                    b[key + "_%d_threads_fps" % THREADS] = round(n / min(t), 1)
+                    b[key + "_bytes_per_frame"] = int(statistics.mean(got))
+            result[kind]["batch%d" % n] = b
+            del store
+        del dev
+        ctx.release_workspace()
+    ctx.close()
+    print(json.dumps(result))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--format", choices=("jpeg", "png"), default="jpeg")
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--trace", action="store_true")
     ap.add_argument("--restart", choices=("row", "none", "both"), default="row")
@@ -71,6 +165,8 @@ def main():
         from PIL import Image
     except ImportError:
         sys.exit("bench_image_encoder.py needs Pillow as its yardstick")
+    if args.format == "png":
+        return main_png(args)
     import torch
     from scannertools_amd import _native
     from scannertools_amd.hip import HipContext, jpeg_encode_bound
